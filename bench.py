@@ -21,6 +21,10 @@ Rank 0 prints ONE JSON line.  Besides the contract fields it carries
   cpu_baseline  the C oracle (oracle/gsr_oracle.c, a port of the reference algorithm -- the
                 reference has no CPU path) timed on the host cores on a bounded sample: the first
                 few views of the same workload at full size.  N = 1 / rank 0 only.
+
+--dump-outputs DIR writes what the timed path handed its caller in the last step of its last timed
+region (image, radii, gradients) as DIR/<name>.npy (see write_outputs); the inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -137,17 +141,19 @@ def build_refinement_workload(device, rank, gs, cams, bg, overlap=True, solo=Fal
     return model, ncams, opt, bg_t, dpix
 
 
-def refinement_step(step, rank, world, model, ncams, opt, bg_t, dpix):
+def refinement_step(step, rank, world, model, ncams, opt, bg_t, dpix, keep=None):
     ncam = ncams[(step * world + rank) % len(ncams)]
     opt.zero_grad(set_to_none=True)
     # parameters in, image out: mesh producer -> SH colours + sigmoid -> rasterizer as one autograd node (harness.py)
-    color, _radii = model.render_channels(ncam, bg_t, depth_channels=0)
+    color, radii = model.render_channels(ncam, bg_t, depth_channels=0)
     color.backward(dpix)
     opt.step()
+    if keep is not None:
+        keep(step, color, radii, dict(model.named_parameters()))
     return color
 
 
-def one_step(step, rank, world, params, means2D, rasters, dpix):
+def one_step(step, rank, world, params, means2D, rasters, dpix, keep=None):
     r = rasters[(step * world + rank) % len(rasters)]
     for p in params.values():
         p.grad = None
@@ -155,7 +161,52 @@ def one_step(step, rank, world, params, means2D, rasters, dpix):
     color, radii = r(means3D=params["means3D"], means2D=means2D, opacities=params["opacities"],
                      colors_precomp=params["colors"], scales=params["scales"], rotations=params["rotations"])
     color.backward(dpix)
+    if keep is not None:
+        keep(step, color, radii, dict(params, means2D=means2D))
     return color
+
+
+class LastStep:
+    """--dump-outputs: keeps references to what the step with index steps - 1 handed its caller (image, radii and the
+    leaves' .grad) while a timed region of mode `armed` runs; a later region of the same mode replaces it.  Holding a
+    reference costs no GPU work.  They are read right after the headline regions, before any other step runs: the
+    rasterizer's image and gradients are fresh tensors of their step anyway, the refinement step's gradients are views of
+    the optimiser's flat buffer (dist.ShardedAdam.grad_views) that the next step would overwrite."""
+
+    def __init__(self, steps):
+        self.last, self.armed, self.taken = steps - 1, None, {}
+
+    def __call__(self, step, color, radii, leaves):
+        if self.armed is not None and step == self.last:
+            out = {"color": color, "radii": radii}
+            out.update(("grad_" + k.lstrip("_"), p.grad) for k, p in leaves.items() if p.grad is not None)
+            self.taken[self.armed] = out
+
+
+DUMP_BUDGET_BYTES = 64_000_000
+
+
+def write_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES):
+    """arrays: name -> tensor.  Writes out_dir/<name>.npy, float64 kept and everything else as float32 (radii are small
+    integers: exact).  If the whole exceeds `budget` bytes, the image stays whole and every other array keeps the same
+    fixed sample of its rows (numpy default_rng(0), sorted, identical from run to run) sized to fit.  Returns
+    name -> shape written."""
+    host = {}
+    for k, v in arrays.items():
+        a = v.detach().cpu().numpy()
+        host[k] = a if a.dtype == np.float64 else a.astype(np.float32)
+    total = sum(a.nbytes for a in host.values())
+    if total > budget:
+        rest = sum(a.nbytes for k, a in host.items() if k != "color")
+        frac = max(0.0, budget - host["color"].nbytes - 4096) / max(rest, 1)
+        for k, a in host.items():
+            if k != "color" and a.ndim >= 1 and a.shape[0] > 1:
+                n = max(1, int(a.shape[0] * frac))
+                host[k] = a[np.sort(np.random.default_rng(0).choice(a.shape[0], size=n, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a))
+    return {k: list(a.shape) for k, a in host.items()}
 
 
 def reference_caller_step(step, cams, bg_t, params, means2D, dpix):
@@ -516,7 +567,12 @@ def main():
                          "alone, so that value(N) / value(1) is the scaling of ONE thing (also GSR_BENCH_SCALE_STEP=1)")
     ap.add_argument("--views-in-flight", type=int, default=2,
                     help="N = 1: independent view pipelines (host thread + HIP stream each, gaustar_amd.pipelines); 1 = one view at a time")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step (image, radii, gradients) "
+                         "as DIR/<name>.npy, float32, at most 64 MB (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # GSR_BENCH_BACKEND=gloo lets the multi-rank path be exercised on a box with fewer GPUs than ranks
     # (ranks then share devices; RCCL itself refuses two ranks on one GPU).  Default: nccl (= RCCL).
@@ -548,6 +604,8 @@ def main():
     spread = lambda dts: {"repeats": len(dts), "ms_per_step_min": round(min(dts) / args.steps * 1e3, 4),
                           "ms_per_step_max": round(max(dts) / args.steps * 1e3, 4)}
     refine, same_step_1gpu_ms = None, None
+    keep = LastStep(args.steps) if args.dump_outputs else None
+    arm = lambda mode: None if keep is None else setattr(keep, "armed", mode)   # (which headline region's last step to keep)
     if world > 1:
         # the SAME step without any exchange, every rank on its own GPU at once: the single-GPU denominator of this step's
         # scaling (the N = 1 line of this script times the rasterizer alone, which is what the metric is quoted on)
@@ -559,12 +617,12 @@ def main():
         same_step_1gpu_ms = med([timed(solo_step, n_solo, world, device) for _ in range(3)]) / n_solo * 1e3
         solo_w[2].close(); del solo_w, solo_step
         refine = build_refinement_workload(device, rank, gs, cams, bg)
-        step = lambda s: refinement_step(s, rank, world, *refine)
+        step = lambda s: refinement_step(s, rank, world, *refine, keep=keep)
     elif scale_step:
         refine = build_refinement_workload(device, rank, gs, cams, bg)
-        step = lambda s: refinement_step(s, 0, 1, *refine)
+        step = lambda s: refinement_step(s, 0, 1, *refine, keep=keep)
     else:
-        step = lambda s: one_step(s, rank, world, params, means2D, rasters, dpix)
+        step = lambda s: one_step(s, rank, world, params, means2D, rasters, dpix, keep=keep)
     raster_step = lambda s: one_step(s, rank, world, params, means2D, rasters, dpix)   # (the instrumented pass below)
 
     for s in range(args.warmup):
@@ -593,7 +651,7 @@ def main():
 
         def pipe_step(t, s):
             ps = leaves[t]
-            one_step(s, 0, 1, {k: v for k, v in ps.items() if k != "means2D"}, ps["means2D"], rasters, dpix)
+            one_step(s, 0, 1, {k: v for k, v in ps.items() if k != "means2D"}, ps["means2D"], rasters, dpix, keep=keep)
         import gc
         clock = {}
         dts_single, dts_pipe = [], []
@@ -607,14 +665,18 @@ def main():
             w_ns, w_n = ctypes.c_longlong(0), ctypes.c_longlong(0)
             for rep in range(R):
                 lib.gsr_debug_host_wait(None, None, 1)
+                arm("single")
                 dts_single.append(timed(step, args.steps, world, device))
+                arm(None)
                 lib.gsr_debug_host_wait(ctypes.byref(w_ns), ctypes.byref(w_n), 0)
                 single_wait_ns += w_ns.value; single_waits += w_n.value
                 gc.disable()   # (timed() switches the collector back on)
                 pipes.run(pipe_step, list(range(2 * V)))   # untimed, like timed()'s own first steps
                 lib.gsr_debug_host_wait(None, None, 1)
+                arm("pipelines")
                 pipes.run(pipe_step, list(range(args.steps)), before=lambda: clock.__setitem__("t0", time.perf_counter()),
                           after=lambda: clock.__setitem__("t1", time.perf_counter()))
+                arm(None)
                 lib.gsr_debug_host_wait(ctypes.byref(w_ns), ctypes.byref(w_n), 0)
                 wait_ns.value += w_ns.value; waits.value += w_n.value
                 dts_pipe.append(clock["t1"] - clock["t0"])
@@ -623,8 +685,11 @@ def main():
             pipe_error = repr(ex)[:200]
         finally:
             gc.enable()
+            arm(None)
         while len(dts_single) < R:
+            arm("single")
             dts_single.append(timed(step, args.steps, world, device))
+            arm(None)
         dt_single = med(dts_single)
         single = {"value": round(args.steps / dt_single, 2), "ms_per_step": round(dt_single / args.steps * 1e3, 4), **spread(dts_single),
                   "what": "the same K steps one view at a time on one stream (how rounds 1 and 2 quoted the metric); median of the "
@@ -642,13 +707,23 @@ def main():
         w_ns, w_n = ctypes.c_longlong(0), ctypes.c_longlong(0)
         for rep in range(R):
             lib.gsr_debug_host_wait(None, None, 1)
+            arm("single")
             dts.append(timed(step, args.steps, world, device))
+            arm(None)
             lib.gsr_debug_host_wait(ctypes.byref(w_ns), ctypes.byref(w_n), 0)
             wait_ns.value += w_ns.value; waits.value += w_n.value
         dt = med(dts)
         value_spread = spread(dts)
     ms_per_step = dt / args.steps * 1e3
     value = args.steps * world / dt
+    dumped = None
+    if keep is not None:   # the last step of the last region of the mode `value` is quoted on, before any other leg runs
+        mode = "pipelines" if V > 1 else "single"
+        if rank == 0:
+            last = (args.steps - 1) * world % len(cams)
+            dumped = {"dir": args.dump_outputs, "mode": mode, "step": args.steps - 1, "camera": last,
+                      "arrays": write_outputs(args.dump_outputs, keep.taken[mode])}
+        keep.taken.clear()
     plan_stats = {k: rz_plan.PLAN_STATS[k] - plan_stats0[k] for k in plan_stats0}
     # the same K steps with planning switched off (every view: scan + scatter + the host round trip between the stages), one
     # view at a time, median of 3 regions -- what the planned figures above are to be compared with
@@ -838,6 +913,8 @@ def main():
                     "was rendered once, untimed, before the timed regions (its first view leaves the plan)"}
         if exact_binning is not None:
             out["exact_binning"] = exact_binning
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         if single is not None:
             out["single_pipeline"] = single
         if reference_caller is not None:

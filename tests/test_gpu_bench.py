@@ -55,6 +55,28 @@ def test_bench_line_at_one_gpu():
     assert "frac_rocprof" in rf and (rf["frac_rocprof"] is None or 0.0 < rf["frac_rocprof"] < 1.0)
 
 
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs DIR: the image, radii and the six gradients of the last timed step (camera K - 1 of the rig), float32,
+    at most 64 MB; --steps sets the timed steps and ms_per_step is in the line."""
+    import numpy as np
+    out = str(tmp_path / "outputs")
+    d = _bench("--steps", "3", "--warmup", "1", "--repeats", "1", "--no-cpu-baseline", "--no-extras", "--dump-outputs", out)
+    assert d["steps"] == 3 and d["ms_per_step"] > 0.0
+    info = d["dumped_outputs"]
+    assert info["step"] == 2 and info["camera"] == 2 and info["mode"] == "pipelines" and info["dir"] == out
+    P = 491520
+    shapes = {"color": (3, 1080, 1920), "radii": (P,), "grad_means3D": (P, 3), "grad_means2D": (P, 3), "grad_opacities": (P, 1),
+              "grad_colors": (P, 3), "grad_scales": (P, 3), "grad_rotations": (P, 4)}
+    assert sorted(os.listdir(out)) == sorted(k + ".npy" for k in shapes)
+    assert sum(os.path.getsize(os.path.join(out, f)) for f in os.listdir(out)) <= 64_000_000
+    for k, shape in shapes.items():
+        a = np.load(os.path.join(out, k + ".npy"))
+        assert a.dtype == np.float32 and a.shape == shape and tuple(info["arrays"][k]) == shape, (k, a.dtype, a.shape)
+        assert np.isfinite(a).all() and np.abs(a).max() > 0.0, k
+    radii = np.load(os.path.join(out, "radii.npy"))
+    assert (radii >= 0).all() and (radii == np.round(radii)).all()
+
+
 def test_bench_other_configs_leg():
     """`other_configs` (B, D, D-depth: BASELINE.json configs[1] and configs[3]) and `scale_base` ride in the default N = 1 line."""
     import bench
