@@ -98,6 +98,12 @@ SIGNATURES = {
                                             c_longlong, c_longlong, c_float, c_void_p, c_int, c_int, c_void_p, c_longlong, c_longlong,
                                             c_void_p, c_longlong, c_longlong, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p,
                                             c_longlong, c_longlong, c_longlong, c_void_p, c_longlong, c_longlong, c_void_p]),
+    # surface-mesh regularisers (refine.py:676-706): int32 topology from gaustar_amd.meshes.MeshTopology
+    "gsr_mesh_reg_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "gsr_mesh_reg_forward": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_float, c_float, c_float, c_void_p, c_void_p, c_void_p]),
+    "gsr_mesh_reg_backward": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_float, c_float, c_float, c_void_p, c_void_p, c_int, c_void_p]),
     "gsr_adam_step": (c_int, [c_longlong, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_double, c_double, c_int,
                               c_void_p]),
     "gsr_adam_step_multi": (c_int, [c_int, POINTER(c_longlong), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),

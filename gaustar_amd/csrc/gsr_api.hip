@@ -1179,6 +1179,68 @@ int gsr_rgb_depth_loss_backward(int C, int H, int W, const float* pred, long lon
     return 0;
 }
 
+size_t gsr_mesh_reg_workspace_bytes(int V, int F, int E, int Q)
+{
+    (void)V; (void)F; (void)E; (void)Q;   // (the partials of at most 2048 workgroups, whatever the mesh)
+    return mesh_reg_workspace_bytes();
+}
+
+static int mesh_reg_check(const char* fn, int V, int F, int E, int Q, const float* verts, const int* faces, const int* edges,
+                          const int* pairs)
+{
+    char msg[160];
+    if (V < 0 || F < 0 || E < 0 || Q < 0) { snprintf(msg, sizeof msg, "%s: negative size", fn); return fail_msg(msg); }
+    if ((long long)Q + E + F >= (1ll << 29)) { snprintf(msg, sizeof msg, "%s: mesh too large", fn); return fail_msg(msg); }
+    if (F > 0 && (V <= 0 || !verts || !faces || !edges || (Q > 0 && !pairs))) {
+        snprintf(msg, sizeof msg, "%s: required pointer is null", fn);
+        return fail_msg(msg);
+    }
+    if ((reinterpret_cast<uintptr_t>(pairs) & 15) || (reinterpret_cast<uintptr_t>(edges) & 7)) {
+        snprintf(msg, sizeof msg, "%s: pairs must be 16-byte and edges 8-byte aligned", fn);
+        return fail_msg(msg);
+    }
+    return 0;
+}
+
+int gsr_mesh_reg_forward(int V, int F, int E, int Q, const float* verts, const int* faces, const int* edges, const int* pairs,
+                         const float* ref_edge_len, const float* ref_area, float nc_factor, float edge_factor, float area_factor,
+                         void* workspace, float* loss_out, gsr_stream_t stream)
+{
+    g_err.clear();
+    if (int rc = mesh_reg_check("gsr_mesh_reg_forward", V, F, E, Q, verts, faces, edges, pairs)) return rc;
+    if (!workspace || !loss_out) return fail_msg("gsr_mesh_reg_forward: required pointer is null");
+    if (F == 0) E = Q = 0;
+    hipStream_t st = (hipStream_t)stream;
+    {
+        Scope sc(ST_LOSS, st);
+        launch_mesh_reg(F, E, Q, verts, faces, edges, pairs, ref_edge_len, ref_area, nc_factor, edge_factor, area_factor, workspace,
+                        loss_out, st);
+    }
+    GSR_CHECK_LAUNCH("mesh_reg forward kernels");
+    return 0;
+}
+
+int gsr_mesh_reg_backward(int V, int F, int E, int Q, const float* verts, const int* faces, const int* edges, const int* pairs,
+                          const int* csr_offsets, const int* csr_entries, const float* ref_edge_len, const float* ref_area,
+                          float nc_factor, float edge_factor, float area_factor, const float* grad_scale, float* dL_dverts,
+                          int accumulate, gsr_stream_t stream)
+{
+    g_err.clear();
+    if (int rc = mesh_reg_check("gsr_mesh_reg_backward", V, F, E, Q, verts, faces, edges, pairs)) return rc;
+    if (accumulate != 0 && accumulate != 1) return fail_msg("gsr_mesh_reg_backward: accumulate must be 0 or 1");
+    if (V == 0) return 0;
+    if (!csr_offsets || !csr_entries || !dL_dverts) return fail_msg("gsr_mesh_reg_backward: required pointer is null");
+    if (F == 0) E = Q = 0;
+    hipStream_t st = (hipStream_t)stream;
+    {
+        Scope sc(ST_LOSS, st);
+        launch_mesh_reg_grad(V, F, E, Q, verts, faces, edges, pairs, csr_offsets, csr_entries, ref_edge_len, ref_area, nc_factor,
+                             edge_factor, area_factor, grad_scale, dL_dverts, accumulate, st);
+    }
+    GSR_CHECK_LAUNCH("mesh_reg_bwd_kernel");
+    return 0;
+}
+
 int gsr_mark_visible(int P, const float* means3D, const float* viewmatrix, const float* projmatrix, uint8_t* present,
                      gsr_stream_t stream)
 {

@@ -350,6 +350,15 @@ void launch_rgb_depth_loss_grad(int C, int H, int W, const float* pred, const lo
                                 const float* scale, float* grad, const long long* gstr, float* dgrad, const long long* dgstr,
                                 hipStream_t st);
 
+// surface-mesh regularisers (gsr_mesh_reg.hip)
+size_t mesh_reg_workspace_bytes();
+void launch_mesh_reg(int F, int E, int Q, const float* verts, const int* faces, const int* edges, const int* pairs,
+                     const float* ref_edge, const float* ref_area, float nc_factor, float edge_factor, float area_factor,
+                     void* workspace, float* loss_out, hipStream_t st);
+void launch_mesh_reg_grad(int V, int F, int E, int Q, const float* verts, const int* faces, const int* edges, const int* pairs,
+                          const int* offsets, const int* entries, const float* ref_edge, const float* ref_area, float nc_factor,
+                          float edge_factor, float area_factor, const float* scale, float* grad, int accumulate, hipStream_t st);
+
 // Optional per-workgroup timeline for tuning (gsr_debug_set_trace): when non-null, the blend kernels store
 // {start, end} of every workgroup (100 MHz wall clock) at trace[2*blockIdx] (forward) / trace[2*(T+blockIdx)].
 extern uint64_t* g_trace;

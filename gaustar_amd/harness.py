@@ -216,6 +216,11 @@ class _RenderMeshBound(torch.autograd.Function):
         d_verts, d_rs, d_rc, d_dt, d_dr = producers._mesh_backward_raw(v, cfg["faces"], cfg["bary"], rs, rc, dr, cfg["lo"], cfg["hi"],
                                                                        has_dt, d_points, d_scaling, d_quats,
                                                                        out=(pre,) + o_mesh[1:] if cleared else o_mesh, verts_cleared=cleared)
+        # (SurfaceGaussians.rgbd_step(mesh_reg=...): the regulariser's vertex gradient lands in the same buffer, before a sink
+        # hears that the buffer is final)
+        hook = cfg.get("verts_grad_hook")
+        if hook is not None and d_verts is not None:
+            hook(d_verts)
         if sink is not None:
             sink.written([p for p, o in zip((p_verts, p_rs, p_rc, p_dt, p_dr), o_mesh) if o is not None and p is not None])
         # (sink views go back to autograd as FRESH tensor objects: AccumulateGrad adopts an incoming gradient as p.grad only
@@ -392,6 +397,16 @@ class SurfaceGaussians(nn.Module):
             return producers.points_rgb_from_directions(directions, sh, levels)
         raise ValueError("Either camera_centers or directions must be provided.")   # :703
 
+    @property
+    def surface_mesh(self):           # sugar_model.py:568-576 (without the vertex-colour texture)
+        from . import meshes
+        return meshes.Meshes(verts=[self._points], faces=[self._surface_mesh_faces])
+
+    def mesh_topology(self):
+        """meshes.MeshTopology of `_surface_mesh_faces` (built once per face tensor)."""
+        from . import meshes
+        return meshes.MeshTopology.of(self._surface_mesh_faces, int(self._points.shape[0]))
+
     # -------------------------------------------------------------------------------- rendering
     def _settings(self, camera: NerfCamera, bg: torch.Tensor, sh_degree: int):
         cam, view, proj, campos = camera.on_device(self.device)
@@ -514,14 +529,19 @@ class SurfaceGaussians(nn.Module):
 
     def rgbd_step(self, camera: NerfCamera, bg: torch.Tensor, gt_rgb: torch.Tensor, gt_depth: torch.Tensor, max_depth: float,
                   dssim_factor: float = 0.2, depth_factor: float = 1.0, mask_factor: float = 1.0, grad_scale: Optional[torch.Tensor] = None,
-                  sh_deg: Optional[int] = None):
+                  sh_deg: Optional[int] = None, mesh_reg: Optional[dict] = None):
         """One refinement iteration's render + image losses + backward WITHOUT an autograd graph: the 4-channel render of
         render_channels(depth_channels=1), losses.rgb_depth_loss on it and both backward passes, run back to back through the very
         functions the autograd path runs (the two Functions' forward / backward bodies, called directly); the parameters' `.grad`
         are set (added to, if present) exactly as `loss.backward()` would.  -> (loss, image, radii), all detached.
         For loops whose only loss is this one: what it takes out is host time -- two Function.apply, the engine's thread
         hand-off and graph walk, eight AccumulateGrad nodes -- about a third of an iteration's Python at config-C size, which
-        is what bounds the loop on a slow host (tools/window_phases.py).  grad_scale: a device scalar d(total)/d(loss), default 1."""
+        is what bounds the loop on a slow host (tools/window_phases.py).  grad_scale: a device scalar d(total)/d(loss), default 1.
+        mesh_reg: the surface-mesh regularisers of refine.py:676-706 as keyword arguments of losses.surface_mesh_loss
+        (nc_factor, ref_edge_len, edge_factor, ref_area, area_factor; `topology` defaults to mesh_topology()): their forward
+        and backward run in the same step, their vertex gradient is added to the mesh producer's in its own buffer, and the
+        returned loss is the image losses + their total -- what `(rgb_depth_loss(...) + surface_mesh_loss(...)).backward()`
+        gives.  None (default): the image losses alone, as before."""
         from . import losses as _losses
         with torch.no_grad():
             cfg = self._channels_cfg(camera, bg, sh_deg, 1, True)
@@ -529,6 +549,15 @@ class SurfaceGaussians(nn.Module):
                       self._delta_t if self._loose_bind else None, self._delta_r if self._loose_bind else None)
             rctx = _PlainCtx(tuple(p is not None and p.requires_grad for p in params) + (False,))
             image, radii = _RenderMeshBound.forward(rctx, *params, cfg)
+            if mesh_reg is not None:
+                kw = dict(mesh_reg)
+                topo = kw.pop("topology", None) or self.mesh_topology()
+                mctx = _PlainCtx((self._points.requires_grad,) + (False,) * 6)
+                reg_total, _reg_parts = _losses._SurfaceMeshLoss.forward(
+                    mctx, self._points, topo, float(kw.pop("nc_factor")), kw.pop("ref_edge_len", None), float(kw.pop("edge_factor", 0.0)),
+                    kw.pop("ref_area", None), float(kw.pop("area_factor", 0.0)))
+                if kw:
+                    raise TypeError(f"mesh_reg: unexpected keys {sorted(kw)}")
             lctx = _PlainCtx((True,) + (False,) * 7)
             loss, _parts = _losses._RGBDepthLoss.forward(lctx, image, gt_rgb, gt_depth, float(dssim_factor), None, float(max_depth),
                                                         float(depth_factor), float(mask_factor))
@@ -537,6 +566,10 @@ class SurfaceGaussians(nn.Module):
                 if one is None or one.device != image.device:
                     one = self._one_cache = torch.ones((), device=image.device)
                 grad_scale = one
+            if mesh_reg is not None:
+                loss = loss + reg_total
+                if mctx.saved_tensors:
+                    cfg["verts_grad_hook"] = lambda dv: _losses._SurfaceMeshLoss.grad_into(mctx, grad_scale, dv, 1)
             d_image = _losses._RGBDepthLoss.backward(lctx, grad_scale, None)[0]
             grads = _RenderMeshBound.backward(rctx, d_image, None)
             for p, g in zip(params, grads):

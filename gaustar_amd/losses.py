@@ -273,3 +273,96 @@ def rgb_depth_loss(render6: torch.Tensor, gt_rgb: torch.Tensor, gt_depth: torch.
                                       None if margin is None else tuple(margin), float(max_depth), float(depth_factor),
                                       float(mask_factor))
     return (loss, parts) if return_parts else loss
+
+
+def _mesh_reg_refs(ref, n, dev, what):
+    if ref is None:
+        return None
+    if ref.requires_grad:
+        raise NotImplementedError(f"gaustar_amd.losses: no gradient w.r.t. {what}")
+    r = ref.detach().to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
+    if r.numel() != n:
+        raise RuntimeError(f"{what} must hold {n} values, got {r.numel()}")
+    return r
+
+
+class _SurfaceMeshLoss(torch.autograd.Function):
+    """The three surface-mesh regularisers of refine.py:676-706 as ONE autograd node over the vertices.  Forward:
+    gsr_mesh_reg_forward (an element pass + a fixed-order reduction) -> {nc, edge, area, total} on the device.  Backward:
+    gsr_mesh_reg_backward, one vertex-major launch scaled by the incoming gradient on the device."""
+
+    @staticmethod
+    def forward(ctx, verts, topo, nc_factor, ref_edge_len, edge_factor, ref_area, area_factor):
+        lib = _lib.load()
+        if not verts.is_cuda:
+            raise RuntimeError("gaustar_amd.losses: verts must live on a HIP (cuda) device -- there is no CPU path")
+        if verts.dim() != 2 or verts.size(1) != 3 or int(verts.size(0)) != topo.V:
+            raise RuntimeError(f"verts must have dimensions ({topo.V}, 3), got {tuple(verts.shape)}")
+        dev = verts.device
+        if topo.device != dev:
+            raise RuntimeError("the mesh topology lives on another device than the vertices")
+        v = verts.detach()
+        if v.dtype != torch.float32 or not v.is_contiguous():
+            v = v.float().contiguous()
+        re = _mesh_reg_refs(ref_edge_len, topo.E, dev, "ref_edge_len")
+        ra = _mesh_reg_refs(ref_area, topo.F, dev, "ref_area")
+        cfg = (float(nc_factor), float(edge_factor), float(area_factor))
+        with _host.on_device(dev):
+            ws = torch.empty(lib.gsr_mesh_reg_workspace_bytes(topo.V, topo.F, topo.E, topo.Q), dtype=torch.uint8, device=dev)
+            out = torch.empty(4, dtype=torch.float32, device=dev)
+            _lib.check(lib.gsr_mesh_reg_forward(
+                topo.V, topo.F, topo.E, topo.Q, _vp(v), _vp(topo.faces), _vp(topo.edges), _vp(topo.pairs), _op(re), _op(ra), *cfg,
+                _vp(ws), _vp(out), _stream()), "gsr_mesh_reg_forward")
+        ctx.topo, ctx.cfg, ctx.in_dtype = topo, cfg, verts.dtype
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(v, re, ra)
+        ctx.mark_non_differentiable(out)
+        ctx.set_materialize_grads(False)
+        return out[3], out
+
+    @staticmethod
+    def grad_into(ctx, g_loss, dL_dverts, accumulate):
+        """gsr_mesh_reg_backward into dL_dverts [V,3] f32 (accumulate = 1: added to what is there, one rounding per element)."""
+        lib = _lib.load()
+        v, re, ra = ctx.saved_tensors
+        topo = ctx.topo
+        dev = v.device
+        if dL_dverts.dtype != torch.float32 or not dL_dverts.is_contiguous() or tuple(dL_dverts.shape) != tuple(v.shape) \
+                or dL_dverts.device != dev:
+            raise RuntimeError(f"dL_dverts must be a contiguous float32 ({topo.V}, 3) tensor on {dev}")
+        with _host.on_device(dev):
+            keep, sp = _scale_ptr(g_loss, dev)
+            _lib.check(lib.gsr_mesh_reg_backward(
+                topo.V, topo.F, topo.E, topo.Q, _vp(v), _vp(topo.faces), _vp(topo.edges), _vp(topo.pairs), _vp(topo.csr_offsets),
+                _vp(topo.csr_entries), _op(re), _op(ra), *ctx.cfg, sp, _vp(dL_dverts), int(accumulate), _stream()),
+                "gsr_mesh_reg_backward")
+        return dL_dverts
+
+    @staticmethod
+    def backward(ctx, g_loss, _g_parts):
+        if not ctx.saved_tensors or g_loss is None:
+            return (None,) * 7
+        v = ctx.saved_tensors[0]
+        grad = _SurfaceMeshLoss.grad_into(ctx, g_loss, torch.empty_like(v), 0)
+        return grad.to(ctx.in_dtype), None, None, None, None, None, None
+
+
+def _vp(t):
+    return ctypes.c_void_p(t.data_ptr())
+
+
+def _op(t):
+    return None if t is None else _vp(t)
+
+
+def surface_mesh_loss(verts: torch.Tensor, topology, nc_factor: float, ref_edge_len: Optional[torch.Tensor] = None,
+                      edge_factor: float = 0.0, ref_area: Optional[torch.Tensor] = None, area_factor: float = 0.0,
+                      return_parts: bool = False):
+    """nc_factor * mesh_normal_consistency(mesh) + edge_factor * ((edge_len - ref_edge_len)**2).mean()
+    + area_factor * (face_area - ref_area).abs().mean()  (refine.py:685-706) on verts [V,3] with the faces of `topology`
+    (gaustar_amd.meshes.MeshTopology; ref_edge_len in its edges_packed order).  A term whose factor is 0 or whose reference
+    is None is left out.  One fused HIP op each way, no host synchronisation; parts = the device vector {nc, edge, area,
+    total}."""
+    loss, parts = _SurfaceMeshLoss.apply(verts, topology, float(nc_factor), ref_edge_len, float(edge_factor), ref_area,
+                                         float(area_factor))
+    return (loss, parts) if return_parts else loss

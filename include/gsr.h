@@ -375,6 +375,35 @@ int gsr_rgb_depth_loss_backward(int C, int H, int W, const float* pred, long lon
                                 float* dL_dpred, long long grad_sc, long long grad_sy, long long grad_sx, float* dL_ddepth,
                                 long long dgrad_sy, long long dgrad_sx, gsr_stream_t stream);
 
+/* ---- Surface-mesh regularisers of a refinement iteration (gaustar_trainers/refine.py:676-706), fused.  Replaces
+ *   nc_factor * pytorch3d.loss.mesh_normal_consistency(mesh)                                   (refine.py:685-688)
+ * + edge_factor * ((|v0 - v1| over Meshes.edges_packed() - ref_edge_len)**2).mean()          (refine.py:690-696)
+ * + area_factor * (Meshes.faces_areas_packed() - ref_area).abs().mean()                       (refine.py:698-702)
+ * on ONE mesh: verts [V,3] f32.  The topology comes from the caller, built once per face tensor (gaustar_amd/meshes.py
+ * MeshTopology), all int32 and contiguous:
+ *   faces [F,3]; edges [E,2] (min, max) in pytorch3d's edges_packed() order; pairs [Q,4] = (e0, e1, a, b), one row per pair of
+ *   faces sharing an edge (e0, e1), a / b their corners not on it (16-byte aligned); csr_offsets [V+1], csr_entries: the
+ *   vertex-major incidence list, entry = element * 4 + role over the element index space pairs [0, Q), edges [Q, Q + E),
+ *   faces [Q + E, Q + E + F) (role: e0 e1 a b / v0 v1 / corner).
+ * A term whose factor is 0 or whose reference array (ref_edge_len [E], ref_area [F]) is NULL is skipped; a mesh without
+ * pairs has nc = 0.  Per pair: 1 - cosine_similarity(n0, n1) (torch, eps 1e-8), n0 = (e1 - e0) x (a - e0),
+ * n1 = -((e1 - e0) x (b - e0)), averaged over all pairs.  Face area 0.5 |(v1 - v0) x (v2 - v0)|.  Gradients at the
+ * non-differentiable points follow torch (d|x|/dx = 0 at 0, d|v|/dv = 0 at v = 0): a zero-area face contributes no area
+ * gradient.  How pytorch3d's own faces_areas_packed backward (a custom kernel) treats that case has not been checked.
+ * gsr_mesh_reg_forward: one element pass + one fixed-order reduction, loss_out [4] device floats = {nc, edge, area, total},
+ *   deterministic; workspace: gsr_mesh_reg_workspace_bytes(V, F, E, Q) bytes.  No host synchronisation.
+ * gsr_mesh_reg_backward: ONE vertex-major launch, no float atomics (bitwise reproducible): dL_dverts [V,3] receives
+ *   grad_scale[0] * d total / d verts (grad_scale a DEVICE scalar, NULL = 1) -- written, or with accumulate = 1 added to what
+ *   is there with one rounding per element (= torch's X + fresh), e.g. the vertex gradient gsr_mesh_gaussians_backward left. */
+size_t gsr_mesh_reg_workspace_bytes(int V, int F, int E, int Q);
+int gsr_mesh_reg_forward(int V, int F, int E, int Q, const float* verts, const int* faces, const int* edges, const int* pairs,
+                         const float* ref_edge_len, const float* ref_area, float nc_factor, float edge_factor, float area_factor,
+                         void* workspace, float* loss_out, gsr_stream_t stream);
+int gsr_mesh_reg_backward(int V, int F, int E, int Q, const float* verts, const int* faces, const int* edges, const int* pairs,
+                          const int* csr_offsets, const int* csr_entries, const float* ref_edge_len, const float* ref_area,
+                          float nc_factor, float edge_factor, float area_factor, const float* grad_scale, float* dL_dverts,
+                          int accumulate, gsr_stream_t stream);
+
 /* Tuning aid: when device_buffer is non-NULL (4*T uint64), the two blend kernels record the start/end wall
  * clock (100 MHz) of every workgroup: forward at [2*b], backward at [2*(T+b)], b = launch index.  NULL = off. */
 int gsr_debug_set_trace(void* device_buffer);

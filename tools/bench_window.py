@@ -8,8 +8,12 @@ frame, train_seq.py:101-244 / gaustar_trainers/refine.py:529-841) assembled from
                -> backward -> gaustar_amd.optim.Adam.step()
   between frames: the optimised parameters are kept (the tracker's warm start), the optimiser state is rebuilt.
 
-Not included (out of scope): mesh regularisers (pytorch3d), topology update (Open3D),
-flow warp.  Prints iterations/s over all frames and the loss at the start / end of every frame."""
+With --mesh-reg every iteration also carries the surface-mesh regularisers of refine.py:676-706 (normal consistency, edge
+and area isometry against the frame-0 mesh, train_seq.py:108-110's factors) through losses.surface_mesh_loss -- or, with
+--fused-step, through rgbd_step(mesh_reg=...).  Off by default.
+
+Not included (out of scope): topology update (Open3D), flow warp.  Prints iterations/s over all
+frames and the loss at the start / end of every frame."""
 import argparse, ctypes, gc, json, os, sys, time
 import numpy as np
 import torch
@@ -58,6 +62,13 @@ def run(a):
     frames, n_it, per_it = [], 0, []
     one = torch.ones((), device=dev)
     fused_step = bool(getattr(a, "fused_step", False))
+    mesh_reg = None
+    if getattr(a, "mesh_reg", False):   # (bench.py builds the namespace without this flag: off)
+        ref = model.surface_mesh
+        ve = ref.verts_packed().detach()[ref.edges_packed()]
+        mesh_reg = dict(topology=model.mesh_topology(), nc_factor=0.5, ref_edge_len=(ve[:, 0] - ve[:, 1]).norm(dim=1),
+                        edge_factor=1000.0, ref_area=ref.faces_areas_packed().detach(), area_factor=5000.0)
+        reg_kw = {k: v_ for k, v_ in mesh_reg.items() if k != "topology"}
     host_wait_ns = 0
     pts_start = model.points.detach().clone()
     t_total = 0.0
@@ -99,10 +110,12 @@ def run(a):
                 ci = gdist.shard_views(len(ncams), fi * a.iters + it, rank, world)
                 opt.zero_grad(set_to_none=True)
                 if fused_step:    # render + losses + both backward passes without an autograd graph (harness.SurfaceGaussians.rgbd_step)
-                    loss = model.rgbd_step(ncams[ci], bg4, gts[ci][0], gts[ci][1], MAX_DEPTH, 0.2, 1.0, 0.5)[0]
+                    loss = model.rgbd_step(ncams[ci], bg4, gts[ci][0], gts[ci][1], MAX_DEPTH, 0.2, 1.0, 0.5, mesh_reg=mesh_reg)[0]
                 else:
                     img = render(model, ncams[ci], bg4)
                     loss = losses.rgb_depth_loss(img, gts[ci][0], gts[ci][1], MAX_DEPTH, 0.2, 1.0, 0.5)
+                    if mesh_reg is not None:
+                        loss = loss + losses.surface_mesh_loss(model._points, mesh_reg["topology"], **reg_kw)
                     loss.backward(one)                 # (the seed is handed over: a bare backward() fills a ones_like per call, 4.5 us on the stream)
                 if reducer is not None:
                     reducer()                      # the hook in front of sugar_optimizer.py:99-101
@@ -142,6 +155,8 @@ def run(a):
     extra["plan_stats"] = dict(_rz.PLAN_STATS)
     if fused_step:
         extra["fused_step"] = True
+    if mesh_reg is not None:
+        extra["mesh_reg"] = True
     return {**extra, "gaussians": N, "image": [a.width, a.height], "cameras": len(ncams), "frames": frames, "iterations": n_it,
             "iterations_per_s": round(n_it / t_total, 1), "ms_per_iteration": round(t_total / n_it * 1e3, 3),
             # the steady state: median over all iterations of the time between their start marks on the stream (the wall
@@ -163,6 +178,8 @@ def main():
     ap.add_argument("--composed", action="store_true", help="render through the composition of autograd nodes instead of the one-node render")
     ap.add_argument("--fused-step", dest="fused_step", action="store_true",
                     help="render + losses + backward through SurfaceGaussians.rgbd_step (no autograd graph) instead of loss.backward()")
+    ap.add_argument("--mesh-reg", dest="mesh_reg", action="store_true",
+                    help="add the surface-mesh regularisers of refine.py:676-706 (normal consistency, edge / area isometry)")
     r = run(ap.parse_args())
     if gdist.rank() == 0:
         print(json.dumps(r))
