@@ -3,6 +3,7 @@
 491 520 mesh-bound surface Gaussians (config C), one view per GPU per step.
 
     python bench.py --gpus 1 --steps 40 --warmup 5
+    python bench.py --gpus 1 --steps 40 --warmup 5 --full      # + every other figure (see below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -13,14 +14,20 @@ gradient reduce-scatter / rank-sharded Adam / parameter all-gather over RCCL tha
 sugar_optimizer.py:99-101 steps Adam) -- see build_refinement_workload.  Rank r renders camera
 (step * N + r) mod 160 of the rig -- views shard, nothing else is exchanged.
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+Rank 0 prints ONE JSON line.  A plain run does what its headline needs and no more: set-up, warm-up,
+the planning pass, the R timed regions of K steps (at N = 1 the pipelined regions interleaved with
+the one-view-at-a-time ones, single_pipeline), --dump-outputs, the line.  With --full the line
+also carries every other figure, each from runs of its own after the headline regions:
   roofline      dominant kernel (the one with the largest summed time), algorithmic bytes per launch
                 (SURVEY.md 8d per-unit figures x the units the launch processed) / its mean launch
                 duration, measured with HIP events on the launch stream in a second, instrumented
                 pass over the same K steps (gsr_profile_*), plus per-kernel means for every stage;
+  exact_binning, reference_caller   the same K steps without plans / driven as the reference's caller;
   cpu_baseline  the C oracle (oracle/gsr_oracle.c, a port of the reference algorithm -- the
                 reference has no CPU path) timed on the host cores on a bounded sample: the first
-                few views of the same workload at full size.  N = 1 / rank 0 only.
+                few views of the same workload at full size.  N = 1 / rank 0 only;
+  other_configs, scale_base, ref_gpu_baseline, window, parity, roofline.issue   (N = 1, unless --no-extras);
+  same_step_on_one_gpu   (N > 1) the refinement step without any exchange, timed before the headline.
 
 --dump-outputs DIR writes what the timed path handed its caller in the last step of its last timed
 region (image, radii, gradients) as DIR/<name>.npy (see write_outputs); the inputs are seeded, so two
@@ -558,8 +565,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=160)   # one pass over the 160-camera rig
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the window / reference-GPU / issue-statistics legs (N = 1 only)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure everything else the line can carry (other modes and configs, roofline, "
+                         "CPU and reference baselines, parity); a plain run times the headline only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="--full: skip the other-config / window / reference-GPU / issue-statistics legs (N = 1 only)")
     ap.add_argument("--repeats", type=int, default=5,
                     help="the K-step timed region is run this many times back to back (modes interleaved); the MEDIAN is reported")
     ap.add_argument("--scale-step", action="store_true",
@@ -607,15 +618,16 @@ def main():
     keep = LastStep(args.steps) if args.dump_outputs else None
     arm = lambda mode: None if keep is None else setattr(keep, "armed", mode)   # (which headline region's last step to keep)
     if world > 1:
-        # the SAME step without any exchange, every rank on its own GPU at once: the single-GPU denominator of this step's
-        # scaling (the N = 1 line of this script times the rasterizer alone, which is what the metric is quoted on)
-        solo_w = build_refinement_workload(device, rank, gs, cams, bg, communicate=False)
-        solo_step = lambda s: refinement_step(s, rank, world, *solo_w)
-        for s in range(5):
-            solo_step(s)
-        n_solo = max(10, min(args.steps, 40))
-        same_step_1gpu_ms = med([timed(solo_step, n_solo, world, device) for _ in range(3)]) / n_solo * 1e3
-        solo_w[2].close(); del solo_w, solo_step
+        if args.full:
+            # the SAME step without any exchange, every rank on its own GPU at once: the single-GPU denominator of this step's
+            # scaling (the N = 1 line of this script times the rasterizer alone, which is what the metric is quoted on)
+            solo_w = build_refinement_workload(device, rank, gs, cams, bg, communicate=False)
+            solo_step = lambda s: refinement_step(s, rank, world, *solo_w)
+            for s in range(5):
+                solo_step(s)
+            n_solo = max(10, min(args.steps, 40))
+            same_step_1gpu_ms = med([timed(solo_step, n_solo, world, device) for _ in range(3)]) / n_solo * 1e3
+            solo_w[2].close(); del solo_w, solo_step
         refine = build_refinement_workload(device, rank, gs, cams, bg)
         step = lambda s: refinement_step(s, rank, world, *refine, keep=keep)
     elif scale_step:
@@ -725,10 +737,11 @@ def main():
                       "arrays": write_outputs(args.dump_outputs, keep.taken[mode])}
         keep.taken.clear()
     plan_stats = {k: rz_plan.PLAN_STATS[k] - plan_stats0[k] for k in plan_stats0}
+    # The headline's figures are complete here; what follows runs under --full only.
     # the same K steps with planning switched off (every view: scan + scatter + the host round trip between the stages), one
     # view at a time, median of 3 regions -- what the planned figures above are to be compared with
     exact_binning = None
-    if world == 1 and not scale_step and rz_plan._PLANNED:
+    if args.full and world == 1 and not scale_step and rz_plan._PLANNED:
         rz_plan._PLANNED = False
         try:
             dts_x = [timed(step, args.steps, world, device) for _ in range(3)]
@@ -742,7 +755,7 @@ def main():
     # task 1).  Its `.cuda()` uploads synchronise the stream, so the host never runs ahead here -- that is the caller's cost,
     # the same with plans (`planned`) and without (`exact`); the pair shows what the plans give THIS caller.
     reference_caller = None
-    if world == 1 and not scale_step:
+    if args.full and world == 1 and not scale_step:
         try:
             prepare_reference_caller(cams)
             bg_t_rc = rasters[0].raster_settings.bg
@@ -796,33 +809,99 @@ def main():
         except Exception as ex:
             reference_caller = {"error": repr(ex)[:300]}
 
-    # instrumented pass: per-kernel HIP-event durations over the same K steps (rank 0's launches)
-    nst = lib.gsr_num_stages()
-    names = [lib.gsr_stage_name(i).decode() for i in range(nst)]
-    ms = (ctypes.c_float * nst)()
-    cnt = (ctypes.c_int * nst)()
-    lib.gsr_profile_enable(1)
-    # (under --scale-step / N > 1 the brackets see the same six rasterizer kernels; the untimed first steps' brackets are dropped)
-    dt_prof = timed(step, args.steps, world, device, on_timed_start=lambda: lib.gsr_profile_read(ms, cnt, 1))
-    _lib.check(lib.gsr_profile_read(ms, cnt, 1), "gsr_profile_read")
-    lib.gsr_profile_enable(0)
+    if args.full:
+        # instrumented pass: per-kernel HIP-event durations over the same K steps (rank 0's launches)
+        nst = lib.gsr_num_stages()
+        names = [lib.gsr_stage_name(i).decode() for i in range(nst)]
+        ms = (ctypes.c_float * nst)()
+        cnt = (ctypes.c_int * nst)()
+        lib.gsr_profile_enable(1)
+        # (under --scale-step / N > 1 the brackets see the same six rasterizer kernels; the untimed first steps' brackets are dropped)
+        dt_prof = timed(step, args.steps, world, device, on_timed_start=lambda: lib.gsr_profile_read(ms, cnt, 1))
+        _lib.check(lib.gsr_profile_read(ms, cnt, 1), "gsr_profile_read")
+        lib.gsr_profile_enable(0)
 
-    # num_rendered of the views this rank rendered (for the algorithmic byte count)
-    from gaustar_amd import rasterizer as rz
-    R_list = []
-    for s in range(min(args.steps, len(rasters))):
-        rs = rasters[(s * world + rank) % len(rasters)].raster_settings
-        e = torch.Tensor([])
-        out = rz.rasterize_gaussians_native(rs.bg, params["means3D"].detach(), params["colors"].detach(),
-                                            params["opacities"].detach(), params["scales"].detach(),
-                                            params["rotations"].detach(), 1.0, e, rs.viewmatrix, rs.projmatrix,
-                                            rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, e, 0, rs.campos,
-                                            False, False, use_plan=False)   # (a planned view returns its plan's CAPACITY)
-        R_list.append(out[0])
-    R_mean = float(np.mean(R_list))
+        # num_rendered of the views this rank rendered (for the algorithmic byte count)
+        from gaustar_amd import rasterizer as rz
+        R_list = []
+        for s in range(min(args.steps, len(rasters))):
+            rs = rasters[(s * world + rank) % len(rasters)].raster_settings
+            e = torch.Tensor([])
+            out = rz.rasterize_gaussians_native(rs.bg, params["means3D"].detach(), params["colors"].detach(),
+                                                params["opacities"].detach(), params["scales"].detach(),
+                                                params["rotations"].detach(), 1.0, e, rs.viewmatrix, rs.projmatrix,
+                                                rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, e, 0, rs.campos,
+                                                False, False, use_plan=False)   # (a planned view returns its plan's CAPACITY)
+            R_list.append(out[0])
+        R_mean = float(np.mean(R_list))
 
     if rank == 0:
         W, H = cams[0].W, cams[0].H
+        out = {
+            "metric": "views/sec fwd+bwd @1920x1080, 500k Gaussians; HBM GB/s vs roofline",
+            "value": round(value, 2), "unit": "views/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f32", "data": "synthetic",
+            "config": {"workload": "config C: 491520 mesh-bound surface Gaussians (icosphere level 6, 6/face), "
+                                   "160-camera rig @1920x1080, colours precomputed (M=0), one view per GPU per step, "
+                                   "fwd+bwd" + ((", inside one refinement step per rank on the reference loop's parameters: mesh + SH "
+                                                 "producers fwd/bwd, reduce-scatter of the %.0f MB of gradients from autograd hooks, Adam on "
+                                                 "this rank's 1/N of the parameters, all-gather of the parameters (dist.ShardedAdam)"
+                                                 % (refine[2].payload_bytes() / 1e6)) if world > 1 else ""),
+                       "gaussians": gs.P, "width": W, "height": H, "views_per_step": world,
+                       "parallelism": f"view-parallel x{world}",
+                       "views_in_flight": V,
+                       "value_definition": (
+                           ("MEDIAN over %d back-to-back timed regions of K = %d steps each, views per second; " % (R, args.steps)) +
+                           ("a step = one complete forward + backward of one 1080p view of config C through the public API; "
+                            if not (scale_step or world > 1) else
+                            "a step = one whole refinement step per rank (mesh + SH producers, rasterizer forward + backward, their "
+                            "backward, sharded Adam) on one view per rank; ") +
+                           (("%d independent views in flight on one GPU (host thread + HIP stream each) -- a sweep / evaluation / "
+                             "V-views-per-optimiser-step schedule; the reference's one-view-then-Adam loop (refine.py:538-548) has no "
+                             "independent views: for it read single_pipeline (same K steps, one view at a time) and window (--full)" % V)
+                            if V > 1 else "one view at a time per GPU") +
+                           "; steady state of the rig: every camera has been rendered before and its views are binned by its plan "
+                           "(config.binning; exact_binning, --full = the same steps without plans)"),
+                       "value_spread": value_spread,
+                       "pipelines": (f"{V} independent view pipelines on the GPU (host thread + HIP stream + leaf tensors each, "
+                                     "gaustar_amd.pipelines): step s = one complete forward + backward of view s on pipeline s % "
+                                     f"{V}; the small kernels of one view run under the blends of another") if V > 1 else "one view at a time"},
+        }
+        out["config"]["host_cpus_pinned"] = len(pinned)
+        out["config"]["binning"] = {
+            "planned_views": plan_stats["planned"], "exact_views": plan_stats["exact"], "misfits": plan_stats["misfit"],
+            "what": "views of the timed regions binned by their camera's plan (no scan, no scatter: include/gsr.h gsr_forward_planned) / "
+                    "rendered the exact way (no valid plan: longest list above 2 032 entries) / that outgrew their plan; every camera "
+                    "was rendered once, untimed, before the timed regions (its first view leaves the plan)"}
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
+        if single is not None:
+            out["single_pipeline"] = single
+        # how long the host sat in the forward's one synchronisation per step (gsr_debug_host_wait): the slack between the
+        # host's own work (Python, autograd, launches) and the GPU's -- near zero means the step is host-bound
+        # (accumulated over the R pipelined repeats and over the V pipeline threads: per pipeline, a thread waits this long
+        # for every view IT renders -- 1 / V of the steps)
+        n_timed = max(int(waits.value), 1)   # forward calls that went through the synchronisation = views rendered
+        out["host"] = {"wait_ms_per_view_per_pipeline": round(wait_ns.value / 1e6 / n_timed, 4),
+                       "wait_ms_per_step": round(wait_ns.value / 1e6 / n_timed / max(V, 1), 4),
+                       "views_counted": int(waits.value), "pipelines": V,
+                       "what": "time the host threads sat in the forward's one synchronisation (gsr_debug_host_wait); "
+                               "wait_ms_per_step = total / steps / pipelines: the share of a step's wall time a pipeline's host thread "
+                               "had nothing to do but wait for its GPU work"}
+        if scale_step:
+            out["config"]["scale_step"] = True
+            out["config"]["workload"] += (", inside one refinement step (mesh + SH producers fwd/bwd, Adam on the reference loop's "
+                                          "%.0f MB of parameters): the step `--gpus N` times, here on one GPU" % (refine[2].payload_bytes() / 1e6))
+        if world > 1:
+            out["config"]["exchange"] = "reduce-scatter + rank-sharded Adam + all-gather"
+            out["config"]["exchange_payload_MB"] = round(refine[2].payload_bytes() / 1e6, 1)
+            out["config"]["optimizer_state_MB_per_rank"] = round(refine[2].state_bytes_per_rank() / 1e6, 1)
+            out["config"]["buckets_issued_during_backward"] = refine[2].issued_early
+
+    # --full: what the runs after the headline measured, then the legs that take runs of their own
+    if rank == 0 and args.full:
+        out["config"]["num_rendered_mean"] = R_mean
         total_b, per_kernel_b = algorithmic_bytes(gs.P, R_mean, W, H)
         kern = {}
         for i, nme in enumerate(names):
@@ -868,55 +947,14 @@ def main():
             except Exception:
                 traffic, valu = None, None
         path_gbs = total_b / (ms_per_step * 1e-3) / 1e9 if world == 1 else total_b * world / (ms_per_step * 1e-3) / 1e9
-        out = {
-            "metric": "views/sec fwd+bwd @1920x1080, 500k Gaussians; HBM GB/s vs roofline",
-            "value": round(value, 2), "unit": "views/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
-            "config": {"workload": "config C: 491520 mesh-bound surface Gaussians (icosphere level 6, 6/face), "
-                                   "160-camera rig @1920x1080, colours precomputed (M=0), one view per GPU per step, "
-                                   "fwd+bwd" + ((", inside one refinement step per rank on the reference loop's parameters: mesh + SH "
-                                                 "producers fwd/bwd, reduce-scatter of the %.0f MB of gradients from autograd hooks, Adam on "
-                                                 "this rank's 1/N of the parameters, all-gather of the parameters (dist.ShardedAdam)"
-                                                 % (refine[2].payload_bytes() / 1e6)) if world > 1 else ""),
-                       "gaussians": gs.P, "width": W, "height": H, "views_per_step": world,
-                       "num_rendered_mean": R_mean, "parallelism": f"view-parallel x{world}",
-                       "views_in_flight": V,
-                       "value_definition": (
-                           ("MEDIAN over %d back-to-back timed regions of K = %d steps each, views per second; " % (R, args.steps)) +
-                           ("a step = one complete forward + backward of one 1080p view of config C through the public API; "
-                            if not (scale_step or world > 1) else
-                            "a step = one whole refinement step per rank (mesh + SH producers, rasterizer forward + backward, their "
-                            "backward, sharded Adam) on one view per rank; ") +
-                           (("%d independent views in flight on one GPU (host thread + HIP stream each) -- a sweep / evaluation / "
-                             "V-views-per-optimiser-step schedule; the reference's one-view-then-Adam loop (refine.py:538-548) has no "
-                             "independent views: for it read single_pipeline (same K steps, one view at a time) and window" % V)
-                            if V > 1 else "one view at a time per GPU") +
-                           "; steady state of the rig: every camera has been rendered before and its views are binned by its plan "
-                           "(config.binning; exact_binning = the same steps without plans)"),
-                       "value_spread": value_spread,
-                       "pipelines": (f"{V} independent view pipelines on the GPU (host thread + HIP stream + leaf tensors each, "
-                                     "gaustar_amd.pipelines): step s = one complete forward + backward of view s on pipeline s % "
-                                     f"{V}; the small kernels of one view run under the blends of another") if V > 1 else "one view at a time"},
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(ach / HBM_PEAK_GBS, 5), "traffic": traffic, "valu": valu,
-                         "path_alg_bytes_per_view": int(total_b), "path_achieved": round(path_gbs, 1),
-                         "path_frac": round(path_gbs / HBM_PEAK_GBS / world, 5),
-                         "instrumented_ms_per_step": round(dt_prof / args.steps * 1e3, 4), "kernels": kern,
-                         "kernels_measured": "one view at a time (a kernel's duration under another view's kernels is not its own)"},
-        }
-        out["config"]["host_cpus_pinned"] = len(pinned)
-        out["config"]["binning"] = {
-            "planned_views": plan_stats["planned"], "exact_views": plan_stats["exact"], "misfits": plan_stats["misfit"],
-            "what": "views of the timed regions binned by their camera's plan (no scan, no scatter: include/gsr.h gsr_forward_planned) / "
-                    "rendered the exact way (no valid plan: longest list above 2 032 entries) / that outgrew their plan; every camera "
-                    "was rendered once, untimed, before the timed regions (its first view leaves the plan)"}
+        out["roofline"] = {"bound": "hbm", "kernel": dom, "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                           "frac": round(ach / HBM_PEAK_GBS, 5), "traffic": traffic, "valu": valu,
+                           "path_alg_bytes_per_view": int(total_b), "path_achieved": round(path_gbs, 1),
+                           "path_frac": round(path_gbs / HBM_PEAK_GBS / world, 5),
+                           "instrumented_ms_per_step": round(dt_prof / args.steps * 1e3, 4), "kernels": kern,
+                           "kernels_measured": "one view at a time (a kernel's duration under another view's kernels is not its own)"}
         if exact_binning is not None:
             out["exact_binning"] = exact_binning
-        if dumped is not None:
-            out["dumped_outputs"] = dumped
-        if single is not None:
-            out["single_pipeline"] = single
         if reference_caller is not None:
             out["reference_caller"] = reference_caller
         # The conservative figures, inside `config` (the driver's record keeps `config` and `roofline`, not the extra keys):
@@ -961,26 +999,7 @@ def main():
                 out["roofline"]["issue"] = iss
             except Exception as ex:   # statistics only
                 out["roofline"]["issue"] = {"error": repr(ex)[:200]}
-        # how long the host sat in the forward's one synchronisation per step (gsr_debug_host_wait): the slack between the
-        # host's own work (Python, autograd, launches) and the GPU's -- near zero means the step is host-bound
-        # (accumulated over the R pipelined repeats and over the V pipeline threads: per pipeline, a thread waits this long
-        # for every view IT renders -- 1 / V of the steps)
-        n_timed = max(int(waits.value), 1)   # forward calls that went through the synchronisation = views rendered
-        out["host"] = {"wait_ms_per_view_per_pipeline": round(wait_ns.value / 1e6 / n_timed, 4),
-                       "wait_ms_per_step": round(wait_ns.value / 1e6 / n_timed / max(V, 1), 4),
-                       "views_counted": int(waits.value), "pipelines": V,
-                       "what": "time the host threads sat in the forward's one synchronisation (gsr_debug_host_wait); "
-                               "wait_ms_per_step = total / steps / pipelines: the share of a step's wall time a pipeline's host thread "
-                               "had nothing to do but wait for its GPU work"}
-        if scale_step:
-            out["config"]["scale_step"] = True
-            out["config"]["workload"] += (", inside one refinement step (mesh + SH producers fwd/bwd, Adam on the reference loop's "
-                                          "%.0f MB of parameters): the step `--gpus N` times, here on one GPU" % (refine[2].payload_bytes() / 1e6))
         if world > 1:
-            out["config"]["exchange"] = "reduce-scatter + rank-sharded Adam + all-gather"
-            out["config"]["exchange_payload_MB"] = round(refine[2].payload_bytes() / 1e6, 1)
-            out["config"]["optimizer_state_MB_per_rank"] = round(refine[2].state_bytes_per_rank() / 1e6, 1)
-            out["config"]["buckets_issued_during_backward"] = refine[2].issued_early
             # `value` / N x this = speed-up of THIS step over one GPU running it without any exchange (max over ranks, measured
             # in this very job); the N = 1 line's value is the rasterizer alone and is not the denominator of this step
             out["same_step_on_one_gpu"] = {"ms_per_step": round(same_step_1gpu_ms, 4),
@@ -1041,6 +1060,7 @@ def main():
             out["config"]["conservative"]["parity_flips_per_view_median"] = (p_.get("flips_per_view") or {}).get("median") \
                 if isinstance(p_.get("flips_per_view"), dict) else p_.get("flips_per_view_median")
             out["config"]["conservative"]["parity_flip_kinds"] = p_.get("flip_kinds")
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:
         tdist.barrier()

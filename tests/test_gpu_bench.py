@@ -1,6 +1,6 @@
 """GPU: the one-line contract of bench.py at N = 1 as the driver runs it (reduced step counts): metric / unit / config names of
-BASELINE.json, medians over interleaved repeats with their spread, the like-for-like single-pipeline figure, roofline and
-(without --no-extras) the other single-GPU configs with their own roofline."""
+BASELINE.json, medians over interleaved repeats with their spread, the like-for-like single-pipeline figure; with --full the
+roofline and (without --no-extras) the other single-GPU configs with their own roofline."""
 import json
 import os
 import subprocess
@@ -23,7 +23,7 @@ def _bench(*args):
 
 
 def test_bench_line_at_one_gpu():
-    d = _bench("--steps", "6", "--warmup", "2", "--repeats", "3", "--no-cpu-baseline", "--no-extras")
+    d = _bench("--steps", "6", "--warmup", "2", "--repeats", "3", "--full", "--no-cpu-baseline", "--no-extras")
     base = json.load(open(os.path.join(ROOT, "BASELINE.json")))
     assert d["metric"].replace("x", "×") == base["metric"] or d["metric"] == base["metric"].replace("×", "x")
     assert d["unit"] == "views/s" and d["n_gpus"] == 1 and d["steps"] == 6 and d["warmup"] == 2 and d["higher_is_better"] is True
@@ -57,11 +57,15 @@ def test_bench_line_at_one_gpu():
 
 def test_bench_dump_outputs(tmp_path):
     """--dump-outputs DIR: the image, radii and the six gradients of the last timed step (camera K - 1 of the rig), float32,
-    at most 64 MB; --steps sets the timed steps and ms_per_step is in the line."""
+    at most 64 MB; --steps sets the timed steps and ms_per_step is in the line.  A plain run (no --full) carries the headline
+    and none of the legs that take runs of their own."""
     import numpy as np
     out = str(tmp_path / "outputs")
-    d = _bench("--steps", "3", "--warmup", "1", "--repeats", "1", "--no-cpu-baseline", "--no-extras", "--dump-outputs", out)
+    d = _bench("--steps", "3", "--warmup", "1", "--repeats", "1", "--dump-outputs", out)
     assert d["steps"] == 3 and d["ms_per_step"] > 0.0
+    assert d["unit"] == "views/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert abs(d["value"] * d["ms_per_step"] / 1e3 - 1.0) < 1e-3 and d["single_pipeline"]["repeats"] == 1
+    assert not set(d) & {"roofline", "exact_binning", "reference_caller", "cpu_baseline", "other_configs", "window", "parity"}
     info = d["dumped_outputs"]
     assert info["step"] == 2 and info["camera"] == 2 and info["mode"] == "pipelines" and info["dir"] == out
     P = 491520
@@ -78,7 +82,7 @@ def test_bench_dump_outputs(tmp_path):
 
 
 def test_bench_other_configs_leg():
-    """`other_configs` (B, D, D-depth: BASELINE.json configs[1] and configs[3]) and `scale_base` ride in the default N = 1 line."""
+    """`other_configs` (B, D, D-depth: BASELINE.json configs[1] and configs[3]) and `scale_base` ride in the N = 1 line of --full."""
     import bench
     import torch
     from gaustar_amd import _lib

@@ -139,7 +139,7 @@ def _torchrun(script_args, env_extra, timeout=900):
 def test_bench_two_ranks_over_gloo():
     """bench.py --gpus 2 as the driver launches it (torch.distributed.run, one rank per process), the two ranks sharing
     this box's GPU over gloo: one JSON line from rank 0, aggregate views/s over both ranks, weak scaling."""
-    d = _torchrun(["bench.py", "--gpus", "2", "--steps", "8", "--warmup", "2", "--no-cpu-baseline"], {})
+    d = _torchrun(["bench.py", "--gpus", "2", "--steps", "8", "--warmup", "2", "--full", "--no-cpu-baseline"], {})
     assert d["n_gpus"] == 2 and d["steps"] == 8 and d["scaling"] == "weak" and d["value"] > 0
     assert d["config"]["views_per_step"] == 2 and "roofline" in d
     # the exchange is the reference loop's REAL optimiser payload, produced by the harness's producers' backward (SURVEY.md

@@ -17,7 +17,7 @@ for N in 2 4 8; do
   PORT=$((PORT + 1))
   echo "== bench.py --gpus $N --steps 10"
   timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $PORT bench.py \
-      --gpus $N --steps 10 --warmup 3 > "$OUT/bench_n$N.json" 2> "$OUT/bench_n$N.err"; echo "rc=$?"
+      --gpus $N --steps 10 --warmup 3 --full > "$OUT/bench_n$N.json" 2> "$OUT/bench_n$N.err"; echo "rc=$?"
   PORT=$((PORT + 1))
   python - "$OUT/bench_n$N.json" <<'PY'
 import json, sys
