@@ -104,6 +104,19 @@ SIGNATURES = {
                                      c_float, c_float, c_float, c_void_p, c_void_p, c_void_p]),
     "gsr_mesh_reg_backward": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_float, c_float, c_float, c_void_p, c_void_p, c_int, c_void_p]),
+    # rig-wide topology-error detection (refined_mesh.py:697-920): gaustar_amd.topology
+    "gsr_topo_view_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "gsr_topo_view": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, POINTER(c_double), c_void_p,
+                              c_void_p, c_void_p]),
+    "gsr_topo_aggregate": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_double, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                   c_void_p]),
+    "gsr_topo_propagate": (c_int, [c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p]),
+    "gsr_topo_voxel_keys": (c_int, [c_int, c_void_p, c_void_p, c_double, c_void_p, c_void_p, c_void_p]),
+    "gsr_topo_voxel_workspace_bytes": (c_size_t, [c_int]),
+    "gsr_topo_voxel_interp": (c_int, [c_int, c_void_p, c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p]),
+    "gsr_topo_faces": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gsr_adam_step": (c_int, [c_longlong, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_double, c_double, c_int,
                               c_void_p]),
     "gsr_adam_step_multi": (c_int, [c_int, POINTER(c_longlong), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),

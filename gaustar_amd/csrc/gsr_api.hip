@@ -1241,6 +1241,103 @@ int gsr_mesh_reg_backward(int V, int F, int E, int Q, const float* verts, const 
     return 0;
 }
 
+size_t gsr_topo_view_workspace_bytes(int H, int W)
+{
+    (void)H; (void)W;   // (the partial maxima of a fixed number of workgroups, whatever the image)
+    return topo_view_workspace_bytes();
+}
+
+int gsr_topo_view(int H, int W, int V, const float* verts, const float* depth_gt, const float* render_depth,
+                  const float* surface_depth, float max_depth, const double* cam, void* workspace, float* row, gsr_stream_t stream)
+{
+    g_err.clear();
+    if (H <= 0 || W <= 0 || V < 0) return fail_msg("gsr_topo_view: sizes must be positive");
+    if ((long long)H * W >= (1ll << 31)) return fail_msg("gsr_topo_view: image too large");
+    if (!depth_gt || !render_depth || !surface_depth || !cam || !workspace || (V > 0 && (!verts || !row)))
+        return fail_msg("gsr_topo_view: required pointer is null");
+    launch_topo_view(H, W, V, verts, depth_gt, render_depth, surface_depth, max_depth, cam, workspace, row, (hipStream_t)stream);
+    GSR_CHECK_LAUNCH("topo view kernels");
+    return 0;
+}
+
+int gsr_topo_aggregate(int C, int V, const float* table, const float* verts, const float* ymin, double depth_scalar,
+                       int min_observe, int detect_floor, double* value, int* count, unsigned char* valid, gsr_stream_t stream)
+{
+    g_err.clear();
+    if (C < 0 || V < 0) return fail_msg("gsr_topo_aggregate: negative size");
+    if (V == 0) return 0;
+    if ((C > 0 && !table) || !verts || !value || !count || !valid || (detect_floor && !ymin))
+        return fail_msg("gsr_topo_aggregate: required pointer is null");
+    launch_topo_aggregate(C, V, table, verts, ymin, depth_scalar, min_observe, detect_floor != 0, value, count, valid,
+                          (hipStream_t)stream);
+    GSR_CHECK_LAUNCH("topo_aggregate_kernel");
+    return 0;
+}
+
+int gsr_topo_propagate(int V, const int* nbr_offsets, const int* nbr, int sweeps, const double* value_in,
+                       const unsigned char* valid_in, double* value_out, double* value_tmp, unsigned char* valid_a,
+                       unsigned char* valid_b, gsr_stream_t stream)
+{
+    g_err.clear();
+    if (V < 0 || sweeps < 0) return fail_msg("gsr_topo_propagate: negative size");
+    if (V == 0) return 0;
+    if (!value_in || !value_out) return fail_msg("gsr_topo_propagate: required pointer is null");
+    hipStream_t st = (hipStream_t)stream;
+    if (sweeps == 0) {
+        GSR_CHECK(hipMemcpyAsync(value_out, value_in, sizeof(double) * V, hipMemcpyDeviceToDevice, st));
+        return 0;
+    }
+    if (!nbr_offsets || !nbr || !valid_in || !value_tmp || !valid_a || !valid_b)
+        return fail_msg("gsr_topo_propagate: required pointer is null");
+    launch_topo_propagate(V, nbr_offsets, nbr, sweeps, value_in, valid_in, value_out, value_tmp, valid_a, valid_b, st);
+    GSR_CHECK_LAUNCH("topo_propagate_kernel");
+    return 0;
+}
+
+int gsr_topo_voxel_keys(int V, const float* verts, const float* vmin, double voxel_size, long long* keys, int* flags,
+                        gsr_stream_t stream)
+{
+    g_err.clear();
+    if (V < 0) return fail_msg("gsr_topo_voxel_keys: negative size");
+    if (!(voxel_size > 0.0)) return fail_msg("gsr_topo_voxel_keys: voxel_size must be positive");
+    if (V == 0) return 0;
+    if (!verts || !vmin || !keys || !flags) return fail_msg("gsr_topo_voxel_keys: required pointer is null");
+    launch_topo_voxel_keys(V, verts, vmin, voxel_size, keys, flags, (hipStream_t)stream);
+    GSR_CHECK_LAUNCH("topo_voxel_key_kernel");
+    return 0;
+}
+
+size_t gsr_topo_voxel_workspace_bytes(int V) { return V > 0 ? topo_voxel_workspace_bytes(V) : 0; }
+
+int gsr_topo_voxel_interp(int V, const float* verts, const float* vmin, double voxel_size, const long long* sorted_keys,
+                          const long long* order, const long long* voxel_id, const double* value, void* workspace,
+                          double* voxel_value, double* out, gsr_stream_t stream)
+{
+    g_err.clear();
+    if (V < 0) return fail_msg("gsr_topo_voxel_interp: negative size");
+    if (!(voxel_size > 0.0)) return fail_msg("gsr_topo_voxel_interp: voxel_size must be positive");
+    if (V == 0) return 0;
+    if (!verts || !vmin || !sorted_keys || !order || !voxel_id || !value || !workspace || !voxel_value || !out)
+        return fail_msg("gsr_topo_voxel_interp: required pointer is null");
+    if (reinterpret_cast<uintptr_t>(workspace) & 15) return fail_msg("gsr_topo_voxel_interp: workspace must be 16-byte aligned");
+    launch_topo_voxel_interp(V, verts, vmin, voxel_size, sorted_keys, order, voxel_id, value, workspace, voxel_value, out,
+                             (hipStream_t)stream);
+    GSR_CHECK_LAUNCH("topo voxel kernels");
+    return 0;
+}
+
+int gsr_topo_faces(int F, const int* faces, const double* value, unsigned char* face_colour, float* face_loss,
+                   gsr_stream_t stream)
+{
+    g_err.clear();
+    if (F < 0) return fail_msg("gsr_topo_faces: negative size");
+    if (F == 0) return 0;
+    if (!faces || !value || !face_colour || !face_loss) return fail_msg("gsr_topo_faces: required pointer is null");
+    launch_topo_faces(F, faces, value, face_colour, face_loss, (hipStream_t)stream);
+    GSR_CHECK_LAUNCH("topo_face_kernel");
+    return 0;
+}
+
 int gsr_mark_visible(int P, const float* means3D, const float* viewmatrix, const float* projmatrix, uint8_t* present,
                      gsr_stream_t stream)
 {

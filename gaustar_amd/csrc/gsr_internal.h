@@ -359,6 +359,22 @@ void launch_mesh_reg_grad(int V, int F, int E, int Q, const float* verts, const 
                           const int* offsets, const int* entries, const float* ref_edge, const float* ref_area, float nc_factor,
                           float edge_factor, float area_factor, const float* scale, float* grad, int accumulate, hipStream_t st);
 
+// rig-wide topology-error detection (gsr_topo.hip)
+size_t topo_view_workspace_bytes();
+void launch_topo_view(int H, int W, int V, const float* verts, const float* gt, const float* render, const float* surface,
+                      float max_depth, const double* cam14, void* workspace, float* row, hipStream_t st);
+void launch_topo_aggregate(int C, int V, const float* table, const float* verts, const float* ymin, double depth_scalar,
+                           int min_observe, int detect_floor, double* value, int* cnt, unsigned char* valid, hipStream_t st);
+void launch_topo_propagate(int V, const int* off, const int* nbr, int sweeps, const double* value_in, const unsigned char* valid_in,
+                           double* value_out, double* value_tmp, unsigned char* valid_a, unsigned char* valid_b, hipStream_t st);
+void launch_topo_voxel_keys(int V, const float* verts, const float* vmin, double voxel_size, long long* keys, int* flags,
+                            hipStream_t st);
+size_t topo_voxel_workspace_bytes(int V);
+void launch_topo_voxel_interp(int V, const float* verts, const float* vmin, double voxel_size, const long long* skeys,
+                              const long long* perm, const long long* vid, const double* value, void* workspace, double* vox_value,
+                              double* out, hipStream_t st);
+void launch_topo_faces(int F, const int* faces, const double* value, unsigned char* colour, float* loss, hipStream_t st);
+
 // Optional per-workgroup timeline for tuning (gsr_debug_set_trace): when non-null, the blend kernels store
 // {start, end} of every workgroup (100 MHz wall clock) at trace[2*blockIdx] (forward) / trace[2*(T+blockIdx)].
 extern uint64_t* g_trace;

@@ -407,6 +407,12 @@ class SurfaceGaussians(nn.Module):
         from . import meshes
         return meshes.MeshTopology.of(self._surface_mesh_faces, int(self._points.shape[0]))
 
+    def detect_topology_errors(self, cameras, gt_depth, **kw):
+        """Where the mesh's topology disagrees with the GT depth of `cameras` (refined_mesh.py:697-920, depth term):
+        topology.detect_topology_errors(self, cameras, gt_depth, **kw)."""
+        from . import topology
+        return topology.detect_topology_errors(self, cameras, gt_depth, **kw)
+
     # -------------------------------------------------------------------------------- rendering
     def _settings(self, camera: NerfCamera, bg: torch.Tensor, sh_degree: int):
         cam, view, proj, campos = camera.on_device(self.device)

@@ -404,6 +404,55 @@ int gsr_mesh_reg_backward(int V, int F, int E, int Q, const float* verts, const 
                           float nc_factor, float edge_factor, float area_factor, const float* grad_scale, float* dL_dverts,
                           int accumulate, gsr_stream_t stream);
 
+/* ---- Rig-wide topology-error detection (gaustar_trainers/refined_mesh.py:697-920 `detect_topo_err` with the depth term only,
+ * as refine.py:720-734 calls it).  All device pointers; every call is asynchronous on `stream`, none synchronises the host,
+ * and none uses float atomics (outputs are bitwise reproducible).
+ * gsr_topo_view: one camera (refined_mesh.py:729-811), three launches.  depth_gt, render_depth, surface_depth [H,W] f32
+ *   contiguous (the GT depth, the depth render and the solid-surface depth render, both with bg = max_depth); verts [V,3] f32;
+ *   cam: [host] 14 doubles = the COLMAP world-to-camera rotation row-major (9), translation (3), fx, fy.  Writes row [V]:
+ *   the vertex's depth loss min(|min(gt, max_depth) - render| (1 - edge_vis) 10, 2) where it is visible, -1 where not.
+ *   Edge map: get_depth_edge(depth_gt, 3) of gaustar_tools/warp_mesh.py:120-130 (3x3 box filter, reflect-101 border),
+ *   edge_vis = min(var / max(var) 1000, 1) (:792).  Projection (warp_mesh.py:57-74) in double without the principal
+ *   point; lookup int(pix + 0.5), valid iff unclipped (:106-117).  Visible iff valid, |z - surface_depth| < 0.005 and
+ *   edge_vis < 0.1 (:790-794).  A camera with no GT pixel below max_depth, or with max(var) = 0, sees nothing.
+ *   workspace: gsr_topo_view_workspace_bytes(H, W) bytes, one per view in flight.
+ * gsr_topo_aggregate: table [C,V] (the rows of all cameras, camera order) -> count [V] int32 (cameras that see the vertex),
+ *   value [V] double = depth_scalar * the mean of the recorded losses where count >= min_observe, else 0 (:826-845);
+ *   with detect_floor, vertices with y < ymin[0] + 0.02 get value 0 and count min_observe + 1 (:869-875; ymin a device
+ *   scalar); valid [V] uint8 = count >= min_observe.
+ * gsr_topo_propagate: mesh_vert_propagate (warp_mesh.py:133-155) as `sweeps` Jacobi sweeps over the symmetric neighbour list
+ *   nbr_offsets [V+1], nbr (int32, trimesh vertex_neighbors): an invalid vertex with a valid neighbour takes the mean of its
+ *   valid neighbours and becomes valid.  value_in / valid_in are not modified; value_out receives the result; value_tmp [V]
+ *   double, valid_a / valid_b [V] uint8 are scratch.
+ * gsr_topo_voxel_keys: open3d VoxelGrid::CreateFromPointCloud's voxel index of every vertex (build_voxel_from_pc,
+ *   warp_mesh.py:185-197): origin = vmin - voxel_size / 2 (vmin [3] f32 device: the per-axis minimum), index =
+ *   floor((v - origin) / voxel_size) in double, packed as keys [V] int64 = (ix << 42) | (iy << 21) | iz.  flags[0] (device
+ *   int, zeroed by the caller) is set to 1 if an index falls outside [0, 2^21).
+ * gsr_topo_voxel_interp: from the keys stably sorted (sorted_keys, order = the permutation) and voxel_id [V] int64 = the
+ *   voxel of each sorted position (inclusive scan of the key changes, minus 1): per voxel the mean of its vertices' value
+ *   (voxel_value [V] double) and the centre origin + (index + 0.5) voxel_size, then
+ *   interpolate_in_voxel (warp_mesh.py:199-213): the 8 nearest centres by f32 squared distance (pytorch3d knn_points, ties
+ *   to the lower voxel id), weights exp(-d^2 / voxel_size^2) + 1e-8, out [V] double = the weighted mean.  workspace:
+ *   gsr_topo_voxel_workspace_bytes(V) bytes, 16-byte aligned.
+ * gsr_topo_faces: faces [F,3] int32 -> face_colour [F] uint8 = (c0 + c1 + c2) / 3 truncated with c = int(min(255 value, 255))
+ *   (trimesh vertex -> face colours, refined_mesh.py:913-915), face_loss [F] f32 = face_colour / 255 (:920). */
+size_t gsr_topo_view_workspace_bytes(int H, int W);
+int gsr_topo_view(int H, int W, int V, const float* verts, const float* depth_gt, const float* render_depth,
+                  const float* surface_depth, float max_depth, const double* cam, void* workspace, float* row, gsr_stream_t stream);
+int gsr_topo_aggregate(int C, int V, const float* table, const float* verts, const float* ymin, double depth_scalar,
+                       int min_observe, int detect_floor, double* value, int* count, unsigned char* valid, gsr_stream_t stream);
+int gsr_topo_propagate(int V, const int* nbr_offsets, const int* nbr, int sweeps, const double* value_in,
+                       const unsigned char* valid_in, double* value_out, double* value_tmp, unsigned char* valid_a,
+                       unsigned char* valid_b, gsr_stream_t stream);
+int gsr_topo_voxel_keys(int V, const float* verts, const float* vmin, double voxel_size, long long* keys, int* flags,
+                        gsr_stream_t stream);
+size_t gsr_topo_voxel_workspace_bytes(int V);
+int gsr_topo_voxel_interp(int V, const float* verts, const float* vmin, double voxel_size, const long long* sorted_keys,
+                          const long long* order, const long long* voxel_id, const double* value, void* workspace,
+                          double* voxel_value, double* out, gsr_stream_t stream);
+int gsr_topo_faces(int F, const int* faces, const double* value, unsigned char* face_colour, float* face_loss,
+                   gsr_stream_t stream);
+
 /* Tuning aid: when device_buffer is non-NULL (4*T uint64), the two blend kernels record the start/end wall
  * clock (100 MHz) of every workgroup: forward at [2*b], backward at [2*(T+b)], b = launch index.  NULL = off. */
 int gsr_debug_set_trace(void* device_buffer);
