@@ -117,6 +117,13 @@ SIGNATURES = {
     "gsr_topo_voxel_interp": (c_int, [c_int, c_void_p, c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_void_p]),
     "gsr_topo_faces": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # scene-flow mesh warping (warp_mesh.py:216-401): gaustar_amd.warp
+    "gsr_vertex_normals": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gsr_warp_view_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "gsr_warp_view": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_int), c_void_p, c_void_p,
+                              POINTER(c_double), POINTER(c_double), c_void_p, c_void_p, c_void_p]),
+    "gsr_warp_aggregate": (c_int, [c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gsr_warp_smooth": (c_int, [c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gsr_adam_step": (c_int, [c_longlong, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_double, c_double, c_int,
                               c_void_p]),
     "gsr_adam_step_multi": (c_int, [c_int, POINTER(c_longlong), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),

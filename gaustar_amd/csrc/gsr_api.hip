@@ -1338,6 +1338,78 @@ int gsr_topo_faces(int F, const int* faces, const double* value, unsigned char* 
     return 0;
 }
 
+int gsr_vertex_normals(int V, int F, const double* verts, const int* faces, const int* vf_offsets, const int* vf_entries,
+                       double* face_scratch, double* normals, gsr_stream_t stream)
+{
+    g_err.clear();
+    if (V < 0 || F < 0) return fail_msg("gsr_vertex_normals: negative size");
+    if (V == 0) return 0;
+    if (!verts || !vf_offsets || !normals || (F > 0 && (!faces || !vf_entries || !face_scratch)))
+        return fail_msg("gsr_vertex_normals: required pointer is null");
+    launch_warp_normals(V, F, verts, faces, vf_offsets, vf_entries, face_scratch, normals, (hipStream_t)stream);
+    GSR_CHECK_LAUNCH("warp normal kernels");
+    return 0;
+}
+
+size_t gsr_warp_view_workspace_bytes(int H, int W)
+{
+    (void)H; (void)W;   // (the partial maxima of a fixed number of workgroups, whatever the image)
+    return warp_view_workspace_bytes();
+}
+
+int gsr_warp_view(int H, int W, int V, const double* verts, const double* normals, const float* flow_f, const float* flow_b,
+                  const int* flow_shape, const float* depth_cur, const float* depth_next, const double* cam,
+                  const double* params, void* workspace, double* row, gsr_stream_t stream)
+{
+    g_err.clear();
+    if (H <= 0 || W <= 0 || V < 0) return fail_msg("gsr_warp_view: sizes must be positive");
+    if ((long long)H * W >= (1ll << 31)) return fail_msg("gsr_warp_view: image too large");
+    if (!flow_f || !flow_b || !flow_shape || !depth_cur || !depth_next || !cam || !params || !workspace ||
+        (V > 0 && (!verts || !normals || !row)))
+        return fail_msg("gsr_warp_view: required pointer is null");
+    if (flow_shape[0] <= 0 || flow_shape[1] <= 0) return fail_msg("gsr_warp_view: flow sizes must be positive");
+    for (int i = 2; i < 6; ++i)
+        if (flow_shape[i] < 0) return fail_msg("gsr_warp_view: flow padding must be non-negative");
+    const long long hp = (long long)flow_shape[0] + flow_shape[2] + flow_shape[3];
+    const long long wp = (long long)flow_shape[1] + flow_shape[4] + flow_shape[5];
+    if (hp >= (1ll << 30) || wp >= (1ll << 30) || (long long)flow_shape[0] * flow_shape[1] >= (1ll << 30))
+        return fail_msg("gsr_warp_view: flow too large");
+    launch_warp_view(H, W, V, verts, normals, flow_f, flow_b, flow_shape, depth_cur, depth_next, cam, params, workspace, row,
+                     (hipStream_t)stream);
+    GSR_CHECK_LAUNCH("warp view kernels");
+    return 0;
+}
+
+int gsr_warp_aggregate(int C, int V, const double* table, int min_observe, double* move, int* observed, int* count,
+                       unsigned char* valid, gsr_stream_t stream)
+{
+    g_err.clear();
+    if (C < 0 || V < 0) return fail_msg("gsr_warp_aggregate: negative size");
+    if (V == 0) return 0;
+    if ((C > 0 && !table) || !move || !observed || !count || !valid) return fail_msg("gsr_warp_aggregate: required pointer is null");
+    launch_warp_aggregate(C, V, table, min_observe, move, observed, count, valid, (hipStream_t)stream);
+    GSR_CHECK_LAUNCH("warp_aggregate_kernel");
+    return 0;
+}
+
+int gsr_warp_smooth(int V, const int* nbr_offsets, const int* nbr, int sweeps, const double* value_in, double* value_out,
+                    double* value_tmp, gsr_stream_t stream)
+{
+    g_err.clear();
+    if (V < 0 || sweeps < 0) return fail_msg("gsr_warp_smooth: negative size");
+    if (V == 0) return 0;
+    if (!value_in || !value_out) return fail_msg("gsr_warp_smooth: required pointer is null");
+    hipStream_t st = (hipStream_t)stream;
+    if (sweeps == 0) {
+        GSR_CHECK(hipMemcpyAsync(value_out, value_in, sizeof(double) * 3 * V, hipMemcpyDeviceToDevice, st));
+        return 0;
+    }
+    if (!nbr_offsets || !nbr || !value_tmp) return fail_msg("gsr_warp_smooth: required pointer is null");
+    launch_warp_smooth(V, nbr_offsets, nbr, sweeps, value_in, value_out, value_tmp, st);
+    GSR_CHECK_LAUNCH("warp_smooth_kernel");
+    return 0;
+}
+
 int gsr_mark_visible(int P, const float* means3D, const float* viewmatrix, const float* projmatrix, uint8_t* present,
                      gsr_stream_t stream)
 {

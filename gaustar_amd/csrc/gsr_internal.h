@@ -375,6 +375,17 @@ void launch_topo_voxel_interp(int V, const float* verts, const float* vmin, doub
                               double* out, hipStream_t st);
 void launch_topo_faces(int F, const int* faces, const double* value, unsigned char* colour, float* loss, hipStream_t st);
 
+// scene-flow mesh warping (gsr_warp.hip)
+size_t warp_view_workspace_bytes();
+void launch_warp_normals(int V, int F, const double* verts, const int* faces, const int* vf_off, const int* vf_ent, double* fbuf,
+                         double* normals, hipStream_t st);
+void launch_warp_view(int H, int W, int V, const double* verts, const double* normals, const float* flow_f, const float* flow_b,
+                      const int* flow_shape, const float* depth_cur, const float* depth_next, const double* cam14,
+                      const double* params, void* workspace, double* row, hipStream_t st);
+void launch_warp_aggregate(int C, int V, const double* table, int min_observe, double* move, int* observed, int* count,
+                           unsigned char* valid, hipStream_t st);
+void launch_warp_smooth(int V, const int* off, const int* nbr, int sweeps, const double* in, double* out, double* tmp, hipStream_t st);
+
 // Optional per-workgroup timeline for tuning (gsr_debug_set_trace): when non-null, the blend kernels store
 // {start, end} of every workgroup (100 MHz wall clock) at trace[2*blockIdx] (forward) / trace[2*(T+blockIdx)].
 extern uint64_t* g_trace;

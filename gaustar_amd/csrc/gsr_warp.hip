@@ -1,0 +1,454 @@
+// gsr_warp.hip -- scene-flow mesh warping to the next frame (gaustar_tools/warp_mesh.py:216-401, `warp_mesh_using_flow`
+// with post_processing = 'mesh'): the refined mesh of frame f, moved along the optical flow of every camera onto the depth of
+// frame f + interval, is the mesh frame f + interval starts from (train_seq.py:112, :242-245).
+//
+// The reference runs it on the host in numpy with trimesh and cv2: per camera two 7x7 edge maps, a pad / resize of the two
+// RAFT flows, a projection and seven lookups per vertex (:259-340); over the rig a Python loop per vertex with outlier removal
+// (:347-358), up to 20 propagation sweeps (:384, :133-155) and 5 smoothing sweeps (:394, :158-171).  Here:
+//   once per warp
+//     warp_face_kernel / warp_vertex_normal_kernel  trimesh Trimesh.vertex_normals in world space (rotated per camera)
+//   per camera  (3 launches, no host round trip)
+//     warp_depth_max_kernel  per-workgroup max of depth_cur / depth_next below 10          -> partials [0, 2 WP_PARTS)
+//     warp_var_max_kernel    per-workgroup max of the 7x7 edge statistic of both maps       -> partials [2, 4 WP_PARTS)
+//     warp_view_kernel       one lane per vertex, :286-340 in f64                           -> one row [V,3] of the [C,V,3] table
+//   over the rig
+//     warp_aggregate_kernel  observed count, remove_outlier, kept count, mean (:347-358) in camera order
+//     (propagation: topo_propagate_kernel of gsr_topo.hip, one call per component)
+//     warp_smooth_kernel     one Jacobi sweep of mesh_color_smoothing (ping-pong)
+// No float atomics anywhere: every output is a pure function of the inputs (bitwise reproducible, independent of how many
+// views are in flight and of how the cameras were sharded over ranks).  Floating point follows the numpy restatement in
+// tests/warp_ref.py operation by operation, so contraction into FMAs is off for this file.
+//
+// Assumptions (cv2 and trimesh are not available to check them against):
+//   * cv2.blur(., (7, 7)): BORDER_REFLECT_101, the 49 values summed in double (row sums, then the rows) times 1/49 and
+//     rounded to f32 -- the convention gsr_topo.hip documents for the 3x3 filter.  While the non-zero values of a window (d and
+//     d^2) lie within a factor of 2^23 of each other the double sum is exact, so its order does not matter.
+//   * cv2.resize(flow, (W, H), INTER_NEAREST) as OpenCV's resizeNN computes it: source column
+//     min(floor(x * (1.0 / ((double)W / w_padded))), w_padded - 1), and the same for rows.
+//   * flow *= H / h_padded multiplies in f32 by the f32-rounded ratio (NumPy 1.x value-based casting of the np.float64 scalar,
+//     as the reference's environment pins it).
+//   * trimesh vertex_normals: a corner-angle-weighted sum of the unit face normals (cross(b - a, c - b), unitised; a face
+//     whose cross product has norm <= 1e-12 contributes zero) in ascending face order, then unitised (a zero sum stays zero).
+//     Corner angles: arccos of the clipped dot products of the unit edge vectors at corners 0 and 1, pi minus both at corner
+//     2, all three zero when one is below 1e-8.  trimesh computes the normals of the camera-space mesh; these are the world
+//     normals rotated into the camera, which differ only by rounding.
+#include "gsr_internal.h"
+
+#pragma clang fp contract(off)
+
+namespace gsr {
+
+namespace {
+
+constexpr int WP_BLOCK = 256;
+constexpr int WP_PARTS = 2048;   // workgroups of the image passes per map (grid-stride), = partials per statistic and map
+constexpr int WP_R = 3;          // get_depth_edge(depth, 7): offsets -3 .. 3
+constexpr float WP_MAX_DEPTH = 10.f;   // the literal 10 of warp_mesh.py:122 and :319
+
+// cv2 BORDER_REFLECT_101 (gfedcb|abcdefgh|gfedcba), for any offset
+__device__ __forceinline__ int reflect101_any(int i, int n)
+{
+    if (n == 1) return 0;
+    while (i < 0 || i >= n) i = i < 0 ? -i : 2 * n - 2 - i;
+    return i;
+}
+
+// get_depth_edge(depth, 7) at (y, x): d = min(depth, m), var = max(blur7(d^2) - blur7(d)^2, 0); d^2 squared in f32 (numpy
+// `depth ** 2`), blur7(d) squared in f32
+__device__ __forceinline__ float edge_var7(const float* __restrict__ g, int H, int W, int y, int x, float m)
+{
+    double s1 = 0.0, s2 = 0.0;
+    int xs[2 * WP_R + 1];
+#pragma unroll
+    for (int dx = -WP_R; dx <= WP_R; ++dx) xs[dx + WP_R] = reflect101_any(x + dx, W);
+#pragma unroll
+    for (int dy = -WP_R; dy <= WP_R; ++dy) {
+        const float* row = g + (size_t)reflect101_any(y + dy, H) * W;
+        double r1 = 0.0, r2 = 0.0;
+#pragma unroll
+        for (int k = 0; k < 2 * WP_R + 1; ++k) {
+            const float d = fminf(row[xs[k]], m);
+            r1 += (double)d;
+            r2 += (double)(d * d);
+        }
+        s1 += r1;
+        s2 += r2;
+    }
+    const float mean = (float)(s1 * (1.0 / 49.0)), sq_mean = (float)(s2 * (1.0 / 49.0));
+    return fmaxf(sq_mean - mean * mean, 0.f);
+}
+
+// max over the WP_PARTS partials at `p`, by the whole workgroup (every lane gets it)
+__device__ float wp_block_max_of_parts(const float* __restrict__ p, float* red)
+{
+    float v = -INFINITY;
+    for (int i = threadIdx.x; i < WP_PARTS; i += WP_BLOCK) v = fmaxf(v, p[i]);
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int s = WP_BLOCK / 2; s > 0; s >>= 1) {
+        if (threadIdx.x < s) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + s]);
+        __syncthreads();
+    }
+    const float r = red[0];
+    __syncthreads();
+    return r;
+}
+
+__device__ void wp_block_store_max(float v, float* red, float* out)
+{
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int s = WP_BLOCK / 2; s > 0; s >>= 1) {
+        if (threadIdx.x < s) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + s]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *out = red[0];
+}
+
+// m = f32(1.1 * max(depth[depth < 10])) (warp_mesh.py:122-123, the product in double as NumPy 1.x evaluates it); -inf when no
+// pixel is below 10
+__device__ __forceinline__ float wp_clip_depth(float dmax) { return dmax == -INFINITY ? -INFINITY : (float)((double)dmax * 1.1); }
+
+// blockIdx.y: 0 = depth_cur, 1 = depth_next
+__global__ void __launch_bounds__(WP_BLOCK) warp_depth_max_kernel(int n, const float* __restrict__ cur, const float* __restrict__ nxt,
+                                                                  float* __restrict__ parts)
+{
+    __shared__ float red[WP_BLOCK];
+    const float* g = blockIdx.y ? nxt : cur;
+    float v = -INFINITY;
+    for (long long i = blockIdx.x * WP_BLOCK + threadIdx.x; i < n; i += WP_PARTS * WP_BLOCK) {   // (64-bit: no overflow near 2^31)
+        const float d = g[i];
+        if (d < WP_MAX_DEPTH) v = fmaxf(v, d);
+    }
+    wp_block_store_max(v, red, parts + blockIdx.y * WP_PARTS + blockIdx.x);
+}
+
+__global__ void __launch_bounds__(WP_BLOCK) warp_var_max_kernel(int H, int W, const float* __restrict__ cur, const float* __restrict__ nxt,
+                                                                float* __restrict__ parts)
+{
+    __shared__ float red[WP_BLOCK];
+    const float* g = blockIdx.y ? nxt : cur;
+    const float m = wp_clip_depth(wp_block_max_of_parts(parts + blockIdx.y * WP_PARTS, red));
+    float v = 0.f;
+    if (m != -INFINITY)
+        for (long long i = blockIdx.x * WP_BLOCK + threadIdx.x; i < (long long)H * W; i += WP_PARTS * WP_BLOCK)
+            v = fmaxf(v, edge_var7(g, H, W, (int)(i / W), (int)(i % W), m));
+    wp_block_store_max(v, red, parts + (2 + blockIdx.y) * WP_PARTS + blockIdx.x);
+}
+
+}  // namespace
+
+struct WarpView {
+    double R[9], t[3];   // COLMAP world-to-camera rotation (row-major) and translation (cmr["extrinsics"][c][:3])
+    double fx, fy;       // cmr["intrinsics"][c][0,0], [1,1]
+};
+
+// one raw RAFT flow [h, w, 2] f32 in (x, y) order, padded by (top, bottom, left, right) zeros to (hp, wp), scaled by `scale`
+// and resized (nearest) to the camera's (H, W); ify / ifx = 1 / (H / hp), 1 / (W / wp) in double as cv2 computes them
+struct WarpFlow {
+    const float* raw;
+    int h, w, top, left, hp, wp;
+    float scale;
+    double ify, ifx;
+};
+
+struct WarpParams {      // warp_config (warp_mesh.py:14-25)
+    double normal_cos;   // cmr_view_max_cos
+    double edge_scalar, edge_threshold;
+    double bi_depth, bi_pix;   // bi_direct_depth_threshold, bi_direct_pix_threshold
+    double max_move;     // max_move_dist
+};
+
+namespace {
+
+// query_at_image's index (warp_mesh.py:106-117): np.int32(pix + 0.5) truncates toward zero, NaN and values out of the int32
+// range become INT_MIN (x86's conversion); the index is clipped to [0, n - 1] and the lookup valid iff clipping changed nothing
+__device__ __forceinline__ int wp_query(double pix, int n, bool& ok)
+{
+    const double y = pix + 0.5;
+    const int p = (y > -2147483649.0 && y < 2147483648.0) ? (int)y : INT_MIN;
+    const int c = min(max(p, 0), n - 1);
+    ok = ok && p == c;
+    return c;
+}
+
+// flow[iy, ix] after pad_and_resize_flow (warp_mesh.py:96-103) and the [..., ::-1] swap (:270-271): (row, col) displacement
+__device__ __forceinline__ void wp_flow_at(const WarpFlow& f, int iy, int ix, float& dr, float& dc)
+{
+    const int sy = min((int)floor((double)iy * f.ify), f.hp - 1);
+    const int sx = min((int)floor((double)ix * f.ifx), f.wp - 1);
+    const int ry = sy - f.top, rx = sx - f.left;
+    if (ry < 0 || ry >= f.h || rx < 0 || rx >= f.w) { dr = 0.f; dc = 0.f; return; }   // np.pad's zeros (times the scale)
+    const float* p = f.raw + ((size_t)ry * f.w + rx) * 2;
+    dr = p[1] * f.scale;
+    dc = p[0] * f.scale;
+}
+
+// edge_vis = min(var / max(var) * edge_scalar, 1) in f32 (warp_mesh.py:298, :313)
+__device__ __forceinline__ float wp_edge_vis(const float* g, int H, int W, int y, int x, float m, float vmax, float scalar)
+{
+    return fminf(__fdiv_rn(edge_var7(g, H, W, y, x, m), vmax) * scalar, 1.f);
+}
+
+__global__ void __launch_bounds__(WP_BLOCK) warp_view_kernel(int H, int W, int V, const double* __restrict__ verts,
+                                                             const double* __restrict__ normals, WarpFlow ff, WarpFlow fb,
+                                                             const float* __restrict__ dcur, const float* __restrict__ dnext,
+                                                             const float* __restrict__ parts, WarpView cam, WarpParams prm,
+                                                             double* __restrict__ row)
+{
+    __shared__ float red[WP_BLOCK];
+    const float gmax_c = wp_block_max_of_parts(parts, red);
+    const float gmax_n = wp_block_max_of_parts(parts + WP_PARTS, red);
+    const float vmax_c = wp_block_max_of_parts(parts + 2 * WP_PARTS, red);
+    const float vmax_n = wp_block_max_of_parts(parts + 3 * WP_PARTS, red);
+    const int v = blockIdx.x * WP_BLOCK + threadIdx.x;
+    if (v >= V) return;
+    double* out = row + 3 * (size_t)v;
+    // a camera whose depth has no pixel below 10 (the reference raises on the empty max) or is flat (max(var) = 0: edge_vis
+    // is NaN and nothing passes `< edge_threshold`) sees no vertex
+    if (gmax_c == -INFINITY || gmax_n == -INFINITY || !(vmax_c > 0.f) || !(vmax_n > 0.f)) {
+        out[0] = out[1] = out[2] = NAN;
+        return;
+    }
+    const float m_c = wp_clip_depth(gmax_c), m_n = wp_clip_depth(gmax_n);
+    const float escale = (float)prm.edge_scalar, ethr = (float)prm.edge_threshold;
+    // 1. project (warp_mesh.py:47-74, no principal point) and look up depth_cur (:287-289)
+    const double px = verts[3 * v], py = verts[3 * v + 1], pz = verts[3 * v + 2];
+    const double lx = cam.R[0] * px + cam.R[1] * py + cam.R[2] * pz + cam.t[0];
+    const double ly = cam.R[3] * px + cam.R[4] * py + cam.R[5] * pz + cam.t[1];
+    const double lz = cam.R[6] * px + cam.R[7] * py + cam.R[8] * pz + cam.t[2];
+    const double pr = cam.fy * (ly / lz) + H * 0.5, pc = cam.fx * (lx / lz) + W * 0.5;
+    bool ok = true;
+    const int iy = wp_query(pr, H, ok), ix = wp_query(pc, W, ok);
+    const float d_cur = dcur[(size_t)iy * W + ix];
+    // 2. visible: valid lookup, |z - depth| < 0.005, camera-space normal z < cmr_view_max_cos (:291-295), edge (:298-300)
+    const double nz = cam.R[6] * normals[3 * v] + cam.R[7] * normals[3 * v + 1] + cam.R[8] * normals[3 * v + 2];
+    bool vis = ok && fabs(lz - (double)d_cur) < 0.005 && nz < prm.normal_cos;
+    vis = vis && wp_edge_vis(dcur, H, W, iy, ix, m_c, vmax_c, escale) < ethr;
+    // 3. pix_next = pix + flow[q(pix)] (:303)
+    float fr, fc;
+    wp_flow_at(ff, iy, ix, fr, fc);
+    const double nr = pr + (double)fr, nc = pc + (double)fc;
+    bool ok_n = true;
+    const int jy = wp_query(nr, H, ok_n), jx = wp_query(nc, W, ok_n);
+    // 4. pix_back = pix_next + flow_back[q(pix_next)] (:306)
+    wp_flow_at(fb, jy, jx, fr, fc);
+    const double br = nr + (double)fr, bc = nc + (double)fc;
+    bool ok_b = true;
+    const int ky = wp_query(br, H, ok_b), kx = wp_query(bc, W, ok_b);
+    // 5. depth consistency in f32 (:307-308)
+    vis = vis && fabsf(dcur[(size_t)ky * W + kx] - d_cur) < (float)prm.bi_depth;
+    // 6. pixel round trip in f64 (:309-310)
+    const double er = br - pr, ec = bc - pc;
+    vis = vis && sqrt(er * er + ec * ec) < prm.bi_pix;
+    // 7. edge in the next frame (:313-315)
+    vis = vis && wp_edge_vis(dnext, H, W, jy, jx, m_n, vmax_n, escale) < ethr;
+    // 8. depth in the next frame (:318-319)
+    const float d_next = dnext[(size_t)jy * W + jx];
+    vis = vis && ok_n && d_next < WP_MAX_DEPTH;
+    // 9. back-project pix_next with that depth (:77-93, :325): R^T (dir d - t)
+    const double dd = (double)d_next;
+    const double a0 = ((nc - W * 0.5) / cam.fx) * dd - cam.t[0];
+    const double a1 = ((nr - H * 0.5) / cam.fy) * dd - cam.t[1];
+    const double a2 = dd - cam.t[2];
+    const double m0 = (cam.R[0] * a0 + cam.R[3] * a1 + cam.R[6] * a2) - px;
+    const double m1 = (cam.R[1] * a0 + cam.R[4] * a1 + cam.R[7] * a2) - py;
+    const double m2 = (cam.R[2] * a0 + cam.R[5] * a1 + cam.R[8] * a2) - pz;
+    // 10. |move| < max_move_dist (:326-328)
+    vis = vis && sqrt(m0 * m0 + m1 * m1 + m2 * m2) < prm.max_move;
+    out[0] = vis ? m0 : NAN;
+    out[1] = vis ? m1 : NAN;
+    out[2] = vis ? m2 : NAN;
+}
+
+__device__ __forceinline__ void unitize3(double& x, double& y, double& z)
+{
+    const double n = sqrt(x * x + y * y + z * z);
+    if (n > 1e-12) { x = x / n; y = y / n; z = z / n; }
+    else { x = 0.0; y = 0.0; z = 0.0; }
+}
+
+// per face: the unit normal and the three corner angles -> fbuf[6 f .. 6 f + 5]
+__global__ void __launch_bounds__(WP_BLOCK) warp_face_kernel(int F, const double* __restrict__ verts, const int* __restrict__ faces,
+                                                             double* __restrict__ fbuf)
+{
+    const int f = blockIdx.x * WP_BLOCK + threadIdx.x;
+    if (f >= F) return;
+    const double* a = verts + 3 * (size_t)faces[3 * f];
+    const double* b = verts + 3 * (size_t)faces[3 * f + 1];
+    const double* c = verts + 3 * (size_t)faces[3 * f + 2];
+    const double e1[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]}, e2[3] = {c[0] - b[0], c[1] - b[1], c[2] - b[2]};
+    double nx = e1[1] * e2[2] - e1[2] * e2[1], ny = e1[2] * e2[0] - e1[0] * e2[2], nz = e1[0] * e2[1] - e1[1] * e2[0];
+    unitize3(nx, ny, nz);
+    double u[3] = {e1[0], e1[1], e1[2]}, v[3] = {c[0] - a[0], c[1] - a[1], c[2] - a[2]}, w[3] = {e2[0], e2[1], e2[2]};
+    unitize3(u[0], u[1], u[2]);
+    unitize3(v[0], v[1], v[2]);
+    unitize3(w[0], w[1], w[2]);
+    const double uv = u[0] * v[0] + u[1] * v[1] + u[2] * v[2];
+    const double uw = -u[0] * w[0] + -u[1] * w[1] + -u[2] * w[2];
+    double a0 = acos(fmin(fmax(uv, -1.0), 1.0)), a1 = acos(fmin(fmax(uw, -1.0), 1.0));
+    double a2 = M_PI - a0 - a1;
+    if (a0 < 1e-8 || a1 < 1e-8 || a2 < 1e-8) a0 = a1 = a2 = 0.0;
+    double* o = fbuf + 6 * (size_t)f;
+    o[0] = nx; o[1] = ny; o[2] = nz;
+    o[3] = a0; o[4] = a1; o[5] = a2;
+}
+
+// per vertex: sum over its (face, corner) incidences in ascending face order of angle * normal, unitised
+__global__ void __launch_bounds__(WP_BLOCK) warp_vertex_normal_kernel(int V, const int* __restrict__ off, const int* __restrict__ ent,
+                                                                      const double* __restrict__ fbuf, double* __restrict__ normals)
+{
+    const int v = blockIdx.x * WP_BLOCK + threadIdx.x;
+    if (v >= V) return;
+    double sx = 0.0, sy = 0.0, sz = 0.0;
+    for (int e = off[v]; e < off[v + 1]; ++e) {
+        const int f = ent[e] / 3, k = ent[e] % 3;
+        const double* o = fbuf + 6 * (size_t)f;
+        const double a = o[3 + k];
+        sx += a * o[0];
+        sy += a * o[1];
+        sz += a * o[2];
+    }
+    unitize3(sx, sy, sz);
+    normals[3 * v] = sx;
+    normals[3 * v + 1] = sy;
+    normals[3 * v + 2] = sz;
+}
+
+// warp_mesh.py:347-358 per vertex, cameras in order.  remove_outlier(threshold=2) (:174-181): mean and population std of the
+// observed moves, z = (x - mean) / std, keep the rows whose three z are all < 2 (one-sided; a NaN z, from std 0, drops the row)
+__global__ void __launch_bounds__(WP_BLOCK) warp_aggregate_kernel(int C, int V, const double* __restrict__ table, int min_observe,
+                                                                  double* __restrict__ move, int* __restrict__ observed,
+                                                                  int* __restrict__ count, unsigned char* __restrict__ valid)
+{
+    const int v = blockIdx.x * WP_BLOCK + threadIdx.x;
+    if (v >= V) return;
+    const size_t stride = 3 * (size_t)V;
+    const double* col = table + 3 * (size_t)v;
+    int n = 0;
+    double s[3] = {0.0, 0.0, 0.0};
+    for (int c = 0; c < C; ++c) {
+        const double* x = col + c * stride;
+        if (x[0] == x[0]) { s[0] += x[0]; s[1] += x[1]; s[2] += x[2]; ++n; }   // (NaN = not visible)
+    }
+    int cnt = n;
+    double mv[3] = {0.0, 0.0, 0.0};
+    if (n >= min_observe) {
+        double mean[3], q[3] = {0.0, 0.0, 0.0}, sd[3];
+        for (int k = 0; k < 3; ++k) mean[k] = s[k] / n;
+        for (int c = 0; c < C; ++c) {
+            const double* x = col + c * stride;
+            if (x[0] == x[0])
+                for (int k = 0; k < 3; ++k) { const double d = x[k] - mean[k]; q[k] += d * d; }
+        }
+        for (int k = 0; k < 3; ++k) sd[k] = sqrt(q[k] / n);
+        int kept = 0;
+        double s2[3] = {0.0, 0.0, 0.0};
+        for (int c = 0; c < C; ++c) {
+            const double* x = col + c * stride;
+            if (x[0] == x[0] && (x[0] - mean[0]) / sd[0] < 2.0 && (x[1] - mean[1]) / sd[1] < 2.0 && (x[2] - mean[2]) / sd[2] < 2.0) {
+                s2[0] += x[0]; s2[1] += x[1]; s2[2] += x[2];
+                ++kept;
+            }
+        }
+        cnt = kept;
+        if (kept >= min_observe)
+            for (int k = 0; k < 3; ++k) mv[k] = s2[k] / kept;
+    }
+    for (int k = 0; k < 3; ++k) move[3 * v + k] = mv[k];
+    observed[v] = n;
+    count[v] = cnt;
+    valid[v] = cnt >= min_observe;
+}
+
+// one sweep of mesh_color_smoothing (warp_mesh.py:158-171): every vertex takes the mean of all its neighbours (ascending);
+// a vertex without neighbours gets 0 / 0 = NaN, as np.average of an empty selection
+__global__ void __launch_bounds__(WP_BLOCK) warp_smooth_kernel(int V, const int* __restrict__ off, const int* __restrict__ nbr,
+                                                               const double* __restrict__ in, double* __restrict__ out)
+{
+    const int v = blockIdx.x * WP_BLOCK + threadIdx.x;
+    if (v >= V) return;
+    double s[3] = {0.0, 0.0, 0.0};
+    int k = 0;
+    for (int e = off[v]; e < off[v + 1]; ++e) {
+        const double* x = in + 3 * (size_t)nbr[e];
+        s[0] += x[0]; s[1] += x[1]; s[2] += x[2];
+        ++k;
+    }
+    const double n = (double)k;
+    for (int j = 0; j < 3; ++j) out[3 * v + j] = s[j] / n;
+}
+
+inline int wblocks(int n) { return (n + WP_BLOCK - 1) / WP_BLOCK; }
+
+WarpFlow make_flow(const float* raw, const int* shape6, int H, int W)
+{
+    // shape6: h, w, top, bottom, left, right
+    WarpFlow f;
+    f.raw = raw;
+    f.h = shape6[0];
+    f.w = shape6[1];
+    f.top = shape6[2];
+    f.left = shape6[4];
+    f.hp = shape6[0] + shape6[2] + shape6[3];
+    f.wp = shape6[1] + shape6[4] + shape6[5];
+    f.scale = (float)((double)H / (double)f.hp);
+    f.ify = 1.0 / ((double)H / (double)f.hp);
+    f.ifx = 1.0 / ((double)W / (double)f.wp);
+    return f;
+}
+
+}  // namespace
+
+size_t warp_view_workspace_bytes() { return 4 * WP_PARTS * sizeof(float); }
+
+void launch_warp_normals(int V, int F, const double* verts, const int* faces, const int* vf_off, const int* vf_ent, double* fbuf,
+                         double* normals, hipStream_t st)
+{
+    if (F > 0) warp_face_kernel<<<wblocks(F), WP_BLOCK, 0, st>>>(F, verts, faces, fbuf);
+    warp_vertex_normal_kernel<<<wblocks(V), WP_BLOCK, 0, st>>>(V, vf_off, vf_ent, fbuf, normals);
+}
+
+void launch_warp_view(int H, int W, int V, const double* verts, const double* normals, const float* flow_f, const float* flow_b,
+                      const int* flow_shape, const float* depth_cur, const float* depth_next, const double* cam14,
+                      const double* params, void* workspace, double* row, hipStream_t st)
+{
+    float* parts = static_cast<float*>(workspace);
+    WarpView cam;
+    for (int i = 0; i < 9; ++i) cam.R[i] = cam14[i];
+    for (int i = 0; i < 3; ++i) cam.t[i] = cam14[9 + i];
+    cam.fx = cam14[12];
+    cam.fy = cam14[13];
+    WarpParams prm;
+    prm.normal_cos = params[0];
+    prm.edge_scalar = params[1];
+    prm.edge_threshold = params[2];
+    prm.bi_depth = params[3];
+    prm.bi_pix = params[4];
+    prm.max_move = params[5];
+    const WarpFlow ff = make_flow(flow_f, flow_shape, H, W), fb = make_flow(flow_b, flow_shape, H, W);
+    warp_depth_max_kernel<<<dim3(WP_PARTS, 2), WP_BLOCK, 0, st>>>(H * W, depth_cur, depth_next, parts);
+    warp_var_max_kernel<<<dim3(WP_PARTS, 2), WP_BLOCK, 0, st>>>(H, W, depth_cur, depth_next, parts);
+    if (V > 0)
+        warp_view_kernel<<<wblocks(V), WP_BLOCK, 0, st>>>(H, W, V, verts, normals, ff, fb, depth_cur, depth_next, parts, cam, prm, row);
+}
+
+void launch_warp_aggregate(int C, int V, const double* table, int min_observe, double* move, int* observed, int* count,
+                           unsigned char* valid, hipStream_t st)
+{
+    warp_aggregate_kernel<<<wblocks(V), WP_BLOCK, 0, st>>>(C, V, table, min_observe, move, observed, count, valid);
+}
+
+void launch_warp_smooth(int V, const int* off, const int* nbr, int sweeps, const double* in, double* out, double* tmp, hipStream_t st)
+{
+    // sweep s writes bufs[(sweeps - 1 - s) % 2], so the last one lands in `out`
+    double* b[2] = {out, tmp};
+    const double* src = in;
+    for (int s = 0; s < sweeps; ++s) {
+        const int k = (sweeps - 1 - s) & 1;
+        warp_smooth_kernel<<<wblocks(V), WP_BLOCK, 0, st>>>(V, off, nbr, src, b[k]);
+        src = b[k];
+    }
+}
+
+}  // namespace gsr

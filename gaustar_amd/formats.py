@@ -7,6 +7,8 @@ SuGaR / GauSTAR `{iter}.pt` checkpoints -- enough to render a real checkpoint wi
 * PLY: gaussian_splatting/scene/gaussian_model.py:177-250 (`save_ply` / `load_ply`): one `vertex` element of
   float32 properties x y z nx ny nz f_dc_0..2 f_rest_0..(3K-1) opacity scale_0..2 rot_0..3, binary little endian;
   f_rest is stored channel-major ([P,3,K] flattened); opacity is a logit, scales are logs, rot is unnormalised.
+* OBJ: the meshes gaustar_tools/warp_mesh.py:230 loads with trimesh (process=False, maintain_order=True) and :364-397
+  exports: `v x y z [r g b]` and triangular `f` lines, vertex order kept (load_obj / save_obj).
 * .pt: sugar_model.py:1313-1318 (`save_model`): {'state_dict': ..., extra keys}; state-dict entries `_points`,
   `_surface_mesh_faces`, `_scales`, `_quaternions`, `all_densities`, `_sh_coordinates_dc`, `_sh_coordinates_rest`,
   `surface_mesh_thickness`, `_delta_t`, `_delta_r`.
@@ -219,3 +221,60 @@ def save_sugar_checkpoint(path: str, verts, faces, raw_scales, raw_complex, dens
     ckpt = {"state_dict": {k: (v.detach().cpu() if hasattr(v, "detach") else v) for k, v in sd.items()}}
     ckpt.update(extra)
     torch.save(ckpt, path)
+
+
+# ---------------------------------------------------------------------------------------------- OBJ
+def load_obj(path: str):
+    """A triangle mesh from an OBJ file -> (verts [V,3] float64, faces [F,3] int64, colours [V,k] float64 or None), vertices
+    in file order (trimesh.load_mesh(process=False, maintain_order=True), warp_mesh.py:230).  `v x y z [r g b ...]` lines
+    (colours as written, kept when every vertex has the same number of them); `f` lines of three corners `a`, `a/b`, `a//c`
+    or `a/b/c` (1-based, negative = relative to the end); `vt`, `vn` and every other statement are skipped.  A face with
+    more than three corners raises ValueError."""
+    verts, cols, faces = [], [], []
+    with open(path) as fh:
+        for ln, line in enumerate(fh, 1):
+            parts = line.split()
+            if not parts:
+                continue
+            tag = parts[0]
+            if tag == "v":
+                vals = [float(x) for x in parts[1:]]
+                if len(vals) < 3:
+                    raise ValueError(f"{path}:{ln}: vertex with {len(vals)} coordinates")
+                verts.append(vals[:3])
+                cols.append(vals[3:])
+            elif tag == "f":
+                corners = parts[1:]
+                if len(corners) != 3:
+                    raise ValueError(f"{path}:{ln}: face with {len(corners)} corners (only triangles are supported)")
+                idx = []
+                for c in corners:
+                    i = int(c.split("/")[0])
+                    idx.append(i - 1 if i > 0 else len(verts) + i)
+                faces.append(idx)
+    v = np.asarray(verts, np.float64).reshape(-1, 3)
+    f = np.asarray(faces, np.int64).reshape(-1, 3)
+    if len(f) and (f.min() < 0 or f.max() >= len(v)):
+        raise ValueError(f"{path}: face index outside [1, {len(v)}]")
+    ncol = {len(c) for c in cols}
+    colours = np.asarray(cols, np.float64) if len(ncol) == 1 and ncol != {0} else None
+    return v, f, colours
+
+
+def _num(x: float) -> str:
+    return repr(float(x))          # the shortest string that reads back to the same double ('nan' for NaN)
+
+
+def save_obj(path: str, verts, faces, colours=None) -> None:
+    """Write `v x y z [colours...]` and `f a b c` (1-based) lines; floats as the shortest repr that reads back exactly."""
+    v = np.asarray(verts, np.float64)
+    f = np.asarray(faces, np.int64)
+    lines = []
+    if colours is None:
+        lines += ["v " + " ".join(map(_num, p)) for p in v.tolist()]
+    else:
+        c = np.asarray(colours, np.float64).reshape(len(v), -1)
+        lines += ["v " + " ".join(map(_num, p + q)) for p, q in zip(v.tolist(), c.tolist())]
+    lines += [f"f {a + 1} {b + 1} {c + 1}" for a, b, c in f.tolist()]
+    with open(path, "w") as fh:
+        fh.write("\n".join(lines) + "\n")

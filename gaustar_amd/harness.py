@@ -413,6 +413,13 @@ class SurfaceGaussians(nn.Module):
         from . import topology
         return topology.detect_topology_errors(self, cameras, gt_depth, **kw)
 
+    def warp_mesh(self, cameras, frames, **kw):
+        """The surface mesh moved to the next frame along the optical flow of `cameras` (warp_mesh.py:216-401):
+        warp.warp_mesh(vertices, faces, topology.rig_from_cameras(cameras), frames, **kw) (`rig` may be passed in kw)."""
+        from . import topology, warp
+        rig = kw.pop("rig", None) or topology.rig_from_cameras(cameras)
+        return warp.warp_mesh(self._points.detach(), self._surface_mesh_faces, rig, frames, **kw)
+
     # -------------------------------------------------------------------------------- rendering
     def _settings(self, camera: NerfCamera, bg: torch.Tensor, sh_degree: int):
         cam, view, proj, campos = camera.on_device(self.device)

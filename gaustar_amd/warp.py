@@ -1,0 +1,308 @@
+"""Scene-flow mesh warping to the next frame (gaustar_tools/warp_mesh.py:216-401, `warp_mesh_using_flow`) on the GPU.
+
+Between two frames the reference moves the refined mesh along the optical flow of every camera (train_seq.py:242-245); the
+warped `{f+interval:04d}/coarse_mesh/warp_smooth.obj` is the mesh the next frame starts from (train_seq.py:112).  The
+reference needs trimesh, cv2, open3d and pytorch3d for it and runs numpy loops per vertex.  Here it runs as HIP kernels
+(include/gsr.h, gsr_warp.hip) behind two calls:
+
+    res = warp_mesh(verts, faces, rig, frames)            # native: move_raw / _propagated / _smoothed [V,3] f64, counts
+    warp_mesh_using_flow(mesh_path, data_root, work_root, f_idx, interval=1)      # the reference's signature and files
+
+Vertex normals are computed once per warp.  Per camera: three launches reduce the two edge maps and write the camera's row
+[V,3] of a [C,V,3] table (the vertex's move, NaN where it is not visible); the RAFT flows are read raw, with the reference's
+pad and nearest resize fused into the lookup.  Cameras are sharded over ranks (sweep.camera_shard) and run `views_in_flight`
+at a time (pipelines.ViewPipelines); the rows come back with one all_gather (sweep.gather_rows).  Over the rig every rank runs
+the same deterministic passes on the same table: outlier removal and mean per vertex, 20 propagation sweeps (gsr_topo.hip's,
+one call per component), 5 smoothing sweeps.  Host synchronisations: ViewPipelines.run waits for the device before the
+cameras start and each pipeline waits for its stream once its cameras are done (with views_in_flight = 1 the cameras run on the
+calling stream without a wait), and warp_mesh waits for its stream once at the end.  The mesh's topology, neighbour lists and
+vertex-face lists are built (with host reads) on first use and kept on the faces tensor, as meshes.MeshTopology.of does.
+
+Only post_processing = 'mesh' (the reference's default) is implemented; 'voxel' and save_inter raise ValueError.  An isolated
+vertex (no neighbours) keeps its move through propagation and becomes NaN in smoothing, as np.average of an empty selection
+makes it; the reference raises IndexError there (its empty neighbour list is a float array).
+"""
+from __future__ import annotations
+
+import ctypes
+import json
+import os
+import threading
+from concurrent.futures import ThreadPoolExecutor
+from dataclasses import asdict, dataclass
+from typing import Callable, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import _lib, formats, sweep
+
+PROP_SWEEPS = 20     # mesh_vert_propagate(max_ite=20) (warp_mesh.py:384, :133)
+SMOOTH_SWEEPS = 5    # mesh_color_smoothing(ite_num=5) (:394)
+FLOW_DIRS = {1: "flow_bi", 2: "flow_bi_2f", 4: "flow_bi_4f", 6: "flow_bi_6f"}    # :242-251
+MAX_PREFETCH_THREADS = 8
+
+
+def _stream():
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _p(t: Optional[torch.Tensor]):
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+@dataclass
+class WarpConfig:
+    """warp_config (warp_mesh.py:14-25): fields and defaults of the reference."""
+    min_observe: int = 4
+    depth_edge_ker_size: int = 7
+    knn_K: int = 8
+    cmr_view_max_cos: float = -0.5
+    max_move_dist: float = 0.2
+    voxel_size: float = 0.04
+    bi_direct_pix_threshold: float = 4
+    bi_direct_depth_threshold: float = 0.004
+    edge_scalar: float = 10000
+    edge_threshold: float = 0.1
+    post_processing: str = "mesh"
+
+    def save_cfg(self, dir: str) -> None:
+        """The reference's config.json: every field, sorted keys, indent 4 (:27-45)."""
+        text = json.dumps(asdict(self), sort_keys=True, indent=4, separators=(",", ": "))
+        with open(os.path.join(dir, "config.json"), "w") as fh:
+            fh.write(text)
+
+    def params(self):
+        """The [host] parameter block of gsr_warp_view."""
+        return (ctypes.c_double * 6)(float(self.cmr_view_max_cos), float(self.edge_scalar), float(self.edge_threshold),
+                                     float(self.bi_direct_depth_threshold), float(self.bi_direct_pix_threshold),
+                                     float(self.max_move_dist))
+
+
+@dataclass
+class MeshWarp:
+    """move_raw [V,3] f64: the rig mean after outlier removal, 0 where count < min_observe (warp_{f:04d}.obj);
+    move_propagated (warp_mesh_prop.obj) and move_smoothed (warp_smooth.obj) [V,3] f64; verts_raw / verts_propagated /
+    verts_smoothed = verts + the move; observed [V] int32: cameras that see the vertex; count [V] int32: after outlier
+    removal (the one :384 uses).  With return_stages: table [C,V,3] f64 (NaN = not visible) and normals [V,3] f64."""
+    move_raw: torch.Tensor
+    move_propagated: torch.Tensor
+    move_smoothed: torch.Tensor
+    verts_raw: torch.Tensor
+    verts_propagated: torch.Tensor
+    verts_smoothed: torch.Tensor
+    observed: torch.Tensor
+    count: torch.Tensor
+    table: Optional[torch.Tensor] = None
+    normals: Optional[torch.Tensor] = None
+
+
+def _cam14(extr: np.ndarray, intr: np.ndarray):
+    vals = list(np.asarray(extr[:3, :3], np.float64).reshape(-1)) + list(np.asarray(extr[:3, 3], np.float64)) + \
+        [float(intr[0, 0]), float(intr[1, 1])]
+    return (ctypes.c_double * 14)(*vals)
+
+
+_VF_ATTR = "_gsr_warp_vertex_faces"
+
+
+def vertex_face_csr(topo):
+    """(offsets [V+1], entries [3F]) int32 for a meshes.MeshTopology: every vertex's incidences face * 3 + corner in ascending
+    face order.  Built once per MeshTopology."""
+    c = getattr(topo, _VF_ATTR, None)
+    if c is not None:
+        return c
+    flat = topo.faces.reshape(-1).long()
+    _, order = torch.sort(flat, stable=True)          # face-major input: a stable sort keeps ascending faces per vertex
+    counts = torch.bincount(flat, minlength=topo.V)
+    off = torch.cat([torch.zeros(1, dtype=torch.long, device=flat.device), torch.cumsum(counts, 0)])
+    c = (off.int().contiguous(), order.int().contiguous())
+    setattr(topo, _VF_ATTR, c)
+    return c
+
+
+def _pad6(flow: torch.Tensor, pad):
+    p = (0, 0, 0, 0) if pad is None else tuple(int(x) for x in np.int32(np.asarray(pad, np.float64)).reshape(-1))
+    if len(p) != 4:
+        raise ValueError(f"pad must be (top, bottom, left, right), got {pad!r}")
+    return (ctypes.c_int * 6)(int(flow.shape[0]), int(flow.shape[1]), *p)
+
+
+@torch.no_grad()
+def warp_mesh(verts, faces, rig: dict, frames: Callable[[int], tuple], cfg: WarpConfig = WarpConfig(), pad=None,
+              views_in_flight: int = 2, rank: Optional[int] = None, world: Optional[int] = None,
+              return_stages: bool = False, device=None) -> MeshWarp:
+    """warp_mesh_using_flow's computation (warp_mesh.py:259-397) for the mesh (verts [V,3], faces [F,3]; numpy or torch) seen
+    by the cameras of `rig` (the `cmr` dict: intrinsics [C,3,3], extrinsics [C,4,4] COLMAP world-to-camera, shape [C,2] =
+    (H, W)).  frames(i) -> (flow_f, flow_b, depth_cur, depth_next) for camera i, on any device: the raw RAFT flows [h,w,2]
+    in (x, y) order and the depth maps [H,W] of frames f and f + interval; called once per camera of this rank's shard.
+    pad: (top, bottom, left, right) of the flows (pad.txt), or None."""
+    from . import pipelines
+    if cfg.post_processing != "mesh":
+        raise ValueError(f"warp_mesh: post_processing={cfg.post_processing!r} is not implemented (only 'mesh')")
+    lib = _lib.load()
+    if device is None:
+        device = verts.device if isinstance(verts, torch.Tensor) and verts.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("warp_mesh needs a GPU")
+    from . import meshes, topology
+    v = torch.as_tensor(np.asarray(verts) if not isinstance(verts, torch.Tensor) else verts).to(dev, torch.float64).contiguous()
+    if v.dim() != 2 or v.shape[1] != 3:
+        raise ValueError(f"verts must be [V,3], got {tuple(v.shape)}")
+    V = int(v.shape[0])
+    ft = faces if isinstance(faces, torch.Tensor) and faces.device == dev and faces.dtype == torch.long else \
+        torch.as_tensor(np.asarray(faces) if not isinstance(faces, torch.Tensor) else faces).to(dev, torch.long)
+    topo = meshes.MeshTopology.of(ft, V)        # (cached on a faces tensor that is passed again)
+    f, F = topo.faces, topo.F
+    C = int(np.asarray(rig["shape"]).shape[0])
+    stream = _stream()
+
+    # ---- once per warp: world-space vertex normals
+    vf_off, vf_ent = vertex_face_csr(topo)
+    fbuf = torch.empty(max(F, 1), 6, dtype=torch.float64, device=dev)
+    normals = torch.empty(V, 3, dtype=torch.float64, device=dev)
+    _lib.check(lib.gsr_vertex_normals(V, F, _p(v), _p(f), _p(vf_off), _p(vf_ent), _p(fbuf), _p(normals), stream),
+               "gsr_vertex_normals")
+
+    # ---- per camera: one row [V,3] of the table
+    mine = sweep.camera_shard(C, rank, world)
+    local = torch.empty(len(mine), 3 * V, dtype=torch.float64, device=dev)
+    ws_bytes = int(lib.gsr_warp_view_workspace_bytes(1, 1))
+    params = cfg.params()
+
+    def to_dev(x, name, i):
+        t = torch.as_tensor(x) if not isinstance(x, torch.Tensor) else x
+        if name.startswith("depth") and t.dim() == 3:
+            t = t[..., 0]
+        return t.to(device=dev, dtype=torch.float32).contiguous()
+
+    def work(_t, j):
+        i = mine[j]
+        ff, fb, dc, dn = (to_dev(x, n, i) for x, n in zip(frames(i), ("flow_f", "flow_b", "depth_cur", "depth_next")))
+        H, W = int(rig["shape"][i][0]), int(rig["shape"][i][1])
+        if tuple(dc.shape) != (H, W) or tuple(dn.shape) != (H, W):
+            raise ValueError(f"camera {i}: depth {tuple(dc.shape)} / {tuple(dn.shape)} vs rig shape {(H, W)}")
+        if ff.dim() != 3 or ff.shape[2] != 2 or ff.shape != fb.shape:
+            raise ValueError(f"camera {i}: flows must be [h,w,2] of one shape, got {tuple(ff.shape)} / {tuple(fb.shape)}")
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        _lib.check(lib.gsr_warp_view(H, W, V, _p(v), _p(normals), _p(ff), _p(fb), _pad6(ff, pad), _p(dc), _p(dn),
+                                     _cam14(rig["extrinsics"][i], rig["intrinsics"][i]), params, _p(ws), _p(local[j]),
+                                     _stream()), "gsr_warp_view")
+
+    if views_in_flight > 1 and len(mine) > 1:
+        pipelines.ViewPipelines(min(int(views_in_flight), len(mine)), dev).run(work, list(range(len(mine))))
+    else:
+        for j in range(len(mine)):
+            work(0, j)
+    table = sweep.gather_rows(local, C, rank, world)
+
+    # ---- over the rig (every rank, same table, same bits)
+    stream = _stream()
+    move = torch.empty(V, 3, dtype=torch.float64, device=dev)
+    observed = torch.empty(V, dtype=torch.int32, device=dev)
+    count = torch.empty(V, dtype=torch.int32, device=dev)
+    valid = torch.empty(V, dtype=torch.uint8, device=dev)
+    _lib.check(lib.gsr_warp_aggregate(C, V, _p(table.contiguous()), int(cfg.min_observe), _p(move), _p(observed), _p(count),
+                                      _p(valid), stream), "gsr_warp_aggregate")
+    off, nbr = topology.vertex_neighbours(topo)
+    # propagation: the valid set evolves independently of the values, so one scalar call per component is the vector result
+    comp = move.t().contiguous()
+    prop_c = torch.empty_like(comp)
+    tmp = torch.empty(V, dtype=torch.float64, device=dev)
+    va, vb = torch.empty_like(valid), torch.empty_like(valid)
+    for k in range(3):
+        _lib.check(lib.gsr_topo_propagate(V, _p(off), _p(nbr), PROP_SWEEPS, _p(comp[k]), _p(valid), _p(prop_c[k]), _p(tmp), _p(va),
+                                          _p(vb), stream), "gsr_topo_propagate")
+    prop = prop_c.t().contiguous()
+    smooth = torch.empty_like(prop)
+    stmp = torch.empty_like(prop)
+    _lib.check(lib.gsr_warp_smooth(V, _p(off), _p(nbr), SMOOTH_SWEEPS, _p(prop), _p(smooth), _p(stmp), stream), "gsr_warp_smooth")
+    res = MeshWarp(move_raw=move, move_propagated=prop, move_smoothed=smooth, verts_raw=v + move, verts_propagated=v + prop,
+                   verts_smoothed=v + smooth, observed=observed, count=count)
+    if return_stages:
+        res.table, res.normals = table.view(C, V, 3), normals
+    torch.cuda.current_stream().synchronize()
+    return res
+
+
+class _Prefetch:
+    """Loads frames(i) for the cameras in `order` on a bounded thread pool, at most `depth` cameras ahead of the consumer, so
+    that npz decompression overlaps the GPU."""
+
+    def __init__(self, load: Callable[[int], tuple], order: Sequence[int], threads: int, depth: int):
+        self.load, self.order, self.depth = load, list(order), depth
+        self.pool = ThreadPoolExecutor(max_workers=threads)
+        self.futures = {}
+        self.next = 0
+        self.lock = threading.Lock()
+
+    def _fill(self, upto: int):
+        while self.next < len(self.order) and self.next <= upto:
+            i = self.order[self.next]
+            self.futures[i] = self.pool.submit(self.load, i)
+            self.next += 1
+
+    def __call__(self, i: int):
+        with self.lock:
+            pos = self.order.index(i)
+            self._fill(pos + self.depth)
+            fut = self.futures.pop(i)
+        return fut.result()
+
+    def close(self):
+        self.pool.shutdown(wait=True, cancel_futures=True)
+
+
+def warp_mesh_using_flow(mesh_path, data_root, work_root, f_idx, interval=1, cmr=None, save_inter=False, from_humanrf=False,
+                         views_in_flight: int = 2, prefetch_threads: int = MAX_PREFETCH_THREADS) -> MeshWarp:
+    """warp_mesh.py:216-401 with the reference's signature, files and errors.  Paths are joined by concatenation as in the
+    reference (data_root and work_root end with '/').  Reads rgb_cameras.npz (unless cmr is given), the mesh (OBJ, vertex
+    order kept), {f:04d}/{flow_dir}/pad.txt and {c:04d}_{f,b}.npz ('flow'), {f:04d}/depth[_humanrf]/img_{c:04d}_depth.npz and
+    the same for f + interval ('depth').  Writes config.json, warp_{f:04d}.obj, warp_mesh_prop.obj and warp_smooth.obj
+    under {f+interval:04d}/coarse_mesh/ (the last two with the input's vertex colours).  Every input is checked before the
+    first launch.  save_inter=True raises ValueError."""
+    if save_inter:
+        raise ValueError("warp_mesh_using_flow: save_inter=True is not implemented")
+    if cmr is None:
+        cmr = np.load(data_root + "rgb_cameras.npz")
+    rig = {k: np.asarray(cmr[k]) for k in ("intrinsics", "extrinsics", "shape")}
+    C = int(rig["shape"].shape[0])
+    cfg = WarpConfig()
+    out_dir = work_root + f"{(f_idx + interval):04d}/coarse_mesh/"
+    os.makedirs(out_dir, exist_ok=True)
+    cfg.save_cfg(out_dir)
+    verts, faces, colours = formats.load_obj(mesh_path)
+    if interval not in FLOW_DIRS:
+        raise RuntimeError("Interval Error!")
+    flow_dir = data_root + f"{f_idx:04d}/{FLOW_DIRS[interval]}/"
+    label = "_humanrf" if from_humanrf else ""
+    pad_path = flow_dir + "pad.txt"
+    pad = np.int32(np.loadtxt(pad_path)) if os.path.exists(pad_path) else None
+    for c in range(C):
+        if not os.path.exists(flow_dir + f"{c:04d}_f.npz"):
+            raise RuntimeError("Flow not found!")
+        if not os.path.exists(data_root + f"{f_idx:04d}/depth{label}/img_{c:04d}_depth.npz"):
+            raise RuntimeError("Depth not found!")
+
+    def load(c):
+        ff = np.load(flow_dir + f"{c:04d}_f.npz")["flow"]
+        fb = np.load(flow_dir + f"{c:04d}_b.npz")["flow"]
+        dc = np.load(data_root + f"{f_idx:04d}/depth{label}/img_{c:04d}_depth.npz")["depth"]
+        dn = np.load(data_root + f"{(f_idx + interval):04d}/depth{label}/img_{c:04d}_depth.npz")["depth"]
+        return tuple(torch.from_numpy(np.ascontiguousarray(x, np.float32)).pin_memory() for x in (ff, fb, dc, dn))
+
+    mine = sweep.camera_shard(C)
+    threads = max(1, min(MAX_PREFETCH_THREADS, int(prefetch_threads), len(mine)))
+    pre = _Prefetch(load, mine, threads, depth=threads + max(1, int(views_in_flight)))   # (each camera pins ~40 MB at 1080p)
+    try:
+        res = warp_mesh(verts, faces, rig, pre, cfg, pad=pad, views_in_flight=views_in_flight)
+    finally:
+        pre.close()
+    formats.save_obj(out_dir + f"warp_{f_idx:04d}.obj", res.verts_raw.cpu().numpy(), faces)
+    formats.save_obj(out_dir + "warp_mesh_prop.obj", res.verts_propagated.cpu().numpy(), faces, colours)
+    formats.save_obj(out_dir + "warp_smooth.obj", res.verts_smoothed.cpu().numpy(), faces, colours)
+    return res
+
+
+__all__ = ["WarpConfig", "MeshWarp", "warp_mesh", "warp_mesh_using_flow", "vertex_face_csr"]

@@ -453,6 +453,45 @@ int gsr_topo_voxel_interp(int V, const float* verts, const float* vmin, double v
 int gsr_topo_faces(int F, const int* faces, const double* value, unsigned char* face_colour, float* face_loss,
                    gsr_stream_t stream);
 
+/* ---- Scene-flow mesh warping to the next frame (gaustar_tools/warp_mesh.py:216-401 `warp_mesh_using_flow`, post_processing
+ * 'mesh', as train_seq.py:242-245 calls it).  All device pointers unless marked [host]; every call is asynchronous on
+ * `stream`, none synchronises the host, and none uses float atomics (outputs are bitwise reproducible).
+ * gsr_vertex_normals: trimesh Trimesh.vertex_normals (warp_mesh.py:291-293) of verts [V,3] double, faces [F,3] int32:
+ *   per face the unit normal of cross(b - a, c - b) (zero if its norm is <= 1e-12) and the corner angles, per vertex their
+ *   angle-weighted sum in ascending face order, unitised (a zero sum stays zero).  vf_offsets [V+1], vf_entries [3F] int32:
+ *   the vertex's incidences face * 3 + corner, vertex-major, ascending face order.  face_scratch [F,6] double.
+ *   Writes normals [V,3] double.
+ * gsr_warp_view: one camera (warp_mesh.py:263-340), three launches.  depth_cur, depth_next [H,W] f32 (frames f and
+ *   f + interval); flow_f, flow_b: the raw RAFT flows [h,w,2] f32 in (x, y) order; flow_shape: [host] 6 ints = h, w and the
+ *   zero padding top, bottom, left, right (pad.txt truncated to int32; zeros when there is none).  pad_and_resize_flow
+ *   (:96-103) is fused into the reads: scale f32(H / h_padded), nearest source pixel min(floor(x / (W / w_padded)),
+ *   w_padded - 1) per axis.  Edge maps: get_depth_edge(depth, 7) (:120-130, 7x7 box filter, reflect-101 border),
+ *   edge_vis = min(var / max(var) edge_scalar, 1) in f32 (:298, :313).  cam: [host] 14 doubles = the COLMAP world-to-camera
+ *   rotation row-major (9), translation (3), fx, fy.  params: [host] 6 doubles = warp_config's cmr_view_max_cos,
+ *   edge_scalar, edge_threshold, bi_direct_depth_threshold, bi_direct_pix_threshold, max_move_dist (:14-25).  verts [V,3]
+ *   double, normals [V,3] double (gsr_vertex_normals).  Writes row [V,3] double: the vertex's move where it passes every
+ *   test of :295-328 (valid lookup, |z - depth_cur| < 0.005, camera-space normal z < cmr_view_max_cos, edge_vis <
+ *   edge_threshold, the f32 depth and f64 pixel round trips, edge_vis of the next frame, a valid depth_next below 10 and
+ *   |move| < max_move_dist), NaN in all three where it does not.  A camera with no depth below 10, or with max(var) = 0, in
+ *   either frame sees nothing.  workspace: gsr_warp_view_workspace_bytes(H, W) bytes, one per view in flight.
+ * gsr_warp_aggregate: table [C,V,3] (the rows of all cameras, camera order) -> observed [V] int32 (cameras that see the
+ *   vertex), count [V] int32 (after remove_outlier, :174-181 and :351-358; = observed where observed < min_observe), move
+ *   [V,3] double = the mean of the kept moves where count >= min_observe, else 0; valid [V] uint8 = count >= min_observe.
+ *   Propagation (:384) is gsr_topo_propagate on each component with this valid mask.
+ * gsr_warp_smooth: mesh_color_smoothing (:158-171) as `sweeps` Jacobi sweeps over value [V,3] double and the neighbour list
+ *   of gsr_topo_propagate: every vertex takes the mean of all its neighbours; one without neighbours becomes NaN.  value_in
+ *   is not modified; value_out receives the result; value_tmp [V,3] double is scratch. */
+int gsr_vertex_normals(int V, int F, const double* verts, const int* faces, const int* vf_offsets, const int* vf_entries,
+                       double* face_scratch, double* normals, gsr_stream_t stream);
+size_t gsr_warp_view_workspace_bytes(int H, int W);
+int gsr_warp_view(int H, int W, int V, const double* verts, const double* normals, const float* flow_f, const float* flow_b,
+                  const int* flow_shape, const float* depth_cur, const float* depth_next, const double* cam,
+                  const double* params, void* workspace, double* row, gsr_stream_t stream);
+int gsr_warp_aggregate(int C, int V, const double* table, int min_observe, double* move, int* observed, int* count,
+                       unsigned char* valid, gsr_stream_t stream);
+int gsr_warp_smooth(int V, const int* nbr_offsets, const int* nbr, int sweeps, const double* value_in, double* value_out,
+                    double* value_tmp, gsr_stream_t stream);
+
 /* Tuning aid: when device_buffer is non-NULL (4*T uint64), the two blend kernels record the start/end wall
  * clock (100 MHz) of every workgroup: forward at [2*b], backward at [2*(T+b)], b = launch index.  NULL = off. */
 int gsr_debug_set_trace(void* device_buffer);
