@@ -104,6 +104,13 @@ SIGNATURES = {
                                      c_float, c_float, c_float, c_void_p, c_void_p, c_void_p]),
     "gsr_mesh_reg_backward": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_float, c_float, c_float, c_void_p, c_void_p, c_int, c_void_p]),
+    # regularisers on the Gaussians' own parameters (refine.py:739-748, :663-669): losses.gaussian_param_loss
+    "gsr_param_reg_workspace_bytes": (c_size_t, [c_int]),
+    "gsr_param_reg_forward": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_longlong, c_longlong, c_float, c_float,
+                                      c_void_p, c_float, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
+    "gsr_param_reg_backward": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_longlong, c_longlong, c_float, c_float,
+                                       c_void_p, c_float, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_int, c_void_p]),
     # rig-wide topology-error detection (refined_mesh.py:697-920): gaustar_amd.topology
     "gsr_topo_view_workspace_bytes": (c_size_t, [c_int, c_int]),
     "gsr_topo_view": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, POINTER(c_double), c_void_p,

@@ -1241,6 +1241,60 @@ int gsr_mesh_reg_backward(int V, int F, int E, int Q, const float* verts, const 
     return 0;
 }
 
+size_t gsr_param_reg_workspace_bytes(int N)
+{
+    (void)N;   // (the partials of at most 2048 workgroups, whatever the model)
+    return param_reg_workspace_bytes();
+}
+
+static int param_reg_check(const char* fn, int N, int M, const float* weight, long long w_rs, long long w_cs)
+{
+    char msg[160];
+    if (N < 0 || M < 0 || M > N) { snprintf(msg, sizeof msg, "%s: need 0 <= M <= N", fn); return fail_msg(msg); }
+    if (N >= (1 << 29)) { snprintf(msg, sizeof msg, "%s: too many Gaussians", fn); return fail_msg(msg); }
+    if (weight && (w_rs < 0 || w_cs < 0)) { snprintf(msg, sizeof msg, "%s: negative weight stride", fn); return fail_msg(msg); }
+    return 0;
+}
+
+int gsr_param_reg_forward(int N, int M, const float* delta_t, const float* delta_r, const float* weight, long long w_row_stride,
+                          long long w_col_stride, float factor_t, float factor_r, const float* densities, float min_opacity,
+                          const float* sh_dc, const float* pre_sh_dc, float sh_factor, void* workspace, float* loss_out,
+                          gsr_stream_t stream)
+{
+    g_err.clear();
+    if (int rc = param_reg_check("gsr_param_reg_forward", N, M, weight, w_row_stride, w_col_stride)) return rc;
+    if (!workspace || !loss_out) return fail_msg("gsr_param_reg_forward: required pointer is null");
+    hipStream_t st = (hipStream_t)stream;
+    {
+        Scope sc(ST_LOSS, st);
+        launch_param_reg(N, M, delta_t, delta_r, weight, w_row_stride, w_col_stride, factor_t, factor_r, densities, min_opacity,
+                         sh_dc, pre_sh_dc, sh_factor, workspace, loss_out, st);
+    }
+    GSR_CHECK_LAUNCH("param_reg forward kernels");
+    return 0;
+}
+
+int gsr_param_reg_backward(int N, int M, const float* delta_t, const float* delta_r, const float* weight, long long w_row_stride,
+                           long long w_col_stride, float factor_t, float factor_r, const float* densities, float min_opacity,
+                           const float* sh_dc, const float* pre_sh_dc, float sh_factor, const float* grad_scale,
+                           float* dL_ddelta_t, float* dL_ddelta_r, float* dL_ddensities, float* dL_dsh_dc, int accumulate,
+                           gsr_stream_t stream)
+{
+    g_err.clear();
+    if (int rc = param_reg_check("gsr_param_reg_backward", N, M, weight, w_row_stride, w_col_stride)) return rc;
+    if (accumulate != 0 && accumulate != 1) return fail_msg("gsr_param_reg_backward: accumulate must be 0 or 1");
+    if (N == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    {
+        Scope sc(ST_LOSS, st);
+        launch_param_reg_grad(N, M, delta_t, delta_r, weight, w_row_stride, w_col_stride, factor_t, factor_r, densities,
+                              min_opacity, sh_dc, pre_sh_dc, sh_factor, grad_scale, dL_ddelta_t, dL_ddelta_r, dL_ddensities,
+                              dL_dsh_dc, accumulate, st);
+    }
+    GSR_CHECK_LAUNCH("param_reg_bwd_kernel");
+    return 0;
+}
+
 size_t gsr_topo_view_workspace_bytes(int H, int W)
 {
     (void)H; (void)W;   // (the partial maxima of a fixed number of workgroups, whatever the image)

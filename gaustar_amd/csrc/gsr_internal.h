@@ -359,6 +359,17 @@ void launch_mesh_reg_grad(int V, int F, int E, int Q, const float* verts, const 
                           const int* offsets, const int* entries, const float* ref_edge, const float* ref_area, float nc_factor,
                           float edge_factor, float area_factor, const float* scale, float* grad, int accumulate, hipStream_t st);
 
+// regularisers on the Gaussians' own parameters (gsr_param_reg.hip)
+size_t param_reg_workspace_bytes();
+void launch_param_reg(int N, int M, const float* delta_t, const float* delta_r, const float* weight, long long w_rs,
+                      long long w_cs, float factor_t, float factor_r, const float* densities, float min_opacity,
+                      const float* sh_dc, const float* pre_sh_dc, float sh_factor, void* workspace, float* loss_out,
+                      hipStream_t st);
+void launch_param_reg_grad(int N, int M, const float* delta_t, const float* delta_r, const float* weight, long long w_rs,
+                           long long w_cs, float factor_t, float factor_r, const float* densities, float min_opacity,
+                           const float* sh_dc, const float* pre_sh_dc, float sh_factor, const float* scale, float* d_delta_t,
+                           float* d_delta_r, float* d_densities, float* d_sh_dc, int accumulate, hipStream_t st);
+
 // rig-wide topology-error detection (gsr_topo.hip)
 size_t topo_view_workspace_bytes();
 void launch_topo_view(int H, int W, int V, const float* verts, const float* gt, const float* render, const float* surface,

@@ -208,6 +208,11 @@ class _RenderMeshBound(torch.autograd.Function):
         d_dc, d_rest, _, d_dens = producers._sh_backward_raw(points, _rasterizer._dev_f32(st.campos, points.device), dc, rest, D, M,
                                                              _rasterizer._dev_f32(view, points.device), cfg["depth_channels"], d_colors, opac, d_opac,
                                                              dpos_inout=d_points, out=(o_dc, o_rest if M > 1 else None, o_dens))
+        # (SurfaceGaussians.rgbd_step(param_reg=...): the parameter regularisers' share lands in the same buffers, before a sink
+        # hears that they are final)
+        hook = cfg.get("sh_grad_hook")
+        if hook is not None:
+            hook(d_dc, d_dens)
         if sink is not None:
             sink.written([p for p, o in ((p_dc, o_dc), (p_rest, o_rest if M > 1 else None), (p_dens, o_dens)) if o is not None])
         o_mesh = (buf(p_verts), buf(p_rs), buf(p_rc), buf(p_dt), buf(p_dr))
@@ -221,6 +226,9 @@ class _RenderMeshBound(torch.autograd.Function):
         hook = cfg.get("verts_grad_hook")
         if hook is not None and d_verts is not None:
             hook(d_verts)
+        hook = cfg.get("delta_grad_hook")
+        if hook is not None and d_dt is not None and d_dr is not None:
+            hook(d_dt, d_dr)
         if sink is not None:
             sink.written([p for p, o in zip((p_verts, p_rs, p_rc, p_dt, p_dr), o_mesh) if o is not None and p is not None])
         # (sink views go back to autograd as FRESH tensor objects: AccumulateGrad adopts an incoming gradient as p.grad only
@@ -266,6 +274,8 @@ class SurfaceGaussians(nn.Module):
         if loose_bind:
             self._delta_t = nn.Parameter(torch.zeros(N, 3, device=dev))
             self._delta_r = nn.Parameter(torch.tensor([1.0, 0.0, 0.0, 0.0], device=dev).repeat(N, 1))
+        # refine.py:737's per-Gaussian weight of the loose-bind penalties; not saved, as in the reference
+        self.register_buffer("unbind_loss_weight", None, persistent=False)
         self._geom_cache = None
         # optional: an object with grad_views() / written(params) (gaustar_amd.dist.ShardedAdam) that receives the parameter
         # gradients of render_channels' backward in place -- see _RenderMeshBound.backward
@@ -295,6 +305,70 @@ class SurfaceGaussians(nn.Module):
             if m._loose_bind:
                 m._delta_t.copy_(ckpt["delta_t"]); m._delta_r.copy_(ckpt["delta_r"])
         return m
+
+    # -------------------------------------------------------------------------------- loose binding on a live model
+    def is_loose_bind(self) -> bool:      # sugar_model.py:602-603
+        return self._loose_bind
+
+    def loose_bind(self, unbind_weight: Optional[torch.Tensor] = None):
+        """sugar_model.py:596-597 on a live model: from now on `_delta_t` / `_delta_r` move the Gaussians off their faces.
+        A model built without them gets `_delta_t` = 0 and `_delta_r` = identity here, as nn.Parameters under the
+        reference's names; they are returned so that an optimiser can take them in (loose_bind_param_groups) -- an empty
+        list if they existed.  unbind_weight ([N], [N,1] or [N,3]; refine.py:737) becomes `unbind_loss_weight`, kept as it
+        is laid out (an expanded view stays one)."""
+        new = []
+        if getattr(self, "_delta_t", None) is None:
+            N, dev = self.n_points, self.device
+            self._delta_t = nn.Parameter(torch.zeros(N, 3, device=dev))
+            self._delta_r = nn.Parameter(torch.tensor([1.0, 0.0, 0.0, 0.0], device=dev).repeat(N, 1))
+            new = [self._delta_t, self._delta_r]
+        self._loose_bind = True
+        self._geom_cache = None
+        if unbind_weight is not None:
+            w = torch.as_tensor(unbind_weight).detach().to(device=self.device, dtype=torch.float32)
+            if w.dim() not in (1, 2) or w.size(0) != self.n_points or (w.dim() == 2 and w.size(1) not in (1, 3)):
+                raise ValueError(f"unbind_weight must have dimensions (N,), (N, 1) or (N, 3) with N = {self.n_points}, "
+                                 f"got {tuple(w.shape)}")
+            self.unbind_loss_weight = w
+        return new
+
+    def rebind(self) -> None:
+        """sugar_model.py:599-600: the deltas stay (parameters and values) and are ignored again."""
+        self._loose_bind = False
+        self._geom_cache = None
+
+    def loose_bind_param_groups(self, position_lr: float, rotation_lr: float):
+        """The two groups of sugar_optimizer.py:86-87, for `optimizer.add_param_group` (torch.optim.Adam, optim.Adam,
+        dist.ShardedAdam -- there between step() and the next backward, on every rank)."""
+        if getattr(self, "_delta_t", None) is None:
+            raise RuntimeError("loose_bind_param_groups: the model has no deltas yet -- call loose_bind() first")
+        return [{"params": [self._delta_t], "lr": float(position_lr), "name": "delta_t"},
+                {"params": [self._delta_r], "lr": float(rotation_lr), "name": "delta_r"}]
+
+    def apply_topology_result(self, res, optimizer=None, min_changed: int = 100, position_lr: float = 0.0,
+                              rotation_lr: float = 0.0) -> bool:
+        """refine.py:729-737 on the result of detect_topology_errors: with fewer than `min_changed` Gaussians of weight 0
+        nothing changes (-> False); otherwise the model is loose-bound with res.unbind_weight, the parameters this created
+        join `optimizer` (if given) as loose_bind_param_groups(position_lr, rotation_lr), -> True."""
+        n = getattr(res, "topo_change_num", None)
+        if n is None:
+            w = res.unbind_weight
+            n = int(((w if w.dim() == 1 else w[:, 0]) == 0).sum())
+        if int(n) < int(min_changed):
+            return False
+        new = self.loose_bind(res.unbind_weight)
+        if optimizer is not None and new:
+            for g in self.loose_bind_param_groups(position_lr, rotation_lr):
+                optimizer.add_param_group(g)
+        return True
+
+    def face_delta(self) -> torch.Tensor:
+        """sugar_model.py:605-611 `get_face_delta`: [F,1], the norm of each face's mean `_delta_t`."""
+        if not self._loose_bind:
+            raise RuntimeError("face_delta: the model is not loose-bound")
+        self._fence(self._delta_t)
+        d = self._delta_t.detach().reshape(-1, self.n_gaussians_per_surface_triangle, 3)
+        return d.mean(dim=1).norm(dim=1, keepdim=True)
 
     def grad_ready_order(self):
         """The optimiser's parameters (sugar_optimizer.py:67-87) in the order their gradients become final in the backward
@@ -542,7 +616,7 @@ class SurfaceGaussians(nn.Module):
 
     def rgbd_step(self, camera: NerfCamera, bg: torch.Tensor, gt_rgb: torch.Tensor, gt_depth: torch.Tensor, max_depth: float,
                   dssim_factor: float = 0.2, depth_factor: float = 1.0, mask_factor: float = 1.0, grad_scale: Optional[torch.Tensor] = None,
-                  sh_deg: Optional[int] = None, mesh_reg: Optional[dict] = None):
+                  sh_deg: Optional[int] = None, mesh_reg: Optional[dict] = None, param_reg: Optional[dict] = None):
         """One refinement iteration's render + image losses + backward WITHOUT an autograd graph: the 4-channel render of
         render_channels(depth_channels=1), losses.rgb_depth_loss on it and both backward passes, run back to back through the very
         functions the autograd path runs (the two Functions' forward / backward bodies, called directly); the parameters' `.grad`
@@ -554,7 +628,13 @@ class SurfaceGaussians(nn.Module):
         (nc_factor, ref_edge_len, edge_factor, ref_area, area_factor; `topology` defaults to mesh_topology()): their forward
         and backward run in the same step, their vertex gradient is added to the mesh producer's in its own buffer, and the
         returned loss is the image losses + their total -- what `(rgb_depth_loss(...) + surface_mesh_loss(...)).backward()`
-        gives.  None (default): the image losses alone, as before."""
+        gives.  None (default): the image losses alone, as before.
+        param_reg: the regularisers on the Gaussians' own parameters (refine.py:739-748, :663-669) as the scalar keyword
+        arguments of losses.gaussian_param_loss (factor_t, factor_r, min_opacity -- None switches the opacity term off --,
+        sh_factor) plus optional `pre_sh_dc` (without it there is no SH term) and `weight` (default: unbind_loss_weight).  The
+        tensors are the model's own parameters; the loose-bind terms are on only while is_loose_bind().  Forward and backward
+        run in the same step, the gradients are added in place to the buffers the render's backward fills (before a sink
+        hears of them) and the total to the returned loss.  None (default): the step as before."""
         from . import losses as _losses
         with torch.no_grad():
             cfg = self._channels_cfg(camera, bg, sh_deg, 1, True)
@@ -571,6 +651,23 @@ class SurfaceGaussians(nn.Module):
                     kw.pop("ref_area", None), float(kw.pop("area_factor", 0.0)))
                 if kw:
                     raise TypeError(f"mesh_reg: unexpected keys {sorted(kw)}")
+            if param_reg is not None:
+                kw = dict(param_reg)
+                loose = self._loose_bind
+                min_op, pre = kw.pop("min_opacity", 0.8), kw.pop("pre_sh_dc", None)
+                weight = kw.pop("weight", None)
+                if weight is None:
+                    weight = getattr(self, "unbind_loss_weight", None)
+                p_dt, p_dr = (self._delta_t, self._delta_r) if loose else (None, None)
+                p_dens = self.all_densities if min_op is not None else None
+                p_dc = self._sh_coordinates_dc if pre is not None else None
+                need = lambda p: p is not None and p.requires_grad
+                pctx = _PlainCtx((need(p_dt), need(p_dr), False, False, False, need(p_dens), False, need(p_dc), False, False))
+                preg_total, _preg_parts = _losses._GaussianParamLoss.forward(
+                    pctx, p_dt, p_dr, weight if loose else None, float(kw.pop("factor_t", 100.0)), float(kw.pop("factor_r", 1.0)), p_dens, 0.0 if min_op is None else float(min_op),
+                    p_dc, pre, float(kw.pop("sh_factor", 1.0)))
+                if kw:
+                    raise TypeError(f"param_reg: unexpected keys {sorted(kw)}")
             lctx = _PlainCtx((True,) + (False,) * 7)
             loss, _parts = _losses._RGBDepthLoss.forward(lctx, image, gt_rgb, gt_depth, float(dssim_factor), None, float(max_depth),
                                                         float(depth_factor), float(mask_factor))
@@ -583,6 +680,14 @@ class SurfaceGaussians(nn.Module):
                 loss = loss + reg_total
                 if mctx.saved_tensors:
                     cfg["verts_grad_hook"] = lambda dv: _losses._SurfaceMeshLoss.grad_into(mctx, grad_scale, dv, 1)
+            if param_reg is not None:
+                loss = loss + preg_total
+                if pctx.saved_tensors:
+                    on = lambda p, buf: buf if (p is not None and p.requires_grad) else None
+                    cfg["sh_grad_hook"] = lambda d_dc, d_dens: _losses._GaussianParamLoss.grad_into(
+                        pctx, grad_scale, (None, None, on(p_dens, d_dens), on(p_dc, d_dc)), 1)
+                    cfg["delta_grad_hook"] = lambda d_dt, d_dr: _losses._GaussianParamLoss.grad_into(
+                        pctx, grad_scale, (on(p_dt, d_dt), on(p_dr, d_dr), None, None), 1)
             d_image = _losses._RGBDepthLoss.backward(lctx, grad_scale, None)[0]
             grads = _RenderMeshBound.backward(rctx, d_image, None)
             for p, g in zip(params, grads):

@@ -366,3 +366,129 @@ def surface_mesh_loss(verts: torch.Tensor, topology, nc_factor: float, ref_edge_
     loss, parts = _SurfaceMeshLoss.apply(verts, topology, float(nc_factor), ref_edge_len, float(edge_factor), ref_area,
                                          float(area_factor))
     return (loss, parts) if return_parts else loss
+
+
+def _flat_f32(t, dev, n_cols, what):
+    """Detached contiguous float32 view (copy only if needed) of a parameter-like tensor holding n_cols floats per Gaussian."""
+    if t is None:
+        return None
+    if not t.is_cuda:
+        raise RuntimeError(f"gaustar_amd.losses: {what} must live on a HIP (cuda) device -- there is no CPU path")
+    x = t.detach()
+    if x.dtype != torch.float32 or not x.is_contiguous() or x.device != dev:
+        x = x.to(device=dev, dtype=torch.float32).contiguous()
+    if x.numel() % n_cols:
+        raise RuntimeError(f"{what} must hold {n_cols} values per Gaussian, got shape {tuple(t.shape)}")
+    return x
+
+
+def _weight_strides(weight, N, dev):
+    """(tensor, row stride, column stride) in elements of a [N], [N,1] or [N,3] weight read in place (expanded views included)."""
+    if weight is None:
+        return None, 0, 0
+    if weight.requires_grad:
+        raise NotImplementedError("gaustar_amd.losses: no gradient w.r.t. weight")
+    w = weight.detach()
+    if w.dtype != torch.float32 or w.device != dev:
+        w = w.to(device=dev, dtype=torch.float32)
+    if w.dim() == 1 and w.size(0) == N:
+        return w, int(w.stride(0)), 0
+    if w.dim() == 2 and w.size(0) == N and w.size(1) in (1, 3):
+        return w, int(w.stride(0)), int(w.stride(1)) if w.size(1) == 3 else 0
+    raise RuntimeError(f"weight must have dimensions ({N},), ({N}, 1) or ({N}, 3), got {tuple(weight.shape)}")
+
+
+class _GaussianParamLoss(torch.autograd.Function):
+    """The regularisers on the Gaussians' own parameters (refine.py:739-740, :743-748, :663-669) as ONE autograd node.
+    Forward: gsr_param_reg_forward -> {loose_t, loose_r, opacity, sh, total} on the device.  Backward: gsr_param_reg_backward,
+    one elementwise launch scaled by the incoming gradient on the device."""
+
+    @staticmethod
+    def forward(ctx, delta_t, delta_r, weight, factor_t, factor_r, densities, min_opacity, sh_dc, pre_sh_dc, sh_factor):
+        lib = _lib.load()
+        given = [t for t in (delta_t, delta_r, densities, sh_dc) if t is not None]
+        if not given:
+            raise RuntimeError("gaussian_param_loss: give at least one of delta_t, delta_r, densities, sh_dc")
+        dev = given[0].device
+        dt, dr = _flat_f32(delta_t, dev, 3, "delta_t"), _flat_f32(delta_r, dev, 4, "delta_r")
+        dens, dc = _flat_f32(densities, dev, 1, "densities"), _flat_f32(sh_dc, dev, 3, "sh_dc")
+        counts = {x.numel() // k for x, k in ((dt, 3), (dr, 4), (dens, 1), (dc, 3)) if x is not None}
+        if len(counts) != 1:
+            raise RuntimeError(f"delta_t, delta_r, densities and sh_dc disagree on the number of Gaussians: {sorted(counts)}")
+        N = counts.pop()
+        if pre_sh_dc is not None and pre_sh_dc.requires_grad:
+            raise NotImplementedError("gaustar_amd.losses: no gradient w.r.t. pre_sh_dc")
+        pre = _flat_f32(pre_sh_dc, dev, 3, "pre_sh_dc")
+        M = pre.numel() // 3 if pre is not None else 0
+        if M > N:
+            raise RuntimeError(f"pre_sh_dc holds {M} rows, more than the {N} Gaussians")
+        w, w_rs, w_cs = _weight_strides(weight, N, dev)
+        cfg = (N, M, w_rs, w_cs, float(factor_t), float(factor_r), float(min_opacity), float(sh_factor))
+        with _host.on_device(dev):
+            ws = torch.empty(lib.gsr_param_reg_workspace_bytes(N), dtype=torch.uint8, device=dev)
+            out = torch.empty(5, dtype=torch.float32, device=dev)
+            _lib.check(lib.gsr_param_reg_forward(
+                N, M, _op(dt), _op(dr), _op(w), w_rs, w_cs, cfg[4], cfg[5], _op(dens), cfg[6], _op(dc), _op(pre), cfg[7],
+                _vp(ws), _vp(out), _stream()), "gsr_param_reg_forward")
+        ctx.cfg = cfg
+        ctx.have = tuple(x is not None for x in (dt, dr, w, dens, dc, pre))
+        ctx.in_meta = tuple(None if t is None else (t.shape, t.dtype) for t in (delta_t, delta_r, densities, sh_dc))
+        if any(ctx.needs_input_grad):
+            ctx.save_for_backward(*[x for x in (dt, dr, w, dens, dc, pre) if x is not None])
+        ctx.mark_non_differentiable(out)
+        ctx.set_materialize_grads(False)
+        return out[4], out
+
+    @staticmethod
+    def grad_into(ctx, g_loss, buffers, accumulate):
+        """gsr_param_reg_backward into buffers = (dL_ddelta_t, dL_ddelta_r, dL_ddensities, dL_dsh_dc): contiguous float32
+        tensors with the inputs' element counts, any of them None (accumulate = 1: added to what is there, one rounding per
+        element).  A term that was skipped in the forward leaves its buffer untouched."""
+        lib = _lib.load()
+        it = iter(ctx.saved_tensors)
+        dt, dr, w, dens, dc, pre = (next(it) if h else None for h in ctx.have)
+        N, M, w_rs, w_cs, factor_t, factor_r, min_opacity, sh_factor = ctx.cfg
+        dev = next(x for x in (dt, dr, dens, dc) if x is not None).device
+        for b, k, what in zip(buffers, (3, 4, 1, 3), ("dL_ddelta_t", "dL_ddelta_r", "dL_ddensities", "dL_dsh_dc")):
+            if b is not None and (b.dtype != torch.float32 or not b.is_contiguous() or b.numel() != N * k or b.device != dev):
+                raise RuntimeError(f"{what} must be a contiguous float32 tensor of {N * k} elements on {dev}")
+        with _host.on_device(dev):
+            keep, sp = _scale_ptr(g_loss, dev)
+            _lib.check(lib.gsr_param_reg_backward(
+                N, M, _op(dt), _op(dr), _op(w), w_rs, w_cs, factor_t, factor_r, _op(dens), min_opacity, _op(dc), _op(pre),
+                sh_factor, sp, *[_op(b) for b in buffers], int(accumulate), _stream()), "gsr_param_reg_backward")
+        return buffers
+
+    @staticmethod
+    def backward(ctx, g_loss, _g_parts):
+        if not ctx.saved_tensors or g_loss is None:
+            return (None,) * 10
+        it = iter(ctx.saved_tensors)
+        dt, dr, _w, dens, dc, pre = (next(it) if h else None for h in ctx.have)
+        _N, M, _rs, _cs, factor_t, factor_r, _mo, sh_factor = ctx.cfg
+        need = ctx.needs_input_grad
+        # (a term that is off leaves its buffer untouched: no buffer is made for it, its input's gradient is None)
+        srcs = (dt if need[0] and factor_t != 0.0 else None, dr if need[1] and factor_r != 0.0 else None,
+                dens if need[5] else None, dc if need[7] and pre is not None and M > 0 and sh_factor != 0.0 else None)
+        bufs = tuple(None if s is None else torch.empty_like(s) for s in srcs)
+        if any(b is not None for b in bufs):
+            _GaussianParamLoss.grad_into(ctx, g_loss, bufs, 0)
+        g = [None if b is None else b.view(m[0]).to(m[1]) for b, m in zip(bufs, ctx.in_meta)]
+        return g[0], g[1], None, None, None, g[2], None, g[3], None, None
+
+
+def gaussian_param_loss(delta_t: Optional[torch.Tensor] = None, delta_r: Optional[torch.Tensor] = None,
+                        weight: Optional[torch.Tensor] = None, factor_t: float = 100.0, factor_r: float = 1.0,
+                        densities: Optional[torch.Tensor] = None, min_opacity: float = 0.8,
+                        sh_dc: Optional[torch.Tensor] = None, pre_sh_dc: Optional[torch.Tensor] = None, sh_factor: float = 1.0,
+                        return_parts: bool = False):
+    """factor_t * (weight * delta_t.abs()).mean() + factor_r * (weight * delta_r[..., 1:].abs()).mean()
+    + relu(min_opacity - sigmoid(densities)).mean() + sh_factor * ((pre_sh_dc - sh_dc[:M]) ** 2).mean()
+    (refine.py:739-740, :743-748, :663-669; defaults of refine.py:29-33) on the model's `_delta_t` [N,3], `_delta_r` [N,4],
+    `all_densities` [N,1] and `_sh_coordinates_dc` [N,1,3]; pre_sh_dc [M,3] or [M,1,3] is the tracked prefix (M <= N).  weight:
+    [N], [N,1] or [N,3], read in place whatever its strides (refine.py:737's expanded view included); None = 1.  A term whose
+    tensor is None or whose factor is 0 is left out.  One fused HIP op each way, no host synchronisation, bit-reproducible;
+    parts = the device vector {loose_t, loose_r, opacity, sh, total}."""
+    loss, parts = _GaussianParamLoss.apply(delta_t, delta_r, weight, float(factor_t), float(factor_r), densities,
+                                           float(min_opacity), sh_dc, pre_sh_dc, float(sh_factor))
+    return (loss, parts) if return_parts else loss

@@ -404,6 +404,36 @@ int gsr_mesh_reg_backward(int V, int F, int E, int Q, const float* verts, const 
                           float nc_factor, float edge_factor, float area_factor, const float* grad_scale, float* dL_dverts,
                           int accumulate, gsr_stream_t stream);
 
+/* ---- Regularisers on the Gaussians' own parameters (gaustar_trainers/refine.py:739-740, :743-748, :663-669), fused.  Replaces
+ *   factor_t * (unbind_loss_weight * delta_t.abs()).mean()                                     (refine.py:739)
+ * + factor_r * (unbind_loss_weight * delta_r[..., 1:].abs()).mean()                            (refine.py:740)
+ * + torch.relu(min_opacity - strengths.view(-1, 1)).mean()                                     (refine.py:743-748)
+ * + sh_factor * ((pre_sh_dc - sh_dc[:M]) ** 2).mean()                                          (refine.py:663-669)
+ * All f32, contiguous device arrays: delta_t [N,3], delta_r [N,4] (w first), densities [N] raw (`all_densities`; strengths =
+ * 1 / (1 + exp(-density)), the expression of gsr_sh_colors_split), sh_dc [N,3] (`_sh_coordinates_dc` viewed flat), pre_sh_dc
+ * [M,3] with 0 <= M <= N: the tracked prefix of refine.py:667 (M == N is :669).  weight is read through two ELEMENT strides --
+ * weight of Gaussian n, axis c at weight[n * w_row_stride + c * w_col_stride] -- so a [N] tensor or an expanded view (column
+ * stride 0) and a materialised [N,3] array are read in place; NULL means 1.
+ * A term is skipped when its input is NULL or its factor is 0 (opacity: densities == NULL; sh: either array NULL): it is 0 in
+ * loss_out and touches no gradient buffer.  Means over 3N, 3N, N and 3M elements.
+ * gsr_param_reg_forward: one element pass + one fixed-order reduction, loss_out [5] device floats = {loose_t, loose_r, opacity,
+ *   sh, total}, each already multiplied by its factor; workspace: gsr_param_reg_workspace_bytes(N) bytes.
+ * gsr_param_reg_backward: one elementwise launch; every output receives grad_scale[0] * d total / d input (grad_scale a DEVICE
+ *   scalar, NULL = 1) -- written, or with accumulate = 1 added to what is there with one rounding per element (= torch's
+ *   X + fresh).  Any output may be NULL.  Kinks as torch: d|x|/dx = 0 at 0, relu'(0) = 0; dL_ddelta_r[:, 0], the rows of
+ *   dL_dsh_dc at or beyond M and the delta gradients of a Gaussian with weight 0 are exactly 0.
+ * No host synchronisation, no float atomics: results are bitwise reproducible across calls and streams. */
+size_t gsr_param_reg_workspace_bytes(int N);
+int gsr_param_reg_forward(int N, int M, const float* delta_t, const float* delta_r, const float* weight, long long w_row_stride,
+                          long long w_col_stride, float factor_t, float factor_r, const float* densities, float min_opacity,
+                          const float* sh_dc, const float* pre_sh_dc, float sh_factor, void* workspace, float* loss_out,
+                          gsr_stream_t stream);
+int gsr_param_reg_backward(int N, int M, const float* delta_t, const float* delta_r, const float* weight, long long w_row_stride,
+                           long long w_col_stride, float factor_t, float factor_r, const float* densities, float min_opacity,
+                           const float* sh_dc, const float* pre_sh_dc, float sh_factor, const float* grad_scale,
+                           float* dL_ddelta_t, float* dL_ddelta_r, float* dL_ddensities, float* dL_dsh_dc, int accumulate,
+                           gsr_stream_t stream);
+
 /* ---- Rig-wide topology-error detection (gaustar_trainers/refined_mesh.py:697-920 `detect_topo_err` with the depth term only,
  * as refine.py:720-734 calls it).  All device pointers; every call is asynchronous on `stream`, none synchronises the host,
  * and none uses float atomics (outputs are bitwise reproducible).

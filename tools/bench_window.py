@@ -11,6 +11,9 @@ frame, train_seq.py:101-244 / gaustar_trainers/refine.py:529-841) assembled from
 With --mesh-reg every iteration also carries the surface-mesh regularisers of refine.py:676-706 (normal consistency, edge
 and area isometry against the frame-0 mesh, train_seq.py:108-110's factors) through losses.surface_mesh_loss -- or, with
 --fused-step, through rgbd_step(mesh_reg=...).  Off by default.
+With --loose-bind the model is loose-bound before the timed region (weight 1 on every other face) and every iteration carries
+the regularisers on the Gaussians' parameters (refine.py:739-748, :663-669): rgbd_step(param_reg=...) with --fused-step, the
+autograd composition of the reference's four torch lines otherwise.  Off by default.
 
 Not included (out of scope): topology update (Open3D), flow warp.  Prints iterations/s over all
 frames and the loss at the start / end of every frame."""
@@ -69,6 +72,14 @@ def run(a):
         mesh_reg = dict(topology=model.mesh_topology(), nc_factor=0.5, ref_edge_len=(ve[:, 0] - ve[:, 1]).norm(dim=1),
                         edge_factor=1000.0, ref_area=ref.faces_areas_packed().detach(), area_factor=5000.0)
         reg_kw = {k: v_ for k, v_ in mesh_reg.items() if k != "topology"}
+    param_reg, loose_groups = None, False
+    if getattr(a, "loose_bind", False):   # (bench.py builds the namespace without this flag: off)
+        w = (torch.arange(N // 6, device=dev) % 2).float().repeat_interleave(6)[:, None].expand(-1, 3)
+        model.loose_bind(w)
+        loose_groups = True
+        if not getattr(a, "no_param_reg", False):   # (tools/bench_param_reg.py: the loose-bound loop without the regularisers)
+            param_reg = dict(factor_t=100.0, factor_r=1.0, min_opacity=0.8, sh_factor=1.0,
+                             pre_sh_dc=model._sh_coordinates_dc.detach()[:, 0].clone())
     host_wait_ns = 0
     pts_start = model.points.detach().clone()
     t_total = 0.0
@@ -88,6 +99,8 @@ def run(a):
         groups = [{"params": [model._points], "lr": 2e-4},
                   {"params": [model._sh_coordinates_dc, model._sh_coordinates_rest], "lr": 5e-3},
                   {"params": [model._scales, model._quaternions, model.all_densities], "lr": 5e-3}]
+        if loose_groups:
+            groups += model.loose_bind_param_groups(2e-4, 1e-3)
         sharded = world > 1 and getattr(a, "exchange", "sharded") == "sharded"
         if sharded:   # reduce-scatter -> Adam on this rank's 1/N -> all-gather (dist.ShardedAdam), the default for N > 1
             reducer = None
@@ -110,12 +123,18 @@ def run(a):
                 ci = gdist.shard_views(len(ncams), fi * a.iters + it, rank, world)
                 opt.zero_grad(set_to_none=True)
                 if fused_step:    # render + losses + both backward passes without an autograd graph (harness.SurfaceGaussians.rgbd_step)
-                    loss = model.rgbd_step(ncams[ci], bg4, gts[ci][0], gts[ci][1], MAX_DEPTH, 0.2, 1.0, 0.5, mesh_reg=mesh_reg)[0]
+                    loss = model.rgbd_step(ncams[ci], bg4, gts[ci][0], gts[ci][1], MAX_DEPTH, 0.2, 1.0, 0.5, mesh_reg=mesh_reg,
+                                           param_reg=param_reg)[0]
                 else:
                     img = render(model, ncams[ci], bg4)
                     loss = losses.rgb_depth_loss(img, gts[ci][0], gts[ci][1], MAX_DEPTH, 0.2, 1.0, 0.5)
                     if mesh_reg is not None:
                         loss = loss + losses.surface_mesh_loss(model._points, mesh_reg["topology"], **reg_kw)
+                    if param_reg is not None:     # refine.py:739-740, :743-748, :669 as the reference writes them
+                        loss = loss + 100.0 * (model.unbind_loss_weight * model._delta_t.abs()).mean()
+                        loss = loss + 1.0 * (model.unbind_loss_weight * model._delta_r[..., 1:].abs()).mean()
+                        loss = loss + torch.relu(0.8 - model.strengths.view(-1, 1)).mean()
+                        loss = loss + 1.0 * ((param_reg["pre_sh_dc"] - model._sh_coordinates_dc[:, 0, :]) ** 2).mean()
                     loss.backward(one)                 # (the seed is handed over: a bare backward() fills a ones_like per call, 4.5 us on the stream)
                 if reducer is not None:
                     reducer()                      # the hook in front of sugar_optimizer.py:99-101
@@ -157,6 +176,8 @@ def run(a):
         extra["fused_step"] = True
     if mesh_reg is not None:
         extra["mesh_reg"] = True
+    if loose_groups:
+        extra["loose_bind"], extra["param_reg"] = True, param_reg is not None
     return {**extra, "gaussians": N, "image": [a.width, a.height], "cameras": len(ncams), "frames": frames, "iterations": n_it,
             "iterations_per_s": round(n_it / t_total, 1), "ms_per_iteration": round(t_total / n_it * 1e3, 3),
             # the steady state: median over all iterations of the time between their start marks on the stream (the wall
@@ -180,6 +201,8 @@ def main():
                     help="render + losses + backward through SurfaceGaussians.rgbd_step (no autograd graph) instead of loss.backward()")
     ap.add_argument("--mesh-reg", dest="mesh_reg", action="store_true",
                     help="add the surface-mesh regularisers of refine.py:676-706 (normal consistency, edge / area isometry)")
+    ap.add_argument("--loose-bind", dest="loose_bind", action="store_true",
+                    help="loose-bind the model and add the regularisers on the Gaussians' parameters (refine.py:739-748, :663-669)")
     r = run(ap.parse_args())
     if gdist.rank() == 0:
         print(json.dumps(r))
