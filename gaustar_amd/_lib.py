@@ -177,3 +177,14 @@ def check(rc: int, what: str) -> None:
     if rc != 0:
         msg = load().gsr_last_error()
         raise GsrError(f"{what} failed: {msg.decode() if msg else rc}")
+
+
+def stream_ptr():
+    """The current torch stream as the ABI's gsr_stream_t."""
+    import torch   # (here: the loader itself stays importable without torch)
+    return c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def ptr(t):
+    """A tensor's data pointer as a c_void_p argument (None: a null pointer)."""
+    return None if t is None else c_void_p(t.data_ptr())

@@ -6,8 +6,8 @@
 // the 3F face-edges, bincount, data-dependent shapes: host synchronisations every iteration).  Here the topology -- edges,
 // the face pairs of every edge, a vertex-major incidence list -- is built once per face tensor (gaustar_amd/meshes.py) and
 // the per-iteration work is two passes over it:
-//   forward   one element pass over {pairs, edges, faces} (per-workgroup partial sums in double, fixed tree) and one
-//             single-workgroup finalise that reduces the partials in a fixed order -> loss_out[4] = {nc, edge, area, total};
+//   forward   one element pass over {pairs, edges, faces} and one single-workgroup finalise, summed in double in a fixed
+//             order (gsr_reduce.h) -> loss_out[4] = {nc, edge, area, total};
 //   backward  ONE vertex-major pass: a workgroup takes MR_VPB consecutive vertices, its lanes recompute the derivative of
 //             every incidence in the vertices' lists (chunks of 256 in LDS), and each vertex's lane sums its own entries in
 //             list order.  No float atomics: two calls give identical bits.
@@ -20,14 +20,13 @@
 // with torch's cosine_similarity: x / max(|x|, eps) . y / max(|y|, eps), whose gradient through the norm is x / |x| (0 at
 // x = 0) even where the clamp is active.  Edge: |v0 - v1|, gradient 0 at length 0.  Face area: 0.5 |(v1 - v0) x (v2 - v0)|
 // with torch's d|c|/dc = 0 at c = 0 and d|x|/dx = 0 at x = 0: a degenerate face contributes no area gradient.
-#include "gsr_internal.h"
+#include "gsr_reduce.h"
 
 namespace gsr {
 
 namespace {
 
-constexpr int MR_BLOCK = 256;
-constexpr int MR_MAX_WGS = 2048;    // element pass: grid-stride beyond 2048 workgroups
+constexpr int MR_BLOCK = 256;       // backward (the forward pair runs RED_BLOCK lanes)
 constexpr int MR_VPB = 32;          // backward: vertices per workgroup (config C: ~24 incidences each -> 3 chunks of 256)
 constexpr float MR_EPS = 1e-8f;     // torch.nn.functional.cosine_similarity's default eps, as pytorch3d calls it
 
@@ -106,64 +105,33 @@ __device__ __forceinline__ float area_term(const MeshRegArgs& m, int f, int corn
     return fabsf(r);
 }
 
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-
-__global__ void __launch_bounds__(MR_BLOCK)
+__global__ void __launch_bounds__(RED_BLOCK)
 mesh_reg_fwd_kernel(MeshRegArgs m, double* __restrict__ partials)
 {
-    __shared__ double red[MR_BLOCK / 64][3];
     const int N = m.Q + m.E + m.F;
-    double s_nc = 0.0, s_e = 0.0, s_a = 0.0;
-    for (int i = (int)(blockIdx.x * MR_BLOCK + threadIdx.x); i < N; i += (int)(gridDim.x * MR_BLOCK)) {
+    double s[3] = {0.0, 0.0, 0.0};   // nc, edge, area
+    for (int i = (int)(blockIdx.x * RED_BLOCK + threadIdx.x); i < N; i += (int)(gridDim.x * RED_BLOCK)) {
         if (i < m.Q) {
-            if (m.use_nc) s_nc += (double)pair_term(m, i, 0, nullptr);
+            if (m.use_nc) s[0] += (double)pair_term(m, i, 0, nullptr);
         } else if (i < m.Q + m.E) {
-            if (m.use_edge) s_e += (double)edge_term(m, i - m.Q, nullptr);
+            if (m.use_edge) s[1] += (double)edge_term(m, i - m.Q, nullptr);
         } else if (m.use_area) {
-            s_a += (double)area_term(m, i - m.Q - m.E, 0, nullptr);
+            s[2] += (double)area_term(m, i - m.Q - m.E, 0, nullptr);
         }
     }
-    s_nc = wave_sum(s_nc); s_e = wave_sum(s_e); s_a = wave_sum(s_a);
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (lane == 0) { red[wv][0] = s_nc; red[wv][1] = s_e; red[wv][2] = s_a; }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        double t = 0.0;
-#pragma unroll
-        for (int w = 0; w < MR_BLOCK / 64; w++) t += red[w][threadIdx.x];
-        partials[4 * blockIdx.x + threadIdx.x] = t;
-    }
+    block_partials(s, partials);
 }
 
-__global__ void __launch_bounds__(MR_BLOCK)
+__global__ void __launch_bounds__(RED_BLOCK)
 mesh_reg_finalize_kernel(int n_wg, const double* __restrict__ partials, int Q, int E, int F, float nc_factor, float edge_factor,
                          float area_factor, int use_nc, int use_edge, int use_area, float* __restrict__ out)
 {
-    __shared__ double r[3][MR_BLOCK];   // fixed-order tree in double: deterministic
-    double v[3] = {0.0, 0.0, 0.0};
-    for (int i = threadIdx.x; i < n_wg; i += MR_BLOCK) {
-#pragma unroll
-        for (int k = 0; k < 3; k++) v[k] += partials[4 * i + k];
-    }
-#pragma unroll
-    for (int k = 0; k < 3; k++) r[k][threadIdx.x] = v[k];
-    __syncthreads();
-    for (int d = MR_BLOCK / 2; d > 0; d >>= 1) {
-        if ((int)threadIdx.x < d) {
-#pragma unroll
-            for (int k = 0; k < 3; k++) r[k][threadIdx.x] += r[k][threadIdx.x + d];
-        }
-        __syncthreads();
-    }
+    double r[3];   // (defined in thread 0 only)
+    tree_total(n_wg, partials, r);
     if (threadIdx.x == 0) {
-        const float nc = use_nc ? (float)((double)nc_factor * (r[0][0] / (double)Q)) : 0.f;
-        const float ed = use_edge ? (float)((double)edge_factor * (r[1][0] / (double)E)) : 0.f;
-        const float ar = use_area ? (float)((double)area_factor * (r[2][0] / (double)F)) : 0.f;
+        const float nc = use_nc ? (float)((double)nc_factor * (r[0] / (double)Q)) : 0.f;
+        const float ed = use_edge ? (float)((double)edge_factor * (r[1] / (double)E)) : 0.f;
+        const float ar = use_area ? (float)((double)area_factor * (r[2] / (double)F)) : 0.f;
         out[0] = nc; out[1] = ed; out[2] = ar;
         out[3] = (nc + ed) + ar;   // refine.py:688, :696, :702: the three additions in the trainer's order
     }
@@ -239,13 +207,13 @@ MeshRegArgs make_args(int F, int E, int Q, const float* verts, const int* faces,
 int fwd_workgroups(int F, int E, int Q)
 {
     const long long n = (long long)Q + E + F;
-    const long long wg = (n + MR_BLOCK - 1) / MR_BLOCK;
-    return (int)(wg < MR_MAX_WGS ? wg : MR_MAX_WGS);
+    const long long wg = (n + RED_BLOCK - 1) / RED_BLOCK;
+    return (int)(wg < RED_MAX_WGS ? wg : RED_MAX_WGS);
 }
 
 }  // namespace
 
-size_t mesh_reg_workspace_bytes() { return align_up(4 * sizeof(double) * MR_MAX_WGS) + 256; }
+size_t mesh_reg_workspace_bytes() { return reduce_workspace_bytes(); }
 
 void launch_mesh_reg(int F, int E, int Q, const float* verts, const int* faces, const int* edges, const int* pairs,
                      const float* ref_edge, const float* ref_area, float nc_factor, float edge_factor, float area_factor,
@@ -254,8 +222,8 @@ void launch_mesh_reg(int F, int E, int Q, const float* verts, const int* faces, 
     const MeshRegArgs m = make_args(F, E, Q, verts, faces, edges, pairs, ref_edge, ref_area, nc_factor, edge_factor, area_factor);
     double* partials = static_cast<double*>(workspace);
     const int n_wg = fwd_workgroups(F, E, Q);
-    if (n_wg > 0) mesh_reg_fwd_kernel<<<n_wg, MR_BLOCK, 0, st>>>(m, partials);
-    mesh_reg_finalize_kernel<<<1, MR_BLOCK, 0, st>>>(n_wg, partials, Q, E, F, nc_factor, edge_factor, area_factor, m.use_nc,
+    if (n_wg > 0) mesh_reg_fwd_kernel<<<n_wg, RED_BLOCK, 0, st>>>(m, partials);
+    mesh_reg_finalize_kernel<<<1, RED_BLOCK, 0, st>>>(n_wg, partials, Q, E, F, nc_factor, edge_factor, area_factor, m.use_nc,
                                                      m.use_edge, m.use_area, loss_out);
 }
 

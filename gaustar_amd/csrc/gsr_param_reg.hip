@@ -7,20 +7,19 @@
 // A pure streaming op.  A thread takes PR_G = 4 consecutive Gaussians, so every array is read and written as whole 16-byte
 // words (the 12-byte rows of delta_t / sh_dc as the flat 3N array they are: 4 rows = 3 float4); a scalar path serves the
 // ragged last group and arrays that are not 16-byte aligned.
-//   forward   one element pass (per-workgroup partial sums in double, fixed tree) and one single-workgroup finalise that
-//             reduces the partials in a fixed order -> loss_out[5] = {loose_t, loose_r, opacity, sh, total};
+//   forward   one element pass and one single-workgroup finalise, summed in double in a fixed order (gsr_reduce.h)
+//             -> loss_out[5] = {loose_t, loose_r, opacity, sh, total};
 //   backward  elementwise; no float atomics anywhere: two calls give identical bits.
 // Gradients at the kinks follow torch: d|x|/dx = 0 at 0 (delta_t starts at exactly 0), relu'(0) = 0; delta_r[:, 0] and the
 // sh_dc rows at or beyond M get exactly 0.
-#include "gsr_internal.h"
+#include "gsr_reduce.h"
 
 namespace gsr {
 
 namespace {
 
-constexpr int PR_BLOCK = 256;
+constexpr int PR_BLOCK = RED_BLOCK;  // forward and backward walk the groups with the same grid
 constexpr int PR_G = 4;             // Gaussians per thread
-constexpr int PR_MAX_WGS = 2048;    // grid-stride beyond 2048 workgroups
 
 struct ParamRegArgs {
     int N, M;
@@ -99,17 +98,9 @@ __device__ __forceinline__ float sigmoidf(float d) { return 1.0f / (1.0f + expf(
 
 __device__ __forceinline__ float sgn(float x) { return x > 0.f ? 1.f : x < 0.f ? -1.f : 0.f; }   // torch.sign: 0 at 0
 
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-
 __global__ void __launch_bounds__(PR_BLOCK)
 param_reg_fwd_kernel(ParamRegArgs a, double* __restrict__ partials)
 {
-    __shared__ double red[PR_BLOCK / 64][4];
     const int n_groups = (a.N + PR_G - 1) / PR_G;
     double s[4] = {0.0, 0.0, 0.0, 0.0};
     for (int g = (int)(blockIdx.x * PR_BLOCK + threadIdx.x); g < n_groups; g += (int)(gridDim.x * PR_BLOCK)) {
@@ -155,48 +146,21 @@ param_reg_fwd_kernel(ParamRegArgs a, double* __restrict__ partials)
             s[3] += (double)t;
         }
     }
-#pragma unroll
-    for (int k = 0; k < 4; k++) s[k] = wave_sum(s[k]);
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < 4; k++) red[wv][k] = s[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < 4) {
-        double t = 0.0;
-#pragma unroll
-        for (int w = 0; w < PR_BLOCK / 64; w++) t += red[w][threadIdx.x];
-        partials[4 * blockIdx.x + threadIdx.x] = t;
-    }
+    block_partials(s, partials);
 }
 
 __global__ void __launch_bounds__(PR_BLOCK)
 param_reg_finalize_kernel(int n_wg, const double* __restrict__ partials, ParamRegArgs a, float factor_t, float factor_r,
                           float sh_factor, float* __restrict__ out)
 {
-    __shared__ double r[4][PR_BLOCK];   // fixed-order tree in double: deterministic
-    double v[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int i = threadIdx.x; i < n_wg; i += PR_BLOCK) {
-#pragma unroll
-        for (int k = 0; k < 4; k++) v[k] += partials[4 * i + k];
-    }
-#pragma unroll
-    for (int k = 0; k < 4; k++) r[k][threadIdx.x] = v[k];
-    __syncthreads();
-    for (int d = PR_BLOCK / 2; d > 0; d >>= 1) {
-        if ((int)threadIdx.x < d) {
-#pragma unroll
-            for (int k = 0; k < 4; k++) r[k][threadIdx.x] += r[k][threadIdx.x + d];
-        }
-        __syncthreads();
-    }
+    double r[4];   // (defined in thread 0 only)
+    tree_total(n_wg, partials, r);
     if (threadIdx.x == 0) {
         const double n3 = 3.0 * (double)a.N, m3 = 3.0 * (double)a.M;
-        const float lt = a.use_t ? (float)((double)factor_t * (r[0][0] / n3)) : 0.f;
-        const float lr = a.use_r ? (float)((double)factor_r * (r[1][0] / n3)) : 0.f;
-        const float op = a.use_o ? (float)(r[2][0] / (double)a.N) : 0.f;
-        const float sh = a.use_sh ? (float)((double)sh_factor * (r[3][0] / m3)) : 0.f;
+        const float lt = a.use_t ? (float)((double)factor_t * (r[0] / n3)) : 0.f;
+        const float lr = a.use_r ? (float)((double)factor_r * (r[1] / n3)) : 0.f;
+        const float op = a.use_o ? (float)(r[2] / (double)a.N) : 0.f;
+        const float sh = a.use_sh ? (float)((double)sh_factor * (r[3] / m3)) : 0.f;
         out[0] = lt; out[1] = lr; out[2] = op; out[3] = sh;
         out[4] = ((lt + lr) + op) + sh;
     }
@@ -288,12 +252,12 @@ int n_workgroups(int N)
 {
     const long long groups = ((long long)N + PR_G - 1) / PR_G;
     const long long wg = (groups + PR_BLOCK - 1) / PR_BLOCK;
-    return (int)(wg < PR_MAX_WGS ? wg : PR_MAX_WGS);
+    return (int)(wg < RED_MAX_WGS ? wg : RED_MAX_WGS);
 }
 
 }  // namespace
 
-size_t param_reg_workspace_bytes() { return align_up(4 * sizeof(double) * PR_MAX_WGS) + 256; }
+size_t param_reg_workspace_bytes() { return reduce_workspace_bytes(); }
 
 void launch_param_reg(int N, int M, const float* delta_t, const float* delta_r, const float* weight, long long w_rs,
                       long long w_cs, float factor_t, float factor_r, const float* densities, float min_opacity,

@@ -6,13 +6,10 @@
 // three lookups per vertex (:57-74, :106-117); over the rig a Python mean per vertex, up to 20 Python propagation sweeps
 // (mesh_vert_propagate, :133-155), an open3d voxel grid (:185-197) and a pytorch3d kNN interpolation (:199-213), then trimesh's
 // vertex-to-face colour.  Here:
-//   per camera  (3 launches, no host round trip)
-//     topo_gt_max_kernel    per-workgroup max of the GT depth below max_depth            -> partials[0, TP_PARTS)
-//     topo_var_max_kernel   per-workgroup max of the edge statistic `var`                -> partials[TP_PARTS, 2 TP_PARTS)
+//   per camera  (3 launches, no host round trip; the camera, the edge statistic and the two image passes are gsr_rig.h's)
+//     topo_gt_max_kernel    per-workgroup max of the GT depth below max_depth            -> partials[0, RIG_PARTS)
+//     topo_var_max_kernel   per-workgroup max of the 3x3 edge statistic `var`            -> partials[RIG_PARTS, 2 RIG_PARTS)
 //     topo_view_kernel      one lane per vertex: f64 projection, lookup, visibility, loss -> one row of the [C, V] table
-//     Each consumer reduces the partials it needs itself (a fixed-size max: order-free, so the result does not depend on
-//     which workgroup ran first), and the two later kernels compute `var` with the same device function, so edge_vis agrees
-//     bit for bit between the maximum and the lookup.
 //   over the rig
 //     topo_aggregate_kernel  count, f64 mean in camera order, depth scalar, floor          (refined_mesh.py:826-891)
 //     topo_propagate_kernel  one Jacobi sweep over a CSR neighbour list (ping-pong)        (mesh_vert_propagate)
@@ -25,7 +22,7 @@
 //
 // Floating point follows the numpy restatement in tests/topo_ref.py operation by operation, so contraction into FMAs is off
 // for this file: a fused multiply-add rounds once where numpy rounds twice.
-#include "gsr_internal.h"
+#include "gsr_rig.h"
 
 #pragma clang fp contract(off)
 
@@ -33,134 +30,45 @@ namespace gsr {
 
 namespace {
 
-constexpr int TP_BLOCK = 256;
-constexpr int TP_PARTS = 2048;  // workgroups of the two image passes (grid-stride), = partials per statistic
+constexpr int TP_BLOCK = RIG_BLOCK;   // the rig-wide kernels and the kNN tile; the per-camera kernels must run RIG_BLOCK lanes
 constexpr int TP_SEED = 16;     // kNN bound: voxels on either side of a vertex's own voxel (sort order)
 constexpr int TP_SPLIT = 8;     // kNN: voxel ranges scanned by separate workgroups
 constexpr int TP_K = 8;         // interpolate_in_voxel(knn_K=8)
 
-// cv2 BORDER_REFLECT_101 (gfedcb|abcdefgh|gfedcba) for an offset of at most one pixel
-__device__ __forceinline__ int reflect101(int i, int n)
+__global__ void __launch_bounds__(RIG_BLOCK) topo_gt_max_kernel(int n, const float* __restrict__ gt, float max_depth,
+                                                                float* __restrict__ parts)
 {
-    if (n == 1) return 0;
-    return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i);
+    depth_max_pass(n, gt, max_depth, 0, parts);
 }
 
-// get_depth_edge(depth_gt, 3) at (y, x): d = min(depth_gt, m), var = max(blur(d^2) - blur(d)^2, 0) with cv2.blur's 3x3
-// normalised box filter.  OpenCV documents the box filter of f32 data as a running sum in double, scaled by 1/9 and rounded
-// to f32 on output; that claim has not been checked against cv2 here (cv2 is not available).  The nine values are summed
-// row by row in double: for depth maps whose values are within 2^29 of each other that sum is exact, so the order of the
-// running sum does not matter.  d^2 is squared in f32 (numpy `depth ** 2`), blur(d) is squared in f32.
-__device__ __forceinline__ float edge_var(const float* __restrict__ g, int H, int W, int y, int x, float m)
+// get_depth_edge(depth_gt, 3): the 3x3 window
+__global__ void __launch_bounds__(RIG_BLOCK) topo_var_max_kernel(int H, int W, const float* __restrict__ gt, float* __restrict__ parts)
 {
-    double s1 = 0.0, s2 = 0.0;
-#pragma unroll
-    for (int dy = -1; dy <= 1; ++dy) {
-        const float* row = g + (size_t)reflect101(y + dy, H) * W;
-        double r1 = 0.0, r2 = 0.0;
-#pragma unroll
-        for (int dx = -1; dx <= 1; ++dx) {
-            const float d = fminf(row[reflect101(x + dx, W)], m);
-            r1 += (double)d;
-            r2 += (double)(d * d);
-        }
-        s1 += r1;
-        s2 += r2;
-    }
-    const float mean = (float)(s1 * (1.0 / 9.0)), sq_mean = (float)(s2 * (1.0 / 9.0));
-    return fmaxf(sq_mean - mean * mean, 0.f);
+    var_max_pass<1>(H, W, gt, 0, 1, parts);
 }
 
-// max over the TP_PARTS partials at `p`, by the whole workgroup (every lane gets it)
-__device__ float block_max_of_parts(const float* __restrict__ p, float* red)
+__global__ void __launch_bounds__(RIG_BLOCK) topo_view_kernel(int H, int W, int V, const float* __restrict__ verts,
+                                                              const float* __restrict__ gt, const float* __restrict__ render,
+                                                              const float* __restrict__ surface, float max_depth,
+                                                              const float* __restrict__ parts, RigCamera cam, float* __restrict__ row)
 {
-    float v = -INFINITY;
-    for (int i = threadIdx.x; i < TP_PARTS; i += TP_BLOCK) v = fmaxf(v, p[i]);
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = TP_BLOCK / 2; s > 0; s >>= 1) {
-        if (threadIdx.x < s) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + s]);
-        __syncthreads();
-    }
-    const float r = red[0];
-    __syncthreads();
-    return r;
-}
-
-__device__ void block_store_max(float v, float* red, float* out)
-{
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = TP_BLOCK / 2; s > 0; s >>= 1) {
-        if (threadIdx.x < s) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + s]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *out = red[0];
-}
-
-// m = f32(1.1 * max(depth_gt[depth_gt < 10])) (warp_mesh.py:123-124: np.float32 max times a Python float, in double as
-// NumPy 1.x evaluates it); -inf when no pixel is below max_depth
-__device__ __forceinline__ float clip_depth(float gmax) { return gmax == -INFINITY ? -INFINITY : (float)((double)gmax * 1.1); }
-
-__global__ void __launch_bounds__(TP_BLOCK) topo_gt_max_kernel(int n, const float* __restrict__ gt, float max_depth,
-                                                               float* __restrict__ parts)
-{
-    __shared__ float red[TP_BLOCK];
-    float v = -INFINITY;
-    for (int i = blockIdx.x * TP_BLOCK + threadIdx.x; i < n; i += TP_PARTS * TP_BLOCK) {
-        const float d = gt[i];
-        if (d < max_depth) v = fmaxf(v, d);
-    }
-    block_store_max(v, red, parts + blockIdx.x);
-}
-
-__global__ void __launch_bounds__(TP_BLOCK) topo_var_max_kernel(int H, int W, const float* __restrict__ gt, float* __restrict__ parts)
-{
-    __shared__ float red[TP_BLOCK];
-    const float m = clip_depth(block_max_of_parts(parts, red));
-    float v = 0.f;
-    if (m != -INFINITY)
-        for (int i = blockIdx.x * TP_BLOCK + threadIdx.x; i < H * W; i += TP_PARTS * TP_BLOCK)
-            v = fmaxf(v, edge_var(gt, H, W, i / W, i % W, m));
-    block_store_max(v, red, parts + TP_PARTS + blockIdx.x);
-}
-
-}  // namespace
-
-struct TopoView {
-    double R[9], t[3];   // COLMAP world-to-camera rotation (row-major) and translation (cmr["extrinsics"][c][:3])
-    double fx, fy;       // cmr["intrinsics"][c][0,0], [1,1]
-};
-
-namespace {
-
-__global__ void __launch_bounds__(TP_BLOCK) topo_view_kernel(int H, int W, int V, const float* __restrict__ verts,
-                                                             const float* __restrict__ gt, const float* __restrict__ render,
-                                                             const float* __restrict__ surface, float max_depth,
-                                                             const float* __restrict__ parts, TopoView cam, float* __restrict__ row)
-{
-    __shared__ float red[TP_BLOCK];
+    __shared__ float red[RIG_BLOCK];
     const float gmax = block_max_of_parts(parts, red);
-    const float vmax = block_max_of_parts(parts + TP_PARTS, red);
-    const int v = blockIdx.x * TP_BLOCK + threadIdx.x;
+    const float vmax = block_max_of_parts(parts + RIG_PARTS, red);
+    const int v = blockIdx.x * RIG_BLOCK + threadIdx.x;
     if (v >= V) return;
     // a camera without GT below max_depth (the reference raises on the empty max) or with a flat GT (max(var) = 0: edge_vis
     // is NaN and nothing passes `< 0.1`) sees no vertex
     if (gmax == -INFINITY || !(vmax > 0.f)) { row[v] = -1.f; return; }
     const float m = clip_depth(gmax);
-    // warp_mesh.py:47-74 in double: local = R v + t, row = fy y / z + H / 2, col = fx x / z + W / 2 (no principal point)
-    const double px = verts[3 * v], py = verts[3 * v + 1], pz = verts[3 * v + 2];
-    const double lx = cam.R[0] * px + cam.R[1] * py + cam.R[2] * pz + cam.t[0];
-    const double ly = cam.R[3] * px + cam.R[4] * py + cam.R[5] * pz + cam.t[1];
-    const double lz = cam.R[6] * px + cam.R[7] * py + cam.R[8] * pz + cam.t[2];
-    const double pr = cam.fy * (ly / lz) + H * 0.5 + 0.5, pc = cam.fx * (lx / lz) + W * 0.5 + 0.5;
-    // query_at_image: np.int32(pix + 0.5) truncates toward zero and the lookup is valid iff clipping changed nothing, i.e.
-    // iff pix + 0.5 lies in (-1, size) -- row -0.9 reads row 0 and is valid; NaN is not
-    if (!(pr > -1.0 && pr < (double)H && pc > -1.0 && pc < (double)W)) { row[v] = -1.f; return; }
-    const int iy = (int)pr, ix = (int)pc;
+    double lx, ly, lz, pr, pc;
+    rig_project(cam, H, W, verts[3 * v], verts[3 * v + 1], verts[3 * v + 2], lx, ly, lz, pr, pc);
+    bool ok = true;
+    const int iy = rig_query(pr, H, ok), ix = rig_query(pc, W, ok);
+    if (!ok) { row[v] = -1.f; return; }
     const size_t p = (size_t)iy * W + ix;
     const float s = surface[p];
-    const float ev = fminf(__fdiv_rn(edge_var(gt, H, W, iy, ix, m), vmax) * 1000.f, 1.f);   // refined_mesh.py:792
+    const float ev = fminf(__fdiv_rn(edge_var<1>(gt, H, W, iy, ix, m), vmax) * 1000.f, 1.f);   // refined_mesh.py:792
     if (!(fabs(lz - (double)s) < 0.005) || !(ev < 0.1f)) { row[v] = -1.f; return; }          // :790-794
     row[v] = fminf(fabsf(fminf(gt[p], max_depth) - render[p]) * (1.f - ev) * 10.f, 2.f);     // :780, :799
 }
@@ -387,20 +295,16 @@ inline int blocks(int n) { return (n + TP_BLOCK - 1) / TP_BLOCK; }
 
 }  // namespace
 
-size_t topo_view_workspace_bytes() { return 2 * TP_PARTS * sizeof(float); }
+size_t topo_view_workspace_bytes() { return 2 * RIG_PARTS * sizeof(float); }
 
 void launch_topo_view(int H, int W, int V, const float* verts, const float* gt, const float* render, const float* surface,
                       float max_depth, const double* cam14, void* workspace, float* row, hipStream_t st)
 {
     float* parts = static_cast<float*>(workspace);
-    TopoView cam;
-    for (int i = 0; i < 9; ++i) cam.R[i] = cam14[i];
-    for (int i = 0; i < 3; ++i) cam.t[i] = cam14[9 + i];
-    cam.fx = cam14[12];
-    cam.fy = cam14[13];
-    topo_gt_max_kernel<<<TP_PARTS, TP_BLOCK, 0, st>>>(H * W, gt, max_depth, parts);
-    topo_var_max_kernel<<<TP_PARTS, TP_BLOCK, 0, st>>>(H, W, gt, parts);
-    if (V > 0) topo_view_kernel<<<blocks(V), TP_BLOCK, 0, st>>>(H, W, V, verts, gt, render, surface, max_depth, parts, cam, row);
+    const RigCamera cam = rig_camera(cam14);
+    topo_gt_max_kernel<<<RIG_PARTS, RIG_BLOCK, 0, st>>>(H * W, gt, max_depth, parts);
+    topo_var_max_kernel<<<RIG_PARTS, RIG_BLOCK, 0, st>>>(H, W, gt, parts);
+    if (V > 0) topo_view_kernel<<<blocks(V), RIG_BLOCK, 0, st>>>(H, W, V, verts, gt, render, surface, max_depth, parts, cam, row);
 }
 
 void launch_topo_aggregate(int C, int V, const float* table, const float* verts, const float* ymin, double depth_scalar,
@@ -413,17 +317,12 @@ void launch_topo_aggregate(int C, int V, const float* table, const float* verts,
 void launch_topo_propagate(int V, const int* off, const int* nbr, int sweeps, const double* value_in, const unsigned char* valid_in,
                            double* value_out, double* value_tmp, unsigned char* valid_a, unsigned char* valid_b, hipStream_t st)
 {
-    // sweep s writes bufs[(sweeps - 1 - s) % 2], so the last one lands in value_out
-    double* vb[2] = {value_out, value_tmp};
     unsigned char* ob[2] = {valid_a, valid_b};
-    const double* src = value_in;
     const unsigned char* osrc = valid_in;
-    for (int s = 0; s < sweeps; ++s) {
-        const int k = (sweeps - 1 - s) & 1;
-        topo_propagate_kernel<<<blocks(V), TP_BLOCK, 0, st>>>(V, off, nbr, src, osrc, vb[k], ob[k]);
-        src = vb[k];
+    ping_pong_sweeps(sweeps, value_in, value_out, value_tmp, [&](const double* src, double* dst, int k) {
+        topo_propagate_kernel<<<blocks(V), TP_BLOCK, 0, st>>>(V, off, nbr, src, osrc, dst, ob[k]);
         osrc = ob[k];
-    }
+    });
 }
 
 void launch_topo_voxel_keys(int V, const float* verts, const float* vmin, double voxel_size, long long* keys, int* flags,

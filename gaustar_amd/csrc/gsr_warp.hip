@@ -7,9 +7,9 @@
 // (:347-358), up to 20 propagation sweeps (:384, :133-155) and 5 smoothing sweeps (:394, :158-171).  Here:
 //   once per warp
 //     warp_face_kernel / warp_vertex_normal_kernel  trimesh Trimesh.vertex_normals in world space (rotated per camera)
-//   per camera  (3 launches, no host round trip)
-//     warp_depth_max_kernel  per-workgroup max of depth_cur / depth_next below 10          -> partials [0, 2 WP_PARTS)
-//     warp_var_max_kernel    per-workgroup max of the 7x7 edge statistic of both maps       -> partials [2, 4 WP_PARTS)
+//   per camera  (3 launches, no host round trip; the camera, the edge statistic and the two image passes are gsr_rig.h's)
+//     warp_depth_max_kernel  per-workgroup max of depth_cur / depth_next below 10          -> partials [0, 2 RIG_PARTS)
+//     warp_var_max_kernel    per-workgroup max of the 7x7 edge statistic of both maps       -> partials [2, 4 RIG_PARTS)
 //     warp_view_kernel       one lane per vertex, :286-340 in f64                           -> one row [V,3] of the [C,V,3] table
 //   over the rig
 //     warp_aggregate_kernel  observed count, remove_outlier, kept count, mean (:347-358) in camera order
@@ -20,9 +20,8 @@
 // tests/warp_ref.py operation by operation, so contraction into FMAs is off for this file.
 //
 // Assumptions (cv2 and trimesh are not available to check them against):
-//   * cv2.blur(., (7, 7)): BORDER_REFLECT_101, the 49 values summed in double (row sums, then the rows) times 1/49 and
-//     rounded to f32 -- the convention gsr_topo.hip documents for the 3x3 filter.  While the non-zero values of a window (d and
-//     d^2) lie within a factor of 2^23 of each other the double sum is exact, so its order does not matter.
+//   * cv2.blur(., (7, 7)): BORDER_REFLECT_101, the 49 values summed in double times 1/49 and rounded to f32 -- edge_var of
+//     gsr_rig.h, which states the convention once for this filter and the detection's 3x3.
 //   * cv2.resize(flow, (W, H), INTER_NEAREST) as OpenCV's resizeNN computes it: source column
 //     min(floor(x * (1.0 / ((double)W / w_padded))), w_padded - 1), and the same for rows.
 //   * flow *= H / h_padded multiplies in f32 by the f32-rounded ratio (NumPy 1.x value-based casting of the np.float64 scalar,
@@ -32,7 +31,7 @@
 //     Corner angles: arccos of the clipped dot products of the unit edge vectors at corners 0 and 1, pi minus both at corner
 //     2, all three zero when one is below 1e-8.  trimesh computes the normals of the camera-space mesh; these are the world
 //     normals rotated into the camera, which differ only by rounding.
-#include "gsr_internal.h"
+#include "gsr_rig.h"
 
 #pragma clang fp contract(off)
 
@@ -40,108 +39,24 @@ namespace gsr {
 
 namespace {
 
-constexpr int WP_BLOCK = 256;
-constexpr int WP_PARTS = 2048;   // workgroups of the image passes per map (grid-stride), = partials per statistic and map
+constexpr int WP_BLOCK = RIG_BLOCK;   // the rig-wide kernels; the per-camera kernels must run RIG_BLOCK lanes
 constexpr int WP_R = 3;          // get_depth_edge(depth, 7): offsets -3 .. 3
 constexpr float WP_MAX_DEPTH = 10.f;   // the literal 10 of warp_mesh.py:122 and :319
 
-// cv2 BORDER_REFLECT_101 (gfedcb|abcdefgh|gfedcba), for any offset
-__device__ __forceinline__ int reflect101_any(int i, int n)
-{
-    if (n == 1) return 0;
-    while (i < 0 || i >= n) i = i < 0 ? -i : 2 * n - 2 - i;
-    return i;
-}
-
-// get_depth_edge(depth, 7) at (y, x): d = min(depth, m), var = max(blur7(d^2) - blur7(d)^2, 0); d^2 squared in f32 (numpy
-// `depth ** 2`), blur7(d) squared in f32
-__device__ __forceinline__ float edge_var7(const float* __restrict__ g, int H, int W, int y, int x, float m)
-{
-    double s1 = 0.0, s2 = 0.0;
-    int xs[2 * WP_R + 1];
-#pragma unroll
-    for (int dx = -WP_R; dx <= WP_R; ++dx) xs[dx + WP_R] = reflect101_any(x + dx, W);
-#pragma unroll
-    for (int dy = -WP_R; dy <= WP_R; ++dy) {
-        const float* row = g + (size_t)reflect101_any(y + dy, H) * W;
-        double r1 = 0.0, r2 = 0.0;
-#pragma unroll
-        for (int k = 0; k < 2 * WP_R + 1; ++k) {
-            const float d = fminf(row[xs[k]], m);
-            r1 += (double)d;
-            r2 += (double)(d * d);
-        }
-        s1 += r1;
-        s2 += r2;
-    }
-    const float mean = (float)(s1 * (1.0 / 49.0)), sq_mean = (float)(s2 * (1.0 / 49.0));
-    return fmaxf(sq_mean - mean * mean, 0.f);
-}
-
-// max over the WP_PARTS partials at `p`, by the whole workgroup (every lane gets it)
-__device__ float wp_block_max_of_parts(const float* __restrict__ p, float* red)
-{
-    float v = -INFINITY;
-    for (int i = threadIdx.x; i < WP_PARTS; i += WP_BLOCK) v = fmaxf(v, p[i]);
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = WP_BLOCK / 2; s > 0; s >>= 1) {
-        if (threadIdx.x < s) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + s]);
-        __syncthreads();
-    }
-    const float r = red[0];
-    __syncthreads();
-    return r;
-}
-
-__device__ void wp_block_store_max(float v, float* red, float* out)
-{
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = WP_BLOCK / 2; s > 0; s >>= 1) {
-        if (threadIdx.x < s) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + s]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *out = red[0];
-}
-
-// m = f32(1.1 * max(depth[depth < 10])) (warp_mesh.py:122-123, the product in double as NumPy 1.x evaluates it); -inf when no
-// pixel is below 10
-__device__ __forceinline__ float wp_clip_depth(float dmax) { return dmax == -INFINITY ? -INFINITY : (float)((double)dmax * 1.1); }
-
 // blockIdx.y: 0 = depth_cur, 1 = depth_next
-__global__ void __launch_bounds__(WP_BLOCK) warp_depth_max_kernel(int n, const float* __restrict__ cur, const float* __restrict__ nxt,
-                                                                  float* __restrict__ parts)
+__global__ void __launch_bounds__(RIG_BLOCK) warp_depth_max_kernel(int n, const float* __restrict__ cur, const float* __restrict__ nxt,
+                                                                   float* __restrict__ parts)
 {
-    __shared__ float red[WP_BLOCK];
-    const float* g = blockIdx.y ? nxt : cur;
-    float v = -INFINITY;
-    for (long long i = blockIdx.x * WP_BLOCK + threadIdx.x; i < n; i += WP_PARTS * WP_BLOCK) {   // (64-bit: no overflow near 2^31)
-        const float d = g[i];
-        if (d < WP_MAX_DEPTH) v = fmaxf(v, d);
-    }
-    wp_block_store_max(v, red, parts + blockIdx.y * WP_PARTS + blockIdx.x);
+    depth_max_pass(n, blockIdx.y ? nxt : cur, WP_MAX_DEPTH, blockIdx.y, parts);
 }
 
-__global__ void __launch_bounds__(WP_BLOCK) warp_var_max_kernel(int H, int W, const float* __restrict__ cur, const float* __restrict__ nxt,
-                                                                float* __restrict__ parts)
+__global__ void __launch_bounds__(RIG_BLOCK) warp_var_max_kernel(int H, int W, const float* __restrict__ cur, const float* __restrict__ nxt,
+                                                                 float* __restrict__ parts)
 {
-    __shared__ float red[WP_BLOCK];
-    const float* g = blockIdx.y ? nxt : cur;
-    const float m = wp_clip_depth(wp_block_max_of_parts(parts + blockIdx.y * WP_PARTS, red));
-    float v = 0.f;
-    if (m != -INFINITY)
-        for (long long i = blockIdx.x * WP_BLOCK + threadIdx.x; i < (long long)H * W; i += WP_PARTS * WP_BLOCK)
-            v = fmaxf(v, edge_var7(g, H, W, (int)(i / W), (int)(i % W), m));
-    wp_block_store_max(v, red, parts + (2 + blockIdx.y) * WP_PARTS + blockIdx.x);
+    var_max_pass<WP_R>(H, W, blockIdx.y ? nxt : cur, blockIdx.y, 2, parts);
 }
 
 }  // namespace
-
-struct WarpView {
-    double R[9], t[3];   // COLMAP world-to-camera rotation (row-major) and translation (cmr["extrinsics"][c][:3])
-    double fx, fy;       // cmr["intrinsics"][c][0,0], [1,1]
-};
 
 // one raw RAFT flow [h, w, 2] f32 in (x, y) order, padded by (top, bottom, left, right) zeros to (hp, wp), scaled by `scale`
 // and resized (nearest) to the camera's (H, W); ify / ifx = 1 / (H / hp), 1 / (W / wp) in double as cv2 computes them
@@ -161,17 +76,6 @@ struct WarpParams {      // warp_config (warp_mesh.py:14-25)
 
 namespace {
 
-// query_at_image's index (warp_mesh.py:106-117): np.int32(pix + 0.5) truncates toward zero, NaN and values out of the int32
-// range become INT_MIN (x86's conversion); the index is clipped to [0, n - 1] and the lookup valid iff clipping changed nothing
-__device__ __forceinline__ int wp_query(double pix, int n, bool& ok)
-{
-    const double y = pix + 0.5;
-    const int p = (y > -2147483649.0 && y < 2147483648.0) ? (int)y : INT_MIN;
-    const int c = min(max(p, 0), n - 1);
-    ok = ok && p == c;
-    return c;
-}
-
 // flow[iy, ix] after pad_and_resize_flow (warp_mesh.py:96-103) and the [..., ::-1] swap (:270-271): (row, col) displacement
 __device__ __forceinline__ void wp_flow_at(const WarpFlow& f, int iy, int ix, float& dr, float& dc)
 {
@@ -187,21 +91,21 @@ __device__ __forceinline__ void wp_flow_at(const WarpFlow& f, int iy, int ix, fl
 // edge_vis = min(var / max(var) * edge_scalar, 1) in f32 (warp_mesh.py:298, :313)
 __device__ __forceinline__ float wp_edge_vis(const float* g, int H, int W, int y, int x, float m, float vmax, float scalar)
 {
-    return fminf(__fdiv_rn(edge_var7(g, H, W, y, x, m), vmax) * scalar, 1.f);
+    return fminf(__fdiv_rn(edge_var<WP_R>(g, H, W, y, x, m), vmax) * scalar, 1.f);
 }
 
-__global__ void __launch_bounds__(WP_BLOCK) warp_view_kernel(int H, int W, int V, const double* __restrict__ verts,
+__global__ void __launch_bounds__(RIG_BLOCK) warp_view_kernel(int H, int W, int V, const double* __restrict__ verts,
                                                              const double* __restrict__ normals, WarpFlow ff, WarpFlow fb,
                                                              const float* __restrict__ dcur, const float* __restrict__ dnext,
-                                                             const float* __restrict__ parts, WarpView cam, WarpParams prm,
+                                                             const float* __restrict__ parts, RigCamera cam, WarpParams prm,
                                                              double* __restrict__ row)
 {
-    __shared__ float red[WP_BLOCK];
-    const float gmax_c = wp_block_max_of_parts(parts, red);
-    const float gmax_n = wp_block_max_of_parts(parts + WP_PARTS, red);
-    const float vmax_c = wp_block_max_of_parts(parts + 2 * WP_PARTS, red);
-    const float vmax_n = wp_block_max_of_parts(parts + 3 * WP_PARTS, red);
-    const int v = blockIdx.x * WP_BLOCK + threadIdx.x;
+    __shared__ float red[RIG_BLOCK];
+    const float gmax_c = block_max_of_parts(parts, red);
+    const float gmax_n = block_max_of_parts(parts + RIG_PARTS, red);
+    const float vmax_c = block_max_of_parts(parts + 2 * RIG_PARTS, red);
+    const float vmax_n = block_max_of_parts(parts + 3 * RIG_PARTS, red);
+    const int v = blockIdx.x * RIG_BLOCK + threadIdx.x;
     if (v >= V) return;
     double* out = row + 3 * (size_t)v;
     // a camera whose depth has no pixel below 10 (the reference raises on the empty max) or is flat (max(var) = 0: edge_vis
@@ -210,16 +114,14 @@ __global__ void __launch_bounds__(WP_BLOCK) warp_view_kernel(int H, int W, int V
         out[0] = out[1] = out[2] = NAN;
         return;
     }
-    const float m_c = wp_clip_depth(gmax_c), m_n = wp_clip_depth(gmax_n);
+    const float m_c = clip_depth(gmax_c), m_n = clip_depth(gmax_n);
     const float escale = (float)prm.edge_scalar, ethr = (float)prm.edge_threshold;
-    // 1. project (warp_mesh.py:47-74, no principal point) and look up depth_cur (:287-289)
+    // 1. project and look up depth_cur (:287-289)
     const double px = verts[3 * v], py = verts[3 * v + 1], pz = verts[3 * v + 2];
-    const double lx = cam.R[0] * px + cam.R[1] * py + cam.R[2] * pz + cam.t[0];
-    const double ly = cam.R[3] * px + cam.R[4] * py + cam.R[5] * pz + cam.t[1];
-    const double lz = cam.R[6] * px + cam.R[7] * py + cam.R[8] * pz + cam.t[2];
-    const double pr = cam.fy * (ly / lz) + H * 0.5, pc = cam.fx * (lx / lz) + W * 0.5;
+    double lx, ly, lz, pr, pc;
+    rig_project(cam, H, W, px, py, pz, lx, ly, lz, pr, pc);
     bool ok = true;
-    const int iy = wp_query(pr, H, ok), ix = wp_query(pc, W, ok);
+    const int iy = rig_query(pr, H, ok), ix = rig_query(pc, W, ok);
     const float d_cur = dcur[(size_t)iy * W + ix];
     // 2. visible: valid lookup, |z - depth| < 0.005, camera-space normal z < cmr_view_max_cos (:291-295), edge (:298-300)
     const double nz = cam.R[6] * normals[3 * v] + cam.R[7] * normals[3 * v + 1] + cam.R[8] * normals[3 * v + 2];
@@ -230,12 +132,12 @@ __global__ void __launch_bounds__(WP_BLOCK) warp_view_kernel(int H, int W, int V
     wp_flow_at(ff, iy, ix, fr, fc);
     const double nr = pr + (double)fr, nc = pc + (double)fc;
     bool ok_n = true;
-    const int jy = wp_query(nr, H, ok_n), jx = wp_query(nc, W, ok_n);
+    const int jy = rig_query(nr, H, ok_n), jx = rig_query(nc, W, ok_n);
     // 4. pix_back = pix_next + flow_back[q(pix_next)] (:306)
     wp_flow_at(fb, jy, jx, fr, fc);
     const double br = nr + (double)fr, bc = nc + (double)fc;
     bool ok_b = true;
-    const int ky = wp_query(br, H, ok_b), kx = wp_query(bc, W, ok_b);
+    const int ky = rig_query(br, H, ok_b), kx = rig_query(bc, W, ok_b);
     // 5. depth consistency in f32 (:307-308)
     vis = vis && fabsf(dcur[(size_t)ky * W + kx] - d_cur) < (float)prm.bi_depth;
     // 6. pixel round trip in f64 (:309-310)
@@ -400,7 +302,7 @@ WarpFlow make_flow(const float* raw, const int* shape6, int H, int W)
 
 }  // namespace
 
-size_t warp_view_workspace_bytes() { return 4 * WP_PARTS * sizeof(float); }
+size_t warp_view_workspace_bytes() { return 4 * RIG_PARTS * sizeof(float); }
 
 void launch_warp_normals(int V, int F, const double* verts, const int* faces, const int* vf_off, const int* vf_ent, double* fbuf,
                          double* normals, hipStream_t st)
@@ -414,11 +316,7 @@ void launch_warp_view(int H, int W, int V, const double* verts, const double* no
                       const double* params, void* workspace, double* row, hipStream_t st)
 {
     float* parts = static_cast<float*>(workspace);
-    WarpView cam;
-    for (int i = 0; i < 9; ++i) cam.R[i] = cam14[i];
-    for (int i = 0; i < 3; ++i) cam.t[i] = cam14[9 + i];
-    cam.fx = cam14[12];
-    cam.fy = cam14[13];
+    const RigCamera cam = rig_camera(cam14);
     WarpParams prm;
     prm.normal_cos = params[0];
     prm.edge_scalar = params[1];
@@ -427,10 +325,10 @@ void launch_warp_view(int H, int W, int V, const double* verts, const double* no
     prm.bi_pix = params[4];
     prm.max_move = params[5];
     const WarpFlow ff = make_flow(flow_f, flow_shape, H, W), fb = make_flow(flow_b, flow_shape, H, W);
-    warp_depth_max_kernel<<<dim3(WP_PARTS, 2), WP_BLOCK, 0, st>>>(H * W, depth_cur, depth_next, parts);
-    warp_var_max_kernel<<<dim3(WP_PARTS, 2), WP_BLOCK, 0, st>>>(H, W, depth_cur, depth_next, parts);
+    warp_depth_max_kernel<<<dim3(RIG_PARTS, 2), RIG_BLOCK, 0, st>>>(H * W, depth_cur, depth_next, parts);
+    warp_var_max_kernel<<<dim3(RIG_PARTS, 2), RIG_BLOCK, 0, st>>>(H, W, depth_cur, depth_next, parts);
     if (V > 0)
-        warp_view_kernel<<<wblocks(V), WP_BLOCK, 0, st>>>(H, W, V, verts, normals, ff, fb, depth_cur, depth_next, parts, cam, prm, row);
+        warp_view_kernel<<<wblocks(V), RIG_BLOCK, 0, st>>>(H, W, V, verts, normals, ff, fb, depth_cur, depth_next, parts, cam, prm, row);
 }
 
 void launch_warp_aggregate(int C, int V, const double* table, int min_observe, double* move, int* observed, int* count,
@@ -441,14 +339,9 @@ void launch_warp_aggregate(int C, int V, const double* table, int min_observe, d
 
 void launch_warp_smooth(int V, const int* off, const int* nbr, int sweeps, const double* in, double* out, double* tmp, hipStream_t st)
 {
-    // sweep s writes bufs[(sweeps - 1 - s) % 2], so the last one lands in `out`
-    double* b[2] = {out, tmp};
-    const double* src = in;
-    for (int s = 0; s < sweeps; ++s) {
-        const int k = (sweeps - 1 - s) & 1;
-        warp_smooth_kernel<<<wblocks(V), WP_BLOCK, 0, st>>>(V, off, nbr, src, b[k]);
-        src = b[k];
-    }
+    ping_pong_sweeps(sweeps, in, out, tmp, [&](const double* src, double* dst, int) {
+        warp_smooth_kernel<<<wblocks(V), WP_BLOCK, 0, st>>>(V, off, nbr, src, dst);
+    });
 }
 
 }  // namespace gsr

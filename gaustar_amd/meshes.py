@@ -14,9 +14,19 @@ Deliberately NOT a package named `pytorch3d`: that would shadow a real install.
 """
 from __future__ import annotations
 
+from functools import cached_property
+
 import torch
 
 _TOPO_ATTR = "_gsr_mesh_topology"   # set on the faces tensor OBJECT: (version, n_verts, MeshTopology)
+
+
+def _csr(owner: torch.Tensor, item: torch.Tensor, n_owners: int, n_items: int) -> tuple:
+    """(offsets [n_owners + 1], items) int32: every owner's items (int64 in [0, n_items)) in ascending order, owner-major."""
+    key, _ = torch.sort(owner * max(n_items, 1) + item)
+    counts = torch.bincount(owner, minlength=n_owners)
+    off = torch.cat([torch.zeros(1, dtype=torch.long, device=owner.device), torch.cumsum(counts, 0)])
+    return off.int().contiguous(), (key % max(n_items, 1)).int().contiguous()
 
 
 class MeshTopology:
@@ -29,7 +39,8 @@ class MeshTopology:
           n faces, in the order of torch.combinations over the edge's face-edges sorted by edge -- with a, b the corners of
           the two faces not on the edge; pair_edge [Q] int64 the pair's edge;
       csr_offsets [V+1], csr_entries int32: every (vertex, element, role) incidence, vertex-major, entry = element * 4 +
-          role over the element index space pairs [0, Q), edges [Q, Q + E), faces [Q + E, Q + E + F) (include/gsr.h).
+          role over the element index space pairs [0, Q), edges [Q, Q + E), faces [Q + E, Q + E + F) (include/gsr.h);
+      vertex_neighbours, vertex_face_csr: two more vertex-major lists, built on first use.
 
     Built with torch operations on the faces' device (host synchronisations: this is not the hot path).  Use
     MeshTopology.of(faces, n_verts) for the cached instance."""
@@ -77,10 +88,18 @@ class MeshTopology:
         role = lambda n: ar(n)[None, :]
         vid = torch.cat([self.pairs.long().reshape(-1), self.edges_packed.reshape(-1), f.reshape(-1)])
         code = torch.cat([ar(4 * Q), ((Q + ar(E))[:, None] * 4 + role(2)).reshape(-1), ((Q + E + ar(F))[:, None] * 4 + role(3)).reshape(-1)])
-        key, _ = torch.sort(vid * max(T4, 1) + code)
-        self.csr_entries = (key % max(T4, 1)).int().contiguous()
-        counts = torch.bincount(vid, minlength=V)
-        self.csr_offsets = torch.cat([torch.zeros(1, dtype=torch.long, device=dev), torch.cumsum(counts, 0)]).int().contiguous()
+        self.csr_offsets, self.csr_entries = _csr(vid, code, V, T4)
+
+    @cached_property
+    def vertex_neighbours(self) -> tuple:
+        """(offsets [V+1], neighbours) int32: trimesh's vertex_neighbors from the edges, each list in ascending order."""
+        e = self.edges_packed
+        return _csr(torch.cat([e[:, 0], e[:, 1]]), torch.cat([e[:, 1], e[:, 0]]), self.V, self.V)
+
+    @cached_property
+    def vertex_face_csr(self) -> tuple:
+        """(offsets [V+1], entries [3F]) int32: every vertex's incidences face * 3 + corner in ascending face order."""
+        return _csr(self.faces.reshape(-1).long(), torch.arange(3 * self.F, device=self.device), self.V, 3 * self.F)
 
     @property
     def device(self):

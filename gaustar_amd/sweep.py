@@ -8,6 +8,7 @@ GPU; `nccl` = RCCL on ROCm, `gloo` for the CPU tests): rank r renders cameras r,
 per-view rows are brought together with one all_gather.  There is no other communication."""
 from __future__ import annotations
 
+import ctypes
 from typing import Callable, List, Optional, Sequence
 
 import numpy as np
@@ -45,6 +46,26 @@ def gather_rows(local_rows: torch.Tensor, n_total: int, rank: Optional[int] = No
         idx = camera_shard(n_total, r, world)
         out[idx] = parts[r][:len(idx)]
     return out
+
+
+def cam14(extr: np.ndarray, intr: np.ndarray):
+    """The [host] camera block of gsr_topo_view / gsr_warp_view from one camera of the reference's `cmr`: the COLMAP
+    world-to-camera rotation (row-major) and translation, fx, fy."""
+    vals = list(np.asarray(extr[:3, :3], np.float64).reshape(-1)) + list(np.asarray(extr[:3, 3], np.float64)) + \
+        [float(intr[0, 0]), float(intr[1, 1])]
+    return (ctypes.c_double * 14)(*vals)
+
+
+def run_shard(work: Callable, n: int, views_in_flight: int, dev) -> None:
+    """work(thread, j) for j in range(n), the cameras of one rank's shard: `views_in_flight` at a time on as many streams
+    (pipelines.ViewPipelines), or a plain loop on the calling stream.  The views must be independent, and whatever cache
+    `work` reads without a lock is filled by the caller before."""
+    if views_in_flight > 1 and n > 1 and torch.device(dev).type == "cuda":
+        from . import pipelines
+        pipelines.ViewPipelines(min(int(views_in_flight), n), dev).run(work, list(range(n)))
+    else:
+        for j in range(n):
+            work(0, j)
 
 
 class ForwardSweep:
@@ -111,18 +132,13 @@ class ForwardSweep:
         worker's stream."""
         mine = camera_shard(len(cameras), rank, world)
         dev = self.means3D.device
-        if views_in_flight > 1 and len(mine) > 1 and dev.type == "cuda":
-            from . import pipelines
-            for cam in (cameras[i] for i in mine):
-                self._cam(cam)                      # upload the matrices before the workers start (the cache is not locked)
-            slots = [None] * len(mine)
+        for i in mine:
+            self._cam(cameras[i])                   # upload the matrices before the workers start (the cache is not locked)
+        rows = [None] * len(mine)
 
-            def work(_t, j):
-                i = mine[j]
-                slots[j] = per_view(i, cameras[i], *self.render_rgb_depth(cameras[i]))
-            pipelines.ViewPipelines(min(int(views_in_flight), len(mine)), dev).run(work, list(range(len(mine))))
-            rows = slots
-        else:
-            rows = [per_view(i, cameras[i], *self.render_rgb_depth(cameras[i])) for i in mine]
+        def work(_t, j):
+            i = mine[j]
+            rows[j] = per_view(i, cameras[i], *self.render_rgb_depth(cameras[i]))
+        run_shard(work, len(mine), views_in_flight, dev)
         local = torch.stack(rows) if rows else torch.zeros(0, 1, device=dev)
         return gather_rows(local, len(cameras), rank, world)

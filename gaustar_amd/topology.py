@@ -21,7 +21,6 @@ Not implemented (ValueError in the adapter): the colour and densifier-gradient t
 """
 from __future__ import annotations
 
-import ctypes
 from dataclasses import dataclass
 from typing import Callable, Optional, Sequence, Union
 
@@ -29,16 +28,9 @@ import numpy as np
 import torch
 
 from . import _lib, sweep
+from ._lib import ptr as _p, stream_ptr as _stream
 
 MAX_DEPTH = 10.0   # refined_mesh.py:24
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _p(t: Optional[torch.Tensor]):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
 def rig_from_cameras(cameras: Sequence) -> dict:
@@ -83,24 +75,9 @@ class TopologyErrors:
     table: Optional[torch.Tensor] = None
 
 
-_NBR_ATTR = "_gsr_topo_neighbours"
-
-
 def vertex_neighbours(topo) -> tuple:
-    """(offsets [V+1], neighbours) int32 on the topology's device: trimesh's vertex_neighbors from MeshTopology's edges, each
-    list in ascending order.  Built once per MeshTopology."""
-    c = getattr(topo, _NBR_ATTR, None)
-    if c is not None:
-        return c
-    V, e = topo.V, topo.edges_packed
-    src = torch.cat([e[:, 0], e[:, 1]])
-    dst = torch.cat([e[:, 1], e[:, 0]])
-    key, _ = torch.sort(src * max(V, 1) + dst)
-    nbr = (key % max(V, 1)).int().contiguous()
-    counts = torch.bincount(src, minlength=V)
-    off = torch.cat([torch.zeros(1, dtype=torch.long, device=e.device), torch.cumsum(counts, 0)]).int().contiguous()
-    setattr(topo, _NBR_ATTR, (off, nbr))
-    return off, nbr
+    """meshes.MeshTopology.vertex_neighbours: (offsets [V+1], neighbours) int32, built once per MeshTopology."""
+    return topo.vertex_neighbours
 
 
 def unbind_weights(face_loss: torch.Tensor, face_colour: torch.Tensor, G: int) -> tuple:
@@ -109,12 +86,6 @@ def unbind_weights(face_loss: torch.Tensor, face_colour: torch.Tensor, G: int) -
     colour 255 -- Gaussians, not faces, despite the reference's name."""
     unbind = (1.0 - face_loss).repeat_interleave(G)[:, None].expand(-1, 3)
     return unbind, (face_colour == 255).sum() * G
-
-
-def _cam14(extr: np.ndarray, intr: np.ndarray):
-    vals = list(np.asarray(extr[:3, :3], np.float64).reshape(-1)) + list(np.asarray(extr[:3, 3], np.float64)) + \
-        [float(intr[0, 0]), float(intr[1, 1])]
-    return (ctypes.c_double * 14)(*vals)
 
 
 class DepthRenders:
@@ -155,7 +126,6 @@ def detect_topology_errors(model, cameras: Sequence, gt_depth: Union[torch.Tenso
     or a callable i -> [H,W] (any device; read once per camera of this rank's shard).  rig: the `cmr` dict the projection
     uses (default rig_from_cameras(cameras)).  Defaults are refine.py:724-727's call.  mesh_prop: propagation sweeps (0 =
     none, as the reference's `if mesh_prop:`)."""
-    from . import pipelines
     lib = _lib.load()
     dev = model.device
     if dev.type != "cuda":
@@ -189,14 +159,10 @@ def detect_topology_errors(model, cameras: Sequence, gt_depth: Union[torch.Tenso
             raise ValueError(f"camera {i}: GT depth {tuple(g.shape)} / render {tuple(render.shape)} vs rig shape {(H, W)}")
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         _lib.check(lib.gsr_topo_view(H, W, V, _p(verts), _p(g), _p(render), _p(surface), float(max_depth),
-                                     _cam14(rig["extrinsics"][i], rig["intrinsics"][i]), _p(ws), _p(local[j]), _stream()),
+                                     sweep.cam14(rig["extrinsics"][i], rig["intrinsics"][i]), _p(ws), _p(local[j]), _stream()),
                    "gsr_topo_view")
 
-    if views_in_flight > 1 and len(mine) > 1:
-        pipelines.ViewPipelines(min(int(views_in_flight), len(mine)), dev).run(work, list(range(len(mine))))
-    else:
-        for j in range(len(mine)):
-            work(0, j)
+    sweep.run_shard(work, len(mine), views_in_flight, dev)
     table = sweep.gather_rows(local, C, rank, world)
 
     # ---- over the rig (every rank, same table, same bits)
@@ -207,7 +173,7 @@ def detect_topology_errors(model, cameras: Sequence, gt_depth: Union[torch.Tenso
     ymin = verts[:, 1].min().reshape(1) if V else None
     _lib.check(lib.gsr_topo_aggregate(C, V, _p(table.contiguous()), _p(verts), _p(ymin), float(depth_scalar), int(min_observe),
                                       int(bool(detect_floor)), _p(value), _p(count), _p(valid), stream), "gsr_topo_aggregate")
-    off, nbr = vertex_neighbours(topo)
+    off, nbr = topo.vertex_neighbours
     sweeps = int(mesh_prop) if mesh_prop else 0
     prop = torch.empty_like(value)
     tmp = torch.empty_like(value)

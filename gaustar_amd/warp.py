@@ -36,19 +36,12 @@ import numpy as np
 import torch
 
 from . import _lib, formats, sweep
+from ._lib import ptr as _p, stream_ptr as _stream
 
 PROP_SWEEPS = 20     # mesh_vert_propagate(max_ite=20) (warp_mesh.py:384, :133)
 SMOOTH_SWEEPS = 5    # mesh_color_smoothing(ite_num=5) (:394)
 FLOW_DIRS = {1: "flow_bi", 2: "flow_bi_2f", 4: "flow_bi_4f", 6: "flow_bi_6f"}    # :242-251
 MAX_PREFETCH_THREADS = 8
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _p(t: Optional[torch.Tensor]):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
 @dataclass
@@ -97,28 +90,9 @@ class MeshWarp:
     normals: Optional[torch.Tensor] = None
 
 
-def _cam14(extr: np.ndarray, intr: np.ndarray):
-    vals = list(np.asarray(extr[:3, :3], np.float64).reshape(-1)) + list(np.asarray(extr[:3, 3], np.float64)) + \
-        [float(intr[0, 0]), float(intr[1, 1])]
-    return (ctypes.c_double * 14)(*vals)
-
-
-_VF_ATTR = "_gsr_warp_vertex_faces"
-
-
 def vertex_face_csr(topo):
-    """(offsets [V+1], entries [3F]) int32 for a meshes.MeshTopology: every vertex's incidences face * 3 + corner in ascending
-    face order.  Built once per MeshTopology."""
-    c = getattr(topo, _VF_ATTR, None)
-    if c is not None:
-        return c
-    flat = topo.faces.reshape(-1).long()
-    _, order = torch.sort(flat, stable=True)          # face-major input: a stable sort keeps ascending faces per vertex
-    counts = torch.bincount(flat, minlength=topo.V)
-    off = torch.cat([torch.zeros(1, dtype=torch.long, device=flat.device), torch.cumsum(counts, 0)])
-    c = (off.int().contiguous(), order.int().contiguous())
-    setattr(topo, _VF_ATTR, c)
-    return c
+    """meshes.MeshTopology.vertex_face_csr: (offsets [V+1], entries [3F]) int32, built once per MeshTopology."""
+    return topo.vertex_face_csr
 
 
 def _pad6(flow: torch.Tensor, pad):
@@ -137,7 +111,6 @@ def warp_mesh(verts, faces, rig: dict, frames: Callable[[int], tuple], cfg: Warp
     (H, W)).  frames(i) -> (flow_f, flow_b, depth_cur, depth_next) for camera i, on any device: the raw RAFT flows [h,w,2]
     in (x, y) order and the depth maps [H,W] of frames f and f + interval; called once per camera of this rank's shard.
     pad: (top, bottom, left, right) of the flows (pad.txt), or None."""
-    from . import pipelines
     if cfg.post_processing != "mesh":
         raise ValueError(f"warp_mesh: post_processing={cfg.post_processing!r} is not implemented (only 'mesh')")
     lib = _lib.load()
@@ -146,7 +119,7 @@ def warp_mesh(verts, faces, rig: dict, frames: Callable[[int], tuple], cfg: Warp
     dev = torch.device(device)
     if dev.type != "cuda":
         raise RuntimeError("warp_mesh needs a GPU")
-    from . import meshes, topology
+    from . import meshes
     v = torch.as_tensor(np.asarray(verts) if not isinstance(verts, torch.Tensor) else verts).to(dev, torch.float64).contiguous()
     if v.dim() != 2 or v.shape[1] != 3:
         raise ValueError(f"verts must be [V,3], got {tuple(v.shape)}")
@@ -159,7 +132,7 @@ def warp_mesh(verts, faces, rig: dict, frames: Callable[[int], tuple], cfg: Warp
     stream = _stream()
 
     # ---- once per warp: world-space vertex normals
-    vf_off, vf_ent = vertex_face_csr(topo)
+    vf_off, vf_ent = topo.vertex_face_csr
     fbuf = torch.empty(max(F, 1), 6, dtype=torch.float64, device=dev)
     normals = torch.empty(V, 3, dtype=torch.float64, device=dev)
     _lib.check(lib.gsr_vertex_normals(V, F, _p(v), _p(f), _p(vf_off), _p(vf_ent), _p(fbuf), _p(normals), stream),
@@ -187,14 +160,10 @@ def warp_mesh(verts, faces, rig: dict, frames: Callable[[int], tuple], cfg: Warp
             raise ValueError(f"camera {i}: flows must be [h,w,2] of one shape, got {tuple(ff.shape)} / {tuple(fb.shape)}")
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         _lib.check(lib.gsr_warp_view(H, W, V, _p(v), _p(normals), _p(ff), _p(fb), _pad6(ff, pad), _p(dc), _p(dn),
-                                     _cam14(rig["extrinsics"][i], rig["intrinsics"][i]), params, _p(ws), _p(local[j]),
+                                     sweep.cam14(rig["extrinsics"][i], rig["intrinsics"][i]), params, _p(ws), _p(local[j]),
                                      _stream()), "gsr_warp_view")
 
-    if views_in_flight > 1 and len(mine) > 1:
-        pipelines.ViewPipelines(min(int(views_in_flight), len(mine)), dev).run(work, list(range(len(mine))))
-    else:
-        for j in range(len(mine)):
-            work(0, j)
+    sweep.run_shard(work, len(mine), views_in_flight, dev)
     table = sweep.gather_rows(local, C, rank, world)
 
     # ---- over the rig (every rank, same table, same bits)
@@ -205,7 +174,7 @@ def warp_mesh(verts, faces, rig: dict, frames: Callable[[int], tuple], cfg: Warp
     valid = torch.empty(V, dtype=torch.uint8, device=dev)
     _lib.check(lib.gsr_warp_aggregate(C, V, _p(table.contiguous()), int(cfg.min_observe), _p(move), _p(observed), _p(count),
                                       _p(valid), stream), "gsr_warp_aggregate")
-    off, nbr = topology.vertex_neighbours(topo)
+    off, nbr = topo.vertex_neighbours
     # propagation: the valid set evolves independently of the values, so one scalar call per component is the vector result
     comp = move.t().contiguous()
     prop_c = torch.empty_like(comp)
