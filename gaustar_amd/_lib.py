@@ -131,6 +131,16 @@ SIGNATURES = {
                               POINTER(c_double), POINTER(c_double), c_void_p, c_void_p, c_void_p]),
     "gsr_warp_aggregate": (c_int, [c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gsr_warp_smooth": (c_int, [c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # TSDF fusion of the rig's renders and mesh extraction (refined_mesh.py:311-459): gaustar_amd.fusion
+    "gsr_fusion_prep_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "gsr_fusion_volume_bytes": (c_size_t, [POINTER(c_int)]),
+    "gsr_fusion_prep": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gsr_fusion_touch": (c_int, [c_int, c_int, c_void_p, POINTER(c_double), c_double, c_double, POINTER(c_int), c_void_p, c_void_p]),
+    "gsr_fusion_integrate": (c_int, [c_int, c_int, c_void_p, c_void_p, POINTER(c_double), c_double, c_double, POINTER(c_int), c_void_p,
+                                     c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gsr_fusion_count": (c_int, [POINTER(c_int), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gsr_fusion_emit": (c_int, [POINTER(c_int), c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                c_void_p, c_void_p, c_void_p]),
     "gsr_adam_step": (c_int, [c_longlong, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_double, c_double, c_int,
                               c_void_p]),
     "gsr_adam_step_multi": (c_int, [c_int, POINTER(c_longlong), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),

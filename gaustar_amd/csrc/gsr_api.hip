@@ -1464,6 +1464,109 @@ int gsr_warp_smooth(int V, const int* nbr_offsets, const int* nbr, int sweeps, c
     return 0;
 }
 
+// the [host] grid block of the fusion calls: a directory of at least one unit per axis whose voxels can be counted in an int
+static const char* fusion_grid_error(const int* grid)
+{
+    if (!grid) return "grid is null";
+    long long units = 1;
+    for (int a = 0; a < 3; ++a) {
+        if (grid[3 + a] <= 0 || grid[3 + a] > (1 << 16)) return "units per axis must be in [1, 65536]";
+        if (grid[a] < -(1 << 24) || grid[a] > (1 << 24)) return "first unit index out of range";
+        units *= grid[3 + a];
+    }
+    return units * 4096 >= (1ll << 31) ? "the volume has 2^31 voxels or more" : nullptr;
+}
+
+static bool fusion_camera_ok(const double* cam)
+{
+    if (!cam) return false;
+    for (int i = 0; i < 28; ++i)
+        if (!(cam[i] - cam[i] == 0.0)) return false;
+    return cam[24] != 0.0 && cam[25] != 0.0;
+}
+
+size_t gsr_fusion_prep_workspace_bytes(int H, int W)
+{
+    return (H > 0 && W > 0 && (long long)H * W < (1ll << 31)) ? fusion_prep_workspace_bytes(H, W) : 0;
+}
+
+size_t gsr_fusion_volume_bytes(const int* grid)
+{
+    if (fusion_grid_error(grid)) return 0;
+    return (size_t)grid[3] * grid[4] * grid[5] * 4096 * 20;
+}
+
+int gsr_fusion_prep(int H, int W, const float* depth_alpha, const float* rgb, int mask_background, int remove_depth_edge,
+                    float depth_trunc, void* workspace, float* depth, unsigned char* rgb8, gsr_stream_t stream)
+{
+    g_err.clear();
+    if (H <= 0 || W <= 0) return fail_msg("gsr_fusion_prep: sizes must be positive");
+    if ((long long)H * W >= (1ll << 31)) return fail_msg("gsr_fusion_prep: image too large");
+    if (!depth_alpha || !rgb || !workspace || !depth || !rgb8) return fail_msg("gsr_fusion_prep: required pointer is null");
+    launch_fusion_prep(H, W, depth_alpha, rgb, mask_background != 0, remove_depth_edge != 0, depth_trunc, workspace, depth, rgb8,
+                       (hipStream_t)stream);
+    GSR_CHECK_LAUNCH("fusion prep kernels");
+    return 0;
+}
+
+int gsr_fusion_touch(int H, int W, const float* depth, const double* cam, double voxel_size, double sdf_trunc, const int* grid,
+                     unsigned char* touched, gsr_stream_t stream)
+{
+    g_err.clear();
+    if (H <= 0 || W <= 0) return fail_msg("gsr_fusion_touch: sizes must be positive");
+    if ((long long)H * W >= (1ll << 31)) return fail_msg("gsr_fusion_touch: image too large");
+    if (!(voxel_size > 0.0) || !(sdf_trunc > 0.0)) return fail_msg("gsr_fusion_touch: voxel_size and sdf_trunc must be positive");
+    if (const char* e = fusion_grid_error(grid)) return fail_msg((std::string("gsr_fusion_touch: ") + e).c_str());
+    if (!fusion_camera_ok(cam)) return fail_msg("gsr_fusion_touch: camera is null or not finite");
+    if (!depth || !touched) return fail_msg("gsr_fusion_touch: required pointer is null");
+    GSR_CHECK(launch_fusion_touch(H, W, depth, cam, voxel_size, sdf_trunc, grid, touched, (hipStream_t)stream));
+    GSR_CHECK_LAUNCH("fusion_touch_kernel");
+    return 0;
+}
+
+int gsr_fusion_integrate(int H, int W, const float* depth, const unsigned char* rgb8, const double* cam, double voxel_size,
+                         double sdf_trunc, const int* grid, const unsigned char* touched, float* tsdf, float* weight, float* color,
+                         gsr_stream_t stream)
+{
+    g_err.clear();
+    if (H <= 0 || W <= 0) return fail_msg("gsr_fusion_integrate: sizes must be positive");
+    if ((long long)H * W >= (1ll << 31)) return fail_msg("gsr_fusion_integrate: image too large");
+    if (!(voxel_size > 0.0) || !(sdf_trunc > 0.0)) return fail_msg("gsr_fusion_integrate: voxel_size and sdf_trunc must be positive");
+    if (const char* e = fusion_grid_error(grid)) return fail_msg((std::string("gsr_fusion_integrate: ") + e).c_str());
+    if (!fusion_camera_ok(cam)) return fail_msg("gsr_fusion_integrate: camera is null or not finite");
+    if (!depth || !rgb8 || !touched || !tsdf || !weight || !color) return fail_msg("gsr_fusion_integrate: required pointer is null");
+    if ((reinterpret_cast<uintptr_t>(tsdf) | reinterpret_cast<uintptr_t>(weight) | reinterpret_cast<uintptr_t>(color)) & 15)
+        return fail_msg("gsr_fusion_integrate: the volume's arrays must be 16-byte aligned");
+    launch_fusion_integrate(H, W, depth, rgb8, cam, voxel_size, sdf_trunc, grid, touched, tsdf, weight, color, (hipStream_t)stream);
+    GSR_CHECK_LAUNCH("fusion_integrate_kernel");
+    return 0;
+}
+
+int gsr_fusion_count(const int* grid, const float* tsdf, const float* weight, const int* table, unsigned char* edge_mask,
+                     int* vert_count, int* tri_count, gsr_stream_t stream)
+{
+    g_err.clear();
+    if (const char* e = fusion_grid_error(grid)) return fail_msg((std::string("gsr_fusion_count: ") + e).c_str());
+    if (!tsdf || !weight || !table || !edge_mask || !vert_count || !tri_count) return fail_msg("gsr_fusion_count: required pointer is null");
+    launch_fusion_count(grid, tsdf, weight, table, edge_mask, vert_count, tri_count, (hipStream_t)stream);
+    GSR_CHECK_LAUNCH("fusion_count_kernel");
+    return 0;
+}
+
+int gsr_fusion_emit(const int* grid, double voxel_size, const float* tsdf, const float* color, const unsigned char* edge_mask,
+                    const int* vert_scan, const int* tri_scan, const int* table, float* verts, int* faces, float* colors,
+                    gsr_stream_t stream)
+{
+    g_err.clear();
+    if (const char* e = fusion_grid_error(grid)) return fail_msg((std::string("gsr_fusion_emit: ") + e).c_str());
+    if (!(voxel_size > 0.0)) return fail_msg("gsr_fusion_emit: voxel_size must be positive");
+    // (verts / faces / colors may be null when the scans' totals are zero: nothing is written then)
+    if (!tsdf || !color || !edge_mask || !vert_scan || !tri_scan || !table) return fail_msg("gsr_fusion_emit: required pointer is null");
+    launch_fusion_emit(grid, voxel_size, tsdf, color, edge_mask, vert_scan, tri_scan, table, verts, faces, colors, (hipStream_t)stream);
+    GSR_CHECK_LAUNCH("fusion_emit_kernel");
+    return 0;
+}
+
 int gsr_mark_visible(int P, const float* means3D, const float* viewmatrix, const float* projmatrix, uint8_t* present,
                      gsr_stream_t stream)
 {

@@ -397,6 +397,21 @@ void launch_warp_aggregate(int C, int V, const double* table, int min_observe, d
                            unsigned char* valid, hipStream_t st);
 void launch_warp_smooth(int V, const int* off, const int* nbr, int sweeps, const double* in, double* out, double* tmp, hipStream_t st);
 
+// TSDF fusion of the rig's renders and mesh extraction (gsr_fusion.hip)
+size_t fusion_prep_workspace_bytes(int H, int W);
+void launch_fusion_prep(int H, int W, const float* depth_alpha, const float* rgb, int mask_background, int remove_depth_edge,
+                        float depth_trunc, void* workspace, float* depth, unsigned char* rgb8, hipStream_t st);
+hipError_t launch_fusion_touch(int H, int W, const float* depth, const double* cam28, double voxel, double trunc, const int* grid6,
+                               unsigned char* touched, hipStream_t st);
+void launch_fusion_integrate(int H, int W, const float* depth, const unsigned char* rgb8, const double* cam28, double voxel,
+                             double trunc, const int* grid6, const unsigned char* touched, float* tsdf, float* weight, float* color,
+                             hipStream_t st);
+void launch_fusion_count(const int* grid6, const float* tsdf, const float* weight, const int* table, unsigned char* edge_mask,
+                         int* vert_count, int* tri_count, hipStream_t st);
+void launch_fusion_emit(const int* grid6, double voxel, const float* tsdf, const float* color, const unsigned char* edge_mask,
+                        const int* vert_scan, const int* tri_scan, const int* table, float* verts, int* faces, float* colors,
+                        hipStream_t st);
+
 // Optional per-workgroup timeline for tuning (gsr_debug_set_trace): when non-null, the blend kernels store
 // {start, end} of every workgroup (100 MHz wall clock) at trace[2*blockIdx] (forward) / trace[2*(T+blockIdx)].
 extern uint64_t* g_trace;

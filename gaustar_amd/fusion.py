@@ -1,0 +1,540 @@
+"""TSDF fusion of the rig's renders and mesh extraction (gaustar_trainers/refined_mesh.py:311-459, `extract_mesh_fusion`) on the GPU.
+
+Once detect_topo_err has switched loose binding on, forward_rendering_and_mesh_update (refined_mesh.py:1024) renders RGB and
+depth/alpha from 60 sampled cameras and the rig, pulls every image to the host, integrates them into an Open3D
+ScalableTSDFVolume on the CPU and extracts the mesh update_mesh_topo cuts its patches from.  Here the renders stay on the
+device and the image preparation, the integration and marching cubes are HIP kernels (include/gsr.h, gsr_fusion.hip):
+
+    res = fuse_mesh(model, cameras)                       # native: FusionMesh (verts, faces, colors: device tensors)
+    res = model.extract_mesh_fusion(cameras)              # the same, as a method of harness.SurfaceGaussians
+    res = extract_mesh_fusion(refined_sugar, nerfmodel, voxel_size=0.008, sdf_trunc=0.02, depth_trunc=6)   # the reference's signature
+    vol = TSDFVolume(lo, hi, 0.008, 0.02, device); integrate_views(vol, depth, rgb8, intrinsic, extrinsic)  # images given
+    verts, faces, colors = extract_triangle_mesh(vol)
+
+The integration follows Open3D's legacy ScalableTSDFVolume(voxel_length, sdf_trunc, RGB8) -- units of 16^3 voxels,
+depth_sampling_stride 4 -- by the rules tests/fusion_ref.py restates; Open3D is not installed where this was written, so
+parity with Open3D itself is NOT pinned.  Known deviations: the units live in a dense directory over the model's bounding
+box (padded by sdf_trunc and one unit), so what a view sees outside it is dropped where Open3D's hash would grow; the colour
+mean is f32 (Open3D: double); marching cubes uses a table generated here (mc_table), not Open3D's, so the triangulation
+inside a cube may differ while the vertices (one per sign-changing edge next to a valid cube) are the same set.
+Views are integrated in list order (sampled cameras first, then the rig), so the running means are bit-reproducible; the
+renders of the next `views_in_flight - 1` views run ahead on their own streams.  Host synchronisation: the rasterizer's own
+per render, the bounding box once, the two totals of the extraction.
+
+Not implemented (ValueError in the adapter): save_dir (no cv2), smooth, simplify_face_num > 0.
+"""
+from __future__ import annotations
+
+import ctypes
+from dataclasses import dataclass
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import ptr as _p, stream_ptr as _stream
+
+UNIT = 16          # voxels along a unit's edge (ScalableTSDFVolume volume_unit_resolution)
+BG_RGB = (0.0, 1.0, 0.0)   # refined_mesh.py:354
+
+
+# ------------------------------------------------------------------------------------------------ marching-cubes table
+def _corner(i: int) -> Tuple[int, int, int]:
+    return (i & 1, (i >> 1) & 1, i >> 2)
+
+
+def _others(axis: int) -> Tuple[int, int]:
+    return (1 if axis == 0 else 0, 1 if axis == 2 else 2)
+
+
+def _edge_between(p, q) -> int:
+    """Edge id 4 axis + j of the cube edge between two neighbouring corners (as coordinate triples)."""
+    axis = [k for k in range(3) if p[k] != q[k]]
+    assert len(axis) == 1
+    b, c = _others(axis[0])
+    return 4 * axis[0] + p[b] + 2 * p[c]
+
+
+def edge_corners(e: int) -> Tuple[int, int]:
+    """The two corner indices (lower, upper) of cube edge e = 4 axis + j."""
+    axis, j = e >> 2, e & 3
+    b, c = _others(axis)
+    p = [0, 0, 0]
+    p[b], p[c] = j & 1, j >> 1
+    lo = p[0] + 2 * p[1] + 4 * p[2]
+    return lo, lo + (1 << axis)
+
+
+def _share_face(e: int, f: int) -> bool:
+    """Two cube edges lie on a common face of the cube."""
+    def faces(e):
+        axis, j = e >> 2, e & 3
+        b, c = _others(axis)
+        return {(b, j & 1), (c, j >> 1)}
+    return bool(faces(e) & faces(f))
+
+
+def _triangulate(loop):
+    """A loop of crossing edges as triangles of the same orientation: the fan from its first vertex, unless one of the fan's
+    diagonals joins two vertices on a common face of the cube.  Such a diagonal lies IN that face, where the neighbouring cube
+    may draw the same one (both faces ambiguous): four triangles would meet in one edge.  Then the fan from the next vertex
+    is tried, and after all fans the other triangulations, split at the first apex that works."""
+    n = len(loop)
+    ok = lambda a, b: not _share_face(a, b)
+    for r in range(n):
+        p = loop[r:] + loop[:r]
+        if all(ok(p[0], p[i]) for i in range(2, n - 1)):
+            return [(p[0], p[i], p[i + 1]) for i in range(1, n - 1)]
+
+    def split(p):       # the side (p[0], p[-1]) with an apex p[k]
+        if len(p) == 3:
+            return [tuple(p)]
+        for k in range(1, len(p) - 1):
+            if (k == 1 or ok(p[0], p[k])) and (k == len(p) - 2 or ok(p[k], p[-1])):
+                left = split(p[:k + 1]) if k > 1 else []
+                right = split(p[k:]) if k < len(p) - 2 else []
+                if left is not None and right is not None:
+                    return left + [(p[0], p[k], p[-1])] + right
+        return None
+
+    for r in range(n):
+        t = split(loop[r:] + loop[:r])
+        if t is not None:
+            return t
+    raise AssertionError(f"no triangulation of {loop} without a diagonal in a face")
+
+
+_MC_TABLE = None
+
+
+def mc_table() -> np.ndarray:
+    """The [256,16] int32 marching-cubes table, GENERATED (none ships with the package): per case up to 5 triangles as triples
+    of cube-edge ids, -1 terminated.  Case bit i = corner i = (i & 1, i >> 1 & 1, i >> 2) is inside (tsdf < 0); edge e = 4 axis
+    + j runs along `axis` from the corner whose other two coordinates, in ascending axis order, are (j & 1, j >> 1).
+    Per face of the cube, marching squares on its four corner signs: two crossings make one segment; four (the two inside
+    corners diagonal) make two, each cutting off one INSIDE corner -- a rule that depends on the face's four signs alone, so
+    the two cubes sharing a face draw the same segments and the surface closes.  Seen from outside the cube every segment
+    runs with the inside on its right; on the cube's surface the segments then chain into closed loops (each crossing edge
+    ends one segment and starts one), clockwise around the inside seen from outside, and a loop's fan (_triangulate: from
+    its lowest edge id where no diagonal falls into a face of the cube) faces away from the inside: normals point toward
+    positive tsdf."""
+    global _MC_TABLE
+    if _MC_TABLE is not None:
+        return _MC_TABLE
+    faces = []
+    for n in range(3):
+        b, c = _others(n)
+        for s in (0, 1):
+            cyc = []
+            for (vb, vc) in ((0, 0), (1, 0), (1, 1), (0, 1)):      # counter-clockwise seen from +(e_b x e_c)
+                p = [0, 0, 0]
+                p[n], p[b], p[c] = s, vb, vc
+                cyc.append(tuple(p))
+            cross_is_plus_n = n != 1                               # e_b x e_c = +e_n for n = 0, 2 and -e_1 for n = 1
+            if cross_is_plus_n != (s == 1):                        # outward normal is +e_n on the s = 1 side
+                cyc.reverse()
+            faces.append(cyc)                                      # counter-clockwise seen from outside the cube
+    table = np.full((256, 16), -1, np.int32)
+    for case in range(256):
+        inside = lambda p: (case >> (p[0] + 2 * p[1] + 4 * p[2])) & 1
+        nxt = {}
+        for cyc in faces:
+            flag = [inside(p) for p in cyc]
+            # walking the face counter-clockwise, edge k goes from corner k to corner k + 1
+            leave = [k for k in range(4) if flag[k] and not flag[(k + 1) % 4]]      # inside -> outside
+            enter = [k for k in range(4) if not flag[k] and flag[(k + 1) % 4]]      # outside -> inside
+            for k in enter:
+                # the inside corner this crossing enters is k + 1; the segment around it (inside on the right) ends where the
+                # walk leaves the inside again: right behind it when the face is ambiguous, else at the only `leave`
+                if len(enter) == 2:
+                    out = (k + 1) % 4
+                    assert out in leave
+                else:
+                    out = leave[0]
+                a = _edge_between(cyc[k], cyc[(k + 1) % 4])
+                z = _edge_between(cyc[out], cyc[(out + 1) % 4])
+                assert a not in nxt
+                nxt[a] = z
+        assert sorted(nxt) == sorted(nxt.values())
+        tris, seen = [], set()
+        for start in sorted(nxt):
+            if start in seen:
+                continue
+            loop, e = [], start
+            while e not in seen:
+                seen.add(e)
+                loop.append(e)
+                e = nxt[e]
+            assert e == start and len(loop) >= 3
+            tris += _triangulate(loop)
+        assert len(tris) <= 5, (case, len(tris))
+        flat = [e for t in tris for e in t]
+        table[case, :len(flat)] = flat
+    _MC_TABLE = table
+    return table
+
+
+# ------------------------------------------------------------------------------------------------ cameras
+def sample_extrinsics(dist: float = 3.0, look_at_y: float = 1.2, flip_xy: bool = False) -> np.ndarray:
+    """sample_cam (refined_mesh.py:55-81): [60,4,4] float64 world-to-camera matrices, azimuth 0..330 in steps of 30 (outer
+    loop), elevation -40..40 in steps of 20, all looking at (0, look_at_y, 0) from `dist`.
+    R is pytorch3d's look_at_view_transform(dist, elev, azim, at=at, degrees=True, up=(0, -1, 0)) restated from its source
+    (pytorch3d is not installed here: parity with it is not pinned), in float32 as pytorch3d computes it:
+        C = at + dist (cos(elev) sin(azim), sin(elev), cos(elev) cos(azim));
+        z = normalize(at - C), x = normalize(up x z), y = normalize(z x x)   (x is never degenerate for |elev| <= 40);
+        R = [x | y | z] as COLUMNS (look_at_rotation returns the transpose of the row stack).
+    The reference then puts this R -- pytorch3d's row-vector convention, unchanged -- into the extrinsic and replaces
+    pytorch3d's T by t = (0, 0, dist) - R at (:65), in double."""
+    at = np.array([0.0, look_at_y, 0.0])
+    up = np.array([0.0, -1.0, 0.0], np.float32)
+    out = []
+    norm = lambda v: v / np.maximum(np.sqrt((v * v).sum(dtype=np.float32)), np.float32(1e-5))   # F.normalize(eps=1e-5)
+    for azim in range(0, 360, 30):
+        for elev in range(-40, 41, 20):
+            el, az = np.float32(np.pi / 180.0 * elev), np.float32(np.pi / 180.0 * azim)
+            d = np.float32(dist)
+            C = np.array([d * np.cos(el) * np.sin(az), d * np.sin(el), d * np.cos(el) * np.cos(az)], np.float32) + at.astype(np.float32)
+            z = norm(at.astype(np.float32) - C)
+            x = norm(np.cross(up, z).astype(np.float32))
+            y = norm(np.cross(z, x).astype(np.float32))
+            R = np.stack([x, y, z], axis=1).astype(np.float32)
+            t = np.array([0.0, 0.0, dist]) - R.astype(np.float64) @ at
+            if flip_xy:
+                R = R.copy()
+                R[:, :2] *= -1
+                t[:2] *= -1
+            E = np.identity(4)
+            E[:3, :3] = R
+            E[:3, 3] = t
+            out.append(E)
+    return np.stack(out)
+
+
+def sample_cameras(camera0, dist: float = 3.0, look_at_y: float = 1.2) -> List:
+    """The 60 cameras of sample_cam with camera0's intrinsics, as the reference renders them (`overwrite_extr`,
+    refined_mesh.py:351-353): camera0.with_extrinsic(E) for E in sample_extrinsics(dist, look_at_y)."""
+    return [camera0.with_extrinsic(E) for E in sample_extrinsics(dist, look_at_y)]
+
+
+def open3d_camera(camera) -> Tuple[Tuple[float, float, float, float], np.ndarray]:
+    """to_cam_open3d (refined_mesh.py:27-52) for a harness.NerfCamera: ((fx, fy, cx, cy), extrinsic [4,4] float64).
+    The intrinsics are the projection matrix times ndc2pix: fx, fy in pixels, cx = (W - 1) / 2 - px W / 2 (cy alike) with
+    (px, py) the principal point in NDC; the extrinsic is the rasterizer's float32 world_view_transform, transposed.  (The
+    reference forms fx in float32; here it is the camera's own double.)"""
+    cam = camera.rasterizer_camera()
+    px, py = (float(v) for v in camera.principal_ndc)
+    W, H = int(camera.width), int(camera.height)
+    intr = (float(camera.fx), float(camera.fy), (W - 1) * 0.5 - px * W * 0.5, (H - 1) * 0.5 - py * H * 0.5)
+    return intr, np.asarray(cam.viewmatrix, np.float64).T.copy()
+
+
+def _intr4(intrinsic) -> Tuple[float, float, float, float]:
+    a = np.asarray(intrinsic, np.float64)
+    if a.shape == (3, 3):
+        return float(a[0, 0]), float(a[1, 1]), float(a[0, 2]), float(a[1, 2])
+    if a.shape == (4,):
+        return tuple(float(v) for v in a)
+    raise ValueError("intrinsic must be (fx, fy, cx, cy) or a [3,3] matrix")
+
+
+def cam28(intrinsic, extrinsic):
+    """The [host] camera block of gsr_fusion_touch / gsr_fusion_integrate: [R | t] (3 rows of 4), its inverse (numpy's, in
+    double), fx, fy, cx, cy."""
+    E = np.asarray(extrinsic, np.float64).reshape(4, 4)
+    Ei = np.linalg.inv(E)
+    return (ctypes.c_double * 28)(*E[:3].reshape(-1), *Ei[:3].reshape(-1), *_intr4(intrinsic))
+
+
+# ------------------------------------------------------------------------------------------------ the volume
+def unit_range(lo, hi, voxel_size: float, sdf_trunc: float) -> Tuple[np.ndarray, np.ndarray]:
+    """(first unit index [3], units [3]) of the dense directory over the box [lo, hi]: padded by sdf_trunc and one unit."""
+    L = UNIT * float(voxel_size)
+    u0 = np.floor((np.asarray(lo, np.float64) - sdf_trunc) / L).astype(np.int64) - 1
+    u1 = np.floor((np.asarray(hi, np.float64) + sdf_trunc) / L).astype(np.int64) + 1
+    return u0, u1 - u0 + 1
+
+
+class TSDFVolume:
+    """A dense directory of 16^3-voxel units over the box [lo, hi] (xyz), padded by sdf_trunc and one unit.  tsdf, weight
+    [nz,ny,nx] f32 and color [3,nz,ny,nx] f32 (0..255), x fastest; voxel (k_x, k_y, k_z)'s centre is origin + (k + 0.5)
+    voxel_size per axis up to rounding (the kernels form it per unit: unit index * 16 voxel_size + (k % 16 + 0.5) voxel_size)."""
+
+    def __init__(self, lo, hi, voxel_size: float = 0.008, sdf_trunc: float = 0.02, device="cuda"):
+        if not (voxel_size > 0 and sdf_trunc > 0):
+            raise ValueError("voxel_size and sdf_trunc must be positive")
+        lo, hi = np.asarray(lo, np.float64).reshape(3), np.asarray(hi, np.float64).reshape(3)
+        if not (np.isfinite(lo).all() and np.isfinite(hi).all() and (hi >= lo).all()):
+            raise ValueError("the box must be finite with hi >= lo")
+        self.voxel_size, self.sdf_trunc = float(voxel_size), float(sdf_trunc)
+        self.u0, self.nu = unit_range(lo, hi, voxel_size, sdf_trunc)
+        self.grid = (ctypes.c_int * 6)(*[int(v) for v in self.u0], *[int(v) for v in self.nu])
+        lib = _lib.load()
+        if int(lib.gsr_fusion_volume_bytes(self.grid)) == 0:
+            raise ValueError(f"a dense volume of {tuple(int(v) for v in self.nu)} units is too large: raise voxel_size or shrink the box")
+        self.device = torch.device(device)
+        nz, ny, nx = (int(UNIT * n) for n in self.nu[::-1])
+        self.tsdf = torch.zeros(nz, ny, nx, dtype=torch.float32, device=self.device)
+        self.weight = torch.zeros(nz, ny, nx, dtype=torch.float32, device=self.device)
+        self.color = torch.zeros(3, nz, ny, nx, dtype=torch.float32, device=self.device)
+        self.touched = torch.zeros(int(np.prod(self.nu)), dtype=torch.uint8, device=self.device)
+        self.n_views = 0
+
+    @property
+    def origin(self) -> np.ndarray:
+        return self.u0.astype(np.float64) * (UNIT * self.voxel_size)
+
+    @property
+    def dims(self) -> Tuple[int, int, int]:
+        """(nx, ny, nz) in voxels."""
+        return tuple(int(UNIT * n) for n in self.nu)
+
+
+def integrate_views(volume: TSDFVolume, depth: torch.Tensor, rgb8: torch.Tensor, intrinsic, extrinsic) -> None:
+    """volume.integrate(rgbd, intrinsic, extrinsic) for images that are given: depth [H,W] f32 (0 = nothing), rgb8 [H,W,3]
+    uint8, intrinsic (fx, fy, cx, cy) or [3,3], extrinsic [4,4] world-to-camera (COLMAP axes).  A stack [V,H,W] / [V,H,W,3]
+    with V intrinsics and extrinsics is integrated view by view, in order."""
+    if depth.dim() == 3:
+        intr = [intrinsic] * depth.shape[0] if np.asarray(intrinsic).ndim == 1 or np.asarray(intrinsic).shape == (3, 3) else intrinsic
+        for i in range(depth.shape[0]):
+            integrate_views(volume, depth[i], rgb8[i], intr[i], extrinsic[i])
+        return
+    lib = _lib.load()
+    H, W = int(depth.shape[0]), int(depth.shape[1])
+    if depth.dtype != torch.float32 or rgb8.dtype != torch.uint8 or tuple(rgb8.shape) != (H, W, 3):
+        raise ValueError("depth must be [H,W] float32 and rgb8 [H,W,3] uint8")
+    if depth.device != volume.device or rgb8.device != volume.device or volume.device.type != "cuda":
+        raise RuntimeError("the images and the volume must be on the same GPU")
+    depth, rgb8 = depth.contiguous(), rgb8.contiguous()
+    cam = cam28(intrinsic, extrinsic)
+    st = _stream()
+    _lib.check(lib.gsr_fusion_touch(H, W, _p(depth), cam, volume.voxel_size, volume.sdf_trunc, volume.grid, _p(volume.touched), st),
+               "gsr_fusion_touch")
+    _lib.check(lib.gsr_fusion_integrate(H, W, _p(depth), _p(rgb8), cam, volume.voxel_size, volume.sdf_trunc, volume.grid,
+                                        _p(volume.touched), _p(volume.tsdf), _p(volume.weight), _p(volume.color), st),
+               "gsr_fusion_integrate")
+    volume.n_views += 1
+
+
+def _table_on(device) -> torch.Tensor:
+    key = str(device)
+    if key not in _table_on.cache:
+        _table_on.cache[key] = torch.from_numpy(mc_table()).to(device).contiguous()
+    return _table_on.cache[key]
+
+
+_table_on.cache = {}
+
+
+def extract_triangle_mesh(volume: TSDFVolume) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """volume.extract_triangle_mesh(): marching cubes over the voxel centres -> (verts [Nv,3] f32, faces [Nf,3] int32, colors
+    [Nv,3] f32 in [0,1]), in voxel order (a voxel's vertices by axis, then its cube's triangles in table order): the same
+    volume gives the same arrays.  The one host read is the two totals."""
+    lib = _lib.load()
+    dev = volume.device
+    n = volume.tsdf.numel()
+    table = _table_on(dev)
+    mask = torch.empty(n, dtype=torch.uint8, device=dev)
+    vcnt = torch.empty(n, dtype=torch.int32, device=dev)
+    tcnt = torch.empty(n, dtype=torch.int32, device=dev)
+    st = _stream()
+    _lib.check(lib.gsr_fusion_count(volume.grid, _p(volume.tsdf), _p(volume.weight), _p(table), _p(mask), _p(vcnt), _p(tcnt), st),
+               "gsr_fusion_count")
+    vscan = torch.cumsum(vcnt, 0, dtype=torch.int32)
+    tscan = torch.cumsum(tcnt, 0, dtype=torch.int32)
+    del vcnt, tcnt
+    nv, nf = (int(v) for v in torch.stack([vscan[-1], tscan[-1]]).cpu())
+    verts = torch.empty(nv, 3, dtype=torch.float32, device=dev)
+    colors = torch.empty(nv, 3, dtype=torch.float32, device=dev)
+    faces = torch.empty(nf, 3, dtype=torch.int32, device=dev)
+    _lib.check(lib.gsr_fusion_emit(volume.grid, volume.voxel_size, _p(volume.tsdf), _p(volume.color), _p(mask), _p(vscan), _p(tscan),
+                                   _p(table), _p(verts) if nv else None, _p(faces) if nf else None, _p(colors) if nv else None, st),
+               "gsr_fusion_emit")
+    return verts, faces, colors
+
+
+# ------------------------------------------------------------------------------------------------ renders and image prep
+class FusionRenders:
+    """The two renders of refined_mesh.py:351-410 for one model state, without autograd.  Called per camera -> (rgb [3,H,W],
+    depth_alpha [3,H,W]), the rasterizer's images: the very calls
+        render_image_gaussian_rasterizer(camera, bg_color=[0, 1, 0], sh_deg=sh_levels - 1, compute_color_in_rasterizer=True)
+        render_image_gaussian_rasterizer(camera, bg_color=[0, 0, 0], sh_deg=0, point_colors=depth_alpha_colors(camera))
+    make (channels first; the reference's clamp of the RGB is part of the image preparation)."""
+
+    def __init__(self, model):
+        self.model = model
+        with torch.no_grad():
+            self.pts, self.ops, self.quats = model.points.detach(), model.strengths.detach().view(-1, 1), model.quaternions.detach()
+            self.scales = model.scaling.detach()
+            self.shs = model.sh_coordinates.detach()
+            self.zeros2d = torch.zeros_like(self.pts)
+            self.ones = torch.ones_like(self.pts[:, :1])
+        self.bg_rgb = torch.tensor(BG_RGB, dtype=torch.float32, device=model.device)
+        self.bg_zero = torch.zeros(3, dtype=torch.float32, device=model.device)
+
+    def depth_alpha_colors(self, camera) -> torch.Tensor:
+        """refined_mesh.py:384-386: (z, z, 1) per Gaussian, z its view-space depth."""
+        _cam, view, _proj, _campos = camera.on_device(self.model.device)
+        z = self.pts @ view[:3, 2:3] + view[3, 2]
+        return torch.cat([z, z, self.ones], dim=1)
+
+    @torch.no_grad()
+    def __call__(self, camera):
+        from . import GaussianRasterizer
+        m = self.model
+        kw = dict(means3D=self.pts, means2D=self.zeros2d, opacities=self.ops, scales=self.scales, rotations=self.quats,
+                  cov3D_precomp=None)
+        settings, _view, _campos = m._settings(camera, self.bg_rgb, m.sh_levels - 1)
+        rgb = GaussianRasterizer(settings)(shs=self.shs, colors_precomp=None, **kw)[0].contiguous()
+        settings, _view, _campos = m._settings(camera, self.bg_zero, 0)
+        da = GaussianRasterizer(settings)(shs=None, colors_precomp=self.depth_alpha_colors(camera), **kw)[0].contiguous()
+        return rgb, da
+
+
+def prepare_images(rgb: torch.Tensor, depth_alpha: torch.Tensor, depth_trunc: float = 6.0, mask_background: bool = True,
+                   remove_depth_edge: bool = True, out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+    """refined_mesh.py:412-445 on the device: rgb, depth_alpha [3,H,W] f32 -> (depth [H,W] f32, rgb8 [H,W,3] uint8)."""
+    lib = _lib.load()
+    _, H, W = (int(v) for v in depth_alpha.shape)
+    if tuple(rgb.shape) != (3, H, W) or rgb.dtype != torch.float32 or depth_alpha.dtype != torch.float32:
+        raise ValueError("rgb and depth_alpha must be [3,H,W] float32")
+    dev = rgb.device
+    rgb, depth_alpha = rgb.contiguous(), depth_alpha.contiguous()
+    depth, rgb8 = out if out is not None else (torch.empty(H, W, dtype=torch.float32, device=dev),
+                                               torch.empty(H, W, 3, dtype=torch.uint8, device=dev))
+    ws = torch.empty(int(lib.gsr_fusion_prep_workspace_bytes(H, W)), dtype=torch.uint8, device=dev)
+    _lib.check(lib.gsr_fusion_prep(H, W, _p(depth_alpha), _p(rgb), int(bool(mask_background)), int(bool(remove_depth_edge)),
+                                   float(depth_trunc), _p(ws), _p(depth), _p(rgb8), _stream()), "gsr_fusion_prep")
+    return depth, rgb8
+
+
+def fusion_inputs(model, camera, depth_trunc: float = 6.0, mask_background: bool = True, remove_depth_edge: bool = True):
+    """One camera's (depth [H,W] f32, rgb8 [H,W,3] uint8) as the integration takes them: the two renders and the image
+    preparation, on the device."""
+    rgb, da = FusionRenders(model)(camera)
+    return prepare_images(rgb, da, depth_trunc, mask_background, remove_depth_edge)
+
+
+# ------------------------------------------------------------------------------------------------ the whole step
+@dataclass
+class FusionMesh:
+    """verts [Nv,3] f32, faces [Nf,3] int32, colors [Nv,3] f32 in [0,1] (device tensors; formats.save_obj(path, verts, faces,
+    colors) writes them); n_blocks = units at least one view touched, n_views = views integrated.  With return_volume: tsdf,
+    weight [nz,ny,nx], color [3,nz,ny,nx] f32 (0..255), origin [3] float64 (the first voxel's lower corner), dims (nx, ny, nz)."""
+    verts: torch.Tensor
+    faces: torch.Tensor
+    colors: torch.Tensor
+    n_blocks: int
+    n_views: int
+    tsdf: Optional[torch.Tensor] = None
+    weight: Optional[torch.Tensor] = None
+    color: Optional[torch.Tensor] = None
+    origin: Optional[np.ndarray] = None
+    dims: Optional[Tuple[int, int, int]] = None
+
+
+def _side_streams(dev, n: int) -> List:
+    """n streams per device, made once: the library keeps a block of tile counters per (device, stream) it has rendered on."""
+    have = _side_streams.cache.setdefault(str(dev), [])
+    while len(have) < n:
+        have.append(torch.cuda.Stream(dev))
+    return have[:n]
+
+
+_side_streams.cache = {}
+
+
+@torch.no_grad()
+def fuse_mesh(model, cameras: Sequence, voxel_size: float = 0.008, sdf_trunc: float = 0.02, depth_trunc: float = 6.0,
+              mask_background: bool = True, remove_depth_edge: bool = True, sample_cameras: bool = True, views_in_flight: int = 2,
+              return_volume: bool = False, sample_dist: float = 3.0, sample_look_at_y: float = 1.2) -> FusionMesh:
+    """extract_mesh_fusion for a harness.SurfaceGaussians `model` seen by `cameras` (NerfCameras): with sample_cameras the 60
+    cameras of sample_cam (intrinsics of cameras[0], refined_mesh.py:339-345) come first, then the rig.  Defaults are the
+    reference's.  views_in_flight: 1 = everything on the calling stream; n > 1 = the renders and the image preparation of
+    the next n - 1 views run on side streams while a view is integrated (the integration itself stays in list order)."""
+    dev = model.device
+    if dev.type != "cuda":
+        raise RuntimeError("fuse_mesh needs the model on a GPU")
+    if not len(cameras):
+        raise ValueError("fuse_mesh needs at least one camera")
+    views = []
+    if sample_cameras:
+        for E in sample_extrinsics(sample_dist, sample_look_at_y):
+            views.append((cameras[0].with_extrinsic(E), open3d_camera(cameras[0])[0], E))     # :342, :353
+    for cam in cameras:
+        intr, extr = open3d_camera(cam)
+        views.append((cam, intr, extr))
+    shapes = {(int(c.height), int(c.width)) for c, _, _ in views}
+    renders = FusionRenders(model)
+    box = torch.stack([renders.pts.amin(0), renders.pts.amax(0)]).cpu().numpy()
+    volume = TSDFVolume(box[0], box[1], voxel_size, sdf_trunc, dev)
+    seen = torch.zeros_like(volume.touched)
+    for c, _, _ in views:
+        c.on_device(dev)
+
+    n = max(1, min(int(views_in_flight), len(views)))
+    main = torch.cuda.current_stream(dev)
+    if n == 1 or len(shapes) != 1:
+        for cam, intr, extr in views:
+            depth, rgb8 = prepare_images(*renders(cam), depth_trunc, mask_background, remove_depth_edge)
+            integrate_views(volume, depth, rgb8, intr, extr)
+            seen |= volume.touched
+    else:
+        H, W = next(iter(shapes))
+        side = _side_streams(dev, n)
+        slots = [(torch.empty(H, W, dtype=torch.float32, device=dev), torch.empty(H, W, 3, dtype=torch.uint8, device=dev)) for _ in range(n)]
+        ready = [None] * n       # slot filled (recorded on its side stream)
+        free = [None] * n        # slot integrated (recorded on the main stream)
+        start = torch.cuda.Event()
+        start.record(main)
+
+        def render(i):
+            k = i % n
+            with torch.cuda.stream(side[k]):
+                side[k].wait_event(free[k] if free[k] is not None else start)
+                prepare_images(*renders(views[i][0]), depth_trunc, mask_background, remove_depth_edge, out=slots[k])
+                ready[k] = torch.cuda.Event()
+                ready[k].record(side[k])
+
+        for i in range(min(n - 1, len(views))):
+            render(i)
+        for i, (_cam, intr, extr) in enumerate(views):
+            k = i % n
+            main.wait_event(ready[k])
+            integrate_views(volume, slots[k][0], slots[k][1], intr, extr)
+            seen |= volume.touched
+            free[k] = torch.cuda.Event()
+            free[k].record(main)
+            if i + n - 1 < len(views):       # (into the slot view i - 1 left; its render's host wait passes under this integration)
+                render(i + n - 1)
+        for s in side:
+            main.wait_stream(s)
+
+    verts, faces, colors = extract_triangle_mesh(volume)
+    res = FusionMesh(verts=verts, faces=faces, colors=colors, n_blocks=int(seen.count_nonzero()), n_views=volume.n_views)
+    if return_volume:
+        res.tsdf, res.weight, res.color, res.origin, res.dims = volume.tsdf, volume.weight, volume.color, volume.origin, volume.dims
+    return res
+
+
+def extract_mesh_fusion(refined_sugar, nerfmodel, voxel_size=0.008, sdf_trunc=0.02, depth_trunc=6, simplify_face_num=0,
+                        mask_backgrond=True, save_dir=None, smooth=False, remove_depth_edge=True, views_in_flight: int = 2) -> FusionMesh:
+    """refined_mesh.py:311-459 with the reference's signature and defaults (its spelling of `mask_backgrond` included);
+    returns a FusionMesh where the reference returns an open3d mesh.  `refined_sugar` is a harness.SurfaceGaussians;
+    `nerfmodel` needs its camera list as `cameras` (harness.NerfCamera).  Raises ValueError for what is not implemented:
+    save_dir (the reference's debug images need cv2), smooth (Laplacian smoothing; the reference's call passes False) and
+    simplify_face_num > 0 (quadric decimation)."""
+    if save_dir:
+        raise ValueError("extract_mesh_fusion: save_dir is not implemented (no image writer)")
+    if smooth:
+        raise ValueError("extract_mesh_fusion: smooth=True is not implemented")
+    if simplify_face_num and simplify_face_num > 0:
+        raise ValueError("extract_mesh_fusion: simplify_face_num > 0 is not implemented")
+    return fuse_mesh(refined_sugar, nerfmodel.cameras, voxel_size=float(voxel_size), sdf_trunc=float(sdf_trunc),
+                     depth_trunc=float(depth_trunc), mask_background=bool(mask_backgrond), remove_depth_edge=bool(remove_depth_edge),
+                     views_in_flight=views_in_flight)
+
+
+__all__ = ["mc_table", "edge_corners", "sample_extrinsics", "sample_cameras", "open3d_camera", "cam28", "unit_range", "TSDFVolume",
+           "integrate_views", "extract_triangle_mesh", "FusionRenders", "prepare_images", "fusion_inputs", "FusionMesh", "fuse_mesh",
+           "extract_mesh_fusion"]

@@ -494,6 +494,12 @@ class SurfaceGaussians(nn.Module):
         rig = kw.pop("rig", None) or topology.rig_from_cameras(cameras)
         return warp.warp_mesh(self._points.detach(), self._surface_mesh_faces, rig, frames, **kw)
 
+    def extract_mesh_fusion(self, cameras, **kw):
+        """The surface the renders of `cameras` (and of the 60 sampled cameras around them) agree on, by TSDF fusion and
+        marching cubes (refined_mesh.py:311-459): fusion.fuse_mesh(self, cameras, **kw) -> fusion.FusionMesh."""
+        from . import fusion
+        return fusion.fuse_mesh(self, cameras, **kw)
+
     # -------------------------------------------------------------------------------- rendering
     def _settings(self, camera: NerfCamera, bg: torch.Tensor, sh_degree: int):
         cam, view, proj, campos = camera.on_device(self.device)

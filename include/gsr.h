@@ -522,6 +522,55 @@ int gsr_warp_aggregate(int C, int V, const double* table, int min_observe, doubl
 int gsr_warp_smooth(int V, const int* nbr_offsets, const int* nbr, int sweeps, const double* value_in, double* value_out,
                     double* value_tmp, gsr_stream_t stream);
 
+/* ---- TSDF fusion of the rig's renders and mesh extraction (gaustar_trainers/refined_mesh.py:311-459 `extract_mesh_fusion`).
+ * The volume follows Open3D's legacy ScalableTSDFVolume(voxel_length, sdf_trunc, RGB8) -- units of 16^3 voxels,
+ * depth_sampling_stride 4 -- by the rules restated in tests/fusion_ref.py (Open3D itself was not available: parity with it
+ * is not pinned), as a DENSE directory of units: grid: [host] 6 ints = the unit index floor(p / (16 voxel_size)) of the first
+ * unit along x, y, z and the number of units along x, y, z.  Storage is a dense voxel grid [16 nz][16 ny][16 nx], x fastest:
+ * tsdf, weight [voxels] f32 and color [3][voxels] f32 (planes R, G, B, 0..255), all zero before the first view, 16-byte
+ * aligned.  What a view sees outside the grid is dropped (Open3D's hash of units is unbounded); colour is averaged in f32
+ * (Open3D: double).  All device pointers unless marked [host]; every call is asynchronous on `stream`, none synchronises the
+ * host, none uses float atomics: the volume is a pure function of the views and their order, the mesh of the volume.
+ * cam: [host] 28 doubles = the world-to-camera matrix [R | t] (COLMAP axes, 3 rows of 4), its inverse (3 rows of 4), fx, fy,
+ *   cx, cy with pixel (i, j)'s ray through ((j - cx) / fx, (i - cy) / fy, 1).
+ * gsr_fusion_prep: one camera's image preparation (refined_mesh.py:412-445).  depth_alpha [3,H,W] f32: the render of the
+ *   colours (z, z, 1) over a zero background; rgb [3,H,W] f32.  depth = ch0 / (alpha + 1e-8); with mask_background
+ *   alpha < 0.5 -> 0; with remove_depth_edge get_depth_edge(depth, 3) of gaustar_tools/warp_mesh.py:120-130 with
+ *   max_depth = None (m = 1.1 max(depth[depth < 10]), 3x3 box filter, reflect-101 border), edge_vis = min(var / max(var)
+ *   1000, 1) > 0.5 -> 0 (a map with nothing below 10 or with max(var) = 0 loses nothing); depth >= depth_trunc -> 0.
+ *   rgb8 [H,W,3] uint8 = clamp(rgb, 0, 1) 255 truncated.  workspace: gsr_fusion_prep_workspace_bytes(H, W) bytes.
+ * gsr_fusion_touch: clears touched [units] uint8 (z, y, x order of the directory) and sets it to 1 for every unit between
+ *   floor((p - sdf_trunc) / L) and floor((p + sdf_trunc) / L) per axis, L = 16 voxel_size, p = inverse(extrinsic) ((j - cx) d /
+ *   fx, (i - cy) d / fy, d) for every pixel with i % 4 == 0, j % 4 == 0 and d = depth[i, j] > 0, in double.
+ * gsr_fusion_integrate: over the touched units, one view into the running means.  Voxel centre = unit index L + (k + 0.5)
+ *   voxel_size per axis; X = extrinsic centre in double; skipped unless X.z > 0; u_f = fx X.x / X.z + cx + 0.5 (v_f alike),
+ *   skipped unless 1e-4 <= u_f < W - 1e-4 and 1e-4 <= v_f < H - 1e-4; u = (int) u_f, v = (int) v_f, d = depth[v, u], skipped
+ *   unless d > 0; in f32 sdf = (d - X.z) sqrt(((u - cx) / fx)^2 + ((v - cy) / fy)^2 + 1); if sdf > -sdf_trunc: t = min(1,
+ *   sdf / sdf_trunc), tsdf = (tsdf w + t) / (w + 1), color = (color w + rgb8[v, u]) / (w + 1), w += 1.
+ * gsr_fusion_count / gsr_fusion_emit: marching cubes over voxel centres.  A cube (its voxel = its lowest corner) is valid when
+ *   all 8 weights are non-zero; corner i = (i & 1, i >> 1 & 1, i >> 2) is inside when tsdf < 0; edge e = 4 axis + j runs along
+ *   `axis` from the corner whose other two coordinates (ascending axis order) are (j & 1, j >> 1) and belongs to the voxel at
+ *   its lower end.  table [256,16] int32: per case up to 5 triangles as edge triples, -1 terminated (gaustar_amd.fusion.mc_table).
+ *   count: edge_mask [voxels] uint8 (bit a: the edge along axis a carries a vertex -- the signs of its ends differ and one of
+ *   the up to four cubes around it is valid), vert_count [voxels] int32 = its bits, tri_count [voxels] int32 = the triangles of
+ *   the voxel's own cube.  emit: vert_scan / tri_scan = the INCLUSIVE scans of the counts in voxel order; a vertex sits at
+ *   pa + f_a / (f_a - f_b) (pb - pa) in f32, its colour is interpolated alike and divided by 255; verts, colors [Nv,3] f32,
+ *   faces [Nf,3] int32, triangles facing positive tsdf. */
+size_t gsr_fusion_prep_workspace_bytes(int H, int W);
+size_t gsr_fusion_volume_bytes(const int* grid);
+int gsr_fusion_prep(int H, int W, const float* depth_alpha, const float* rgb, int mask_background, int remove_depth_edge,
+                    float depth_trunc, void* workspace, float* depth, unsigned char* rgb8, gsr_stream_t stream);
+int gsr_fusion_touch(int H, int W, const float* depth, const double* cam, double voxel_size, double sdf_trunc, const int* grid,
+                     unsigned char* touched, gsr_stream_t stream);
+int gsr_fusion_integrate(int H, int W, const float* depth, const unsigned char* rgb8, const double* cam, double voxel_size,
+                         double sdf_trunc, const int* grid, const unsigned char* touched, float* tsdf, float* weight, float* color,
+                         gsr_stream_t stream);
+int gsr_fusion_count(const int* grid, const float* tsdf, const float* weight, const int* table, unsigned char* edge_mask,
+                     int* vert_count, int* tri_count, gsr_stream_t stream);
+int gsr_fusion_emit(const int* grid, double voxel_size, const float* tsdf, const float* color, const unsigned char* edge_mask,
+                    const int* vert_scan, const int* tri_scan, const int* table, float* verts, int* faces, float* colors,
+                    gsr_stream_t stream);
+
 /* Tuning aid: when device_buffer is non-NULL (4*T uint64), the two blend kernels record the start/end wall
  * clock (100 MHz) of every workgroup: forward at [2*b], backward at [2*(T+b)], b = launch index.  NULL = off. */
 int gsr_debug_set_trace(void* device_buffer);
