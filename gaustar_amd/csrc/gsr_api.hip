@@ -1567,6 +1567,160 @@ int gsr_fusion_emit(const int* grid, double voxel_size, const float* tsdf, const
     return 0;
 }
 
+// 3 F face-edges are counted in an int
+static bool regions_faces_ok(int F) { return F >= 0 && F <= 0x7fffffff / 3; }
+
+int gsr_regions_edge_keys(int F, const int* faces, const unsigned char* mask, const unsigned char* colour, int cut,
+                          unsigned char* selected, long long* keys, int* err, gsr_stream_t stream)
+{
+    g_err.clear();
+    if (!regions_faces_ok(F)) return fail_msg("gsr_regions_edge_keys: F must be in [0, (2^31 - 1) / 3]");
+    if (F == 0) return 0;
+    if (!faces || !selected || !keys || !err) return fail_msg("gsr_regions_edge_keys: required pointer is null");
+    launch_regions_edge_keys(F, faces, mask, colour, cut, selected, keys, err, (hipStream_t)stream);
+    GSR_CHECK_LAUNCH("regions_edge_key_kernel");
+    return 0;
+}
+
+int gsr_regions_edge_runs(int F, const long long* sorted_keys, const long long* order, int* counts, int* pairs, gsr_stream_t stream)
+{
+    g_err.clear();
+    if (!regions_faces_ok(F)) return fail_msg("gsr_regions_edge_runs: F must be in [0, (2^31 - 1) / 3]");
+    if (F == 0) return 0;
+    if (!sorted_keys || !order || !counts || !pairs) return fail_msg("gsr_regions_edge_runs: required pointer is null");
+    if (reinterpret_cast<uintptr_t>(pairs) & 7) return fail_msg("gsr_regions_edge_runs: pairs must be 8-byte aligned");
+    launch_regions_edge_runs(F, sorted_keys, order, counts, pairs, (hipStream_t)stream);
+    GSR_CHECK_LAUNCH("regions_edge_run_kernel");
+    return 0;
+}
+
+int gsr_regions_components(int F, const int* pairs, const unsigned char* selected, int* parent, int* root_flag, gsr_stream_t stream)
+{
+    g_err.clear();
+    if (!regions_faces_ok(F)) return fail_msg("gsr_regions_components: F must be in [0, (2^31 - 1) / 3]");
+    if (F == 0) return 0;
+    if (!pairs || !selected || !parent || !root_flag) return fail_msg("gsr_regions_components: required pointer is null");
+    if (reinterpret_cast<uintptr_t>(pairs) & 7) return fail_msg("gsr_regions_components: pairs must be 8-byte aligned");
+    launch_regions_components(F, pairs, selected, parent, root_flag, (hipStream_t)stream);
+    GSR_CHECK_LAUNCH("regions union-find kernels");
+    return 0;
+}
+
+int gsr_regions_labels(int F, const int* parent, const int* root_scan, const unsigned char* selected, int* label, int* count,
+                       gsr_stream_t stream)
+{
+    g_err.clear();
+    if (!regions_faces_ok(F)) return fail_msg("gsr_regions_labels: F must be in [0, (2^31 - 1) / 3]");
+    if (F == 0) return 0;
+    if (!parent || !root_scan || !selected || !label || !count) return fail_msg("gsr_regions_labels: required pointer is null");
+    launch_regions_labels(F, parent, root_scan, selected, label, count, (hipStream_t)stream);
+    GSR_CHECK_LAUNCH("regions_label_kernel");
+    return 0;
+}
+
+int gsr_regions_select(int F, const int* count, int face_threshold, const int* kept_scan, const int* label, int cap, int* kept_label,
+                       int* kept_count, int* region, gsr_stream_t stream)
+{
+    g_err.clear();
+    if (!regions_faces_ok(F) || cap < 0) return fail_msg("gsr_regions_select: negative size or too many faces");
+    if (face_threshold < 0) return fail_msg("gsr_regions_select: face_threshold must not be negative");
+    if (F == 0) return 0;
+    if (!count || !kept_scan || !label || !region || (cap > 0 && (!kept_label || !kept_count)))
+        return fail_msg("gsr_regions_select: required pointer is null");
+    launch_regions_select(F, count, face_threshold, kept_scan, label, cap, kept_label, kept_count, region, (hipStream_t)stream);
+    GSR_CHECK_LAUNCH("regions_select_kernel");
+    return 0;
+}
+
+int gsr_regions_boxes(int F, int G, int V, const int* faces, const float* verts, const float* points, const int* region, int cap,
+                      unsigned int* boxes, int* err, gsr_stream_t stream)
+{
+    g_err.clear();
+    if (!regions_faces_ok(F) || G < 0 || V < 0 || cap < 0) return fail_msg("gsr_regions_boxes: negative size or too many faces");
+    if (cap == 0) return 0;
+    if (!boxes || (F > 0 && (!faces || !verts || !region || !err || (G > 0 && !points))))
+        return fail_msg("gsr_regions_boxes: required pointer is null");
+    launch_regions_boxes(F, G, V, faces, verts, points, region, cap, boxes, err, (hipStream_t)stream);
+    GSR_CHECK_LAUNCH("regions box kernels");
+    return 0;
+}
+
+int gsr_regions_inside(int V, const float* verts, const double* box, unsigned char* inside, gsr_stream_t stream)
+{
+    g_err.clear();
+    if (V < 0) return fail_msg("gsr_regions_inside: negative size");
+    if (!box) return fail_msg("gsr_regions_inside: box is null");
+    for (int i = 0; i < 6; ++i)
+        if (box[i] != box[i]) return fail_msg("gsr_regions_inside: box holds a NaN");
+    if (V == 0) return 0;
+    if (!verts || !inside) return fail_msg("gsr_regions_inside: required pointer is null");
+    launch_regions_inside(V, verts, box, inside, (hipStream_t)stream);
+    GSR_CHECK_LAUNCH("regions_inside_kernel");
+    return 0;
+}
+
+int gsr_regions_cut_mark(int F, int V, const int* faces, const unsigned char* inside, int cut_inner, int* keep, int* referenced,
+                         int* err, gsr_stream_t stream)
+{
+    g_err.clear();
+    if (!regions_faces_ok(F) || V < 0) return fail_msg("gsr_regions_cut_mark: negative size or too many faces");
+    if ((V > 0 && (!inside || !referenced)) || (F > 0 && (!faces || !keep || !err)))
+        return fail_msg("gsr_regions_cut_mark: required pointer is null");
+    GSR_CHECK(launch_regions_cut_mark(F, V, faces, inside, cut_inner != 0, keep, referenced, err, (hipStream_t)stream));
+    GSR_CHECK_LAUNCH("regions_cut_mark_kernel");
+    return 0;
+}
+
+int gsr_regions_cut_emit(int F, int V, const int* faces, const int* keep, const int* keep_scan, const int* referenced,
+                         const int* referenced_scan, int* faces_out, unsigned char* face_mask, int* vert_map, int* old_of_new,
+                         gsr_stream_t stream)
+{
+    g_err.clear();
+    if (!regions_faces_ok(F) || V < 0) return fail_msg("gsr_regions_cut_emit: negative size or too many faces");
+    // (faces_out / old_of_new may be null when the scans' totals are zero: nothing is written then)
+    if ((F > 0 && (!faces || !keep || !keep_scan || !face_mask || !referenced_scan)) || (V > 0 && (!referenced || !referenced_scan || !vert_map)))
+        return fail_msg("gsr_regions_cut_emit: required pointer is null");
+    launch_regions_cut_emit(F, V, faces, keep, keep_scan, referenced, referenced_scan, faces_out, face_mask, vert_map, old_of_new,
+                            (hipStream_t)stream);
+    GSR_CHECK_LAUNCH("regions cut kernels");
+    return 0;
+}
+
+int gsr_regions_gather(int n_rows, int C, const int* old_of_new, const void* src, void* dst, gsr_stream_t stream)
+{
+    g_err.clear();
+    if (n_rows < 0 || C < 0) return fail_msg("gsr_regions_gather: negative size");
+    if (n_rows == 0 || C == 0) return 0;
+    if (!old_of_new || !src || !dst) return fail_msg("gsr_regions_gather: required pointer is null");
+    if ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 3) return fail_msg("gsr_regions_gather: arrays must be 4-byte aligned");
+    launch_regions_gather(n_rows, C, old_of_new, src, dst, (hipStream_t)stream);
+    GSR_CHECK_LAUNCH("regions_gather_kernel");
+    return 0;
+}
+
+int gsr_regions_boundary(int F, int V, const int* faces, const int* counts, const unsigned char* inside, unsigned char* edge_mark,
+                         unsigned char* face_mark, int* err, gsr_stream_t stream)
+{
+    g_err.clear();
+    if (!regions_faces_ok(F) || V < 0) return fail_msg("gsr_regions_boundary: negative size or too many faces");
+    if ((V > 0 && (!edge_mark || (inside && !face_mark))) || (F > 0 && (!faces || !counts || !err)))
+        return fail_msg("gsr_regions_boundary: required pointer is null");
+    GSR_CHECK(launch_regions_boundary(F, V, faces, counts, inside, edge_mark, face_mark, err, (hipStream_t)stream));
+    GSR_CHECK_LAUNCH("regions_boundary_kernel");
+    return 0;
+}
+
+int gsr_regions_label_mask(int F, const int* label, const int* count, int min_count, unsigned char* out, gsr_stream_t stream)
+{
+    g_err.clear();
+    if (!regions_faces_ok(F)) return fail_msg("gsr_regions_label_mask: F must be in [0, (2^31 - 1) / 3]");
+    if (F == 0) return 0;
+    if (!label || !count || !out) return fail_msg("gsr_regions_label_mask: required pointer is null");
+    launch_regions_label_mask(F, label, count, min_count, out, (hipStream_t)stream);
+    GSR_CHECK_LAUNCH("regions_label_mask_kernel");
+    return 0;
+}
+
 int gsr_mark_visible(int P, const float* means3D, const float* viewmatrix, const float* projmatrix, uint8_t* present,
                      gsr_stream_t stream)
 {

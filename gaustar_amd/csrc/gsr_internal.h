@@ -412,6 +412,26 @@ void launch_fusion_emit(const int* grid6, double voxel, const float* tsdf, const
                         const int* vert_scan, const int* tri_scan, const int* table, float* verts, int* faces, float* colors,
                         hipStream_t st);
 
+// re-mesh regions at topology errors: edge multiplicity, face components, boxes, cuts (gsr_regions.hip)
+void launch_regions_edge_keys(int F, const int* faces, const unsigned char* mask, const unsigned char* colour, int cut,
+                              unsigned char* sel, long long* keys, int* err, hipStream_t st);
+void launch_regions_edge_runs(int F, const long long* skeys, const long long* order, int* counts, int* pairs, hipStream_t st);
+void launch_regions_components(int F, const int* pairs, const unsigned char* sel, int* parent, int* root_flag, hipStream_t st);
+void launch_regions_labels(int F, const int* parent, const int* scan, const unsigned char* sel, int* label, int* count, hipStream_t st);
+void launch_regions_select(int F, const int* count, int thr, const int* kscan, const int* label, int cap, int* sel_label,
+                           int* sel_count, int* region, hipStream_t st);
+void launch_regions_boxes(int F, int G, int V, const int* faces, const float* verts, const float* points, const int* region, int cap,
+                          unsigned* boxes, int* err, hipStream_t st);
+void launch_regions_inside(int V, const float* verts, const double* box6, unsigned char* inside, hipStream_t st);
+hipError_t launch_regions_cut_mark(int F, int V, const int* faces, const unsigned char* inside, int cut_inner, int* keep, int* ref,
+                                   int* err, hipStream_t st);
+void launch_regions_cut_emit(int F, int V, const int* faces, const int* keep, const int* kscan, const int* ref, const int* vscan,
+                             int* faces_out, unsigned char* face_mask, int* vert_map, int* old_of_new, hipStream_t st);
+void launch_regions_gather(int n_rows, int C, const int* old_of_new, const void* src, void* dst, hipStream_t st);
+hipError_t launch_regions_boundary(int F, int V, const int* faces, const int* counts, const unsigned char* inside, unsigned char* bmark,
+                                   unsigned char* fmark, int* err, hipStream_t st);
+void launch_regions_label_mask(int F, const int* label, const int* count, int min_count, unsigned char* out, hipStream_t st);
+
 // Optional per-workgroup timeline for tuning (gsr_debug_set_trace): when non-null, the blend kernels store
 // {start, end} of every workgroup (100 MHz wall clock) at trace[2*blockIdx] (forward) / trace[2*(T+blockIdx)].
 extern uint64_t* g_trace;

@@ -1,0 +1,492 @@
+// gsr_regions.hip -- the front half of update_mesh_topo (gaustar_trainers/refined_mesh.py:463-693): which faces of the base mesh
+// are re-meshed, the boxes around them, and the cuts of the base mesh and of the fused surface by those boxes.
+//
+// The reference does this on the host with trimesh (group_rows over the sorted edges, scipy's connected_components, update_faces,
+// remove_unreferenced_vertices).  Here, over device tensors:
+//   edge multiplicity   regions_edge_key_kernel    a 64-bit key (min << 32 | max) per face-edge, a sentinel outside the mask
+//                       (torch.sort of the keys, as topology.py sorts its voxel keys)
+//                       regions_edge_run_kernel    per sorted key the length of its run, written back to its face-edge; a run of
+//                                                  exactly two face-edges of two different faces is an adjacency pair
+//   components          regions_uf_init / _hook / _flatten_kernel   union-find over the pairs: the larger root is pointed at the
+//                                                  smaller by compare-and-swap, so a tree's root is its smallest face whatever
+//                                                  order the hooks landed in; flatten finds it without a store to any other
+//                                                  face's word and writes it to parent[f], once
+//                       (torch.cumsum over the root flags)
+//                       regions_label_kernel       dense labels in ascending order of the smallest face, faces per label
+//   selection           regions_select_kernel      components above the face threshold, in label order
+//                       regions_box_kernel         per kept component min / max over its faces' vertices and Gaussian centres
+//   cut                 regions_inside_kernel, regions_cut_mark_kernel, (two cumsums), regions_cut_faces_kernel,
+//                       regions_cut_verts_kernel, regions_gather_kernel
+//   primitives          regions_boundary_kernel (find_boundary_verts, :84-111), regions_label_mask_kernel (get_outlier_cc_mask, :291-307)
+// Every output is an integer or an exactly defined float: counts are integer adds, boxes integer min / max on an order-preserving
+// encoding of the f32, ids come from scans.  No float atomics.
+//
+// Workgroups on different XCDs hook concurrently: every read of `parent` inside a find is an agent-scope atomic load, every
+// write an agent-scope atomic store or compare-and-swap.
+#include "gsr_internal.h"
+
+namespace gsr {
+
+namespace {
+
+constexpr int RG_BLOCK = 256;
+constexpr long long RG_SENTINEL = 0x7fffffffffffffffll;   // above every key: min, max <= 2^31 - 1
+constexpr int RG_ERR_INDEX = 1, RG_ERR_NAN = 2;               // bits of the calls' err word
+constexpr int RG_WALK = 8;                                 // neighbours looked at before a run's end is found by bisection
+
+struct RegionBox { double lo[3], hi[3]; };
+
+__device__ __forceinline__ int uf_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void uf_store(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+__device__ __forceinline__ long long edge_key(int a, int b)
+{
+    const int lo = a < b ? a : b, hi = a < b ? b : a;
+    return ((long long)lo << 32) | (long long)(unsigned)hi;
+}
+
+// ---------------------------------------------------------------------------------------------------- edge multiplicity
+// Face-edge e of face (a, b, c) is (a, b), (b, c), (c, a) for e = 0, 1, 2 (trimesh's faces_to_edges).
+__global__ void __launch_bounds__(RG_BLOCK) regions_edge_key_kernel(int F, const int* __restrict__ faces, const unsigned char* __restrict__ mask,
+                                                                    const unsigned char* __restrict__ colour, int cut,
+                                                                    unsigned char* __restrict__ sel, long long* __restrict__ keys,
+                                                                    int* __restrict__ err)
+{
+    const int f = blockIdx.x * RG_BLOCK + threadIdx.x;
+    if (f >= F) return;
+    const int a = faces[3 * (size_t)f], b = faces[3 * (size_t)f + 1], c = faces[3 * (size_t)f + 2];
+    bool on = (!mask || mask[f]) && (!colour || (int)colour[f] >= cut);
+    if ((a | b | c) < 0) { atomicOr(err, RG_ERR_INDEX); on = false; }
+    sel[f] = on;
+    long long* k = keys + 3 * (size_t)f;
+    k[0] = on ? edge_key(a, b) : RG_SENTINEL;
+    k[1] = on ? edge_key(b, c) : RG_SENTINEL;
+    k[2] = on ? edge_key(c, a) : RG_SENTINEL;
+}
+
+// n = 3 F sorted keys; order[i] = the face-edge (3 f + e) key i came from.  counts [3 F] by face-edge; pairs [3 F] by sorted
+// position: (face, face) at the first key of a run of two from different faces, (-1, -1) elsewhere.
+__global__ void __launch_bounds__(RG_BLOCK) regions_edge_run_kernel(int n, const long long* __restrict__ skeys, const long long* __restrict__ order,
+                                                                    int* __restrict__ counts, int2* __restrict__ pairs)
+{
+    const int i = blockIdx.x * RG_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const long long k = skeys[i];
+    const int slot = (int)order[i];
+    int2 pr = make_int2(-1, -1);
+    if (k == RG_SENTINEL) {
+        counts[slot] = 0;
+        pairs[i] = pr;
+        return;
+    }
+    int lo = i, hi = i + 1;      // the run is [lo, hi)
+    for (int s = 0; s < RG_WALK && lo > 0 && skeys[lo - 1] == k; ++s) --lo;
+    if (lo > 0 && skeys[lo - 1] == k) {          // a long run: the first position holding k, by bisection over [0, lo)
+        int l = 0, r = lo - 1;                   // skeys[r] == k
+        while (l < r) {
+            const int m = l + (r - l) / 2;
+            if (skeys[m] < k) l = m + 1; else r = m;
+        }
+        lo = l;
+    }
+    for (int s = 0; s < RG_WALK && hi < n && skeys[hi] == k; ++s) ++hi;
+    if (hi < n && skeys[hi] == k) {              // the first position above k, over (hi, n]
+        int l = hi + 1, r = n;
+        while (l < r) {
+            const int m = l + (r - l) / 2;
+            if (skeys[m] <= k) l = m + 1; else r = m;
+        }
+        hi = l;
+    }
+    counts[slot] = hi - lo;
+    if (i == lo && hi - lo == 2) {
+        const int fa = (int)(order[lo] / 3), fb = (int)(order[lo + 1] / 3);
+        if (fa != fb) pr = make_int2(fa, fb);    // (two face-edges of one degenerate face link nothing)
+    }
+    pairs[i] = pr;
+}
+
+// ---------------------------------------------------------------------------------------------------- components
+__global__ void __launch_bounds__(RG_BLOCK) regions_uf_init_kernel(int F, int* __restrict__ parent)
+{
+    const int f = blockIdx.x * RG_BLOCK + threadIdx.x;
+    if (f < F) parent[f] = f;
+}
+
+// The root of x, halving the path on the way: for the HOOK kernel only, where any ancestor is as good as another.
+// parent[x] <= x always; a face that has a parent below itself never becomes a root again, so the halving store (to an
+// ancestor, of a non-root) and the hooks' compare-and-swap (on roots only) never meet on one word.
+__device__ __forceinline__ int uf_find(int* parent, int x)
+{
+    for (;;) {
+        const int p = uf_load(parent + x);
+        if (p == x) return x;
+        const int g = uf_load(parent + p);
+        if (g == p) return p;
+        uf_store(parent + x, g);
+        x = g;
+    }
+}
+
+// The root of x without a store: for the FLATTEN kernel, where parent[f] must end as the final root.  There every word has one
+// writer, the thread of its own face, and the one value it writes is the root; a reader meets either the entry the hooks left
+// (an ancestor) or that root, and walks on until parent[x] == x.  No hook runs any more, so roots stay roots.
+__device__ __forceinline__ int uf_root(const int* parent, int x)
+{
+    for (;;) {
+        const int p = uf_load(parent + x);
+        if (p == x) return x;
+        x = p;
+    }
+}
+
+__global__ void __launch_bounds__(RG_BLOCK) regions_uf_hook_kernel(int n, const int2* __restrict__ pairs, int* __restrict__ parent)
+{
+    const int i = blockIdx.x * RG_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const int2 pr = pairs[i];
+    if (pr.x < 0) return;
+    int a = pr.x, b = pr.y;
+    for (;;) {
+        a = uf_find(parent, a);
+        b = uf_find(parent, b);
+        if (a == b) break;
+        if (a < b) { const int t = a; a = b; b = t; }       // a: the larger root, pointed at the smaller
+        const int old = atomicCAS(parent + a, a, b);
+        if (old == a) break;
+        a = old;                                            // someone hooked a first: go on from where it points
+    }
+}
+
+__global__ void __launch_bounds__(RG_BLOCK) regions_uf_flatten_kernel(int F, const unsigned char* __restrict__ sel, int* __restrict__ parent,
+                                                                      int* __restrict__ root_flag)
+{
+    const int f = blockIdx.x * RG_BLOCK + threadIdx.x;
+    if (f >= F) return;
+    const int r = uf_root(parent, f);
+    uf_store(parent + f, r);      // (the only store to this word in this kernel)
+    root_flag[f] = (sel[f] && r == f) ? 1 : 0;
+}
+
+// scan: the inclusive scan of root_flag.  count must be zero.  One add per wave and label.
+__global__ void __launch_bounds__(RG_BLOCK) regions_label_kernel(int F, const int* __restrict__ parent, const int* __restrict__ scan,
+                                                                 const unsigned char* __restrict__ sel, int* __restrict__ label,
+                                                                 int* __restrict__ count)
+{
+    const int f = blockIdx.x * RG_BLOCK + threadIdx.x;
+    int lab = -1;
+    if (f < F) {
+        if (sel[f]) lab = scan[parent[f]] - 1;
+        label[f] = lab;
+    }
+    const int lane = threadIdx.x & 63;
+    unsigned long long todo = __ballot(lab >= 0);
+    while (todo) {
+        const int leader = __ffsll((long long)todo) - 1;
+        const int L = __shfl(lab, leader);
+        const unsigned long long same = __ballot(lab == L);
+        if (lane == leader) atomicAdd(count + L, __popcll(same));
+        todo &= ~same;
+    }
+}
+
+// As a label l = f: a component with more than `thr` faces is region kscan[l] - 1 (kscan: the inclusive scan of count > thr
+// over the labels).  As a face: its region, or -1.
+__global__ void __launch_bounds__(RG_BLOCK) regions_select_kernel(int F, const int* __restrict__ count, int thr, const int* __restrict__ kscan,
+                                                                  const int* __restrict__ label, int cap, int* __restrict__ sel_label,
+                                                                  int* __restrict__ sel_count, int* __restrict__ region)
+{
+    const int f = blockIdx.x * RG_BLOCK + threadIdx.x;
+    if (f >= F) return;
+    const int c = count[f];
+    if (c > thr) {
+        const int r = kscan[f] - 1;
+        if (r < cap) { sel_label[r] = f; sel_count[r] = c; }
+    }
+    const int lab = label[f];
+    region[f] = (lab >= 0 && count[lab] > thr) ? kscan[lab] - 1 : -1;
+}
+
+// f32 -> uint32 whose unsigned order is the floats' order
+__device__ __forceinline__ unsigned order_bits(float v)
+{
+    const unsigned u = __float_as_uint(v + 0.f);          // (-0 -> +0)
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+__global__ void __launch_bounds__(RG_BLOCK) regions_box_init_kernel(int n, unsigned* __restrict__ boxes)
+{
+    const int i = blockIdx.x * RG_BLOCK + threadIdx.x;
+    if (i < n) boxes[i] = (i % 6) < 3 ? 0xffffffffu : 0u;
+}
+
+// boxes [cap][2][3] uint32 (order_bits of the min and of the max).  A lane's face gives its own min / max; lanes of equal
+// region are combined along the wave (min and max may take the same value twice), and the last lane of each run issues six
+// integer atomics.
+__global__ void __launch_bounds__(RG_BLOCK) regions_box_kernel(int F, int G, int V, const int* __restrict__ faces, const float* __restrict__ verts,
+                                                               const float* __restrict__ points, const int* __restrict__ region, int cap,
+                                                               unsigned* __restrict__ boxes, int* __restrict__ err)
+{
+    const int f = blockIdx.x * RG_BLOCK + threadIdx.x;
+    int r = -1;
+    unsigned lo[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, hi[3] = {0u, 0u, 0u};
+    if (f < F) {
+        r = region[f];
+        if (r >= cap) r = -1;
+        if (r >= 0) {
+            const int* fv = faces + 3 * (size_t)f;
+            for (int k = 0; k < 3; ++k) {
+                const int v = fv[k];
+                if ((unsigned)v >= (unsigned)V) { atomicOr(err, RG_ERR_INDEX); continue; }
+                for (int a = 0; a < 3; ++a) {
+                    const float x = verts[3 * (size_t)v + a];
+                    if (x != x) atomicOr(err, RG_ERR_NAN);
+                    const unsigned u = order_bits(x);
+                    lo[a] = min(lo[a], u);
+                    hi[a] = max(hi[a], u);
+                }
+            }
+            const float* p = points + 3 * (size_t)G * f;
+            for (int g = 0; g < G; ++g)
+                for (int a = 0; a < 3; ++a) {
+                    const float x = p[3 * g + a];
+                    if (x != x) atomicOr(err, RG_ERR_NAN);     // (numpy's min / max would give NaN; the bit order would not)
+                    const unsigned u = order_bits(x);
+                    lo[a] = min(lo[a], u);
+                    hi[a] = max(hi[a], u);
+                }
+        }
+    }
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int rr = __shfl_up(r, d);
+        const bool take = lane >= d && rr == r;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const unsigned l = __shfl_up(lo[a], d), h = __shfl_up(hi[a], d);
+            if (take) { lo[a] = min(lo[a], l); hi[a] = max(hi[a], h); }
+        }
+    }
+    const int next = __shfl_down(r, 1);
+    if (r >= 0 && (lane == 63 || next != r)) {
+        unsigned* b = boxes + 6 * (size_t)r;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            atomicMin(b + a, lo[a]);
+            atomicMax(b + 3 + a, hi[a]);
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------- cut
+// find_points_in_boundingbox (:218-224): strictly between the bounds on all three axes, compared in double.
+__global__ void __launch_bounds__(RG_BLOCK) regions_inside_kernel(int V, const float* __restrict__ verts, RegionBox box,
+                                                                  unsigned char* __restrict__ inside)
+{
+    const int v = blockIdx.x * RG_BLOCK + threadIdx.x;
+    if (v >= V) return;
+    bool in = true;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const double x = (double)verts[3 * (size_t)v + a];
+        in = in && x > box.lo[a] && x < box.hi[a];
+    }
+    inside[v] = in;
+}
+
+// ref must be zero.  keep: any vertex inside (cut_inner = 0) / no vertex inside (cut_inner = 1).
+__global__ void __launch_bounds__(RG_BLOCK) regions_cut_mark_kernel(int F, int V, const int* __restrict__ faces, const unsigned char* __restrict__ inside,
+                                                                    int cut_inner, int* __restrict__ keep, int* __restrict__ ref,
+                                                                    int* __restrict__ err)
+{
+    const int f = blockIdx.x * RG_BLOCK + threadIdx.x;
+    if (f >= F) return;
+    const int a = faces[3 * (size_t)f], b = faces[3 * (size_t)f + 1], c = faces[3 * (size_t)f + 2];
+    if ((unsigned)a >= (unsigned)V || (unsigned)b >= (unsigned)V || (unsigned)c >= (unsigned)V) {
+        atomicOr(err, RG_ERR_INDEX);
+        keep[f] = 0;
+        return;
+    }
+    const int k = inside[a] + inside[b] + inside[c];
+    const int kp = cut_inner ? (k == 0) : (k > 0);
+    keep[f] = kp;
+    if (kp) { ref[a] = 1; ref[b] = 1; ref[c] = 1; }
+}
+
+// kscan / vscan: the inclusive scans of keep / ref.  Kept faces keep their order; referenced vertices are renumbered in
+// ascending old index (remove_unreferenced_vertices).
+__global__ void __launch_bounds__(RG_BLOCK) regions_cut_faces_kernel(int F, const int* __restrict__ faces, const int* __restrict__ keep,
+                                                                     const int* __restrict__ kscan, const int* __restrict__ vscan,
+                                                                     int* __restrict__ faces_out, unsigned char* __restrict__ face_mask)
+{
+    const int f = blockIdx.x * RG_BLOCK + threadIdx.x;
+    if (f >= F) return;
+    const int kp = keep[f];
+    face_mask[f] = kp != 0;
+    if (!kp) return;
+    int* o = faces_out + 3 * (size_t)(kscan[f] - 1);
+    o[0] = vscan[faces[3 * (size_t)f]] - 1;
+    o[1] = vscan[faces[3 * (size_t)f + 1]] - 1;
+    o[2] = vscan[faces[3 * (size_t)f + 2]] - 1;
+}
+
+__global__ void __launch_bounds__(RG_BLOCK) regions_cut_verts_kernel(int V, const int* __restrict__ ref, const int* __restrict__ vscan,
+                                                                     int* __restrict__ vert_map, int* __restrict__ old_of_new)
+{
+    const int v = blockIdx.x * RG_BLOCK + threadIdx.x;
+    if (v >= V) return;
+    const int n = ref[v] ? vscan[v] - 1 : -1;
+    vert_map[v] = n;
+    if (n >= 0) old_of_new[n] = v;
+}
+
+// dst [n_rows][C] = src [old_of_new[row]][C], 4-byte elements, four per thread: one 16-byte store where dst is aligned, one
+// 16-byte load too where a row is a whole number of quads (vec bit 0: dst aligned, bit 1: src rows are aligned quads).
+__global__ void __launch_bounds__(RG_BLOCK) regions_gather_kernel(long long n_el, int C, const int* __restrict__ old_of_new,
+                                                                  const unsigned* __restrict__ src, unsigned* __restrict__ dst, int vec)
+{
+    const long long q = ((long long)blockIdx.x * RG_BLOCK + threadIdx.x) * 4;
+    if (q >= n_el) return;
+    long long row = q / C;
+    int col = (int)(q - row * C);
+    if ((vec & 2) && (vec & 1)) {       // C % 4 == 0: the quad lies in one row
+        *reinterpret_cast<uint4*>(dst + q) = *reinterpret_cast<const uint4*>(src + (long long)old_of_new[row] * C + col);
+        return;
+    }
+    unsigned v[4] = {0u, 0u, 0u, 0u};
+    const int n = n_el - q < 4 ? (int)(n_el - q) : 4;
+    long long base = (long long)old_of_new[row] * C;
+    for (int j = 0; j < n; ++j) {
+        v[j] = src[base + col];
+        if (++col == C && j + 1 < n) { col = 0; ++row; base = (long long)old_of_new[row] * C; }
+    }
+    if ((vec & 1) && n == 4) {
+        *reinterpret_cast<uint4*>(dst + q) = make_uint4(v[0], v[1], v[2], v[3]);
+    } else {
+        for (int j = 0; j < n; ++j) dst[q + j] = v[j];
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------- primitives
+// find_boundary_verts (:84-111).  bmark [V] (zero before): vertices of face-edges of count exactly 1.  With `inside`: fmark [V]
+// (zero before): vertices of faces with some but not all of their vertices inside (:102-109).
+__global__ void __launch_bounds__(RG_BLOCK) regions_boundary_kernel(int F, int V, const int* __restrict__ faces, const int* __restrict__ counts,
+                                                                    const unsigned char* __restrict__ inside, unsigned char* __restrict__ bmark,
+                                                                    unsigned char* __restrict__ fmark, int* __restrict__ err)
+{
+    const int f = blockIdx.x * RG_BLOCK + threadIdx.x;
+    if (f >= F) return;
+    int v[3];
+    for (int k = 0; k < 3; ++k) v[k] = faces[3 * (size_t)f + k];
+    if ((unsigned)v[0] >= (unsigned)V || (unsigned)v[1] >= (unsigned)V || (unsigned)v[2] >= (unsigned)V) { atomicOr(err, RG_ERR_INDEX); return; }
+    for (int e = 0; e < 3; ++e)
+        if (counts[3 * (size_t)f + e] == 1) { bmark[v[e]] = 1; bmark[v[(e + 1) % 3]] = 1; }
+    if (inside) {
+        const int k = inside[v[0]] + inside[v[1]] + inside[v[2]];
+        if (k > 0 && k < 3) { fmark[v[0]] = 1; fmark[v[1]] = 1; fmark[v[2]] = 1; }
+    }
+}
+
+// out[f] = the face's component has at least `min_count` faces (get_outlier_cc_mask, :303-306)
+__global__ void __launch_bounds__(RG_BLOCK) regions_label_mask_kernel(int F, const int* __restrict__ label, const int* __restrict__ count,
+                                                                      int min_count, unsigned char* __restrict__ out)
+{
+    const int f = blockIdx.x * RG_BLOCK + threadIdx.x;
+    if (f >= F) return;
+    const int lab = label[f];
+    out[f] = lab >= 0 && count[lab] >= min_count;
+}
+
+inline unsigned blocks(long long n) { return (unsigned)((n + RG_BLOCK - 1) / RG_BLOCK); }
+
+}  // namespace
+
+void launch_regions_edge_keys(int F, const int* faces, const unsigned char* mask, const unsigned char* colour, int cut,
+                              unsigned char* sel, long long* keys, int* err, hipStream_t st)
+{
+    regions_edge_key_kernel<<<blocks(F), RG_BLOCK, 0, st>>>(F, faces, mask, colour, cut, sel, keys, err);
+}
+
+void launch_regions_edge_runs(int F, const long long* skeys, const long long* order, int* counts, int* pairs, hipStream_t st)
+{
+    regions_edge_run_kernel<<<blocks(3ll * F), RG_BLOCK, 0, st>>>(3 * F, skeys, order, counts, reinterpret_cast<int2*>(pairs));
+}
+
+void launch_regions_components(int F, const int* pairs, const unsigned char* sel, int* parent, int* root_flag, hipStream_t st)
+{
+    regions_uf_init_kernel<<<blocks(F), RG_BLOCK, 0, st>>>(F, parent);
+    regions_uf_hook_kernel<<<blocks(3ll * F), RG_BLOCK, 0, st>>>(3 * F, reinterpret_cast<const int2*>(pairs), parent);
+    regions_uf_flatten_kernel<<<blocks(F), RG_BLOCK, 0, st>>>(F, sel, parent, root_flag);
+}
+
+void launch_regions_labels(int F, const int* parent, const int* scan, const unsigned char* sel, int* label, int* count, hipStream_t st)
+{
+    regions_label_kernel<<<blocks(F), RG_BLOCK, 0, st>>>(F, parent, scan, sel, label, count);
+}
+
+void launch_regions_select(int F, const int* count, int thr, const int* kscan, const int* label, int cap, int* sel_label,
+                           int* sel_count, int* region, hipStream_t st)
+{
+    regions_select_kernel<<<blocks(F), RG_BLOCK, 0, st>>>(F, count, thr, kscan, label, cap, sel_label, sel_count, region);
+}
+
+void launch_regions_boxes(int F, int G, int V, const int* faces, const float* verts, const float* points, const int* region, int cap,
+                          unsigned* boxes, int* err, hipStream_t st)
+{
+    if (cap > 0) regions_box_init_kernel<<<blocks(6ll * cap), RG_BLOCK, 0, st>>>(6 * cap, boxes);
+    if (cap > 0 && F > 0) regions_box_kernel<<<blocks(F), RG_BLOCK, 0, st>>>(F, G, V, faces, verts, points, region, cap, boxes, err);
+}
+
+void launch_regions_inside(int V, const float* verts, const double* box6, unsigned char* inside, hipStream_t st)
+{
+    RegionBox b;
+    for (int a = 0; a < 3; ++a) { b.lo[a] = box6[a]; b.hi[a] = box6[3 + a]; }
+    regions_inside_kernel<<<blocks(V), RG_BLOCK, 0, st>>>(V, verts, b, inside);
+}
+
+hipError_t launch_regions_cut_mark(int F, int V, const int* faces, const unsigned char* inside, int cut_inner, int* keep, int* ref,
+                                   int* err, hipStream_t st)
+{
+    if (V > 0) {
+        const hipError_t e = hipMemsetAsync(ref, 0, sizeof(int) * (size_t)V, st);
+        if (e != hipSuccess) return e;
+    }
+    if (F > 0) regions_cut_mark_kernel<<<blocks(F), RG_BLOCK, 0, st>>>(F, V, faces, inside, cut_inner, keep, ref, err);
+    return hipSuccess;
+}
+
+void launch_regions_cut_emit(int F, int V, const int* faces, const int* keep, const int* kscan, const int* ref, const int* vscan,
+                             int* faces_out, unsigned char* face_mask, int* vert_map, int* old_of_new, hipStream_t st)
+{
+    if (F > 0) regions_cut_faces_kernel<<<blocks(F), RG_BLOCK, 0, st>>>(F, faces, keep, kscan, vscan, faces_out, face_mask);
+    if (V > 0) regions_cut_verts_kernel<<<blocks(V), RG_BLOCK, 0, st>>>(V, ref, vscan, vert_map, old_of_new);
+}
+
+void launch_regions_gather(int n_rows, int C, const int* old_of_new, const void* src, void* dst, hipStream_t st)
+{
+    const long long n_el = (long long)n_rows * C;
+    const int vec = ((reinterpret_cast<uintptr_t>(dst) & 15) == 0 ? 1 : 0) |
+                    ((C % 4 == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0) ? 2 : 0);
+    regions_gather_kernel<<<blocks((n_el + 3) / 4), RG_BLOCK, 0, st>>>(n_el, C, old_of_new, static_cast<const unsigned*>(src),
+                                                                      static_cast<unsigned*>(dst), vec);
+}
+
+hipError_t launch_regions_boundary(int F, int V, const int* faces, const int* counts, const unsigned char* inside, unsigned char* bmark,
+                                   unsigned char* fmark, int* err, hipStream_t st)
+{
+    if (V > 0) {
+        hipError_t e = hipMemsetAsync(bmark, 0, (size_t)V, st);
+        if (e == hipSuccess && inside) e = hipMemsetAsync(fmark, 0, (size_t)V, st);
+        if (e != hipSuccess) return e;
+    }
+    if (F > 0) regions_boundary_kernel<<<blocks(F), RG_BLOCK, 0, st>>>(F, V, faces, counts, inside, bmark, fmark, err);
+    return hipSuccess;
+}
+
+void launch_regions_label_mask(int F, const int* label, const int* count, int min_count, unsigned char* out, hipStream_t st)
+{
+    regions_label_mask_kernel<<<blocks(F), RG_BLOCK, 0, st>>>(F, label, count, min_count, out);
+}
+
+}  // namespace gsr

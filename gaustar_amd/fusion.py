@@ -3,7 +3,8 @@
 Once detect_topo_err has switched loose binding on, forward_rendering_and_mesh_update (refined_mesh.py:1024) renders RGB and
 depth/alpha from 60 sampled cameras and the rig, pulls every image to the host, integrates them into an Open3D
 ScalableTSDFVolume on the CPU and extracts the mesh update_mesh_topo cuts its patches from.  Here the renders stay on the
-device and the image preparation, the integration and marching cubes are HIP kernels (include/gsr.h, gsr_fusion.hip):
+device and the image preparation, the integration and marching cubes are HIP kernels (include/gsr.h, gsr_fusion.hip); the
+FusionMesh goes to the cuts of gaustar_amd.regions (update_mesh_topo's front half) as device tensors:
 
     res = fuse_mesh(model, cameras)                       # native: FusionMesh (verts, faces, colors: device tensors)
     res = model.extract_mesh_fusion(cameras)              # the same, as a method of harness.SurfaceGaussians

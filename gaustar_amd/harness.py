@@ -500,6 +500,31 @@ class SurfaceGaussians(nn.Module):
         from . import fusion
         return fusion.fuse_mesh(self, cameras, **kw)
 
+    def topology_update_regions(self, res, **kw):
+        """The regions of the mesh that update_mesh_topo re-meshes (refined_mesh.py:516-571), from the face colours of
+        detect_topology_errors' result `res`: regions.select_update_regions(vertices, faces, points, res.face_colour, G, **kw)
+        -> regions.UpdateRegions.  Once per frame: it does not depend on aabb_pad."""
+        from . import regions
+        with torch.no_grad():
+            return regions.select_update_regions(self._points.detach().float(), self._surface_mesh_faces, self.points.detach(),
+                                                 res.face_colour, self.n_gaussians_per_surface_triangle, **kw)
+
+    def cut_update_regions(self, update_regions, fusion_mesh, aabb_pad: float = 0.02):
+        """Per merged box of update_regions.boxes(aabb_pad) a regions.RegionCut: the box, the patch of `fusion_mesh`
+        (fusion.FusionMesh) with any vertex inside it, colours carried (refined_mesh.py:583), and the base mesh without the
+        faces that have a vertex inside it, with its face_mask over the base mesh's faces (:609-614).  Each cut is made from
+        the UNCUT base mesh: the reference cuts what the previous box's splice left (`base_mesh = connected_mesh`, :660), and
+        that chaining belongs to the splice, which is not implemented."""
+        from . import regions
+        verts, faces = self._points.detach().float(), self._surface_mesh_faces.int()
+        out = []
+        for box in update_regions.boxes(aabb_pad):
+            out.append(regions.RegionCut(box=box,
+                                         fusion_patch=regions.cut_mesh_by_box(fusion_mesh.verts, fusion_mesh.faces, box, False,
+                                                                              attrs=(fusion_mesh.colors,)),
+                                         base_cut=regions.cut_mesh_by_box(verts, faces, box, True)))
+        return out
+
     # -------------------------------------------------------------------------------- rendering
     def _settings(self, camera: NerfCamera, bg: torch.Tensor, sh_degree: int):
         cam, view, proj, campos = camera.on_device(self.device)

@@ -1,0 +1,397 @@
+"""Which regions of the mesh are re-meshed at topology errors, and the cuts around them: the front half of update_mesh_topo
+(gaustar_trainers/refined_mesh.py:463-693) on the GPU.
+
+After detect_topo_err has coloured the faces and extract_mesh_fusion has given the TSDF surface, update_mesh_topo takes the
+faces above the colour cut-off (:516), groups them into connected components (:524), keeps the large ones (:526), puts a box
+around each one's vertices and Gaussian centres (:552-571), merges boxes that overlap (:574) and cuts the fused surface and the
+base mesh by every box (:583, :609).  The reference does that with trimesh, scipy and numpy on the host; here the meshes stay
+device tensors and the passes are HIP kernels (include/gsr.h, gsr_regions.hip):
+
+    counts = face_edge_counts(faces)                                   # [F,3] int32: faces sharing each face-edge
+    label, count = face_components(faces, mask)                        # trimesh.graph.connected_component_labels(face_adjacency)
+    regions = select_update_regions(verts, faces, points, face_colour, G)        # once per frame: UpdateRegions
+    boxes = regions.boxes(aabb_pad)                                    # per aabb_pad trial: float64 [m,2,3], host numpy
+    cut = cut_mesh_by_box(verts, faces, box, cut_inner, attrs=(colors,))         # cut_mesh_by_boundingbox (:227-251): CutMesh
+    idx = boundary_vertices(verts, faces, box, cut_inner)              # find_boundary_verts (:84-111)
+    keep = outlier_component_mask(faces, face_num_threshold)           # get_outlier_cc_mask (:291-307)
+
+Vertex identity is the vertex index: nothing merges vertices by position, and the reference's OBJ round trip of the detected
+mesh is not reproduced.  Two faces are adjacent iff they share an edge that exactly two face-edges of the mesh have and they
+are different faces; an edge of three or more faces links nothing.  With a mask the edges are counted among the masked faces
+only, as the reference counts them after update_faces.  Components are numbered by ascending smallest face index, the order
+scipy.sparse.csgraph.connected_components gives.  Every output is an integer or an exactly defined float: the same inputs give
+the same bits.
+
+What follows the cut in the reference -- fill_holes, connect_two_meshes, merge_vert_around_holes, the watertight test and the
+choice among the aabb_pad trials (:589-693) -- is not here.  The reference applies find_boundary_verts and get_outlier_cc_mask
+after fill_holes; here they are primitives on whatever mesh they are given.
+"""
+from __future__ import annotations
+
+import ctypes
+import itertools
+import math
+from dataclasses import dataclass
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import ptr as _p, stream_ptr as _stream
+
+MAX_FACES = (2 ** 31 - 1) // 3      # 3 F face-edges are counted in an int32
+
+
+def _faces_i32(faces: torch.Tensor) -> torch.Tensor:
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError("faces must be [F,3]")
+    if faces.shape[0] > MAX_FACES:
+        raise ValueError(f"{faces.shape[0]} faces: more than 2^31 / 3, the face-edges cannot be indexed in int32")
+    if faces.dtype not in (torch.int32, torch.int64):
+        raise ValueError("faces must be int32 or int64")
+    if faces.device.type != "cuda":
+        raise RuntimeError("the mesh must be on a GPU")
+    return faces.to(torch.int32).contiguous()
+
+
+def _verts_f32(verts: torch.Tensor, dev) -> torch.Tensor:
+    if verts.dim() != 2 or verts.shape[1] != 3 or verts.dtype != torch.float32:
+        raise ValueError("verts must be [V,3] float32")
+    if verts.device != dev:
+        raise RuntimeError("verts and faces must be on the same GPU")
+    return verts.detach().contiguous()
+
+
+def _box6(box) -> Tuple[np.ndarray, ctypes.Array]:
+    b = np.asarray(box, np.float64)
+    if b.shape != (2, 3) or np.isnan(b).any():
+        raise ValueError("box must be [2,3] (lo, hi) without NaN")
+    return b, (ctypes.c_double * 6)(*b.reshape(-1))
+
+
+def _raise_if(err: int) -> None:
+    """The kernels' err word: bit 0 = a vertex index outside the mesh, bit 1 = a NaN among a box's coordinates."""
+    if err & 1:
+        raise ValueError("faces hold a vertex index outside the mesh")
+    if err & 2:
+        raise ValueError("a vertex or Gaussian centre of a kept region is NaN: its box is not defined")
+
+
+# ------------------------------------------------------------------------------------------------ edges and components
+def _edge_runs(faces: torch.Tensor, mask: Optional[torch.Tensor], colour: Optional[torch.Tensor], cut: int, err: torch.Tensor):
+    """faces [F,3] int32 (F > 0) -> (selected [F] uint8, counts [F,3] int32, pairs [3F,2] int32)."""
+    lib = _lib.load()
+    dev, F = faces.device, int(faces.shape[0])
+    sel = torch.empty(F, dtype=torch.uint8, device=dev)
+    keys = torch.empty(3 * F, dtype=torch.int64, device=dev)
+    st = _stream()
+    _lib.check(lib.gsr_regions_edge_keys(F, _p(faces), _p(mask), _p(colour), int(cut), _p(sel), _p(keys), _p(err), st),
+               "gsr_regions_edge_keys")
+    skeys, order = torch.sort(keys, stable=True)
+    del keys
+    counts = torch.empty(F, 3, dtype=torch.int32, device=dev)
+    pairs = torch.empty(3 * F, 2, dtype=torch.int32, device=dev)
+    _lib.check(lib.gsr_regions_edge_runs(F, _p(skeys), _p(order), _p(counts), _p(pairs), st), "gsr_regions_edge_runs")
+    return sel, counts, pairs
+
+
+def _mask_u8(mask: Optional[torch.Tensor], F: int, dev) -> Optional[torch.Tensor]:
+    if mask is None:
+        return None
+    if tuple(mask.shape) != (F,) or mask.dtype not in (torch.bool, torch.uint8):
+        raise ValueError("mask must be [F] bool or uint8")
+    if mask.device != dev:
+        raise RuntimeError("mask and faces must be on the same GPU")
+    return mask.contiguous().view(torch.uint8) if mask.dtype == torch.bool else mask.contiguous()
+
+
+def face_edge_counts(faces: torch.Tensor, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """[F,3] int32: for face-edge e of face (a, b, c) -- (a, b), (b, c), (c, a) -- how many face-edges of the mesh have the same
+    vertex pair, itself included (trimesh: group_rows(edges_sorted, require_count=1) are the ones, require_count=2 the twos).
+    With a mask the masked faces' edges are counted among themselves and the others get 0.  The call has no vertex count:
+    a negative index raises ValueError, an index past the mesh's vertices is an edge end like any other and is only caught by
+    the calls that take verts."""
+    faces = _faces_i32(faces)
+    F = int(faces.shape[0])
+    if F == 0:
+        return torch.empty(0, 3, dtype=torch.int32, device=faces.device)
+    err = torch.zeros(1, dtype=torch.int32, device=faces.device)
+    _sel, counts, _pairs = _edge_runs(faces, _mask_u8(mask, F, faces.device), None, 0, err)
+    _raise_if(int(err.cpu()))
+    return counts
+
+
+def _components(faces: torch.Tensor, mask: Optional[torch.Tensor], colour: Optional[torch.Tensor], cut: int, err: torch.Tensor):
+    """faces [F,3] int32 (F > 0) -> (label [F] int32, count [F] int32 with the faces of label l at l and zeros behind, n [1]
+    int32 on the device = the number of components, parent [F] int32 = the smallest face of every face's component).  Nothing
+    is read back."""
+    lib = _lib.load()
+    dev, F = faces.device, int(faces.shape[0])
+    sel, _counts, pairs = _edge_runs(faces, mask, colour, cut, err)
+    parent = torch.empty(F, dtype=torch.int32, device=dev)
+    flag = torch.empty(F, dtype=torch.int32, device=dev)
+    st = _stream()
+    _lib.check(lib.gsr_regions_components(F, _p(pairs), _p(sel), _p(parent), _p(flag), st), "gsr_regions_components")
+    scan = torch.cumsum(flag, 0, dtype=torch.int32)
+    label = torch.empty(F, dtype=torch.int32, device=dev)
+    count = torch.zeros(F, dtype=torch.int32, device=dev)
+    _lib.check(lib.gsr_regions_labels(F, _p(parent), _p(scan), _p(sel), _p(label), _p(count), st), "gsr_regions_labels")
+    return label, count, scan[-1:], parent
+
+
+def face_components(faces: torch.Tensor, mask: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(label [F] int32, count [n] int32): the connected components of the faces with `mask` set (all without one) under the
+    adjacency of the module docstring, numbered by ascending smallest face index; label is -1 outside the mask.  What
+    trimesh.graph.connected_component_labels(mesh.face_adjacency, node_count=F) and np.bincount give for the masked mesh
+    (refined_mesh.py:524-525).  One host read: n.  As face_edge_counts, it has no vertex count: only a negative index raises."""
+    faces = _faces_i32(faces)
+    dev, F = faces.device, int(faces.shape[0])
+    if F == 0:
+        return torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.int32, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    label, count, n, _parent = _components(faces, _mask_u8(mask, F, dev), None, 0, err)
+    head = torch.cat([n, err]).cpu()
+    _raise_if(int(head[1]))
+    return label, count[:int(head[0])]
+
+
+# ------------------------------------------------------------------------------------------------ selection and boxes
+def combine_overlap_aabbs(boxes: Sequence[np.ndarray]) -> List[np.ndarray]:
+    """combine_overlap_aabbs (refined_mesh.py:254-288), its order dependence included: box j joins the first merged entry i
+    for which one of j's eight corners lies strictly inside the i-th box OF THE INPUT LIST (:269 tests aabb_list[i], not the
+    merged list), by min / max; whenever a pass merged something the result goes through again."""
+    boxes = [np.asarray(b, np.float64) for b in boxes]
+    out: List[np.ndarray] = []
+    for b in boxes:
+        corners = np.array([[b[i, 0], b[j, 1], b[k, 2]] for i, j, k in itertools.product((0, 1), repeat=3)])
+        hit = -1
+        for i in range(len(out)):
+            lo, hi = boxes[i][0], boxes[i][1]
+            if ((corners > lo) & (corners < hi)).all(axis=1).any():
+                hit = i
+                break
+        if hit < 0:
+            out.append(b)
+        else:
+            out[hit] = np.stack([np.minimum(out[hit][0], b[0]), np.maximum(out[hit][1], b[1])])
+    return out if len(out) == len(boxes) else combine_overlap_aabbs(out)
+
+
+@dataclass
+class UpdateRegions:
+    """What select_update_regions found.  component [F] int32: the component of every face above the cut-off (-1 below);
+    region [F] int32: its kept region (-1: none); n_components; n_regions; labels [n_regions]: the component each region is;
+    counts [n_regions]: its faces; raw_boxes float64 [n_regions,2,3]: min and max over the region's vertices and Gaussian
+    centres (f32 values, exact); nothing_to_update = no region (the reference's cc_update_num == -1, :528-529).  component and
+    region are device tensors, the rest numpy."""
+    component: torch.Tensor
+    region: torch.Tensor
+    n_components: int
+    n_regions: int
+    labels: np.ndarray
+    counts: np.ndarray
+    raw_boxes: np.ndarray
+
+    @property
+    def nothing_to_update(self) -> bool:
+        return self.n_regions == 0
+
+    def boxes(self, aabb_pad: float = 0.02) -> np.ndarray:
+        """float64 [m,2,3]: every raw box grown by aabb_pad in float64 (refined_mesh.py:567-569), then merged by
+        combine_overlap_aabbs (:574).  Host numpy on a handful of boxes."""
+        grown = self.raw_boxes.copy()
+        grown[:, 0] -= float(aabb_pad)
+        grown[:, 1] += float(aabb_pad)
+        merged = combine_overlap_aabbs(list(grown))
+        return np.stack(merged) if merged else np.zeros((0, 2, 3))
+
+
+def _decode_boxes(enc: np.ndarray) -> np.ndarray:
+    """gsr_regions_boxes' uint32 [n,2,3] -> float64 (the f32 values, widened)."""
+    u = enc.astype(np.uint32)
+    bits = np.where(u & np.uint32(0x80000000), u ^ np.uint32(0x80000000), ~u).astype(np.uint32)
+    return bits.view(np.float32).astype(np.float64)
+
+
+@torch.no_grad()
+def select_update_regions(verts: torch.Tensor, faces: torch.Tensor, points: torch.Tensor, face_colour: torch.Tensor, G: int,
+                          delta_threshold: float = 0.6, cc_face_threshold: int = 80) -> UpdateRegions:
+    """refined_mesh.py:516-571 without the pad: the faces with face_colour >= 255 delta_threshold (:516), their components
+    (:524), those with MORE than cc_face_threshold faces (:526) in label order, and per kept component the box of its faces'
+    vertices and of its faces' G Gaussian centres (points [F G,3], face-major; :538-567).  face_colour: [F] uint8
+    (topology.TopologyErrors.face_colour).  Does not depend on aabb_pad: once per frame.  One host read (the kept components'
+    counts and boxes).  A NaN among a kept region's vertices or centres raises ValueError (numpy's min / max would answer NaN)."""
+    lib = _lib.load()
+    faces = _faces_i32(faces)
+    dev, F, G = faces.device, int(faces.shape[0]), int(G)
+    verts = _verts_f32(verts, dev)
+    V = int(verts.shape[0])
+    thr = int(cc_face_threshold)
+    if thr < 0 or G < 0:
+        raise ValueError("cc_face_threshold and G must not be negative")
+    if tuple(points.shape) != (F * G, 3) or points.dtype != torch.float32 or points.device != dev:
+        raise ValueError("points must be [F G,3] float32 on the faces' GPU")
+    if tuple(face_colour.shape) != (F,) or face_colour.dtype != torch.uint8 or face_colour.device != dev:
+        raise ValueError("face_colour must be [F] uint8 on the faces' GPU")
+    cut = math.ceil(255 * float(delta_threshold))     # an integer colour c has c >= x iff c >= ceil(x); x in float64 (:516)
+    empty = torch.empty(0, dtype=torch.int32, device=dev)
+    if F == 0:
+        return UpdateRegions(empty, empty, 0, 0, np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros((0, 2, 3)))
+    points, face_colour = points.detach().contiguous(), face_colour.contiguous()
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    label, count, n, _parent = _components(faces, None, face_colour, cut, err)
+    kscan = torch.cumsum(count > thr, 0, dtype=torch.int32)
+    cap = F // (thr + 1)                               # (a kept component has at least thr + 1 faces)
+    kept_label = torch.zeros(cap, dtype=torch.int32, device=dev)
+    kept_count = torch.zeros(cap, dtype=torch.int32, device=dev)
+    region = torch.empty(F, dtype=torch.int32, device=dev)
+    enc = torch.empty(cap, 6, dtype=torch.int32, device=dev)
+    st = _stream()
+    _lib.check(lib.gsr_regions_select(F, _p(count), thr, _p(kscan), _p(label), cap, _p(kept_label), _p(kept_count), _p(region), st),
+               "gsr_regions_select")
+    _lib.check(lib.gsr_regions_boxes(F, G, V, _p(faces), _p(verts), _p(points), _p(region), cap, _p(enc), _p(err), st),
+               "gsr_regions_boxes")
+    head = torch.cat([n, kscan[-1:], err, kept_label, kept_count, enc.reshape(-1)]).cpu().numpy()
+    _raise_if(int(head[2]))
+    m = int(head[1])
+    body = head[3:]
+    return UpdateRegions(component=label, region=region, n_components=int(head[0]), n_regions=m, labels=body[:m].copy(),
+                         counts=body[cap:cap + m].copy(),
+                         raw_boxes=_decode_boxes(body[2 * cap:2 * cap + 6 * m].view(np.uint32).reshape(m, 2, 3)))
+
+
+# ------------------------------------------------------------------------------------------------ cut
+@dataclass
+class CutMesh:
+    """verts [Nv,3] f32, faces [Nf,3] int32 (new vertex numbers), face_mask [F] bool (the input faces kept: the reference's
+    'inside_face_mask'), vert_map [V] int32 (old vertex -> new, -1 = dropped), attrs (the per-vertex arrays given, gathered)."""
+    verts: torch.Tensor
+    faces: torch.Tensor
+    face_mask: torch.Tensor
+    vert_map: torch.Tensor
+    attrs: Tuple[torch.Tensor, ...]
+
+
+def _inside(verts: torch.Tensor, box6) -> torch.Tensor:
+    lib = _lib.load()
+    V = int(verts.shape[0])
+    inside = torch.empty(V, dtype=torch.uint8, device=verts.device)
+    _lib.check(lib.gsr_regions_inside(V, _p(verts), box6, _p(inside), _stream()), "gsr_regions_inside")
+    return inside
+
+
+def _gather(old_of_new: torch.Tensor, src: torch.Tensor) -> torch.Tensor:
+    lib = _lib.load()
+    n = int(old_of_new.shape[0])
+    C = int(np.prod(src.shape[1:])) if src.dim() > 1 else 1
+    out = torch.empty((n, *src.shape[1:]), dtype=src.dtype, device=src.device)
+    _lib.check(lib.gsr_regions_gather(n, C, _p(old_of_new), _p(src), _p(out), _stream()), "gsr_regions_gather")
+    return out
+
+
+@torch.no_grad()
+def cut_mesh_by_box(verts: torch.Tensor, faces: torch.Tensor, box, cut_inner: bool, attrs: Sequence[torch.Tensor] = ()) -> CutMesh:
+    """cut_mesh_by_boundingbox (refined_mesh.py:218-251).  box: [2,3] (lo, hi), taken as float64.  A vertex is inside iff all
+    three coordinates are strictly between the bounds, compared in float64 (the f32 coordinate widens exactly).
+    cut_inner=False keeps the faces with any vertex inside, cut_inner=True those with none.  Kept faces keep their order;
+    the vertices they use are renumbered in ascending old index (remove_unreferenced_vertices).  attrs: per-vertex arrays
+    [V, ...] of a 4-byte dtype (the fusion's colours) that follow the vertices.  An empty result is legal.  One host read: the
+    two totals."""
+    lib = _lib.load()
+    faces = _faces_i32(faces)
+    dev, F = faces.device, int(faces.shape[0])
+    verts = _verts_f32(verts, dev)
+    V = int(verts.shape[0])
+    _b, box6 = _box6(box)
+    attrs = tuple(attrs)
+    for a in attrs:
+        if a.dim() < 1 or a.shape[0] != V or a.element_size() != 4 or a.device != dev:
+            raise ValueError("attrs must be per-vertex arrays [V, ...] of a 4-byte dtype on the mesh's GPU")
+    st = _stream()
+    inside = _inside(verts, box6)
+    keep = torch.empty(F, dtype=torch.int32, device=dev)
+    ref = torch.empty(V, dtype=torch.int32, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    _lib.check(lib.gsr_regions_cut_mark(F, V, _p(faces), _p(inside), int(bool(cut_inner)), _p(keep), _p(ref), _p(err), st),
+               "gsr_regions_cut_mark")
+    kscan = torch.cumsum(keep, 0, dtype=torch.int32)
+    vscan = torch.cumsum(ref, 0, dtype=torch.int32)
+    zero = torch.zeros(1, dtype=torch.int32, device=dev)
+    head = torch.cat([kscan[-1:] if F else zero, vscan[-1:] if V else zero, err]).cpu()
+    _raise_if(int(head[2]))
+    nf, nv = int(head[0]), int(head[1])
+    faces_out = torch.empty(nf, 3, dtype=torch.int32, device=dev)
+    face_mask = torch.empty(F, dtype=torch.bool, device=dev)
+    vert_map = torch.empty(V, dtype=torch.int32, device=dev)
+    old_of_new = torch.empty(nv, dtype=torch.int32, device=dev)
+    _lib.check(lib.gsr_regions_cut_emit(F, V, _p(faces), _p(keep), _p(kscan), _p(ref), _p(vscan), _p(faces_out), _p(face_mask),
+                                        _p(vert_map), _p(old_of_new), st), "gsr_regions_cut_emit")
+    return CutMesh(verts=_gather(old_of_new, verts), faces=faces_out, face_mask=face_mask, vert_map=vert_map,
+                   attrs=tuple(_gather(old_of_new, a.detach().contiguous()) for a in attrs))
+
+
+@dataclass
+class RegionCut:
+    """One merged box of a frame (harness.SurfaceGaussians.cut_update_regions): box float64 [2,3]; fusion_patch: the fused
+    surface's faces with any vertex inside it (attrs[0]: the vertex colours); base_cut: the base mesh without the faces that
+    have a vertex inside it."""
+    box: np.ndarray
+    fusion_patch: CutMesh
+    base_cut: CutMesh
+
+
+# ------------------------------------------------------------------------------------------------ primitives
+@torch.no_grad()
+def boundary_vertices(verts: torch.Tensor, faces: torch.Tensor, box=None, cut_inner: bool = False, pad: float = 0.02) -> torch.Tensor:
+    """find_boundary_verts (refined_mesh.py:84-111): the vertices on edges that exactly one face-edge has, as ascending int32
+    indices.  With a box and cut_inner=True those inside the box grown by `pad` (:94-99, grown in float64); with a box and
+    cut_inner=False those that belong to a face with some but not all of its vertices inside the box (:101-111).
+    A primitive on the mesh it is given: the reference calls it after fill_holes (:589-600, :617-619), which is not part of
+    this module."""
+    lib = _lib.load()
+    faces = _faces_i32(faces)
+    dev, F = faces.device, int(faces.shape[0])
+    verts = _verts_f32(verts, dev)
+    V = int(verts.shape[0])
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    counts = _edge_runs(faces, None, None, 0, err)[1] if F else None
+    bmark = torch.empty(V, dtype=torch.uint8, device=dev)
+    fmark = inside = None
+    if box is not None:
+        b, box6 = _box6(box)
+        if cut_inner:
+            grown = np.stack([b[0] - float(pad), b[1] + float(pad)])
+            grown_inside = _inside(verts, (ctypes.c_double * 6)(*grown.reshape(-1)))
+        else:
+            inside = _inside(verts, box6)
+            fmark = torch.empty(V, dtype=torch.uint8, device=dev)
+    _lib.check(lib.gsr_regions_boundary(F, V, _p(faces), _p(counts), _p(inside), _p(bmark), _p(fmark), _p(err), _stream()),
+               "gsr_regions_boundary")
+    sel = bmark if box is None else (bmark & grown_inside if cut_inner else bmark & fmark)
+    idx = torch.nonzero(sel).view(-1).to(torch.int32)
+    _raise_if(int(err.cpu()))
+    return idx
+
+
+@torch.no_grad()
+def outlier_component_mask(faces: torch.Tensor, face_num_threshold: Optional[float] = None) -> torch.Tensor:
+    """get_outlier_cc_mask (refined_mesh.py:291-307): [F] bool, True for the faces of components with at least
+    min(face_num_threshold, 0.3 max count) faces -- 0.3 max count when the threshold is None -- the product in float64 on the
+    host.  A primitive on the mesh it is given: the reference calls it after fill_holes (:589-592), which is not part of this
+    module.  One host read: the components' counts."""
+    lib = _lib.load()
+    label, count = face_components(faces)
+    F = int(label.shape[0])
+    out = torch.empty(F, dtype=torch.bool, device=label.device)
+    if F == 0:
+        return out
+    bound = float(count.max().cpu()) * 0.3
+    if face_num_threshold is not None:
+        bound = min(float(face_num_threshold), bound)
+    _lib.check(lib.gsr_regions_label_mask(F, _p(label), _p(count), int(math.ceil(bound)), _p(out), _stream()), "gsr_regions_label_mask")
+    return out
+
+
+__all__ = ["MAX_FACES", "face_edge_counts", "face_components", "combine_overlap_aabbs", "UpdateRegions", "select_update_regions",
+           "CutMesh", "RegionCut", "cut_mesh_by_box", "boundary_vertices", "outlier_component_mask"]

@@ -571,6 +571,63 @@ int gsr_fusion_emit(const int* grid, double voxel_size, const float* tsdf, const
                     const int* vert_scan, const int* tri_scan, const int* table, float* verts, int* faces, float* colors,
                     gsr_stream_t stream);
 
+/* ---- Re-mesh regions at topology errors: the front half of update_mesh_topo (gaustar_trainers/refined_mesh.py:463-693) up to
+ * the cuts (:516-574, :583, :609) and the primitives find_boundary_verts (:84-111) and get_outlier_cc_mask (:291-307):
+ * gaustar_amd.regions.  Vertex identity is the vertex index.  faces [F,3] int32, F <= (2^31 - 1) / 3; face-edge e of face
+ * (a, b, c) is (a, b), (b, c), (c, a).  All device pointers unless marked [host]; every call is asynchronous on `stream`,
+ * none synchronises the host, none uses float atomics: every output is a pure function of the inputs.  err [1] int32 (zero
+ * before): bit 0 is set when a face holds a vertex index outside [0, V) (a negative one, where V is not given: the calls
+ * without V cannot see an index >= V); such a face is left out.  Bit 1 is set by gsr_regions_boxes when a coordinate it takes
+ * into a box is NaN (the box is then not defined).
+ * gsr_regions_edge_keys: selected [F] uint8 = (mask == NULL or mask[f]) and (colour == NULL or colour[f] >= cut); keys [3 F]
+ *   int64 = min << 32 | max of the face-edge's vertex pair, 2^63 - 1 for the face-edges of faces that are not selected.
+ * gsr_regions_edge_runs: sorted_keys = keys in ascending order, order [3 F] int64 = the face-edge each came from.  counts
+ *   [3 F] int32 by face-edge: how many selected face-edges have its vertex pair (0 when not selected).  pairs [3 F][2] int32
+ *   by sorted position: (face, face) at the first key of a run of exactly two face-edges of two different faces (trimesh's
+ *   face_adjacency: group_rows(edges_sorted, require_count=2) minus the pairs within one face), (-1, -1) elsewhere.
+ * gsr_regions_components: union-find over the pairs.  parent [F] int32 = the smallest face index of f's component, for every
+ *   f (parent[parent[f]] == parent[f]): the hooks point the larger root at the smaller, and the flatten pass that follows
+ *   writes each word once, from its own face's thread, after a find that stores nothing; root_flag [F] int32 = 1 for the
+ *   selected faces with parent[f] == f.
+ * gsr_regions_labels: root_scan = the INCLUSIVE scan of root_flag.  label [F] int32 = root_scan[parent[f]] - 1 -- components
+ *   numbered by ascending smallest face, as scipy's connected_components numbers them -- and -1 where not selected; count [F]
+ *   int32 (zero before): faces per label.
+ * gsr_regions_select: kept_scan = the INCLUSIVE scan over the labels of count > face_threshold.  Region r = kept_scan[l] - 1
+ *   of a kept label l: kept_label [cap], kept_count [cap]; region [F] int32 = the face's region or -1.
+ * gsr_regions_boxes: boxes [cap][2][3] uint32, per region the minimum and maximum over the three vertices of its faces (verts
+ *   [V,3] f32) and over its faces' G points (points [F G,3] f32, face-major), each as the f32's bits b mapped to b | 2^31
+ *   (b >= 0) or ~b: unsigned order = float order, -0 counted as +0; a slot no face reached holds 2^32 - 1 (min) / 0 (max).
+ * gsr_regions_inside: box: [host] 6 doubles (lo xyz, hi xyz); inside [V] uint8 = lo < (double) v < hi on all three axes.
+ * gsr_regions_cut_mark: keep [F] int32 = any (cut_inner = 0) / none (cut_inner = 1) of the face's vertices is inside
+ *   (cut_mesh_by_boundingbox, :227-251); referenced [V] int32 = the vertex belongs to a kept face.
+ * gsr_regions_cut_emit: with the INCLUSIVE scans of keep and referenced: faces_out [kept,3] int32 in the faces' order with the
+ *   vertices renumbered in ascending old index (remove_unreferenced_vertices), face_mask [F] uint8, vert_map [V] int32 (-1:
+ *   dropped), old_of_new [referenced] int32.
+ * gsr_regions_gather: dst [n_rows][C] = src [old_of_new[row]][C] for 4-byte elements.
+ * gsr_regions_boundary: edge_mark [V] uint8 = the vertex lies on a face-edge of count exactly 1; with inside != NULL, face_mark
+ *   [V] uint8 = it belongs to a face with some but not all of its vertices inside (:102-109).
+ * gsr_regions_label_mask: out [F] uint8 = label[f] >= 0 and count[label[f]] >= min_count. */
+int gsr_regions_edge_keys(int F, const int* faces, const unsigned char* mask, const unsigned char* colour, int cut,
+                          unsigned char* selected, long long* keys, int* err, gsr_stream_t stream);
+int gsr_regions_edge_runs(int F, const long long* sorted_keys, const long long* order, int* counts, int* pairs, gsr_stream_t stream);
+int gsr_regions_components(int F, const int* pairs, const unsigned char* selected, int* parent, int* root_flag, gsr_stream_t stream);
+int gsr_regions_labels(int F, const int* parent, const int* root_scan, const unsigned char* selected, int* label, int* count,
+                       gsr_stream_t stream);
+int gsr_regions_select(int F, const int* count, int face_threshold, const int* kept_scan, const int* label, int cap, int* kept_label,
+                       int* kept_count, int* region, gsr_stream_t stream);
+int gsr_regions_boxes(int F, int G, int V, const int* faces, const float* verts, const float* points, const int* region, int cap,
+                      unsigned int* boxes, int* err, gsr_stream_t stream);
+int gsr_regions_inside(int V, const float* verts, const double* box, unsigned char* inside, gsr_stream_t stream);
+int gsr_regions_cut_mark(int F, int V, const int* faces, const unsigned char* inside, int cut_inner, int* keep, int* referenced,
+                         int* err, gsr_stream_t stream);
+int gsr_regions_cut_emit(int F, int V, const int* faces, const int* keep, const int* keep_scan, const int* referenced,
+                         const int* referenced_scan, int* faces_out, unsigned char* face_mask, int* vert_map, int* old_of_new,
+                         gsr_stream_t stream);
+int gsr_regions_gather(int n_rows, int C, const int* old_of_new, const void* src, void* dst, gsr_stream_t stream);
+int gsr_regions_boundary(int F, int V, const int* faces, const int* counts, const unsigned char* inside, unsigned char* edge_mark,
+                         unsigned char* face_mark, int* err, gsr_stream_t stream);
+int gsr_regions_label_mask(int F, const int* label, const int* count, int min_count, unsigned char* out, gsr_stream_t stream);
+
 /* Tuning aid: when device_buffer is non-NULL (4*T uint64), the two blend kernels record the start/end wall
  * clock (100 MHz) of every workgroup: forward at [2*b], backward at [2*(T+b)], b = launch index.  NULL = off. */
 int gsr_debug_set_trace(void* device_buffer);
