@@ -22,7 +22,10 @@
 // from a scan in voxel order -- every output is a pure function of the inputs and of the order of the views.
 //
 // Floating point follows the numpy restatement in tests/fusion_ref.py operation by operation, so contraction into FMAs is off.
+#include "../../include/gsr.h"
+#include "gsr_entry.h"
 #include "gsr_rig.h"
+#include <string>
 
 #pragma clang fp contract(off)
 
@@ -336,24 +339,7 @@ inline int blocks(size_t n) { return (int)((n + RIG_BLOCK - 1) / RIG_BLOCK); }
 
 inline Dims dims_of(const FusionGrid& g) { return Dims{g.nu[0] * FU, g.nu[1] * FU, g.nu[2] * FU}; }
 
-}  // namespace
-
-size_t fusion_prep_workspace_bytes(int H, int W) { return 2 * RIG_PARTS * sizeof(float) + (size_t)H * W * sizeof(float); }
-
-void launch_fusion_prep(int H, int W, const float* depth_alpha, const float* rgb, int mask_background, int remove_depth_edge,
-                        float depth_trunc, void* workspace, float* depth, unsigned char* rgb8, hipStream_t st)
-{
-    float* parts = static_cast<float*>(workspace);
-    float* depth0 = parts + 2 * RIG_PARTS;
-    const int n = H * W;
-    fusion_depth_kernel<<<blocks(n), RIG_BLOCK, 0, st>>>(n, depth_alpha, depth_alpha + 2 * (size_t)n, mask_background, depth0);
-    if (remove_depth_edge) {
-        fusion_gt_max_kernel<<<RIG_PARTS, RIG_BLOCK, 0, st>>>(n, depth0, parts);
-        fusion_var_max_kernel<<<RIG_PARTS, RIG_BLOCK, 0, st>>>(H, W, depth0, parts);
-    }
-    fusion_prep_kernel<<<blocks(n), RIG_BLOCK, 0, st>>>(H, W, depth0, rgb, remove_depth_edge ? parts : nullptr, depth_trunc, depth, rgb8);
-}
-
+// gsr_fusion_touch: clears the flags, then marks
 hipError_t launch_fusion_touch(int H, int W, const float* depth, const double* cam28, double voxel, double trunc, const int* grid6,
                                unsigned char* touched, hipStream_t st)
 {
@@ -365,30 +351,131 @@ hipError_t launch_fusion_touch(int H, int W, const float* depth, const double* c
     return hipSuccess;
 }
 
-void launch_fusion_integrate(int H, int W, const float* depth, const unsigned char* rgb8, const double* cam28, double voxel,
-                             double trunc, const int* grid6, const unsigned char* touched, float* tsdf, float* weight, float* color,
-                             hipStream_t st)
+// the [host] grid block of the fusion calls: a directory of at least one unit per axis whose voxels can be counted in an int
+const char* fusion_grid_error(const int* grid)
 {
-    const FusionGrid g = fusion_grid(grid6);
-    fusion_integrate_kernel<<<g.nu[0] * g.nu[1] * g.nu[2], RIG_BLOCK, 0, st>>>(H, W, depth, rgb8, fusion_camera(cam28), voxel,
-                                                                                 (float)trunc, g, touched, tsdf, weight, color);
+    if (!grid) return "grid is null";
+    long long units = 1;
+    for (int a = 0; a < 3; ++a) {
+        if (grid[3 + a] <= 0 || grid[3 + a] > (1 << 16)) return "units per axis must be in [1, 65536]";
+        if (grid[a] < -(1 << 24) || grid[a] > (1 << 24)) return "first unit index out of range";
+        units *= grid[3 + a];
+    }
+    return units * 4096 >= (1ll << 31) ? "the volume has 2^31 voxels or more" : nullptr;
 }
 
-void launch_fusion_count(const int* grid6, const float* tsdf, const float* weight, const int* table, unsigned char* edge_mask,
-                         int* vert_count, int* tri_count, hipStream_t st)
+bool fusion_camera_ok(const double* cam)
 {
-    const Dims d = dims_of(fusion_grid(grid6));
-    fusion_count_kernel<<<blocks((size_t)d.nx * d.ny * d.nz), RIG_BLOCK, 0, st>>>(d, tsdf, weight, table, edge_mask, vert_count, tri_count);
+    if (!cam) return false;
+    for (int i = 0; i < 28; ++i)
+        if (!(cam[i] - cam[i] == 0.0)) return false;
+    return cam[24] != 0.0 && cam[25] != 0.0;
 }
 
-void launch_fusion_emit(const int* grid6, double voxel, const float* tsdf, const float* color, const unsigned char* edge_mask,
-                        const int* vert_scan, const int* tri_scan, const int* table, float* verts, int* faces, float* colors,
-                        hipStream_t st)
-{
-    const FusionGrid g = fusion_grid(grid6);
-    const Dims d = dims_of(g);
-    fusion_emit_kernel<<<blocks((size_t)d.nx * d.ny * d.nz), RIG_BLOCK, 0, st>>>(d, g, voxel, tsdf, color, edge_mask, vert_scan, tri_scan,
-                                                                                 table, verts, faces, colors);
-}
+}  // namespace
 
 }  // namespace gsr
+
+// ---------------------------------------------------------------- C entry points (include/gsr.h)
+using namespace gsr;
+
+extern "C" {
+
+size_t gsr_fusion_prep_workspace_bytes(int H, int W)
+{
+    return (H > 0 && W > 0 && (long long)H * W < (1ll << 31)) ? 2 * RIG_PARTS * sizeof(float) + (size_t)H * W * sizeof(float) : 0;
+}
+
+size_t gsr_fusion_volume_bytes(const int* grid)
+{
+    if (fusion_grid_error(grid)) return 0;
+    return (size_t)grid[3] * grid[4] * grid[5] * 4096 * 20;
+}
+
+int gsr_fusion_prep(int H, int W, const float* depth_alpha, const float* rgb, int mask_background, int remove_depth_edge,
+                    float depth_trunc, void* workspace, float* depth, unsigned char* rgb8, gsr_stream_t stream)
+{
+    clear_error();
+    if (H <= 0 || W <= 0) return fail_msg("gsr_fusion_prep: sizes must be positive");
+    if ((long long)H * W >= (1ll << 31)) return fail_msg("gsr_fusion_prep: image too large");
+    if (!depth_alpha || !rgb || !workspace || !depth || !rgb8) return fail_msg("gsr_fusion_prep: required pointer is null");
+    hipStream_t st = (hipStream_t)stream;
+    float* parts = static_cast<float*>(workspace);
+    float* depth0 = parts + 2 * RIG_PARTS;
+    const int n = H * W;
+    fusion_depth_kernel<<<blocks(n), RIG_BLOCK, 0, st>>>(n, depth_alpha, depth_alpha + 2 * (size_t)n, mask_background != 0, depth0);
+    if (remove_depth_edge) {
+        fusion_gt_max_kernel<<<RIG_PARTS, RIG_BLOCK, 0, st>>>(n, depth0, parts);
+        fusion_var_max_kernel<<<RIG_PARTS, RIG_BLOCK, 0, st>>>(H, W, depth0, parts);
+    }
+    fusion_prep_kernel<<<blocks(n), RIG_BLOCK, 0, st>>>(H, W, depth0, rgb, remove_depth_edge ? parts : nullptr, depth_trunc, depth, rgb8);
+    GSR_CHECK_LAUNCH("fusion prep kernels");
+    return 0;
+}
+
+int gsr_fusion_touch(int H, int W, const float* depth, const double* cam, double voxel_size, double sdf_trunc, const int* grid,
+                     unsigned char* touched, gsr_stream_t stream)
+{
+    clear_error();
+    if (H <= 0 || W <= 0) return fail_msg("gsr_fusion_touch: sizes must be positive");
+    if ((long long)H * W >= (1ll << 31)) return fail_msg("gsr_fusion_touch: image too large");
+    if (!(voxel_size > 0.0) || !(sdf_trunc > 0.0)) return fail_msg("gsr_fusion_touch: voxel_size and sdf_trunc must be positive");
+    if (const char* e = fusion_grid_error(grid)) return fail_msg((std::string("gsr_fusion_touch: ") + e).c_str());
+    if (!fusion_camera_ok(cam)) return fail_msg("gsr_fusion_touch: camera is null or not finite");
+    if (!depth || !touched) return fail_msg("gsr_fusion_touch: required pointer is null");
+    GSR_CHECK(launch_fusion_touch(H, W, depth, cam, voxel_size, sdf_trunc, grid, touched, (hipStream_t)stream));
+    GSR_CHECK_LAUNCH("fusion_touch_kernel");
+    return 0;
+}
+
+int gsr_fusion_integrate(int H, int W, const float* depth, const unsigned char* rgb8, const double* cam, double voxel_size,
+                         double sdf_trunc, const int* grid, const unsigned char* touched, float* tsdf, float* weight, float* color,
+                         gsr_stream_t stream)
+{
+    clear_error();
+    if (H <= 0 || W <= 0) return fail_msg("gsr_fusion_integrate: sizes must be positive");
+    if ((long long)H * W >= (1ll << 31)) return fail_msg("gsr_fusion_integrate: image too large");
+    if (!(voxel_size > 0.0) || !(sdf_trunc > 0.0)) return fail_msg("gsr_fusion_integrate: voxel_size and sdf_trunc must be positive");
+    if (const char* e = fusion_grid_error(grid)) return fail_msg((std::string("gsr_fusion_integrate: ") + e).c_str());
+    if (!fusion_camera_ok(cam)) return fail_msg("gsr_fusion_integrate: camera is null or not finite");
+    if (!depth || !rgb8 || !touched || !tsdf || !weight || !color) return fail_msg("gsr_fusion_integrate: required pointer is null");
+    if ((reinterpret_cast<uintptr_t>(tsdf) | reinterpret_cast<uintptr_t>(weight) | reinterpret_cast<uintptr_t>(color)) & 15)
+        return fail_msg("gsr_fusion_integrate: the volume's arrays must be 16-byte aligned");
+    const FusionGrid g = fusion_grid(grid);
+    fusion_integrate_kernel<<<g.nu[0] * g.nu[1] * g.nu[2], RIG_BLOCK, 0, (hipStream_t)stream>>>(
+        H, W, depth, rgb8, fusion_camera(cam), voxel_size, (float)sdf_trunc, g, touched, tsdf, weight, color);
+    GSR_CHECK_LAUNCH("fusion_integrate_kernel");
+    return 0;
+}
+
+int gsr_fusion_count(const int* grid, const float* tsdf, const float* weight, const int* table, unsigned char* edge_mask,
+                     int* vert_count, int* tri_count, gsr_stream_t stream)
+{
+    clear_error();
+    if (const char* e = fusion_grid_error(grid)) return fail_msg((std::string("gsr_fusion_count: ") + e).c_str());
+    if (!tsdf || !weight || !table || !edge_mask || !vert_count || !tri_count) return fail_msg("gsr_fusion_count: required pointer is null");
+    const Dims d = dims_of(fusion_grid(grid));
+    fusion_count_kernel<<<blocks((size_t)d.nx * d.ny * d.nz), RIG_BLOCK, 0, (hipStream_t)stream>>>(d, tsdf, weight, table, edge_mask,
+                                                                                                   vert_count, tri_count);
+    GSR_CHECK_LAUNCH("fusion_count_kernel");
+    return 0;
+}
+
+int gsr_fusion_emit(const int* grid, double voxel_size, const float* tsdf, const float* color, const unsigned char* edge_mask,
+                    const int* vert_scan, const int* tri_scan, const int* table, float* verts, int* faces, float* colors,
+                    gsr_stream_t stream)
+{
+    clear_error();
+    if (const char* e = fusion_grid_error(grid)) return fail_msg((std::string("gsr_fusion_emit: ") + e).c_str());
+    if (!(voxel_size > 0.0)) return fail_msg("gsr_fusion_emit: voxel_size must be positive");
+    // (verts / faces / colors may be null when the scans' totals are zero: nothing is written then)
+    if (!tsdf || !color || !edge_mask || !vert_scan || !tri_scan || !table) return fail_msg("gsr_fusion_emit: required pointer is null");
+    const FusionGrid g = fusion_grid(grid);
+    const Dims d = dims_of(g);
+    fusion_emit_kernel<<<blocks((size_t)d.nx * d.ny * d.nz), RIG_BLOCK, 0, (hipStream_t)stream>>>(
+        d, g, voxel_size, tsdf, color, edge_mask, vert_scan, tri_scan, table, verts, faces, colors);
+    GSR_CHECK_LAUNCH("fusion_emit_kernel");
+    return 0;
+}
+
+}  // extern "C"

@@ -218,21 +218,18 @@ geom_bwd_kernel(int P, int D, int M, int C, const float* __restrict__ means3D, c
     }
 }
 
-void launch_geom_bwd(int P, int D, int M, const float* means3D, const float* shs, const float* scales,
-                     float scale_modifier, const float* rotations, const float* cov3D_precomp, const float* view,
-                     const float* proj, const float* campos, int W, int H, float tan_fovx, float tan_fovy,
-                     const int* radii, GeomState g, int C, const float* grad_acc, float* dL_dmean2D, float* dL_dopacity,
-                     float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale,
-                     float* dL_drot, hipStream_t st)
+void launch_geom_bwd(const ViewArgs& v, GeomState g, int C, const float* grad_acc, float* dL_dmean2D, float* dL_dopacity,
+                     float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
+                     hipStream_t st)
 {
-    const float focal_y = H / (2.0f * tan_fovy), focal_x = W / (2.0f * tan_fovx);   // rasterizer_impl.cu:381-382
-    const size_t lds = shs ? sh_stage_bytes(M, 4) : 0;
-    geom_bwd_kernel<<<(P + 255) / 256, 256, lds, st>>>(P, D, M, C, means3D, shs, scales, scale_modifier, rotations,
-                                                     cov3D_precomp, view, proj, campos, tan_fovx, tan_fovy, focal_x,
-                                                     focal_y, 0.5f * W, 0.5f * H, radii, g.g0, g.g1,
-                                                     reinterpret_cast<const float4*>(grad_acc), dL_dmean2D,
-                                                     dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale,
-                                                     dL_drot);
+    const float focal_y = v.H / (2.0f * v.tan_fovy), focal_x = v.W / (2.0f * v.tan_fovx);   // rasterizer_impl.cu:381-382
+    const size_t lds = v.shs ? sh_stage_bytes(v.M, 4) : 0;
+    geom_bwd_kernel<<<(v.P + 255) / 256, 256, lds, st>>>(v.P, v.D, v.M, C, v.means3D, v.shs, v.scales, v.scale_modifier, v.rotations,
+                                                       v.cov3D_precomp, v.viewmatrix, v.projmatrix, v.campos, v.tan_fovx, v.tan_fovy,
+                                                       focal_x, focal_y, 0.5f * v.W, 0.5f * v.H, v.radii, g.g0, g.g1,
+                                                       reinterpret_cast<const float4*>(grad_acc), dL_dmean2D,
+                                                       dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale,
+                                                       dL_drot);
 }
 
 }  // namespace gsr

@@ -289,148 +289,6 @@ struct PlanRun {             // what the planned kernels get besides the exact p
     uint32_t host_seq;
     uint32_t token;          // this view's token
 };
-void launch_preprocess_planned(int P, int D, int M, const float* means3D, const float* shs, const float* colors_precomp,
-                               const float* opacities, const float* scales, float scale_modifier, const float* rotations,
-                               const float* cov3D_precomp, const float* view, const float* proj, const float* campos, int W,
-                               int H, float tan_fovx, float tan_fovy, int* radii, GeomState g, ImageState im, PlanRun plan,
-                               hipStream_t st);
-void launch_blend_fwd_planned(int C, int W, int H, const float* bg, const float* feats, GeomState g, ImageState im, BinState b,
-                              float* out_color, bool keep_masks, void* zero_ptr, size_t zero_bytes, PlanRun plan, hipStream_t st,
-                              const struct PlanJob* job = nullptr);
-
-// producers of rasterizer inputs (gsr_producers.hip)
-void launch_adam(long long n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float step_size,
-                 float one_minus_b1, float b2, float one_minus_b2, float eps, float bc2s, hipStream_t st);
-void launch_sh_to_rgb(int P, int D, int M, const float* positions, const float* campos, const float* shs, const float* shs_rest,
-                      const float* view, int depth_channels, float* out, const float* densities, float* opacity, hipStream_t st);
-void launch_sh_to_rgb_bwd(int P, int D, int M, const float* positions, const float* campos, const float* shs,
-                          const float* shs_rest, const float* view, int depth_channels, const float* dL_dout, float* dL_dsh,
-                          float* dL_dsh_rest, float* dL_dpos, int accumulate_pos, const float* opacity, const float* dL_dopacity,
-                          float* dL_ddensity, hipStream_t st);
-void launch_zero_f32(float* p, size_t n, hipStream_t st);
-struct AdamTensor { float* param; const float* grad; float* exp_avg; float* exp_avg_sq; long long n; float step_size; unsigned block0; };
-constexpr int ADAM_BATCH = 16;
-struct AdamBatch { AdamTensor t[ADAM_BATCH]; int count; unsigned blocks; };
-void launch_adam_multi(const AdamBatch& b, float one_minus_b1, float b2, float one_minus_b2, float eps, float bc2s, hipStream_t st);
-
-void launch_mesh_gaussians(int F, int G, const float* verts, const long long* faces, const float* bary,
-                           const float* raw_scales, const float* raw_complex, float thickness, float min_scale,
-                           float max_scale, const float* delta_t, const float* delta_r, float* points, float* scaling,
-                           float* quats, float* clear, long long clear_n, hipStream_t st);
-void launch_mesh_gaussians_bwd(int F, int G, const float* verts, const long long* faces, const float* bary,
-                               const float* raw_scales, const float* raw_complex, float min_scale, float max_scale,
-                               const float* delta_r, const float* dL_dpoints, const float* dL_dscaling,
-                               const float* dL_dquats, float* dL_dverts, float* dL_draw_scales, float* dL_draw_complex,
-                               float* dL_ddelta_t, float* dL_ddelta_r, hipStream_t st);
-
-// image-space losses (gsr_loss.hip)
-size_t l1_ssim_workspace_bytes(int C, int H, int W);
-void launch_l1_ssim(int C, int H, int W, const float* pred, const long long* pred_strides, const float* gt,
-                    const long long* gt_strides, float dssim_factor, void* workspace, float* loss_out, float* grad,
-                    const long long* grad_strides, hipStream_t st);
-void launch_l1_ssim_grad(int C, int H, int W, const float* pred, const long long* pred_strides, const float* gt,
-                         const long long* gt_strides, float dssim_factor, const void* workspace, const float* scale, float* grad,
-                         const long long* grad_strides, hipStream_t st);
-size_t depth_l1_workspace_bytes();
-void launch_depth_l1(int H, int W, const float* pred, const long long* pred_strides, const float* gt,
-                     const long long* gt_strides, float max_depth, float depth_factor, float mask_factor,
-                     void* workspace, float* loss_out, float* grad, const long long* grad_strides, hipStream_t st);
-
-void launch_depth_l1_grad(int H, int W, const float* pred, const long long* pred_strides, const float* gt,
-                          const long long* gt_strides, float max_depth, float depth_factor, float mask_factor,
-                          const float* stats, const float* scale, float* grad, const long long* grad_strides, hipStream_t st);
-void launch_rgb_depth_loss(int C, int H, int W, const float* pred, const long long* ps, const float* gt, const long long* gs_, float f,
-                           void* ws_ssim, int Hd, int Wd, const float* dpred, const long long* dps, const float* dgt,
-                           const long long* dgs, float max_depth, float depth_factor, float mask_factor, void* ws_depth,
-                           float* out8, hipStream_t st);
-
-void launch_rgb_depth_loss_grad(int C, int H, int W, const float* pred, const long long* ps, const float* gt, const long long* gs_, float f,
-                                const void* ws_ssim, int Hd, int Wd, const float* dpred, const long long* dps, const float* dgt,
-                                const long long* dgs, float max_depth, float depth_factor, float mask_factor, const float* stats,
-                                const float* scale, float* grad, const long long* gstr, float* dgrad, const long long* dgstr,
-                                hipStream_t st);
-
-// surface-mesh regularisers (gsr_mesh_reg.hip)
-size_t mesh_reg_workspace_bytes();
-void launch_mesh_reg(int F, int E, int Q, const float* verts, const int* faces, const int* edges, const int* pairs,
-                     const float* ref_edge, const float* ref_area, float nc_factor, float edge_factor, float area_factor,
-                     void* workspace, float* loss_out, hipStream_t st);
-void launch_mesh_reg_grad(int V, int F, int E, int Q, const float* verts, const int* faces, const int* edges, const int* pairs,
-                          const int* offsets, const int* entries, const float* ref_edge, const float* ref_area, float nc_factor,
-                          float edge_factor, float area_factor, const float* scale, float* grad, int accumulate, hipStream_t st);
-
-// regularisers on the Gaussians' own parameters (gsr_param_reg.hip)
-size_t param_reg_workspace_bytes();
-void launch_param_reg(int N, int M, const float* delta_t, const float* delta_r, const float* weight, long long w_rs,
-                      long long w_cs, float factor_t, float factor_r, const float* densities, float min_opacity,
-                      const float* sh_dc, const float* pre_sh_dc, float sh_factor, void* workspace, float* loss_out,
-                      hipStream_t st);
-void launch_param_reg_grad(int N, int M, const float* delta_t, const float* delta_r, const float* weight, long long w_rs,
-                           long long w_cs, float factor_t, float factor_r, const float* densities, float min_opacity,
-                           const float* sh_dc, const float* pre_sh_dc, float sh_factor, const float* scale, float* d_delta_t,
-                           float* d_delta_r, float* d_densities, float* d_sh_dc, int accumulate, hipStream_t st);
-
-// rig-wide topology-error detection (gsr_topo.hip)
-size_t topo_view_workspace_bytes();
-void launch_topo_view(int H, int W, int V, const float* verts, const float* gt, const float* render, const float* surface,
-                      float max_depth, const double* cam14, void* workspace, float* row, hipStream_t st);
-void launch_topo_aggregate(int C, int V, const float* table, const float* verts, const float* ymin, double depth_scalar,
-                           int min_observe, int detect_floor, double* value, int* cnt, unsigned char* valid, hipStream_t st);
-void launch_topo_propagate(int V, const int* off, const int* nbr, int sweeps, const double* value_in, const unsigned char* valid_in,
-                           double* value_out, double* value_tmp, unsigned char* valid_a, unsigned char* valid_b, hipStream_t st);
-void launch_topo_voxel_keys(int V, const float* verts, const float* vmin, double voxel_size, long long* keys, int* flags,
-                            hipStream_t st);
-size_t topo_voxel_workspace_bytes(int V);
-void launch_topo_voxel_interp(int V, const float* verts, const float* vmin, double voxel_size, const long long* skeys,
-                              const long long* perm, const long long* vid, const double* value, void* workspace, double* vox_value,
-                              double* out, hipStream_t st);
-void launch_topo_faces(int F, const int* faces, const double* value, unsigned char* colour, float* loss, hipStream_t st);
-
-// scene-flow mesh warping (gsr_warp.hip)
-size_t warp_view_workspace_bytes();
-void launch_warp_normals(int V, int F, const double* verts, const int* faces, const int* vf_off, const int* vf_ent, double* fbuf,
-                         double* normals, hipStream_t st);
-void launch_warp_view(int H, int W, int V, const double* verts, const double* normals, const float* flow_f, const float* flow_b,
-                      const int* flow_shape, const float* depth_cur, const float* depth_next, const double* cam14,
-                      const double* params, void* workspace, double* row, hipStream_t st);
-void launch_warp_aggregate(int C, int V, const double* table, int min_observe, double* move, int* observed, int* count,
-                           unsigned char* valid, hipStream_t st);
-void launch_warp_smooth(int V, const int* off, const int* nbr, int sweeps, const double* in, double* out, double* tmp, hipStream_t st);
-
-// TSDF fusion of the rig's renders and mesh extraction (gsr_fusion.hip)
-size_t fusion_prep_workspace_bytes(int H, int W);
-void launch_fusion_prep(int H, int W, const float* depth_alpha, const float* rgb, int mask_background, int remove_depth_edge,
-                        float depth_trunc, void* workspace, float* depth, unsigned char* rgb8, hipStream_t st);
-hipError_t launch_fusion_touch(int H, int W, const float* depth, const double* cam28, double voxel, double trunc, const int* grid6,
-                               unsigned char* touched, hipStream_t st);
-void launch_fusion_integrate(int H, int W, const float* depth, const unsigned char* rgb8, const double* cam28, double voxel,
-                             double trunc, const int* grid6, const unsigned char* touched, float* tsdf, float* weight, float* color,
-                             hipStream_t st);
-void launch_fusion_count(const int* grid6, const float* tsdf, const float* weight, const int* table, unsigned char* edge_mask,
-                         int* vert_count, int* tri_count, hipStream_t st);
-void launch_fusion_emit(const int* grid6, double voxel, const float* tsdf, const float* color, const unsigned char* edge_mask,
-                        const int* vert_scan, const int* tri_scan, const int* table, float* verts, int* faces, float* colors,
-                        hipStream_t st);
-
-// re-mesh regions at topology errors: edge multiplicity, face components, boxes, cuts (gsr_regions.hip)
-void launch_regions_edge_keys(int F, const int* faces, const unsigned char* mask, const unsigned char* colour, int cut,
-                              unsigned char* sel, long long* keys, int* err, hipStream_t st);
-void launch_regions_edge_runs(int F, const long long* skeys, const long long* order, int* counts, int* pairs, hipStream_t st);
-void launch_regions_components(int F, const int* pairs, const unsigned char* sel, int* parent, int* root_flag, hipStream_t st);
-void launch_regions_labels(int F, const int* parent, const int* scan, const unsigned char* sel, int* label, int* count, hipStream_t st);
-void launch_regions_select(int F, const int* count, int thr, const int* kscan, const int* label, int cap, int* sel_label,
-                           int* sel_count, int* region, hipStream_t st);
-void launch_regions_boxes(int F, int G, int V, const int* faces, const float* verts, const float* points, const int* region, int cap,
-                          unsigned* boxes, int* err, hipStream_t st);
-void launch_regions_inside(int V, const float* verts, const double* box6, unsigned char* inside, hipStream_t st);
-hipError_t launch_regions_cut_mark(int F, int V, const int* faces, const unsigned char* inside, int cut_inner, int* keep, int* ref,
-                                   int* err, hipStream_t st);
-void launch_regions_cut_emit(int F, int V, const int* faces, const int* keep, const int* kscan, const int* ref, const int* vscan,
-                             int* faces_out, unsigned char* face_mask, int* vert_map, int* old_of_new, hipStream_t st);
-void launch_regions_gather(int n_rows, int C, const int* old_of_new, const void* src, void* dst, hipStream_t st);
-hipError_t launch_regions_boundary(int F, int V, const int* faces, const int* counts, const unsigned char* inside, unsigned char* bmark,
-                                   unsigned char* fmark, int* err, hipStream_t st);
-void launch_regions_label_mask(int F, const int* label, const int* count, int min_count, unsigned char* out, hipStream_t st);
 
 // Optional per-workgroup timeline for tuning (gsr_debug_set_trace): when non-null, the blend kernels store
 // {start, end} of every workgroup (100 MHz wall clock) at trace[2*blockIdx] (forward) / trace[2*(T+blockIdx)].
@@ -446,11 +304,29 @@ struct Camera {              // passed by value to kernels (lands in SGPRs / ker
     int W, H;
 };
 
-void launch_preprocess(int P, int D, int M, const float* means3D, const float* shs, const float* colors_precomp,
-                       const float* opacities, const float* scales, float scale_modifier, const float* rotations,
-                       const float* cov3D_precomp, const float* view, const float* proj, const float* campos, int W,
-                       int H, float tan_fovx, float tan_fovy, int* radii, GeomState g, ImageState im, uint32_t view_token,
-                       hipStream_t st);
+// One view's scene and camera inputs, as the C entry points receive them.  The entry points fill it once, by field name; the
+// drivers and launchers below pass it on by reference, and the kernels get the same scalars in the same order as ever.
+struct ViewArgs {
+    int P, D, M;
+    const float* means3D;
+    const float* shs;
+    const float* colors_precomp;
+    const float* opacities;
+    const float* scales;
+    float scale_modifier;
+    const float* rotations;
+    const float* cov3D_precomp;
+    const float* viewmatrix;
+    const float* projmatrix;
+    const float* campos;
+    int W, H;
+    float tan_fovx, tan_fovy;
+    int* radii;              // written by preprocess, read by the backward
+    Tiles tiles() const { return tiles_of(W, H); }
+};
+
+void launch_preprocess(const ViewArgs& v, GeomState g, ImageState im, uint32_t view_token, hipStream_t st);
+void launch_preprocess_planned(const ViewArgs& v, GeomState g, ImageState im, PlanRun plan, hipStream_t st);
 void launch_tile_scan(ImageState im, int T, uint32_t* host_totals, uint32_t host_seq, uint32_t view_token, hipStream_t st);
 void launch_scatter(int P, int W, int H, int R, uint32_t max_count, GeomState g, ImageState im, BinState b, hipStream_t st);
 // the same launch before the host knows R, U and max_count (gsr_forward_fused): the kernel carves `binning_base` itself from
@@ -469,17 +345,18 @@ inline int front_of_order(int R, int T)
     return (int)(bound < (long long)T ? bound : (long long)T);
 }
 struct PlanJob;   // gsr_plan.h
+void launch_blend_fwd_planned(int C, int W, int H, const float* bg, const float* feats, GeomState g, ImageState im, BinState b,
+                              float* out_color, bool keep_masks, void* zero_ptr, size_t zero_bytes, PlanRun plan, hipStream_t st,
+                              const PlanJob* job = nullptr);
 void launch_blend_fwd(int C, int W, int H, int R, int U, uint32_t max_count, const float* bg, const float* feats, GeomState g, ImageState im,
                       BinState b, float* out_color, bool keep_masks, void* zero_ptr, size_t zero_bytes, uint32_t* counters,
                       bool sort_small, hipStream_t st, const PlanJob* job = nullptr, bool* job_rides = nullptr, int num_parts = -1);
 void launch_blend_bwd(int C, int W, int H, int U, const float* bg, const float* feats, GeomState g, ImageState im, BinState b,
                       const float* dL_dpix, float* grad_acc, hipStream_t st);
-void launch_geom_bwd(int P, int D, int M, const float* means3D, const float* shs, const float* scales,
-                     float scale_modifier, const float* rotations, const float* cov3D_precomp, const float* view,
-                     const float* proj, const float* campos, int W, int H, float tan_fovx, float tan_fovy,
-                     const int* radii, GeomState g, int C, const float* grad_acc, float* dL_dmean2D, float* dL_dopacity,
-                     float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale,
-                     float* dL_drot, hipStream_t st);
+// (v.opacities and v.colors_precomp are not read; v.scales / v.rotations are null under v.cov3D_precomp)
+void launch_geom_bwd(const ViewArgs& v, GeomState g, int C, const float* grad_acc, float* dL_dmean2D, float* dL_dopacity,
+                     float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
+                     hipStream_t st);
 void launch_mark_visible(int P, const float* means3D, const float* view, uint8_t* present, hipStream_t st);
 void preprocess_occupancy(int* exact, int* planned);   // tuning: resident workgroups per CU of the two preprocess kernels
 

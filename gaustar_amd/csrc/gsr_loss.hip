@@ -14,6 +14,8 @@
 //   pass 2  the adjoint of the window (the window is symmetric): dS_sum/dx(p) = (w*D1)(p) + 2 x(p) (w*D2)(p) + y(p) (w*D3)(p)
 //           and dL/dx = (1-f)/N sign(x-y) - f/N dS_sum/dx, written in the planar [C,H,W] layout the backward blend reads.
 // Partial sums are reduced in a fixed order in double: the loss value is deterministic.
+#include "../../include/gsr.h"
+#include "gsr_entry.h"
 #include "gsr_internal.h"
 
 namespace gsr {
@@ -505,7 +507,7 @@ ssim_grad_kernel(int H, int W, View x, View y, const float* __restrict__ D, floa
     }
 }
 
-size_t l1_ssim_workspace_bytes(int C, int H, int W)
+static size_t l1_ssim_workspace_bytes(int C, int H, int W)
 {
     const size_t n = (size_t)C * H * W;
     const size_t n_wg = (size_t)C * ((H + LTY - 1) / LTY) * ((W + LT - 1) / LT);
@@ -539,8 +541,8 @@ static int launch_ssim_stats(int C, int H, int W, const float* pred, const long 
 }
 
 // pass 2 alone, from the D maps pass 1 left in `workspace`
-void launch_l1_ssim_grad(int C, int H, int W, const float* pred, const long long* ps, const float* gt, const long long* gs_,
-                         float f, const void* workspace, const float* scale, float* grad, const long long* gstr, hipStream_t st)
+static void launch_l1_ssim_grad(int C, int H, int W, const float* pred, const long long* ps, const float* gt, const long long* gs_,
+                                float f, const void* workspace, const float* scale, float* grad, const long long* gstr, hipStream_t st)
 {
     const size_t n = (size_t)C * H * W;
     const dim3 grid((W + LT - 1) / LT, (H + LTY - 1) / LTY, C);
@@ -551,8 +553,8 @@ void launch_l1_ssim_grad(int C, int H, int W, const float* pred, const long long
     else ssim_grad_kernel<false><<<grid, 256, 0, st>>>(H, W, x, y, static_cast<const float*>(workspace), (1.f - f) / (float)n, f / (float)n, scale, g, C, DepthPlane{});
 }
 
-void launch_l1_ssim(int C, int H, int W, const float* pred, const long long* ps, const float* gt, const long long* gs_,
-                    float f, void* workspace, float* loss_out, float* grad, const long long* gstr, hipStream_t st)
+static void launch_l1_ssim(int C, int H, int W, const float* pred, const long long* ps, const float* gt, const long long* gs_,
+                           float f, void* workspace, float* loss_out, float* grad, const long long* gstr, hipStream_t st)
 {
     const size_t n = (size_t)C * H * W;
     const float* partials = reinterpret_cast<const float*>(static_cast<char*>(workspace) + align_up(3 * n * sizeof(float)));
@@ -624,20 +626,20 @@ depth_grad_kernel(int H, int W, const float* __restrict__ pred, long long psy, l
     grad[yy * qsy + xx * qsx] = depth_grad_value(p, g, max_depth, cf, cb);
 }
 
-size_t depth_l1_workspace_bytes() { return align_up(4 * DEPTH_WGS * sizeof(float)) + 256; }
+static size_t depth_l1_workspace_bytes() { return align_up(4 * DEPTH_WGS * sizeof(float)) + 256; }
 
-void launch_depth_l1_grad(int H, int W, const float* pred, const long long* ps, const float* gt, const long long* gs_,
-                          float max_depth, float depth_factor, float mask_factor, const float* stats, const float* scale,
-                          float* grad, const long long* gstr, hipStream_t st)
+static void launch_depth_l1_grad(int H, int W, const float* pred, const long long* ps, const float* gt, const long long* gs_,
+                                 float max_depth, float depth_factor, float mask_factor, const float* stats, const float* scale,
+                                 float* grad, const long long* gstr, hipStream_t st)
 {
     depth_grad_kernel<<<dim3((unsigned)((W + 255) / 256), (unsigned)H), 256, 0, st>>>(H, W, pred, ps[0], ps[1], gt, gs_[0], gs_[1],
                                                                   max_depth, depth_factor, mask_factor, stats, scale,
                                                                   grad, gstr[0], gstr[1]);
 }
 
-void launch_depth_l1(int H, int W, const float* pred, const long long* ps, const float* gt, const long long* gs_,
-                     float max_depth, float depth_factor, float mask_factor, void* workspace, float* loss_out,
-                     float* grad, const long long* gstr, hipStream_t st)
+static void launch_depth_l1(int H, int W, const float* pred, const long long* ps, const float* gt, const long long* gs_,
+                            float max_depth, float depth_factor, float mask_factor, void* workspace, float* loss_out,
+                            float* grad, const long long* gstr, hipStream_t st)
 {
     const int n_wg = H < DEPTH_WGS ? H : DEPTH_WGS;   // workgroups walk whole rows
     float* partials = static_cast<float*>(workspace);
@@ -698,10 +700,10 @@ rgb_depth_finalize_kernel(int n_wg, const float* __restrict__ partials, double i
     }
 }
 
-void launch_rgb_depth_loss(int C, int H, int W, const float* pred, const long long* ps, const float* gt, const long long* gs_, float f,
-                           void* ws_ssim, int Hd, int Wd, const float* dpred, const long long* dps, const float* dgt,
-                           const long long* dgs, float max_depth, float depth_factor, float mask_factor, void* ws_depth,
-                           float* out8, hipStream_t st)
+static void launch_rgb_depth_loss(int C, int H, int W, const float* pred, const long long* ps, const float* gt, const long long* gs_, float f,
+                                  void* ws_ssim, int Hd, int Wd, const float* dpred, const long long* dps, const float* dgt,
+                                  const long long* dgs, float max_depth, float depth_factor, float mask_factor, void* ws_depth,
+                                  float* out8, hipStream_t st)
 {
     const size_t n = (size_t)C * H * W;
     const float* partials = reinterpret_cast<const float*>(static_cast<char*>(ws_ssim) + align_up(3 * n * sizeof(float)));
@@ -715,11 +717,11 @@ void launch_rgb_depth_loss(int C, int H, int W, const float* pred, const long lo
 }
 
 // both gradient passes in ONE launch (the depth image as one more z-plane of the SSIM gradient kernel)
-void launch_rgb_depth_loss_grad(int C, int H, int W, const float* pred, const long long* ps, const float* gt, const long long* gs_, float f,
-                                const void* ws_ssim, int Hd, int Wd, const float* dpred, const long long* dps, const float* dgt,
-                                const long long* dgs, float max_depth, float depth_factor, float mask_factor, const float* stats,
-                                const float* scale, float* grad, const long long* gstr, float* dgrad, const long long* dgstr,
-                                hipStream_t st)
+static void launch_rgb_depth_loss_grad(int C, int H, int W, const float* pred, const long long* ps, const float* gt, const long long* gs_, float f,
+                                       const void* ws_ssim, int Hd, int Wd, const float* dpred, const long long* dps, const float* dgt,
+                                       const long long* dgs, float max_depth, float depth_factor, float mask_factor, const float* stats,
+                                       const float* scale, float* grad, const long long* gstr, float* dgrad, const long long* dgstr,
+                                       hipStream_t st)
 {
     const size_t n = (size_t)C * H * W;
     const dim3 grid((W + LT - 1) / LT, (H + LTY - 1) / LTY, C + 1);
@@ -735,3 +737,140 @@ void launch_rgb_depth_loss_grad(int C, int H, int W, const float* pred, const lo
 }
 
 }  // namespace gsr
+
+// ---------------------------------------------------------------- C entry points (include/gsr.h)
+using namespace gsr;
+
+extern "C" {
+
+size_t gsr_l1_ssim_workspace_bytes(int C, int H, int W)
+{
+    return l1_ssim_workspace_bytes(C > 0 ? C : 0, H > 0 ? H : 0, W > 0 ? W : 0);
+}
+
+int gsr_l1_ssim(int C, int H, int W, const float* pred, long long pred_sc, long long pred_sy, long long pred_sx,
+                const float* gt, long long gt_sc, long long gt_sy, long long gt_sx, float dssim_factor,
+                void* workspace, float* loss_out, float* dL_dpred, long long grad_sc, long long grad_sy,
+                long long grad_sx, gsr_stream_t stream)
+{
+    clear_error();
+    if (C <= 0 || H <= 0 || W <= 0) return fail_msg("gsr_l1_ssim: image size must be positive");
+    if (C > 65535) return fail_msg("gsr_l1_ssim: too many channels");
+    if (!pred || !gt || !workspace || !loss_out) return fail_msg("gsr_l1_ssim: required pointer is null");
+    const long long ps[3] = {pred_sc, pred_sy, pred_sx}, gs_[3] = {gt_sc, gt_sy, gt_sx},
+                    qs[3] = {grad_sc, grad_sy, grad_sx};
+    hipStream_t st = (hipStream_t)stream;
+    {
+        Scope sc(ST_LOSS, st);
+        launch_l1_ssim(C, H, W, pred, ps, gt, gs_, dssim_factor, workspace, loss_out, dL_dpred, qs, st);
+    }
+    GSR_CHECK_LAUNCH("l1_ssim kernels");
+    return 0;
+}
+
+size_t gsr_depth_l1_workspace_bytes(void) { return depth_l1_workspace_bytes(); }
+
+int gsr_depth_l1(int H, int W, const float* pred, long long pred_sy, long long pred_sx, const float* gt,
+                 long long gt_sy, long long gt_sx, float max_depth, float depth_factor, float mask_factor,
+                 void* workspace, float* loss_out, float* dL_dpred, long long grad_sy, long long grad_sx,
+                 gsr_stream_t stream)
+{
+    clear_error();
+    if (H <= 0 || W <= 0) return fail_msg("gsr_depth_l1: image size must be positive");
+    if (!pred || !gt || !workspace || !loss_out) return fail_msg("gsr_depth_l1: required pointer is null");
+    const long long ps[2] = {pred_sy, pred_sx}, gs_[2] = {gt_sy, gt_sx}, qs[2] = {grad_sy, grad_sx};
+    hipStream_t st = (hipStream_t)stream;
+    {
+        Scope sc(ST_LOSS, st);
+        launch_depth_l1(H, W, pred, ps, gt, gs_, max_depth, depth_factor, mask_factor, workspace, loss_out, dL_dpred, qs, st);
+    }
+    GSR_CHECK_LAUNCH("depth_l1 kernels");
+    return 0;
+}
+
+int gsr_l1_ssim_backward(int C, int H, int W, const float* pred, long long pred_sc, long long pred_sy, long long pred_sx,
+                         const float* gt, long long gt_sc, long long gt_sy, long long gt_sx, float dssim_factor,
+                         const void* workspace, const float* grad_scale, float* dL_dpred, long long grad_sc, long long grad_sy,
+                         long long grad_sx, gsr_stream_t stream)
+{
+    clear_error();
+    if (C <= 0 || H <= 0 || W <= 0) return fail_msg("gsr_l1_ssim_backward: image size must be positive");
+    if (C > 65535) return fail_msg("gsr_l1_ssim_backward: too many channels");
+    if (!pred || !gt || !workspace || !dL_dpred) return fail_msg("gsr_l1_ssim_backward: required pointer is null");
+    const long long ps[3] = {pred_sc, pred_sy, pred_sx}, gs_[3] = {gt_sc, gt_sy, gt_sx}, qs[3] = {grad_sc, grad_sy, grad_sx};
+    hipStream_t st = (hipStream_t)stream;
+    {
+        Scope sc(ST_LOSS, st);
+        launch_l1_ssim_grad(C, H, W, pred, ps, gt, gs_, dssim_factor, workspace, grad_scale, dL_dpred, qs, st);
+    }
+    GSR_CHECK_LAUNCH("ssim_grad_kernel");
+    return 0;
+}
+
+int gsr_depth_l1_backward(int H, int W, const float* pred, long long pred_sy, long long pred_sx, const float* gt,
+                          long long gt_sy, long long gt_sx, float max_depth, float depth_factor, float mask_factor,
+                          const float* stats, const float* grad_scale, float* dL_dpred, long long grad_sy, long long grad_sx,
+                          gsr_stream_t stream)
+{
+    clear_error();
+    if (H <= 0 || W <= 0) return fail_msg("gsr_depth_l1_backward: image size must be positive");
+    if (!pred || !gt || !stats || !dL_dpred) return fail_msg("gsr_depth_l1_backward: required pointer is null");
+    const long long ps[2] = {pred_sy, pred_sx}, gs_[2] = {gt_sy, gt_sx}, qs[2] = {grad_sy, grad_sx};
+    hipStream_t st = (hipStream_t)stream;
+    {
+        Scope sc(ST_LOSS, st);
+        launch_depth_l1_grad(H, W, pred, ps, gt, gs_, max_depth, depth_factor, mask_factor, stats, grad_scale, dL_dpred, qs, st);
+    }
+    GSR_CHECK_LAUNCH("depth_grad_kernel");
+    return 0;
+}
+
+int gsr_rgb_depth_loss(int C, int H, int W, const float* pred, long long pred_sc, long long pred_sy, long long pred_sx,
+                       const float* gt, long long gt_sc, long long gt_sy, long long gt_sx, float dssim_factor,
+                       void* ssim_workspace, int Hd, int Wd, const float* depth_pred, long long dpred_sy, long long dpred_sx,
+                       const float* depth_gt, long long dgt_sy, long long dgt_sx, float max_depth, float depth_factor,
+                       float mask_factor, void* depth_workspace, float* loss_out, gsr_stream_t stream)
+{
+    clear_error();
+    if (C <= 0 || H <= 0 || W <= 0 || Hd <= 0 || Wd <= 0) return fail_msg("gsr_rgb_depth_loss: image size must be positive");
+    if (C > 65534) return fail_msg("gsr_rgb_depth_loss: too many channels");
+    if (!pred || !gt || !ssim_workspace || !depth_pred || !depth_gt || !depth_workspace || !loss_out)
+        return fail_msg("gsr_rgb_depth_loss: required pointer is null");
+    const long long ps[3] = {pred_sc, pred_sy, pred_sx}, gs_[3] = {gt_sc, gt_sy, gt_sx};
+    const long long dps[2] = {dpred_sy, dpred_sx}, dgs[2] = {dgt_sy, dgt_sx};
+    hipStream_t st = (hipStream_t)stream;
+    {
+        Scope sc(ST_LOSS, st);
+        launch_rgb_depth_loss(C, H, W, pred, ps, gt, gs_, dssim_factor, ssim_workspace, Hd, Wd, depth_pred, dps, depth_gt, dgs,
+                              max_depth, depth_factor, mask_factor, depth_workspace, loss_out, st);
+    }
+    GSR_CHECK_LAUNCH("rgb_depth_loss kernels");
+    return 0;
+}
+
+int gsr_rgb_depth_loss_backward(int C, int H, int W, const float* pred, long long pred_sc, long long pred_sy, long long pred_sx,
+                                const float* gt, long long gt_sc, long long gt_sy, long long gt_sx, float dssim_factor,
+                                const void* ssim_workspace, int Hd, int Wd, const float* depth_pred, long long dpred_sy,
+                                long long dpred_sx, const float* depth_gt, long long dgt_sy, long long dgt_sx, float max_depth,
+                                float depth_factor, float mask_factor, const float* loss_out, const float* grad_scale,
+                                float* dL_dpred, long long grad_sc, long long grad_sy, long long grad_sx, float* dL_ddepth,
+                                long long dgrad_sy, long long dgrad_sx, gsr_stream_t stream)
+{
+    clear_error();
+    if (C <= 0 || H <= 0 || W <= 0 || Hd <= 0 || Wd <= 0) return fail_msg("gsr_rgb_depth_loss_backward: image size must be positive");
+    if (C > 65534) return fail_msg("gsr_rgb_depth_loss_backward: too many channels");
+    if (!pred || !gt || !ssim_workspace || !depth_pred || !depth_gt || !loss_out || !dL_dpred || !dL_ddepth)
+        return fail_msg("gsr_rgb_depth_loss_backward: required pointer is null");
+    const long long ps[3] = {pred_sc, pred_sy, pred_sx}, gs_[3] = {gt_sc, gt_sy, gt_sx}, qs[3] = {grad_sc, grad_sy, grad_sx};
+    const long long dps[2] = {dpred_sy, dpred_sx}, dgs[2] = {dgt_sy, dgt_sx}, dqs[2] = {dgrad_sy, dgrad_sx};
+    hipStream_t st = (hipStream_t)stream;
+    {
+        Scope sc(ST_LOSS, st);
+        launch_rgb_depth_loss_grad(C, H, W, pred, ps, gt, gs_, dssim_factor, ssim_workspace, Hd, Wd, depth_pred, dps, depth_gt, dgs,
+                                   max_depth, depth_factor, mask_factor, loss_out + 3, grad_scale, dL_dpred, qs, dL_ddepth, dqs, st);
+    }
+    GSR_CHECK_LAUNCH("rgb_depth_loss gradient kernel");
+    return 0;
+}
+
+}  // extern "C"

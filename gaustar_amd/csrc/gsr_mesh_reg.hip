@@ -20,7 +20,10 @@
 // with torch's cosine_similarity: x / max(|x|, eps) . y / max(|y|, eps), whose gradient through the norm is x / |x| (0 at
 // x = 0) even where the clamp is active.  Edge: |v0 - v1|, gradient 0 at length 0.  Face area: 0.5 |(v1 - v0) x (v2 - v0)|
 // with torch's d|c|/dc = 0 at c = 0 and d|x|/dx = 0 at x = 0: a degenerate face contributes no area gradient.
+#include "../../include/gsr.h"
+#include "gsr_entry.h"
 #include "gsr_reduce.h"
+#include <cstdio>
 
 namespace gsr {
 
@@ -211,29 +214,80 @@ int fwd_workgroups(int F, int E, int Q)
     return (int)(wg < RED_MAX_WGS ? wg : RED_MAX_WGS);
 }
 
+int mesh_reg_check(const char* fn, int V, int F, int E, int Q, const float* verts, const int* faces, const int* edges,
+                   const int* pairs)
+{
+    char msg[160];
+    if (V < 0 || F < 0 || E < 0 || Q < 0) { snprintf(msg, sizeof msg, "%s: negative size", fn); return fail_msg(msg); }
+    if ((long long)Q + E + F >= (1ll << 29)) { snprintf(msg, sizeof msg, "%s: mesh too large", fn); return fail_msg(msg); }
+    if (F > 0 && (V <= 0 || !verts || !faces || !edges || (Q > 0 && !pairs))) {
+        snprintf(msg, sizeof msg, "%s: required pointer is null", fn);
+        return fail_msg(msg);
+    }
+    if ((reinterpret_cast<uintptr_t>(pairs) & 15) || (reinterpret_cast<uintptr_t>(edges) & 7)) {
+        snprintf(msg, sizeof msg, "%s: pairs must be 16-byte and edges 8-byte aligned", fn);
+        return fail_msg(msg);
+    }
+    return 0;
+}
+
 }  // namespace
 
-size_t mesh_reg_workspace_bytes() { return reduce_workspace_bytes(); }
-
-void launch_mesh_reg(int F, int E, int Q, const float* verts, const int* faces, const int* edges, const int* pairs,
-                     const float* ref_edge, const float* ref_area, float nc_factor, float edge_factor, float area_factor,
-                     void* workspace, float* loss_out, hipStream_t st)
-{
-    const MeshRegArgs m = make_args(F, E, Q, verts, faces, edges, pairs, ref_edge, ref_area, nc_factor, edge_factor, area_factor);
-    double* partials = static_cast<double*>(workspace);
-    const int n_wg = fwd_workgroups(F, E, Q);
-    if (n_wg > 0) mesh_reg_fwd_kernel<<<n_wg, RED_BLOCK, 0, st>>>(m, partials);
-    mesh_reg_finalize_kernel<<<1, RED_BLOCK, 0, st>>>(n_wg, partials, Q, E, F, nc_factor, edge_factor, area_factor, m.use_nc,
-                                                     m.use_edge, m.use_area, loss_out);
-}
-
-void launch_mesh_reg_grad(int V, int F, int E, int Q, const float* verts, const int* faces, const int* edges, const int* pairs,
-                          const int* offsets, const int* entries, const float* ref_edge, const float* ref_area, float nc_factor,
-                          float edge_factor, float area_factor, const float* scale, float* grad, int accumulate, hipStream_t st)
-{
-    const MeshRegArgs m = make_args(F, E, Q, verts, faces, edges, pairs, ref_edge, ref_area, nc_factor, edge_factor, area_factor);
-    const int n_wg = (V + MR_VPB - 1) / MR_VPB;
-    mesh_reg_bwd_kernel<<<n_wg, MR_BLOCK, 0, st>>>(m, V, offsets, entries, scale, grad, accumulate);
-}
-
 }  // namespace gsr
+
+// ---------------------------------------------------------------- C entry points (include/gsr.h)
+using namespace gsr;
+
+extern "C" {
+
+size_t gsr_mesh_reg_workspace_bytes(int V, int F, int E, int Q)
+{
+    (void)V; (void)F; (void)E; (void)Q;   // (the partials of at most 2048 workgroups, whatever the mesh)
+    return reduce_workspace_bytes();
+}
+
+int gsr_mesh_reg_forward(int V, int F, int E, int Q, const float* verts, const int* faces, const int* edges, const int* pairs,
+                         const float* ref_edge_len, const float* ref_area, float nc_factor, float edge_factor, float area_factor,
+                         void* workspace, float* loss_out, gsr_stream_t stream)
+{
+    clear_error();
+    if (int rc = mesh_reg_check("gsr_mesh_reg_forward", V, F, E, Q, verts, faces, edges, pairs)) return rc;
+    if (!workspace || !loss_out) return fail_msg("gsr_mesh_reg_forward: required pointer is null");
+    if (F == 0) E = Q = 0;
+    hipStream_t st = (hipStream_t)stream;
+    {
+        Scope sc(ST_LOSS, st);
+        const MeshRegArgs m = make_args(F, E, Q, verts, faces, edges, pairs, ref_edge_len, ref_area, nc_factor, edge_factor, area_factor);
+        double* partials = static_cast<double*>(workspace);
+        const int n_wg = fwd_workgroups(F, E, Q);
+        if (n_wg > 0) mesh_reg_fwd_kernel<<<n_wg, RED_BLOCK, 0, st>>>(m, partials);
+        mesh_reg_finalize_kernel<<<1, RED_BLOCK, 0, st>>>(n_wg, partials, Q, E, F, nc_factor, edge_factor, area_factor, m.use_nc,
+                                                         m.use_edge, m.use_area, loss_out);
+    }
+    GSR_CHECK_LAUNCH("mesh_reg forward kernels");
+    return 0;
+}
+
+int gsr_mesh_reg_backward(int V, int F, int E, int Q, const float* verts, const int* faces, const int* edges, const int* pairs,
+                          const int* csr_offsets, const int* csr_entries, const float* ref_edge_len, const float* ref_area,
+                          float nc_factor, float edge_factor, float area_factor, const float* grad_scale, float* dL_dverts,
+                          int accumulate, gsr_stream_t stream)
+{
+    clear_error();
+    if (int rc = mesh_reg_check("gsr_mesh_reg_backward", V, F, E, Q, verts, faces, edges, pairs)) return rc;
+    if (accumulate != 0 && accumulate != 1) return fail_msg("gsr_mesh_reg_backward: accumulate must be 0 or 1");
+    if (V == 0) return 0;
+    if (!csr_offsets || !csr_entries || !dL_dverts) return fail_msg("gsr_mesh_reg_backward: required pointer is null");
+    if (F == 0) E = Q = 0;
+    hipStream_t st = (hipStream_t)stream;
+    {
+        Scope sc(ST_LOSS, st);
+        const MeshRegArgs m = make_args(F, E, Q, verts, faces, edges, pairs, ref_edge_len, ref_area, nc_factor, edge_factor, area_factor);
+        mesh_reg_bwd_kernel<<<(V + MR_VPB - 1) / MR_VPB, MR_BLOCK, 0, st>>>(m, V, csr_offsets, csr_entries, grad_scale, dL_dverts,
+                                                                          accumulate);
+    }
+    GSR_CHECK_LAUNCH("mesh_reg_bwd_kernel");
+    return 0;
+}
+
+}  // extern "C"

@@ -9,9 +9,17 @@
 //     m += (g - m) (1 - beta1)                      exp_avg.lerp_(grad, 1 - beta1)
 //     v  = v beta2 + g g (1 - beta2)                exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value = 1 - beta2)
 //     p -= step_size * m / (sqrt(v) / bc2s + eps)   step_size = lr / (1 - beta1^t), bc2s = sqrt(1 - beta2^t)
+#include "../../include/gsr.h"
+#include "gsr_entry.h"
 #include "gsr_internal.h"
+#include <cmath>
 
 namespace gsr {
+
+// the tensor table of one adam_multi_kernel launch (a kernel argument)
+struct AdamTensor { float* param; const float* grad; float* exp_avg; float* exp_avg_sq; long long n; float step_size; unsigned block0; };
+constexpr int ADAM_BATCH = 16;
+struct AdamBatch { AdamTensor t[ADAM_BATCH]; int count; unsigned blocks; };
 
 __device__ __forceinline__ void adam_update(float& p, float g, float& m, float& v, float step_size, float one_minus_b1,
                                             float b2, float one_minus_b2, float eps, float bc2s)
@@ -83,22 +91,81 @@ adam_multi_kernel(AdamBatch b, float one_minus_b1, float b2, float one_minus_b2,
                     eps, bc2s);
 }
 
-void launch_adam_multi(const AdamBatch& b, float one_minus_b1, float b2, float one_minus_b2, float eps, float bc2s, hipStream_t st)
-{
-    adam_multi_kernel<<<b.blocks, 256, 0, st>>>(b, one_minus_b1, b2, one_minus_b2, eps, bc2s);
-}
-
-void launch_adam(long long n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float step_size,
-                 float one_minus_b1, float b2, float one_minus_b2, float eps, float bc2s, hipStream_t st)
-{
-    // one 16-byte element per thread up to 256 k workgroups (grid caps between 2 k and 16 k workgroups all measured
-    // slower or no faster: 5.3 - 6.1 TB/s, run-to-run spread included)
-    const long long n4 = n >> 2;
-    long long blocks = (n4 + 255) / 256;
-    if (blocks < 1) blocks = 1;
-    if (blocks > 256 * 1024) blocks = 256 * 1024;
-    adam_kernel<<<(unsigned)blocks, 256, 0, st>>>(n, param, grad, exp_avg, exp_avg_sq, step_size, one_minus_b1, b2, one_minus_b2,
-                                                  eps, bc2s);
-}
-
 }  // namespace gsr
+
+// ---------------------------------------------------------------- C entry points (include/gsr.h)
+using namespace gsr;
+
+extern "C" {
+
+int gsr_adam_step_multi(int count, const long long* numel, float* const* params, const float* const* grads,
+                        float* const* exp_avgs, float* const* exp_avg_sqs, const double* lrs, double beta1, double beta2,
+                        double eps, int step, gsr_stream_t stream)
+{
+    clear_error();
+    if (count <= 0) return 0;
+    if (!numel || !params || !grads || !exp_avgs || !exp_avg_sqs || !lrs) return fail_msg("gsr_adam_step_multi: required pointer is null");
+    if (step < 1) return fail_msg("gsr_adam_step_multi: step counts from 1");
+    for (int i = 0; i < count; i++) {
+        if (numel[i] <= 0) continue;
+        if (!params[i] || !grads[i] || !exp_avgs[i] || !exp_avg_sqs[i]) return fail_msg("gsr_adam_step_multi: a tensor pointer is null");
+        if (((uintptr_t)params[i] | (uintptr_t)grads[i] | (uintptr_t)exp_avgs[i] | (uintptr_t)exp_avg_sqs[i]) & 15u)
+            return fail_msg("gsr_adam_step_multi: arrays must be 16-byte aligned");
+    }
+    const double bc1 = 1.0 - std::pow(beta1, (double)step), bc2 = 1.0 - std::pow(beta2, (double)step);
+    hipStream_t st = (hipStream_t)stream;
+    {
+        Scope sc(ST_OPTIM, st);
+        AdamBatch b;
+        b.count = 0; b.blocks = 0;
+        const auto flush = [&]() {
+            if (b.count)
+                adam_multi_kernel<<<b.blocks, 256, 0, st>>>(b, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps,
+                                                            (float)std::sqrt(bc2));
+            b.count = 0; b.blocks = 0;
+        };
+        for (int i = 0; i < count; i++) {
+            if (numel[i] <= 0) continue;
+            // one 16-byte element per thread, 256 threads per workgroup (as gsr_adam_step); a launch takes up to 16 tensors
+            const long long want = ((numel[i] >> 2) + 255) / 256;
+            const unsigned nb = (unsigned)(want < 1 ? 1 : (want > 256 * 1024 ? 256 * 1024 : want));
+            if (b.count == ADAM_BATCH || (unsigned long long)b.blocks + nb > 0x7fffffffull) flush();
+            AdamTensor& t = b.t[b.count++];
+            t.param = params[i]; t.grad = grads[i]; t.exp_avg = exp_avgs[i]; t.exp_avg_sq = exp_avg_sqs[i];
+            t.n = numel[i]; t.step_size = (float)(lrs[i] / bc1); t.block0 = b.blocks;
+            b.blocks += nb;
+        }
+        flush();
+    }
+    GSR_CHECK_LAUNCH("adam_multi_kernel");
+    return 0;
+}
+
+int gsr_adam_step(long long n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, double lr, double beta1,
+                  double beta2, double eps, int step, gsr_stream_t stream)
+{
+    clear_error();
+    if (n <= 0) return 0;
+    if (!param || !grad || !exp_avg || !exp_avg_sq) return fail_msg("gsr_adam_step: required pointer is null");
+    if (step < 1) return fail_msg("gsr_adam_step: step counts from 1");
+    if (((uintptr_t)param | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15u)
+        return fail_msg("gsr_adam_step: arrays must be 16-byte aligned");
+    // bias corrections in double, as torch/optim/adam.py computes them in Python floats
+    const double bc1 = 1.0 - std::pow(beta1, (double)step), bc2 = 1.0 - std::pow(beta2, (double)step);
+    hipStream_t st = (hipStream_t)stream;
+    {
+        Scope sc(ST_OPTIM, st);
+        // one 16-byte element per thread up to 256 k workgroups (grid caps between 2 k and 16 k workgroups all measured
+        // slower or no faster: 5.3 - 6.1 TB/s, run-to-run spread included)
+        const long long n4 = n >> 2;
+        long long blocks = (n4 + 255) / 256;
+        if (blocks < 1) blocks = 1;
+        if (blocks > 256 * 1024) blocks = 256 * 1024;
+        adam_kernel<<<(unsigned)blocks, 256, 0, st>>>(n, param, grad, exp_avg, exp_avg_sq, (float)(lr / bc1), (float)(1.0 - beta1),
+                                                      (float)beta2, (float)(1.0 - beta2), (float)eps, (float)std::sqrt(bc2));
+    }
+    GSR_CHECK_LAUNCH("adam_kernel");
+    return 0;
+}
+
+}  // extern "C"

@@ -12,7 +12,10 @@
 //   backward  elementwise; no float atomics anywhere: two calls give identical bits.
 // Gradients at the kinks follow torch: d|x|/dx = 0 at 0 (delta_t starts at exactly 0), relu'(0) = 0; delta_r[:, 0] and the
 // sh_dc rows at or beyond M get exactly 0.
+#include "../../include/gsr.h"
+#include "gsr_entry.h"
 #include "gsr_reduce.h"
+#include <cstdio>
 
 namespace gsr {
 
@@ -255,43 +258,90 @@ int n_workgroups(int N)
     return (int)(wg < RED_MAX_WGS ? wg : RED_MAX_WGS);
 }
 
-}  // namespace
-
-size_t param_reg_workspace_bytes() { return reduce_workspace_bytes(); }
-
-void launch_param_reg(int N, int M, const float* delta_t, const float* delta_r, const float* weight, long long w_rs,
-                      long long w_cs, float factor_t, float factor_r, const float* densities, float min_opacity,
-                      const float* sh_dc, const float* pre_sh_dc, float sh_factor, void* workspace, float* loss_out,
-                      hipStream_t st)
-{
-    const ParamRegArgs a = make_args(N, M, delta_t, delta_r, weight, w_rs, w_cs, factor_t, factor_r, densities, min_opacity,
-                                     sh_dc, pre_sh_dc, sh_factor);
-    double* partials = static_cast<double*>(workspace);
-    const int n_wg = (a.use_t || a.use_r || a.use_o || a.use_sh) ? n_workgroups(N) : 0;
-    if (n_wg > 0) param_reg_fwd_kernel<<<n_wg, PR_BLOCK, 0, st>>>(a, partials);
-    param_reg_finalize_kernel<<<1, PR_BLOCK, 0, st>>>(n_wg, partials, a, factor_t, factor_r, sh_factor, loss_out);
-}
-
-void launch_param_reg_grad(int N, int M, const float* delta_t, const float* delta_r, const float* weight, long long w_rs,
-                           long long w_cs, float factor_t, float factor_r, const float* densities, float min_opacity,
-                           const float* sh_dc, const float* pre_sh_dc, float sh_factor, const float* scale, float* d_delta_t,
+// gsr_param_reg_backward's launch: a skipped term touches no gradient buffer
+void launch_param_reg_grad(ParamRegArgs a, float factor_t, float factor_r, float sh_factor, const float* scale, float* d_delta_t,
                            float* d_delta_r, float* d_densities, float* d_sh_dc, int accumulate, hipStream_t st)
 {
-    ParamRegArgs a = make_args(N, M, delta_t, delta_r, weight, w_rs, w_cs, factor_t, factor_r, densities, min_opacity, sh_dc,
-                               pre_sh_dc, sh_factor);
     ParamRegGrads o{};
-    // a skipped term touches no gradient buffer
     o.d_t = a.use_t ? d_delta_t : nullptr;
     o.d_r = a.use_r ? d_delta_r : nullptr;
     o.d_dens = a.use_o ? d_densities : nullptr;
     o.d_sh = a.use_sh ? d_sh_dc : nullptr;
     if (!o.d_t && !o.d_r && !o.d_dens && !o.d_sh) return;
     a.vec = a.vec && aligned16(o.d_t) && aligned16(o.d_r) && aligned16(o.d_dens) && aligned16(o.d_sh);
-    o.ct = a.use_t ? (float)((double)factor_t / (3.0 * (double)N)) : 0.f;
-    o.cr = a.use_r ? (float)((double)factor_r / (3.0 * (double)N)) : 0.f;
-    o.co = a.use_o ? (float)(1.0 / (double)N) : 0.f;
-    o.csh = a.use_sh ? (float)(2.0 * (double)sh_factor / (3.0 * (double)M)) : 0.f;
-    param_reg_bwd_kernel<<<n_workgroups(N), PR_BLOCK, 0, st>>>(a, o, scale, accumulate);
+    o.ct = a.use_t ? (float)((double)factor_t / (3.0 * (double)a.N)) : 0.f;
+    o.cr = a.use_r ? (float)((double)factor_r / (3.0 * (double)a.N)) : 0.f;
+    o.co = a.use_o ? (float)(1.0 / (double)a.N) : 0.f;
+    o.csh = a.use_sh ? (float)(2.0 * (double)sh_factor / (3.0 * (double)a.M)) : 0.f;
+    param_reg_bwd_kernel<<<n_workgroups(a.N), PR_BLOCK, 0, st>>>(a, o, scale, accumulate);
 }
 
+int param_reg_check(const char* fn, int N, int M, const float* weight, long long w_rs, long long w_cs)
+{
+    char msg[160];
+    if (N < 0 || M < 0 || M > N) { snprintf(msg, sizeof msg, "%s: need 0 <= M <= N", fn); return fail_msg(msg); }
+    if (N >= (1 << 29)) { snprintf(msg, sizeof msg, "%s: too many Gaussians", fn); return fail_msg(msg); }
+    if (weight && (w_rs < 0 || w_cs < 0)) { snprintf(msg, sizeof msg, "%s: negative weight stride", fn); return fail_msg(msg); }
+    return 0;
+}
+
+}  // namespace
+
 }  // namespace gsr
+
+// ---------------------------------------------------------------- C entry points (include/gsr.h)
+using namespace gsr;
+
+extern "C" {
+
+size_t gsr_param_reg_workspace_bytes(int N)
+{
+    (void)N;   // (the partials of at most 2048 workgroups, whatever the model)
+    return reduce_workspace_bytes();
+}
+
+int gsr_param_reg_forward(int N, int M, const float* delta_t, const float* delta_r, const float* weight, long long w_row_stride,
+                          long long w_col_stride, float factor_t, float factor_r, const float* densities, float min_opacity,
+                          const float* sh_dc, const float* pre_sh_dc, float sh_factor, void* workspace, float* loss_out,
+                          gsr_stream_t stream)
+{
+    clear_error();
+    if (int rc = param_reg_check("gsr_param_reg_forward", N, M, weight, w_row_stride, w_col_stride)) return rc;
+    if (!workspace || !loss_out) return fail_msg("gsr_param_reg_forward: required pointer is null");
+    hipStream_t st = (hipStream_t)stream;
+    {
+        Scope sc(ST_LOSS, st);
+        const ParamRegArgs a = make_args(N, M, delta_t, delta_r, weight, w_row_stride, w_col_stride, factor_t, factor_r, densities,
+                                         min_opacity, sh_dc, pre_sh_dc, sh_factor);
+        double* partials = static_cast<double*>(workspace);
+        const int n_wg = (a.use_t || a.use_r || a.use_o || a.use_sh) ? n_workgroups(N) : 0;
+        if (n_wg > 0) param_reg_fwd_kernel<<<n_wg, PR_BLOCK, 0, st>>>(a, partials);
+        param_reg_finalize_kernel<<<1, PR_BLOCK, 0, st>>>(n_wg, partials, a, factor_t, factor_r, sh_factor, loss_out);
+    }
+    GSR_CHECK_LAUNCH("param_reg forward kernels");
+    return 0;
+}
+
+int gsr_param_reg_backward(int N, int M, const float* delta_t, const float* delta_r, const float* weight, long long w_row_stride,
+                           long long w_col_stride, float factor_t, float factor_r, const float* densities, float min_opacity,
+                           const float* sh_dc, const float* pre_sh_dc, float sh_factor, const float* grad_scale,
+                           float* dL_ddelta_t, float* dL_ddelta_r, float* dL_ddensities, float* dL_dsh_dc, int accumulate,
+                           gsr_stream_t stream)
+{
+    clear_error();
+    if (int rc = param_reg_check("gsr_param_reg_backward", N, M, weight, w_row_stride, w_col_stride)) return rc;
+    if (accumulate != 0 && accumulate != 1) return fail_msg("gsr_param_reg_backward: accumulate must be 0 or 1");
+    if (N == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    {
+        Scope sc(ST_LOSS, st);
+        launch_param_reg_grad(make_args(N, M, delta_t, delta_r, weight, w_row_stride, w_col_stride, factor_t, factor_r, densities,
+                                        min_opacity, sh_dc, pre_sh_dc, sh_factor),
+                              factor_t, factor_r, sh_factor, grad_scale, dL_ddelta_t, dL_ddelta_r, dL_ddensities, dL_dsh_dc, accumulate,
+                              st);
+    }
+    GSR_CHECK_LAUNCH("param_reg_bwd_kernel");
+    return 0;
+}
+
+}  // extern "C"

@@ -277,36 +277,28 @@ preprocess_kernel(int P, int D, int M, const float* __restrict__ means3D, const 
     }
 }
 
-void launch_preprocess(int P, int D, int M, const float* means3D, const float* shs, const float* colors_precomp,
-                       const float* opacities, const float* scales, float scale_modifier, const float* rotations,
-                       const float* cov3D_precomp, const float* view, const float* proj, const float* campos, int W,
-                       int H, float tan_fovx, float tan_fovy, int* radii, GeomState g, ImageState im, uint32_t view_token,
-                       hipStream_t st)
+void launch_preprocess(const ViewArgs& v, GeomState g, ImageState im, uint32_t view_token, hipStream_t st)
 {
-    const Tiles t = tiles_of(W, H);
-    const float focal_y = H / (2.0f * tan_fovy), focal_x = W / (2.0f * tan_fovx);   // rasterizer_impl.cu:222-223
-    const size_t lds = colors_precomp ? 0 : sh_stage_bytes(M, 4);
-    preprocess_kernel<false><<<(P + 255) / 256, 256, lds, st>>>(P, D, M, means3D, shs, colors_precomp, opacities, scales,
-                                                       scale_modifier, rotations, cov3D_precomp, view, proj, campos, W,
-                                                       H, tan_fovx, tan_fovy, focal_x, focal_y, t.gx, t.gy, radii,
-                                                       g.g0, g.g1, g.depth, g.rect, g.rgb, im.tile_count, g.wg_recs, g.wg_tab,
-                                                       g.wg_nrec, im.totals, view_token, PlanRun{});
+    const Tiles t = v.tiles();
+    const float focal_y = v.H / (2.0f * v.tan_fovy), focal_x = v.W / (2.0f * v.tan_fovx);   // rasterizer_impl.cu:222-223
+    const size_t lds = v.colors_precomp ? 0 : sh_stage_bytes(v.M, 4);
+    preprocess_kernel<false><<<(v.P + 255) / 256, 256, lds, st>>>(v.P, v.D, v.M, v.means3D, v.shs, v.colors_precomp, v.opacities, v.scales,
+                                                         v.scale_modifier, v.rotations, v.cov3D_precomp, v.viewmatrix, v.projmatrix,
+                                                         v.campos, v.W, v.H, v.tan_fovx, v.tan_fovy, focal_x, focal_y, t.gx, t.gy,
+                                                         v.radii, g.g0, g.g1, g.depth, g.rect, g.rgb, im.tile_count, g.wg_recs,
+                                                         g.wg_tab, g.wg_nrec, im.totals, view_token, PlanRun{});
 }
 
-void launch_preprocess_planned(int P, int D, int M, const float* means3D, const float* shs, const float* colors_precomp,
-                               const float* opacities, const float* scales, float scale_modifier, const float* rotations,
-                               const float* cov3D_precomp, const float* view, const float* proj, const float* campos, int W,
-                               int H, float tan_fovx, float tan_fovy, int* radii, GeomState g, ImageState im, PlanRun plan,
-                               hipStream_t st)
+void launch_preprocess_planned(const ViewArgs& v, GeomState g, ImageState im, PlanRun plan, hipStream_t st)
 {
-    const Tiles t = tiles_of(W, H);
-    const float focal_y = H / (2.0f * tan_fovy), focal_x = W / (2.0f * tan_fovx);
-    const size_t lds = colors_precomp ? 0 : sh_stage_bytes(M, 4);
-    preprocess_kernel<true><<<(P + 255) / 256, 256, lds, st>>>(P, D, M, means3D, shs, colors_precomp, opacities, scales,
-                                                      scale_modifier, rotations, cov3D_precomp, view, proj, campos, W,
-                                                      H, tan_fovx, tan_fovy, focal_x, focal_y, t.gx, t.gy, radii,
-                                                      g.g0, g.g1, g.depth, g.rect, g.rgb, im.tile_count, g.wg_recs, g.wg_tab,
-                                                      g.wg_nrec, im.totals, plan.token, plan);
+    const Tiles t = v.tiles();
+    const float focal_y = v.H / (2.0f * v.tan_fovy), focal_x = v.W / (2.0f * v.tan_fovx);
+    const size_t lds = v.colors_precomp ? 0 : sh_stage_bytes(v.M, 4);
+    preprocess_kernel<true><<<(v.P + 255) / 256, 256, lds, st>>>(v.P, v.D, v.M, v.means3D, v.shs, v.colors_precomp, v.opacities, v.scales,
+                                                        v.scale_modifier, v.rotations, v.cov3D_precomp, v.viewmatrix, v.projmatrix,
+                                                        v.campos, v.W, v.H, v.tan_fovx, v.tan_fovy, focal_x, focal_y, t.gx, t.gy,
+                                                        v.radii, g.g0, g.g1, g.depth, g.rect, g.rgb, im.tile_count, g.wg_recs,
+                                                        g.wg_tab, g.wg_nrec, im.totals, plan.token, plan);
 }
 
 // (tuning: resident workgroups per CU the runtime computes for the two preprocess kernels)

@@ -8,6 +8,8 @@
 // DGR/cuda_rasterizer/forward.cu:20-71 / backward.cu:20-139), so the two kernels below share sh_basis() and
 // sh_colour_backward() with gsr_preprocess.hip / gsr_geom_bwd.hip.  One thread per point; sh is [P, M, 3]
 // (the reference's sh_coordinates layout), only the first (D+1)^2 coefficients are used.
+#include "../../include/gsr.h"
+#include "gsr_entry.h"
 #include "gsr_internal.h"
 #include "gsr_sort.h"   // lane_xor_u32: DPP / ds_swizzle lane exchanges
 
@@ -496,42 +498,6 @@ mesh_gaussians_bwd8_kernel(int F, int G, const float* __restrict__ verts, const 
     }
 }
 
-void launch_mesh_gaussians(int F, int G, const float* verts, const long long* faces, const float* bary,
-                           const float* raw_scales, const float* raw_complex, float thickness, float min_scale,
-                           float max_scale, const float* delta_t, const float* delta_r, float* points, float* scaling,
-                           float* quats, float* clear, long long clear_n, hipStream_t st)
-{
-    if (G <= LPF) {
-        const long long lanes = (long long)F * LPF;
-        mesh_gaussians_fwd8_kernel<<<(unsigned)((lanes + 255) / 256), 256, 0, st>>>(F, G, verts, faces, bary, raw_scales, raw_complex,
-                                                                                    thickness, min_scale, max_scale, delta_t, delta_r,
-                                                                                    points, scaling, quats, clear, clear_n);
-        return;
-    }
-    mesh_gaussians_fwd_kernel<<<(F + 127) / 128, 128, 0, st>>>(F, G, verts, faces, bary, raw_scales, raw_complex, thickness,
-                                                              min_scale, max_scale, delta_t, delta_r, points, scaling, quats, clear,
-                                                              clear_n);
-}
-
-void launch_mesh_gaussians_bwd(int F, int G, const float* verts, const long long* faces, const float* bary,
-                               const float* raw_scales, const float* raw_complex, float min_scale, float max_scale,
-                               const float* delta_r, const float* dL_dpoints, const float* dL_dscaling,
-                               const float* dL_dquats, float* dL_dverts, float* dL_draw_scales, float* dL_draw_complex,
-                               float* dL_ddelta_t, float* dL_ddelta_r, hipStream_t st)
-{
-    if (G <= LPF) {
-        const long long lanes = (long long)F * LPF;
-        mesh_gaussians_bwd8_kernel<<<(unsigned)((lanes + MBB - 1) / MBB), MBB, 0, st>>>(F, G, verts, faces, bary, raw_scales, raw_complex,
-                                                                                    min_scale, max_scale, delta_r, dL_dpoints, dL_dscaling,
-                                                                                    dL_dquats, dL_dverts, dL_draw_scales, dL_draw_complex,
-                                                                                    dL_ddelta_t, dL_ddelta_r);
-        return;
-    }
-    mesh_gaussians_bwd_kernel<<<(F + 127) / 128, 128, 0, st>>>(F, G, verts, faces, bary, raw_scales, raw_complex, min_scale,
-                                                              max_scale, delta_r, dL_dpoints, dL_dscaling, dL_dquats, dL_dverts,
-                                                              dL_draw_scales, dL_draw_complex, dL_ddelta_t, dL_ddelta_r);
-}
-
 // Zero fill of a small array (the vertex-gradient accumulator in front of the mesh producer's backward): hipMemsetAsync of
 // 0.5 MB goes out as TWO runtime kernels (aligned body + remainder), 10 us on the stream for what one launch does in 2.
 __global__ void __launch_bounds__(256) zero_f32_kernel(float* __restrict__ p, size_t n)
@@ -543,7 +509,7 @@ __global__ void __launch_bounds__(256) zero_f32_kernel(float* __restrict__ p, si
     if (t < n) p[t] = 0.f;
 }
 
-void launch_zero_f32(float* p, size_t n, hipStream_t st)
+static void launch_zero_f32(float* p, size_t n, hipStream_t st)
 {
     if (n == 0) return;
     if (((uintptr_t)p & 15u) != 0) { (void)hipMemsetAsync(p, 0, n * sizeof(float), st); return; }
@@ -559,18 +525,19 @@ static void sh_lds_limit(const void* fn, size_t bytes)
     if (bytes > 64 * 1024) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
 
-void launch_sh_to_rgb(int P, int D, int M, const float* positions, const float* campos, const float* shs, const float* shs_rest,
-                      const float* view, int depth_channels, float* out, const float* densities, float* opacity, hipStream_t st)
+static void launch_sh_to_rgb(int P, int D, int M, const float* positions, const float* campos, const float* shs,
+                             const float* shs_rest, const float* view, int depth_channels, float* out, const float* densities,
+                             float* opacity, hipStream_t st)
 {
     sh_lds_limit(reinterpret_cast<const void*>(&sh_to_rgb_kernel), sh_stage_bytes(M, 4));
     sh_to_rgb_kernel<<<(P + 255) / 256, 256, sh_stage_bytes(M, 4), st>>>(P, D, M, positions, campos, shs, shs_rest, view, out,
                                                                           view ? 3 + depth_channels : 3, densities, opacity);
 }
 
-void launch_sh_to_rgb_bwd(int P, int D, int M, const float* positions, const float* campos, const float* shs,
-                          const float* shs_rest, const float* view, int depth_channels, const float* dL_dout, float* dL_dsh,
-                          float* dL_dsh_rest, float* dL_dpos, int accumulate_pos, const float* opacity, const float* dL_dopacity,
-                          float* dL_ddensity, hipStream_t st)
+static void launch_sh_to_rgb_bwd(int P, int D, int M, const float* positions, const float* campos, const float* shs,
+                                 const float* shs_rest, const float* view, int depth_channels, const float* dL_dout, float* dL_dsh,
+                                 float* dL_dsh_rest, float* dL_dpos, int accumulate_pos, const float* opacity,
+                                 const float* dL_dopacity, float* dL_ddensity, hipStream_t st)
 {
     sh_lds_limit(reinterpret_cast<const void*>(&sh_to_rgb_bwd_kernel), sh_stage_bytes(M, 4));
     sh_to_rgb_bwd_kernel<<<(P + 255) / 256, 256, sh_stage_bytes(M, 4), st>>>(
@@ -579,3 +546,198 @@ void launch_sh_to_rgb_bwd(int P, int D, int M, const float* positions, const flo
 }
 
 }  // namespace gsr
+
+// ---------------------------------------------------------------- C entry points (include/gsr.h)
+using namespace gsr;
+
+extern "C" {
+
+int gsr_sh_to_rgb(int P, int D, int M, const float* positions, const float* campos, const float* shs, float* rgb,
+                  gsr_stream_t stream)
+{
+    clear_error();
+    if (P <= 0) return 0;
+    if (!positions || !campos || !shs || !rgb) return fail_msg("gsr_sh_to_rgb: required pointer is null");
+    if (D < 0 || D > 4 || (D + 1) * (D + 1) > M) return fail_msg("gsr_sh_to_rgb: sh degree must be 0..4 and fit in M coefficients");
+    hipStream_t st = (hipStream_t)stream;
+    {
+        Scope sc(ST_PRODUCERS, st);
+        launch_sh_to_rgb(P, D, M, positions, campos, shs, nullptr, nullptr, 0, rgb, nullptr, nullptr, st);
+    }
+    GSR_CHECK_LAUNCH("sh_to_rgb_kernel");
+    return 0;
+}
+
+int gsr_sh_to_rgb_backward(int P, int D, int M, const float* positions, const float* campos, const float* shs,
+                           const float* dL_drgb, float* dL_dsh, float* dL_dpos, gsr_stream_t stream)
+{
+    clear_error();
+    if (P <= 0) return 0;
+    if (!positions || !campos || !shs || !dL_drgb || !dL_dsh || !dL_dpos)
+        return fail_msg("gsr_sh_to_rgb_backward: required pointer is null");
+    if (D < 0 || D > 4 || (D + 1) * (D + 1) > M)
+        return fail_msg("gsr_sh_to_rgb_backward: sh degree must be 0..4 and fit in M coefficients");
+    hipStream_t st = (hipStream_t)stream;
+    {
+        Scope sc(ST_PRODUCERS, st);
+        launch_sh_to_rgb_bwd(P, D, M, positions, campos, shs, nullptr, nullptr, 0, dL_drgb, dL_dsh, nullptr, dL_dpos, 0, nullptr, nullptr, nullptr, st);
+    }
+    GSR_CHECK_LAUNCH("sh_to_rgb_bwd_kernel");
+    return 0;
+}
+
+int gsr_sh_to_rgbd(int P, int D, int M, const float* positions, const float* campos, const float* shs,
+                   const float* viewmatrix, int depth_channels, float* colors6, gsr_stream_t stream)
+{
+    clear_error();
+    if (depth_channels != 1 && depth_channels != 3) return fail_msg("gsr_sh_to_rgbd: depth_channels must be 1 or 3");
+    if (P <= 0) return 0;
+    if (!positions || !campos || !shs || !viewmatrix || !colors6) return fail_msg("gsr_sh_to_rgbd: required pointer is null");
+    if (D < 0 || D > 4 || (D + 1) * (D + 1) > M) return fail_msg("gsr_sh_to_rgbd: sh degree must be 0..4 and fit in M coefficients");
+    hipStream_t st = (hipStream_t)stream;
+    {
+        Scope sc(ST_PRODUCERS, st);
+        launch_sh_to_rgb(P, D, M, positions, campos, shs, nullptr, viewmatrix, depth_channels, colors6, nullptr, nullptr, st);
+    }
+    GSR_CHECK_LAUNCH("sh_to_rgb_kernel");
+    return 0;
+}
+
+int gsr_sh_to_rgbd_backward(int P, int D, int M, const float* positions, const float* campos, const float* shs,
+                            const float* viewmatrix, int depth_channels, const float* dL_dcolors6, float* dL_dsh,
+                            float* dL_dpos, gsr_stream_t stream)
+{
+    clear_error();
+    if (depth_channels != 1 && depth_channels != 3) return fail_msg("gsr_sh_to_rgbd_backward: depth_channels must be 1 or 3");
+    if (P <= 0) return 0;
+    if (!positions || !campos || !shs || !viewmatrix || !dL_dcolors6 || !dL_dsh || !dL_dpos)
+        return fail_msg("gsr_sh_to_rgbd_backward: required pointer is null");
+    if (D < 0 || D > 4 || (D + 1) * (D + 1) > M)
+        return fail_msg("gsr_sh_to_rgbd_backward: sh degree must be 0..4 and fit in M coefficients");
+    hipStream_t st = (hipStream_t)stream;
+    {
+        Scope sc(ST_PRODUCERS, st);
+        launch_sh_to_rgb_bwd(P, D, M, positions, campos, shs, nullptr, viewmatrix, depth_channels, dL_dcolors6, dL_dsh, nullptr, dL_dpos, 0, nullptr, nullptr, nullptr, st);
+    }
+    GSR_CHECK_LAUNCH("sh_to_rgb_bwd_kernel");
+    return 0;
+}
+
+int gsr_sh_colors_split(int P, int D, int M, const float* positions, const float* campos, const float* sh_dc,
+                        const float* sh_rest, const float* viewmatrix, int depth_channels, const float* densities,
+                        float* colors, float* opacity, gsr_stream_t stream)
+{
+    clear_error();
+    if (viewmatrix ? (depth_channels != 1 && depth_channels != 3) : depth_channels != 0)
+        return fail_msg("gsr_sh_colors_split: depth_channels must be 1 or 3 with a view matrix, 0 without");
+    if (P <= 0) return 0;
+    if (!positions || !campos || !sh_dc || !colors || (M > 1 && !sh_rest)) return fail_msg("gsr_sh_colors_split: required pointer is null");
+    if ((densities == nullptr) != (opacity == nullptr)) return fail_msg("gsr_sh_colors_split: densities and opacity go together");
+    if (D < 0 || D > 4 || (D + 1) * (D + 1) > M) return fail_msg("gsr_sh_colors_split: sh degree must be 0..4 and fit in M coefficients");
+    hipStream_t st = (hipStream_t)stream;
+    {
+        Scope sc(ST_PRODUCERS, st);
+        // (M == 1: the one-array layout IS the dc array)
+        launch_sh_to_rgb(P, D, M, positions, campos, sh_dc, M > 1 ? sh_rest : nullptr, viewmatrix, depth_channels, colors, densities,
+                         opacity, st);
+    }
+    GSR_CHECK_LAUNCH("sh_to_rgb_kernel");
+    return 0;
+}
+
+int gsr_sh_colors_split_backward(int P, int D, int M, const float* positions, const float* campos, const float* sh_dc,
+                                 const float* sh_rest, const float* viewmatrix, int depth_channels, const float* dL_dcolors,
+                                 const float* opacity, const float* dL_dopacity, float* dL_dsh_dc, float* dL_dsh_rest,
+                                 float* dL_dpos, int accumulate_pos, float* dL_ddensities, gsr_stream_t stream)
+{
+    clear_error();
+    if (viewmatrix ? (depth_channels != 1 && depth_channels != 3) : depth_channels != 0)
+        return fail_msg("gsr_sh_colors_split_backward: depth_channels must be 1 or 3 with a view matrix, 0 without");
+    if (P <= 0) return 0;
+    if (!positions || !campos || !sh_dc || !dL_dcolors || !dL_dsh_dc || !dL_dpos || (M > 1 && (!sh_rest || !dL_dsh_rest)))
+        return fail_msg("gsr_sh_colors_split_backward: required pointer is null");
+    if ((opacity == nullptr) != (dL_dopacity == nullptr) || (opacity == nullptr) != (dL_ddensities == nullptr))
+        return fail_msg("gsr_sh_colors_split_backward: opacity, dL_dopacity and dL_ddensities go together");
+    if (D < 0 || D > 4 || (D + 1) * (D + 1) > M)
+        return fail_msg("gsr_sh_colors_split_backward: sh degree must be 0..4 and fit in M coefficients");
+    hipStream_t st = (hipStream_t)stream;
+    {
+        Scope sc(ST_PRODUCERS, st);
+        launch_sh_to_rgb_bwd(P, D, M, positions, campos, sh_dc, M > 1 ? sh_rest : nullptr, viewmatrix, depth_channels, dL_dcolors,
+                             dL_dsh_dc, M > 1 ? dL_dsh_rest : nullptr, dL_dpos, accumulate_pos ? 1 : 0, opacity, dL_dopacity,
+                             dL_ddensities, st);
+    }
+    GSR_CHECK_LAUNCH("sh_to_rgb_bwd_kernel");
+    return 0;
+}
+
+int gsr_mesh_gaussians(int F, int G, const float* verts, const long long* faces, const float* bary,
+                       const float* raw_scales, const float* raw_complex, float thickness, float min_scale,
+                       float max_scale, const float* delta_t, const float* delta_r, float* points, float* scaling,
+                       float* quaternions, float* clear_dL_dverts, int V, gsr_stream_t stream)
+{
+    clear_error();
+    if (V < 0) return fail_msg("gsr_mesh_gaussians: negative V");
+    const long long clear_n = clear_dL_dverts ? 3ll * V : 0ll;
+    if (F <= 0) {
+        if (clear_n > 0) launch_zero_f32(clear_dL_dverts, (size_t)clear_n, (hipStream_t)stream);
+        return 0;
+    }
+    if (G <= 0 || G > 64) return fail_msg("gsr_mesh_gaussians: Gaussians per face must be 1..64");
+    if (!verts || !faces || !bary || !raw_scales || !raw_complex || !points || !scaling || !quaternions)
+        return fail_msg("gsr_mesh_gaussians: required pointer is null");
+    hipStream_t st = (hipStream_t)stream;
+    {
+        Scope sc(ST_PRODUCERS, st);
+        if (G <= LPF) {
+            const long long lanes = (long long)F * LPF;
+            mesh_gaussians_fwd8_kernel<<<(unsigned)((lanes + 255) / 256), 256, 0, st>>>(
+                F, G, verts, faces, bary, raw_scales, raw_complex, thickness, min_scale, max_scale, delta_t, delta_r, points, scaling,
+                quaternions, clear_dL_dverts, clear_n);
+        } else {
+            mesh_gaussians_fwd_kernel<<<(F + 127) / 128, 128, 0, st>>>(F, G, verts, faces, bary, raw_scales, raw_complex, thickness,
+                                                                      min_scale, max_scale, delta_t, delta_r, points, scaling,
+                                                                      quaternions, clear_dL_dverts, clear_n);
+        }
+    }
+    GSR_CHECK_LAUNCH("mesh_gaussians_fwd_kernel");
+    return 0;
+}
+
+int gsr_mesh_gaussians_backward(int F, int G, int V, const float* verts, const long long* faces, const float* bary,
+                                const float* raw_scales, const float* raw_complex, float min_scale, float max_scale,
+                                const float* delta_r, const float* dL_dpoints, const float* dL_dscaling,
+                                const float* dL_dquaternions, float* dL_dverts, float* dL_draw_scales,
+                                float* dL_draw_complex, float* dL_ddelta_t, float* dL_ddelta_r, int dL_dverts_cleared,
+                                gsr_stream_t stream)
+{
+    clear_error();
+    if (V < 0) return fail_msg("gsr_mesh_gaussians_backward: negative V");
+    if (V > 0 && !dL_dverts) return fail_msg("gsr_mesh_gaussians_backward: dL_dverts is null");
+    hipStream_t st = (hipStream_t)stream;
+    if (V > 0 && !dL_dverts_cleared) launch_zero_f32(dL_dverts, 3 * (size_t)V, st);
+    if (F <= 0) return 0;
+    if (G <= 0 || G > 64) return fail_msg("gsr_mesh_gaussians_backward: Gaussians per face must be 1..64");
+    if (!verts || !faces || !bary || !raw_scales || !raw_complex || !dL_draw_scales || !dL_draw_complex)
+        return fail_msg("gsr_mesh_gaussians_backward: required pointer is null");
+    if (delta_r == nullptr && dL_ddelta_r != nullptr)
+        return fail_msg("gsr_mesh_gaussians_backward: dL_ddelta_r given without delta_r");
+    {
+        Scope sc(ST_PRODUCERS, st);
+        if (G <= LPF) {
+            const long long lanes = (long long)F * LPF;
+            mesh_gaussians_bwd8_kernel<<<(unsigned)((lanes + MBB - 1) / MBB), MBB, 0, st>>>(
+                F, G, verts, faces, bary, raw_scales, raw_complex, min_scale, max_scale, delta_r, dL_dpoints, dL_dscaling,
+                dL_dquaternions, dL_dverts, dL_draw_scales, dL_draw_complex, dL_ddelta_t, dL_ddelta_r);
+        } else {
+            mesh_gaussians_bwd_kernel<<<(F + 127) / 128, 128, 0, st>>>(F, G, verts, faces, bary, raw_scales, raw_complex, min_scale,
+                                                                      max_scale, delta_r, dL_dpoints, dL_dscaling, dL_dquaternions,
+                                                                      dL_dverts, dL_draw_scales, dL_draw_complex, dL_ddelta_t,
+                                                                      dL_ddelta_r);
+        }
+    }
+    GSR_CHECK_LAUNCH("mesh_gaussians_bwd_kernel");
+    return 0;
+}
+
+}  // extern "C"

@@ -23,6 +23,8 @@
 //
 // Workgroups on different XCDs hook concurrently: every read of `parent` inside a find is an agent-scope atomic load, every
 // write an agent-scope atomic store or compare-and-swap.
+#include "../../include/gsr.h"
+#include "gsr_entry.h"
 #include "gsr_internal.h"
 
 namespace gsr {
@@ -400,51 +402,7 @@ __global__ void __launch_bounds__(RG_BLOCK) regions_label_mask_kernel(int F, con
 
 inline unsigned blocks(long long n) { return (unsigned)((n + RG_BLOCK - 1) / RG_BLOCK); }
 
-}  // namespace
-
-void launch_regions_edge_keys(int F, const int* faces, const unsigned char* mask, const unsigned char* colour, int cut,
-                              unsigned char* sel, long long* keys, int* err, hipStream_t st)
-{
-    regions_edge_key_kernel<<<blocks(F), RG_BLOCK, 0, st>>>(F, faces, mask, colour, cut, sel, keys, err);
-}
-
-void launch_regions_edge_runs(int F, const long long* skeys, const long long* order, int* counts, int* pairs, hipStream_t st)
-{
-    regions_edge_run_kernel<<<blocks(3ll * F), RG_BLOCK, 0, st>>>(3 * F, skeys, order, counts, reinterpret_cast<int2*>(pairs));
-}
-
-void launch_regions_components(int F, const int* pairs, const unsigned char* sel, int* parent, int* root_flag, hipStream_t st)
-{
-    regions_uf_init_kernel<<<blocks(F), RG_BLOCK, 0, st>>>(F, parent);
-    regions_uf_hook_kernel<<<blocks(3ll * F), RG_BLOCK, 0, st>>>(3 * F, reinterpret_cast<const int2*>(pairs), parent);
-    regions_uf_flatten_kernel<<<blocks(F), RG_BLOCK, 0, st>>>(F, sel, parent, root_flag);
-}
-
-void launch_regions_labels(int F, const int* parent, const int* scan, const unsigned char* sel, int* label, int* count, hipStream_t st)
-{
-    regions_label_kernel<<<blocks(F), RG_BLOCK, 0, st>>>(F, parent, scan, sel, label, count);
-}
-
-void launch_regions_select(int F, const int* count, int thr, const int* kscan, const int* label, int cap, int* sel_label,
-                           int* sel_count, int* region, hipStream_t st)
-{
-    regions_select_kernel<<<blocks(F), RG_BLOCK, 0, st>>>(F, count, thr, kscan, label, cap, sel_label, sel_count, region);
-}
-
-void launch_regions_boxes(int F, int G, int V, const int* faces, const float* verts, const float* points, const int* region, int cap,
-                          unsigned* boxes, int* err, hipStream_t st)
-{
-    if (cap > 0) regions_box_init_kernel<<<blocks(6ll * cap), RG_BLOCK, 0, st>>>(6 * cap, boxes);
-    if (cap > 0 && F > 0) regions_box_kernel<<<blocks(F), RG_BLOCK, 0, st>>>(F, G, V, faces, verts, points, region, cap, boxes, err);
-}
-
-void launch_regions_inside(int V, const float* verts, const double* box6, unsigned char* inside, hipStream_t st)
-{
-    RegionBox b;
-    for (int a = 0; a < 3; ++a) { b.lo[a] = box6[a]; b.hi[a] = box6[3 + a]; }
-    regions_inside_kernel<<<blocks(V), RG_BLOCK, 0, st>>>(V, verts, b, inside);
-}
-
+// gsr_regions_cut_mark: clears the reference flags, then marks
 hipError_t launch_regions_cut_mark(int F, int V, const int* faces, const unsigned char* inside, int cut_inner, int* keep, int* ref,
                                    int* err, hipStream_t st)
 {
@@ -456,22 +414,7 @@ hipError_t launch_regions_cut_mark(int F, int V, const int* faces, const unsigne
     return hipSuccess;
 }
 
-void launch_regions_cut_emit(int F, int V, const int* faces, const int* keep, const int* kscan, const int* ref, const int* vscan,
-                             int* faces_out, unsigned char* face_mask, int* vert_map, int* old_of_new, hipStream_t st)
-{
-    if (F > 0) regions_cut_faces_kernel<<<blocks(F), RG_BLOCK, 0, st>>>(F, faces, keep, kscan, vscan, faces_out, face_mask);
-    if (V > 0) regions_cut_verts_kernel<<<blocks(V), RG_BLOCK, 0, st>>>(V, ref, vscan, vert_map, old_of_new);
-}
-
-void launch_regions_gather(int n_rows, int C, const int* old_of_new, const void* src, void* dst, hipStream_t st)
-{
-    const long long n_el = (long long)n_rows * C;
-    const int vec = ((reinterpret_cast<uintptr_t>(dst) & 15) == 0 ? 1 : 0) |
-                    ((C % 4 == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0) ? 2 : 0);
-    regions_gather_kernel<<<blocks((n_el + 3) / 4), RG_BLOCK, 0, st>>>(n_el, C, old_of_new, static_cast<const unsigned*>(src),
-                                                                      static_cast<unsigned*>(dst), vec);
-}
-
+// gsr_regions_boundary: clears the marks, then marks
 hipError_t launch_regions_boundary(int F, int V, const int* faces, const int* counts, const unsigned char* inside, unsigned char* bmark,
                                    unsigned char* fmark, int* err, hipStream_t st)
 {
@@ -484,9 +427,181 @@ hipError_t launch_regions_boundary(int F, int V, const int* faces, const int* co
     return hipSuccess;
 }
 
-void launch_regions_label_mask(int F, const int* label, const int* count, int min_count, unsigned char* out, hipStream_t st)
-{
-    regions_label_mask_kernel<<<blocks(F), RG_BLOCK, 0, st>>>(F, label, count, min_count, out);
-}
+// 3 F face-edges are counted in an int
+bool regions_faces_ok(int F) { return F >= 0 && F <= 0x7fffffff / 3; }
+
+}  // namespace
 
 }  // namespace gsr
+
+// ---------------------------------------------------------------- C entry points (include/gsr.h)
+using namespace gsr;
+
+extern "C" {
+
+int gsr_regions_edge_keys(int F, const int* faces, const unsigned char* mask, const unsigned char* colour, int cut,
+                          unsigned char* selected, long long* keys, int* err, gsr_stream_t stream)
+{
+    clear_error();
+    if (!regions_faces_ok(F)) return fail_msg("gsr_regions_edge_keys: F must be in [0, (2^31 - 1) / 3]");
+    if (F == 0) return 0;
+    if (!faces || !selected || !keys || !err) return fail_msg("gsr_regions_edge_keys: required pointer is null");
+    regions_edge_key_kernel<<<blocks(F), RG_BLOCK, 0, (hipStream_t)stream>>>(F, faces, mask, colour, cut, selected, keys, err);
+    GSR_CHECK_LAUNCH("regions_edge_key_kernel");
+    return 0;
+}
+
+int gsr_regions_edge_runs(int F, const long long* sorted_keys, const long long* order, int* counts, int* pairs, gsr_stream_t stream)
+{
+    clear_error();
+    if (!regions_faces_ok(F)) return fail_msg("gsr_regions_edge_runs: F must be in [0, (2^31 - 1) / 3]");
+    if (F == 0) return 0;
+    if (!sorted_keys || !order || !counts || !pairs) return fail_msg("gsr_regions_edge_runs: required pointer is null");
+    if (reinterpret_cast<uintptr_t>(pairs) & 7) return fail_msg("gsr_regions_edge_runs: pairs must be 8-byte aligned");
+    regions_edge_run_kernel<<<blocks(3ll * F), RG_BLOCK, 0, (hipStream_t)stream>>>(3 * F, sorted_keys, order, counts,
+                                                                                   reinterpret_cast<int2*>(pairs));
+    GSR_CHECK_LAUNCH("regions_edge_run_kernel");
+    return 0;
+}
+
+int gsr_regions_components(int F, const int* pairs, const unsigned char* selected, int* parent, int* root_flag, gsr_stream_t stream)
+{
+    clear_error();
+    if (!regions_faces_ok(F)) return fail_msg("gsr_regions_components: F must be in [0, (2^31 - 1) / 3]");
+    if (F == 0) return 0;
+    if (!pairs || !selected || !parent || !root_flag) return fail_msg("gsr_regions_components: required pointer is null");
+    if (reinterpret_cast<uintptr_t>(pairs) & 7) return fail_msg("gsr_regions_components: pairs must be 8-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    regions_uf_init_kernel<<<blocks(F), RG_BLOCK, 0, st>>>(F, parent);
+    regions_uf_hook_kernel<<<blocks(3ll * F), RG_BLOCK, 0, st>>>(3 * F, reinterpret_cast<const int2*>(pairs), parent);
+    regions_uf_flatten_kernel<<<blocks(F), RG_BLOCK, 0, st>>>(F, selected, parent, root_flag);
+    GSR_CHECK_LAUNCH("regions union-find kernels");
+    return 0;
+}
+
+int gsr_regions_labels(int F, const int* parent, const int* root_scan, const unsigned char* selected, int* label, int* count,
+                       gsr_stream_t stream)
+{
+    clear_error();
+    if (!regions_faces_ok(F)) return fail_msg("gsr_regions_labels: F must be in [0, (2^31 - 1) / 3]");
+    if (F == 0) return 0;
+    if (!parent || !root_scan || !selected || !label || !count) return fail_msg("gsr_regions_labels: required pointer is null");
+    regions_label_kernel<<<blocks(F), RG_BLOCK, 0, (hipStream_t)stream>>>(F, parent, root_scan, selected, label, count);
+    GSR_CHECK_LAUNCH("regions_label_kernel");
+    return 0;
+}
+
+int gsr_regions_select(int F, const int* count, int face_threshold, const int* kept_scan, const int* label, int cap, int* kept_label,
+                       int* kept_count, int* region, gsr_stream_t stream)
+{
+    clear_error();
+    if (!regions_faces_ok(F) || cap < 0) return fail_msg("gsr_regions_select: negative size or too many faces");
+    if (face_threshold < 0) return fail_msg("gsr_regions_select: face_threshold must not be negative");
+    if (F == 0) return 0;
+    if (!count || !kept_scan || !label || !region || (cap > 0 && (!kept_label || !kept_count)))
+        return fail_msg("gsr_regions_select: required pointer is null");
+    regions_select_kernel<<<blocks(F), RG_BLOCK, 0, (hipStream_t)stream>>>(F, count, face_threshold, kept_scan, label, cap, kept_label,
+                                                                           kept_count, region);
+    GSR_CHECK_LAUNCH("regions_select_kernel");
+    return 0;
+}
+
+int gsr_regions_boxes(int F, int G, int V, const int* faces, const float* verts, const float* points, const int* region, int cap,
+                      unsigned int* boxes, int* err, gsr_stream_t stream)
+{
+    clear_error();
+    if (!regions_faces_ok(F) || G < 0 || V < 0 || cap < 0) return fail_msg("gsr_regions_boxes: negative size or too many faces");
+    if (cap == 0) return 0;
+    if (!boxes || (F > 0 && (!faces || !verts || !region || !err || (G > 0 && !points))))
+        return fail_msg("gsr_regions_boxes: required pointer is null");
+    hipStream_t st = (hipStream_t)stream;
+    regions_box_init_kernel<<<blocks(6ll * cap), RG_BLOCK, 0, st>>>(6 * cap, boxes);
+    if (F > 0) regions_box_kernel<<<blocks(F), RG_BLOCK, 0, st>>>(F, G, V, faces, verts, points, region, cap, boxes, err);
+    GSR_CHECK_LAUNCH("regions box kernels");
+    return 0;
+}
+
+int gsr_regions_inside(int V, const float* verts, const double* box, unsigned char* inside, gsr_stream_t stream)
+{
+    clear_error();
+    if (V < 0) return fail_msg("gsr_regions_inside: negative size");
+    if (!box) return fail_msg("gsr_regions_inside: box is null");
+    for (int i = 0; i < 6; ++i)
+        if (box[i] != box[i]) return fail_msg("gsr_regions_inside: box holds a NaN");
+    if (V == 0) return 0;
+    if (!verts || !inside) return fail_msg("gsr_regions_inside: required pointer is null");
+    RegionBox b;
+    for (int a = 0; a < 3; ++a) { b.lo[a] = box[a]; b.hi[a] = box[3 + a]; }
+    regions_inside_kernel<<<blocks(V), RG_BLOCK, 0, (hipStream_t)stream>>>(V, verts, b, inside);
+    GSR_CHECK_LAUNCH("regions_inside_kernel");
+    return 0;
+}
+
+int gsr_regions_cut_mark(int F, int V, const int* faces, const unsigned char* inside, int cut_inner, int* keep, int* referenced,
+                         int* err, gsr_stream_t stream)
+{
+    clear_error();
+    if (!regions_faces_ok(F) || V < 0) return fail_msg("gsr_regions_cut_mark: negative size or too many faces");
+    if ((V > 0 && (!inside || !referenced)) || (F > 0 && (!faces || !keep || !err)))
+        return fail_msg("gsr_regions_cut_mark: required pointer is null");
+    GSR_CHECK(launch_regions_cut_mark(F, V, faces, inside, cut_inner != 0, keep, referenced, err, (hipStream_t)stream));
+    GSR_CHECK_LAUNCH("regions_cut_mark_kernel");
+    return 0;
+}
+
+int gsr_regions_cut_emit(int F, int V, const int* faces, const int* keep, const int* keep_scan, const int* referenced,
+                         const int* referenced_scan, int* faces_out, unsigned char* face_mask, int* vert_map, int* old_of_new,
+                         gsr_stream_t stream)
+{
+    clear_error();
+    if (!regions_faces_ok(F) || V < 0) return fail_msg("gsr_regions_cut_emit: negative size or too many faces");
+    // (faces_out / old_of_new may be null when the scans' totals are zero: nothing is written then)
+    if ((F > 0 && (!faces || !keep || !keep_scan || !face_mask || !referenced_scan)) || (V > 0 && (!referenced || !referenced_scan || !vert_map)))
+        return fail_msg("gsr_regions_cut_emit: required pointer is null");
+    hipStream_t st = (hipStream_t)stream;
+    if (F > 0) regions_cut_faces_kernel<<<blocks(F), RG_BLOCK, 0, st>>>(F, faces, keep, keep_scan, referenced_scan, faces_out, face_mask);
+    if (V > 0) regions_cut_verts_kernel<<<blocks(V), RG_BLOCK, 0, st>>>(V, referenced, referenced_scan, vert_map, old_of_new);
+    GSR_CHECK_LAUNCH("regions cut kernels");
+    return 0;
+}
+
+int gsr_regions_gather(int n_rows, int C, const int* old_of_new, const void* src, void* dst, gsr_stream_t stream)
+{
+    clear_error();
+    if (n_rows < 0 || C < 0) return fail_msg("gsr_regions_gather: negative size");
+    if (n_rows == 0 || C == 0) return 0;
+    if (!old_of_new || !src || !dst) return fail_msg("gsr_regions_gather: required pointer is null");
+    if ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 3) return fail_msg("gsr_regions_gather: arrays must be 4-byte aligned");
+    const long long n_el = (long long)n_rows * C;
+    const int vec = ((reinterpret_cast<uintptr_t>(dst) & 15) == 0 ? 1 : 0) |
+                    ((C % 4 == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0) ? 2 : 0);
+    regions_gather_kernel<<<blocks((n_el + 3) / 4), RG_BLOCK, 0, (hipStream_t)stream>>>(
+        n_el, C, old_of_new, static_cast<const unsigned*>(src), static_cast<unsigned*>(dst), vec);
+    GSR_CHECK_LAUNCH("regions_gather_kernel");
+    return 0;
+}
+
+int gsr_regions_boundary(int F, int V, const int* faces, const int* counts, const unsigned char* inside, unsigned char* edge_mark,
+                         unsigned char* face_mark, int* err, gsr_stream_t stream)
+{
+    clear_error();
+    if (!regions_faces_ok(F) || V < 0) return fail_msg("gsr_regions_boundary: negative size or too many faces");
+    if ((V > 0 && (!edge_mark || (inside && !face_mark))) || (F > 0 && (!faces || !counts || !err)))
+        return fail_msg("gsr_regions_boundary: required pointer is null");
+    GSR_CHECK(launch_regions_boundary(F, V, faces, counts, inside, edge_mark, face_mark, err, (hipStream_t)stream));
+    GSR_CHECK_LAUNCH("regions_boundary_kernel");
+    return 0;
+}
+
+int gsr_regions_label_mask(int F, const int* label, const int* count, int min_count, unsigned char* out, gsr_stream_t stream)
+{
+    clear_error();
+    if (!regions_faces_ok(F)) return fail_msg("gsr_regions_label_mask: F must be in [0, (2^31 - 1) / 3]");
+    if (F == 0) return 0;
+    if (!label || !count || !out) return fail_msg("gsr_regions_label_mask: required pointer is null");
+    regions_label_mask_kernel<<<blocks(F), RG_BLOCK, 0, (hipStream_t)stream>>>(F, label, count, min_count, out);
+    GSR_CHECK_LAUNCH("regions_label_mask_kernel");
+    return 0;
+}
+
+}  // extern "C"

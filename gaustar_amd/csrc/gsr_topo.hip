@@ -22,6 +22,8 @@
 //
 // Floating point follows the numpy restatement in tests/topo_ref.py operation by operation, so contraction into FMAs is off
 // for this file: a fused multiply-add rounds once where numpy rounds twice.
+#include "../../include/gsr.h"
+#include "gsr_entry.h"
 #include "gsr_rig.h"
 
 #pragma clang fp contract(off)
@@ -295,67 +297,132 @@ inline int blocks(int n) { return (n + TP_BLOCK - 1) / TP_BLOCK; }
 
 }  // namespace
 
-size_t topo_view_workspace_bytes() { return 2 * RIG_PARTS * sizeof(float); }
+}  // namespace gsr
 
-void launch_topo_view(int H, int W, int V, const float* verts, const float* gt, const float* render, const float* surface,
-                      float max_depth, const double* cam14, void* workspace, float* row, hipStream_t st)
+// ---------------------------------------------------------------- C entry points (include/gsr.h)
+using namespace gsr;
+
+extern "C" {
+
+size_t gsr_topo_view_workspace_bytes(int H, int W)
 {
+    (void)H; (void)W;   // (the partial maxima of a fixed number of workgroups, whatever the image)
+    return 2 * RIG_PARTS * sizeof(float);
+}
+
+int gsr_topo_view(int H, int W, int V, const float* verts, const float* depth_gt, const float* render_depth,
+                  const float* surface_depth, float max_depth, const double* cam, void* workspace, float* row, gsr_stream_t stream)
+{
+    clear_error();
+    if (H <= 0 || W <= 0 || V < 0) return fail_msg("gsr_topo_view: sizes must be positive");
+    if ((long long)H * W >= (1ll << 31)) return fail_msg("gsr_topo_view: image too large");
+    if (!depth_gt || !render_depth || !surface_depth || !cam || !workspace || (V > 0 && (!verts || !row)))
+        return fail_msg("gsr_topo_view: required pointer is null");
+    hipStream_t st = (hipStream_t)stream;
     float* parts = static_cast<float*>(workspace);
-    const RigCamera cam = rig_camera(cam14);
-    topo_gt_max_kernel<<<RIG_PARTS, RIG_BLOCK, 0, st>>>(H * W, gt, max_depth, parts);
-    topo_var_max_kernel<<<RIG_PARTS, RIG_BLOCK, 0, st>>>(H, W, gt, parts);
-    if (V > 0) topo_view_kernel<<<blocks(V), RIG_BLOCK, 0, st>>>(H, W, V, verts, gt, render, surface, max_depth, parts, cam, row);
+    topo_gt_max_kernel<<<RIG_PARTS, RIG_BLOCK, 0, st>>>(H * W, depth_gt, max_depth, parts);
+    topo_var_max_kernel<<<RIG_PARTS, RIG_BLOCK, 0, st>>>(H, W, depth_gt, parts);
+    if (V > 0)
+        topo_view_kernel<<<blocks(V), RIG_BLOCK, 0, st>>>(H, W, V, verts, depth_gt, render_depth, surface_depth, max_depth, parts,
+                                                          rig_camera(cam), row);
+    GSR_CHECK_LAUNCH("topo view kernels");
+    return 0;
 }
 
-void launch_topo_aggregate(int C, int V, const float* table, const float* verts, const float* ymin, double depth_scalar,
-                           int min_observe, int detect_floor, double* value, int* cnt, unsigned char* valid, hipStream_t st)
+int gsr_topo_aggregate(int C, int V, const float* table, const float* verts, const float* ymin, double depth_scalar,
+                       int min_observe, int detect_floor, double* value, int* count, unsigned char* valid, gsr_stream_t stream)
 {
-    topo_aggregate_kernel<<<blocks(V), TP_BLOCK, 0, st>>>(C, V, table, verts, ymin, depth_scalar, min_observe, detect_floor, value,
-                                                          cnt, valid);
+    clear_error();
+    if (C < 0 || V < 0) return fail_msg("gsr_topo_aggregate: negative size");
+    if (V == 0) return 0;
+    if ((C > 0 && !table) || !verts || !value || !count || !valid || (detect_floor && !ymin))
+        return fail_msg("gsr_topo_aggregate: required pointer is null");
+    topo_aggregate_kernel<<<blocks(V), TP_BLOCK, 0, (hipStream_t)stream>>>(C, V, table, verts, ymin, depth_scalar, min_observe,
+                                                                           detect_floor != 0, value, count, valid);
+    GSR_CHECK_LAUNCH("topo_aggregate_kernel");
+    return 0;
 }
 
-void launch_topo_propagate(int V, const int* off, const int* nbr, int sweeps, const double* value_in, const unsigned char* valid_in,
-                           double* value_out, double* value_tmp, unsigned char* valid_a, unsigned char* valid_b, hipStream_t st)
+int gsr_topo_propagate(int V, const int* nbr_offsets, const int* nbr, int sweeps, const double* value_in,
+                       const unsigned char* valid_in, double* value_out, double* value_tmp, unsigned char* valid_a,
+                       unsigned char* valid_b, gsr_stream_t stream)
 {
+    clear_error();
+    if (V < 0 || sweeps < 0) return fail_msg("gsr_topo_propagate: negative size");
+    if (V == 0) return 0;
+    if (!value_in || !value_out) return fail_msg("gsr_topo_propagate: required pointer is null");
+    hipStream_t st = (hipStream_t)stream;
+    if (sweeps == 0) {
+        GSR_CHECK(hipMemcpyAsync(value_out, value_in, sizeof(double) * V, hipMemcpyDeviceToDevice, st));
+        return 0;
+    }
+    if (!nbr_offsets || !nbr || !valid_in || !value_tmp || !valid_a || !valid_b)
+        return fail_msg("gsr_topo_propagate: required pointer is null");
     unsigned char* ob[2] = {valid_a, valid_b};
     const unsigned char* osrc = valid_in;
     ping_pong_sweeps(sweeps, value_in, value_out, value_tmp, [&](const double* src, double* dst, int k) {
-        topo_propagate_kernel<<<blocks(V), TP_BLOCK, 0, st>>>(V, off, nbr, src, osrc, dst, ob[k]);
+        topo_propagate_kernel<<<blocks(V), TP_BLOCK, 0, st>>>(V, nbr_offsets, nbr, src, osrc, dst, ob[k]);
         osrc = ob[k];
     });
+    GSR_CHECK_LAUNCH("topo_propagate_kernel");
+    return 0;
 }
 
-void launch_topo_voxel_keys(int V, const float* verts, const float* vmin, double voxel_size, long long* keys, int* flags,
-                            hipStream_t st)
+int gsr_topo_voxel_keys(int V, const float* verts, const float* vmin, double voxel_size, long long* keys, int* flags,
+                        gsr_stream_t stream)
 {
-    topo_voxel_key_kernel<<<blocks(V), TP_BLOCK, 0, st>>>(V, verts, vmin, voxel_size, keys, flags);
+    clear_error();
+    if (V < 0) return fail_msg("gsr_topo_voxel_keys: negative size");
+    if (!(voxel_size > 0.0)) return fail_msg("gsr_topo_voxel_keys: voxel_size must be positive");
+    if (V == 0) return 0;
+    if (!verts || !vmin || !keys || !flags) return fail_msg("gsr_topo_voxel_keys: required pointer is null");
+    topo_voxel_key_kernel<<<blocks(V), TP_BLOCK, 0, (hipStream_t)stream>>>(V, verts, vmin, voxel_size, keys, flags);
+    GSR_CHECK_LAUNCH("topo_voxel_key_kernel");
+    return 0;
 }
 
-size_t topo_voxel_workspace_bytes(int V)
+size_t gsr_topo_voxel_workspace_bytes(int V)
 {
     // centres [V] float4, own voxel [V] int, tau [V] float, TP_SPLIT partial top-8 lists of (float, int)
-    return (size_t)V * (16 + 4 + 4 + (size_t)TP_SPLIT * TP_K * 8);
+    return V > 0 ? (size_t)V * (16 + 4 + 4 + (size_t)TP_SPLIT * TP_K * 8) : 0;
 }
 
-void launch_topo_voxel_interp(int V, const float* verts, const float* vmin, double voxel_size, const long long* skeys,
-                              const long long* perm, const long long* vid, const double* value, void* workspace, double* vox_value,
-                              double* out, hipStream_t st)
+int gsr_topo_voxel_interp(int V, const float* verts, const float* vmin, double voxel_size, const long long* sorted_keys,
+                          const long long* order, const long long* voxel_id, const double* value, void* workspace,
+                          double* voxel_value, double* out, gsr_stream_t stream)
 {
+    clear_error();
+    if (V < 0) return fail_msg("gsr_topo_voxel_interp: negative size");
+    if (!(voxel_size > 0.0)) return fail_msg("gsr_topo_voxel_interp: voxel_size must be positive");
+    if (V == 0) return 0;
+    if (!verts || !vmin || !sorted_keys || !order || !voxel_id || !value || !workspace || !voxel_value || !out)
+        return fail_msg("gsr_topo_voxel_interp: required pointer is null");
+    if (reinterpret_cast<uintptr_t>(workspace) & 15) return fail_msg("gsr_topo_voxel_interp: workspace must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
     float4* c4 = static_cast<float4*>(workspace);
     int* own = reinterpret_cast<int*>(c4 + V);
     float* tau = reinterpret_cast<float*>(own + V);
     float* part_d = tau + V;
     int* part_i = reinterpret_cast<int*>(part_d + (size_t)TP_SPLIT * TP_K * V);
-    const long long* last = vid + (V - 1);
-    topo_voxel_reduce_kernel<<<blocks(V), TP_BLOCK, 0, st>>>(V, skeys, perm, vid, value, vmin, voxel_size, c4, vox_value, own);
+    const long long* last = voxel_id + (V - 1);
+    topo_voxel_reduce_kernel<<<blocks(V), TP_BLOCK, 0, st>>>(V, sorted_keys, order, voxel_id, value, vmin, voxel_size, c4, voxel_value, own);
     topo_knn_bound_kernel<<<blocks(V), TP_BLOCK, 0, st>>>(V, verts, c4, last, own, tau);
     topo_knn_part_kernel<<<dim3(blocks(V), TP_SPLIT), TP_BLOCK, 0, st>>>(V, verts, c4, last, tau, part_d, part_i);
-    topo_knn_merge_kernel<<<blocks(V), TP_BLOCK, 0, st>>>(V, part_d, part_i, vox_value, voxel_size * voxel_size, out);
+    topo_knn_merge_kernel<<<blocks(V), TP_BLOCK, 0, st>>>(V, part_d, part_i, voxel_value, voxel_size * voxel_size, out);
+    GSR_CHECK_LAUNCH("topo voxel kernels");
+    return 0;
 }
 
-void launch_topo_faces(int F, const int* faces, const double* value, unsigned char* colour, float* loss, hipStream_t st)
+int gsr_topo_faces(int F, const int* faces, const double* value, unsigned char* face_colour, float* face_loss,
+                   gsr_stream_t stream)
 {
-    topo_face_kernel<<<blocks(F), TP_BLOCK, 0, st>>>(F, faces, value, colour, loss);
+    clear_error();
+    if (F < 0) return fail_msg("gsr_topo_faces: negative size");
+    if (F == 0) return 0;
+    if (!faces || !value || !face_colour || !face_loss) return fail_msg("gsr_topo_faces: required pointer is null");
+    topo_face_kernel<<<blocks(F), TP_BLOCK, 0, (hipStream_t)stream>>>(F, faces, value, face_colour, face_loss);
+    GSR_CHECK_LAUNCH("topo_face_kernel");
+    return 0;
 }
 
-}  // namespace gsr
+}  // extern "C"

@@ -31,6 +31,8 @@
 //     Corner angles: arccos of the clipped dot products of the unit edge vectors at corners 0 and 1, pi minus both at corner
 //     2, all three zero when one is below 1e-8.  trimesh computes the normals of the camera-space mesh; these are the world
 //     normals rotated into the camera, which differ only by rounding.
+#include "../../include/gsr.h"
+#include "gsr_entry.h"
 #include "gsr_rig.h"
 
 #pragma clang fp contract(off)
@@ -302,21 +304,53 @@ WarpFlow make_flow(const float* raw, const int* shape6, int H, int W)
 
 }  // namespace
 
-size_t warp_view_workspace_bytes() { return 4 * RIG_PARTS * sizeof(float); }
+}  // namespace gsr
 
-void launch_warp_normals(int V, int F, const double* verts, const int* faces, const int* vf_off, const int* vf_ent, double* fbuf,
-                         double* normals, hipStream_t st)
+// ---------------------------------------------------------------- C entry points (include/gsr.h)
+using namespace gsr;
+
+extern "C" {
+
+int gsr_vertex_normals(int V, int F, const double* verts, const int* faces, const int* vf_offsets, const int* vf_entries,
+                       double* face_scratch, double* normals, gsr_stream_t stream)
 {
-    if (F > 0) warp_face_kernel<<<wblocks(F), WP_BLOCK, 0, st>>>(F, verts, faces, fbuf);
-    warp_vertex_normal_kernel<<<wblocks(V), WP_BLOCK, 0, st>>>(V, vf_off, vf_ent, fbuf, normals);
+    clear_error();
+    if (V < 0 || F < 0) return fail_msg("gsr_vertex_normals: negative size");
+    if (V == 0) return 0;
+    if (!verts || !vf_offsets || !normals || (F > 0 && (!faces || !vf_entries || !face_scratch)))
+        return fail_msg("gsr_vertex_normals: required pointer is null");
+    hipStream_t st = (hipStream_t)stream;
+    if (F > 0) warp_face_kernel<<<wblocks(F), WP_BLOCK, 0, st>>>(F, verts, faces, face_scratch);
+    warp_vertex_normal_kernel<<<wblocks(V), WP_BLOCK, 0, st>>>(V, vf_offsets, vf_entries, face_scratch, normals);
+    GSR_CHECK_LAUNCH("warp normal kernels");
+    return 0;
 }
 
-void launch_warp_view(int H, int W, int V, const double* verts, const double* normals, const float* flow_f, const float* flow_b,
-                      const int* flow_shape, const float* depth_cur, const float* depth_next, const double* cam14,
-                      const double* params, void* workspace, double* row, hipStream_t st)
+size_t gsr_warp_view_workspace_bytes(int H, int W)
 {
+    (void)H; (void)W;   // (the partial maxima of a fixed number of workgroups, whatever the image)
+    return 4 * RIG_PARTS * sizeof(float);
+}
+
+int gsr_warp_view(int H, int W, int V, const double* verts, const double* normals, const float* flow_f, const float* flow_b,
+                  const int* flow_shape, const float* depth_cur, const float* depth_next, const double* cam,
+                  const double* params, void* workspace, double* row, gsr_stream_t stream)
+{
+    clear_error();
+    if (H <= 0 || W <= 0 || V < 0) return fail_msg("gsr_warp_view: sizes must be positive");
+    if ((long long)H * W >= (1ll << 31)) return fail_msg("gsr_warp_view: image too large");
+    if (!flow_f || !flow_b || !flow_shape || !depth_cur || !depth_next || !cam || !params || !workspace ||
+        (V > 0 && (!verts || !normals || !row)))
+        return fail_msg("gsr_warp_view: required pointer is null");
+    if (flow_shape[0] <= 0 || flow_shape[1] <= 0) return fail_msg("gsr_warp_view: flow sizes must be positive");
+    for (int i = 2; i < 6; ++i)
+        if (flow_shape[i] < 0) return fail_msg("gsr_warp_view: flow padding must be non-negative");
+    const long long hp = (long long)flow_shape[0] + flow_shape[2] + flow_shape[3];
+    const long long wp = (long long)flow_shape[1] + flow_shape[4] + flow_shape[5];
+    if (hp >= (1ll << 30) || wp >= (1ll << 30) || (long long)flow_shape[0] * flow_shape[1] >= (1ll << 30))
+        return fail_msg("gsr_warp_view: flow too large");
+    hipStream_t st = (hipStream_t)stream;
     float* parts = static_cast<float*>(workspace);
-    const RigCamera cam = rig_camera(cam14);
     WarpParams prm;
     prm.normal_cos = params[0];
     prm.edge_scalar = params[1];
@@ -328,20 +362,42 @@ void launch_warp_view(int H, int W, int V, const double* verts, const double* no
     warp_depth_max_kernel<<<dim3(RIG_PARTS, 2), RIG_BLOCK, 0, st>>>(H * W, depth_cur, depth_next, parts);
     warp_var_max_kernel<<<dim3(RIG_PARTS, 2), RIG_BLOCK, 0, st>>>(H, W, depth_cur, depth_next, parts);
     if (V > 0)
-        warp_view_kernel<<<wblocks(V), RIG_BLOCK, 0, st>>>(H, W, V, verts, normals, ff, fb, depth_cur, depth_next, parts, cam, prm, row);
+        warp_view_kernel<<<wblocks(V), RIG_BLOCK, 0, st>>>(H, W, V, verts, normals, ff, fb, depth_cur, depth_next, parts,
+                                                           rig_camera(cam), prm, row);
+    GSR_CHECK_LAUNCH("warp view kernels");
+    return 0;
 }
 
-void launch_warp_aggregate(int C, int V, const double* table, int min_observe, double* move, int* observed, int* count,
-                           unsigned char* valid, hipStream_t st)
+int gsr_warp_aggregate(int C, int V, const double* table, int min_observe, double* move, int* observed, int* count,
+                       unsigned char* valid, gsr_stream_t stream)
 {
-    warp_aggregate_kernel<<<wblocks(V), WP_BLOCK, 0, st>>>(C, V, table, min_observe, move, observed, count, valid);
+    clear_error();
+    if (C < 0 || V < 0) return fail_msg("gsr_warp_aggregate: negative size");
+    if (V == 0) return 0;
+    if ((C > 0 && !table) || !move || !observed || !count || !valid) return fail_msg("gsr_warp_aggregate: required pointer is null");
+    warp_aggregate_kernel<<<wblocks(V), WP_BLOCK, 0, (hipStream_t)stream>>>(C, V, table, min_observe, move, observed, count, valid);
+    GSR_CHECK_LAUNCH("warp_aggregate_kernel");
+    return 0;
 }
 
-void launch_warp_smooth(int V, const int* off, const int* nbr, int sweeps, const double* in, double* out, double* tmp, hipStream_t st)
+int gsr_warp_smooth(int V, const int* nbr_offsets, const int* nbr, int sweeps, const double* value_in, double* value_out,
+                    double* value_tmp, gsr_stream_t stream)
 {
-    ping_pong_sweeps(sweeps, in, out, tmp, [&](const double* src, double* dst, int) {
-        warp_smooth_kernel<<<wblocks(V), WP_BLOCK, 0, st>>>(V, off, nbr, src, dst);
+    clear_error();
+    if (V < 0 || sweeps < 0) return fail_msg("gsr_warp_smooth: negative size");
+    if (V == 0) return 0;
+    if (!value_in || !value_out) return fail_msg("gsr_warp_smooth: required pointer is null");
+    hipStream_t st = (hipStream_t)stream;
+    if (sweeps == 0) {
+        GSR_CHECK(hipMemcpyAsync(value_out, value_in, sizeof(double) * 3 * V, hipMemcpyDeviceToDevice, st));
+        return 0;
+    }
+    if (!nbr_offsets || !nbr || !value_tmp) return fail_msg("gsr_warp_smooth: required pointer is null");
+    ping_pong_sweeps(sweeps, value_in, value_out, value_tmp, [&](const double* src, double* dst, int) {
+        warp_smooth_kernel<<<wblocks(V), WP_BLOCK, 0, st>>>(V, nbr_offsets, nbr, src, dst);
     });
+    GSR_CHECK_LAUNCH("warp_smooth_kernel");
+    return 0;
 }
 
-}  // namespace gsr
+}  // extern "C"

@@ -57,6 +57,18 @@ def test_library_loads_and_exports_every_symbol(hip_lib):
     assert hip_lib.gsr_abi_version() == 16
 
 
+def test_library_keeps_every_message(hip_lib):
+    """tests/golden/abi_messages.txt lists the printable strings of the library that start with gsr_ or hold a "%s: " format
+    (exported names and the texts of gsr_last_error), as the library had them before the entry points moved into their
+    features' source files.  Wherever an entry point lives, its messages stay byte for byte."""
+    from gaustar_amd import _lib
+    blob = open(_lib.LIB_PATH, "rb").read()
+    lines = open(os.path.join(ROOT, "tests", "golden", "abi_messages.txt")).read().splitlines()
+    assert len(lines) > 250
+    missing = [s for s in lines if s.encode() not in blob]
+    assert not missing, missing
+
+
 def test_scratch_sizes(hip_lib):
     # 44 B/Gaussian geometry state + 12 B SH-colour slot + what a 256-Gaussian preprocess workgroup leaves for scatter
     # (2 048 instance records of 16 B, a 512-slot tile table of 8 B, four counts), 8 B/pixel (+ alignment slack)
