@@ -156,6 +156,21 @@ SIGNATURES = {
     "gsr_regions_gather": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gsr_regions_boundary": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gsr_regions_label_mask": (c_int, [c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    # the stitch of the fused patch into the cut base mesh (refined_mesh.py:114-215, :639, :656-658): gaustar_amd.regions
+    "gsr_stitch_nn_tile": (c_int, []),
+    "gsr_stitch_nn_queries": (c_int, []),
+    "gsr_stitch_nearest": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gsr_stitch_check_list": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gsr_stitch_snap_groups": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gsr_stitch_mark": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gsr_stitch_hole_components": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gsr_stitch_hole_move": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gsr_stitch_pos_keys": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gsr_stitch_pos_heads": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gsr_stitch_pos_remap": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gsr_stitch_compose_mask": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "gsr_stitch_vert_map": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gsr_stitch_watertight": (c_int, [c_int, c_void_p, c_void_p, c_void_p]),
     "gsr_adam_step": (c_int, [c_longlong, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_double, c_double, c_int,
                               c_void_p]),
     "gsr_adam_step_multi": (c_int, [c_int, POINTER(c_longlong), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),

@@ -7,7 +7,7 @@
 //                       (torch.sort of the keys, as topology.py sorts its voxel keys)
 //                       regions_edge_run_kernel    per sorted key the length of its run, written back to its face-edge; a run of
 //                                                  exactly two face-edges of two different faces is an adjacency pair
-//   components          regions_uf_init / _hook / _flatten_kernel   union-find over the pairs: the larger root is pointed at the
+//   components          uf_init / uf_hook / uf_flatten_kernel (gsr_unionfind.h)   union-find over the pairs: the larger root is pointed at the
 //                                                  smaller by compare-and-swap, so a tree's root is its smallest face whatever
 //                                                  order the hooks landed in; flatten finds it without a store to any other
 //                                                  face's word and writes it to parent[f], once
@@ -26,6 +26,7 @@
 #include "../../include/gsr.h"
 #include "gsr_entry.h"
 #include "gsr_internal.h"
+#include "gsr_unionfind.h"
 
 namespace gsr {
 
@@ -37,9 +38,6 @@ constexpr int RG_ERR_INDEX = 1, RG_ERR_NAN = 2;               // bits of the cal
 constexpr int RG_WALK = 8;                                 // neighbours looked at before a run's end is found by bisection
 
 struct RegionBox { double lo[3], hi[3]; };
-
-__device__ __forceinline__ int uf_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void uf_store(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 __device__ __forceinline__ long long edge_key(int a, int b)
 {
@@ -109,67 +107,7 @@ __global__ void __launch_bounds__(RG_BLOCK) regions_edge_run_kernel(int n, const
 }
 
 // ---------------------------------------------------------------------------------------------------- components
-__global__ void __launch_bounds__(RG_BLOCK) regions_uf_init_kernel(int F, int* __restrict__ parent)
-{
-    const int f = blockIdx.x * RG_BLOCK + threadIdx.x;
-    if (f < F) parent[f] = f;
-}
-
-// The root of x, halving the path on the way: for the HOOK kernel only, where any ancestor is as good as another.
-// parent[x] <= x always; a face that has a parent below itself never becomes a root again, so the halving store (to an
-// ancestor, of a non-root) and the hooks' compare-and-swap (on roots only) never meet on one word.
-__device__ __forceinline__ int uf_find(int* parent, int x)
-{
-    for (;;) {
-        const int p = uf_load(parent + x);
-        if (p == x) return x;
-        const int g = uf_load(parent + p);
-        if (g == p) return p;
-        uf_store(parent + x, g);
-        x = g;
-    }
-}
-
-// The root of x without a store: for the FLATTEN kernel, where parent[f] must end as the final root.  There every word has one
-// writer, the thread of its own face, and the one value it writes is the root; a reader meets either the entry the hooks left
-// (an ancestor) or that root, and walks on until parent[x] == x.  No hook runs any more, so roots stay roots.
-__device__ __forceinline__ int uf_root(const int* parent, int x)
-{
-    for (;;) {
-        const int p = uf_load(parent + x);
-        if (p == x) return x;
-        x = p;
-    }
-}
-
-__global__ void __launch_bounds__(RG_BLOCK) regions_uf_hook_kernel(int n, const int2* __restrict__ pairs, int* __restrict__ parent)
-{
-    const int i = blockIdx.x * RG_BLOCK + threadIdx.x;
-    if (i >= n) return;
-    const int2 pr = pairs[i];
-    if (pr.x < 0) return;
-    int a = pr.x, b = pr.y;
-    for (;;) {
-        a = uf_find(parent, a);
-        b = uf_find(parent, b);
-        if (a == b) break;
-        if (a < b) { const int t = a; a = b; b = t; }       // a: the larger root, pointed at the smaller
-        const int old = atomicCAS(parent + a, a, b);
-        if (old == a) break;
-        a = old;                                            // someone hooked a first: go on from where it points
-    }
-}
-
-__global__ void __launch_bounds__(RG_BLOCK) regions_uf_flatten_kernel(int F, const unsigned char* __restrict__ sel, int* __restrict__ parent,
-                                                                      int* __restrict__ root_flag)
-{
-    const int f = blockIdx.x * RG_BLOCK + threadIdx.x;
-    if (f >= F) return;
-    const int r = uf_root(parent, f);
-    uf_store(parent + f, r);      // (the only store to this word in this kernel)
-    root_flag[f] = (sel[f] && r == f) ? 1 : 0;
-}
-
+// (the union-find itself: gsr_unionfind.h)
 // scan: the inclusive scan of root_flag.  count must be zero.  One add per wave and label.
 __global__ void __launch_bounds__(RG_BLOCK) regions_label_kernel(int F, const int* __restrict__ parent, const int* __restrict__ scan,
                                                                  const unsigned char* __restrict__ sel, int* __restrict__ label,
@@ -471,10 +409,7 @@ int gsr_regions_components(int F, const int* pairs, const unsigned char* selecte
     if (F == 0) return 0;
     if (!pairs || !selected || !parent || !root_flag) return fail_msg("gsr_regions_components: required pointer is null");
     if (reinterpret_cast<uintptr_t>(pairs) & 7) return fail_msg("gsr_regions_components: pairs must be 8-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    regions_uf_init_kernel<<<blocks(F), RG_BLOCK, 0, st>>>(F, parent);
-    regions_uf_hook_kernel<<<blocks(3ll * F), RG_BLOCK, 0, st>>>(3 * F, reinterpret_cast<const int2*>(pairs), parent);
-    regions_uf_flatten_kernel<<<blocks(F), RG_BLOCK, 0, st>>>(F, selected, parent, root_flag);
+    launch_union_find(F, 3ll * F, reinterpret_cast<const int2*>(pairs), selected, parent, root_flag, (hipStream_t)stream);
     GSR_CHECK_LAUNCH("regions union-find kernels");
     return 0;
 }

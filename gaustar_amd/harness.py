@@ -513,8 +513,8 @@ class SurfaceGaussians(nn.Module):
         """Per merged box of update_regions.boxes(aabb_pad) a regions.RegionCut: the box, the patch of `fusion_mesh`
         (fusion.FusionMesh) with any vertex inside it, colours carried (refined_mesh.py:583), and the base mesh without the
         faces that have a vertex inside it, with its face_mask over the base mesh's faces (:609-614).  Each cut is made from
-        the UNCUT base mesh: the reference cuts what the previous box's splice left (`base_mesh = connected_mesh`, :660), and
-        that chaining belongs to the splice, which is not implemented."""
+        the UNCUT base mesh: the reference cuts what the previous box's splice left (`base_mesh = connected_mesh`, :660);
+        stitch_update_region joins one box's two cuts, and that chaining over boxes is the caller's."""
         from . import regions
         verts, faces = self._points.detach().float(), self._surface_mesh_faces.int()
         out = []
@@ -524,6 +524,34 @@ class SurfaceGaussians(nn.Module):
                                                                               attrs=(fusion_mesh.colors,)),
                                          base_cut=regions.cut_mesh_by_box(verts, faces, box, True)))
         return out
+
+    def stitch_update_region(self, cut, outlier_face_threshold=50, pad: float = 0.02):
+        """One box of update_mesh_topo's loop (refined_mesh.py:583-658) without fill_holes: the fused patch of `cut`
+        (regions.RegionCut) loses its outlier components (:590-599), its boundary vertices across the box (:600) and the base
+        cut's boundary vertices inside the box grown by `pad` (:619) are found, and regions.connect_two_meshes joins the base
+        cut (mesh 1) and the patch (mesh 2) along them (:628).  -> regions.RegionStitch: stitched (regions.StitchedMesh), patch
+        (the patch that was stitched, colours in attrs[0]) and base_face_mask [F_base] bool over the UNCUT base mesh's faces:
+        cut.base_cut.face_mask with the stitch's face_mask written into its True entries (:656-658).  None where the
+        reference sets cc_success_flag = 0: an empty cut or no boundary vertices (:586, :601, :611, :620).
+
+        Holes that fill_holes would have closed (:589, :617, :652) remain and can make `stitched.watertight` False.  What to do
+        with a result that is not watertight (the reference skips the box, :639-643) is the caller's decision, and so is the
+        chaining over several boxes (:660-664): every RegionCut of cut_update_regions was cut from the uncut base mesh."""
+        from . import regions
+        patch, base = cut.fusion_patch, cut.base_cut
+        if patch.verts.shape[0] == 0 or base.verts.shape[0] == 0:
+            return None
+        keep = regions.outlier_component_mask(patch.faces, outlier_face_threshold)
+        patch = regions.select_faces(patch.verts, patch.faces, keep, attrs=patch.attrs)
+        patch_boundary = regions.boundary_vertices(patch.verts, patch.faces, cut.box, cut_inner=False)
+        if patch_boundary.shape[0] == 0:
+            return None
+        base_boundary = regions.boundary_vertices(base.verts, base.faces, cut.box, cut_inner=True, pad=pad)
+        if base_boundary.shape[0] == 0:
+            return None
+        st = regions.connect_two_meshes(base.verts, base.faces, base_boundary, patch.verts, patch.faces, patch_boundary)
+        base_face_mask = regions.compose_face_mask(base.face_mask, st.face_mask[:int(base.faces.shape[0])])
+        return regions.RegionStitch(stitched=st, patch=patch, base_face_mask=base_face_mask)
 
     # -------------------------------------------------------------------------------- rendering
     def _settings(self, camera: NerfCamera, bg: torch.Tensor, sh_degree: int):

@@ -22,9 +22,26 @@ only, as the reference counts them after update_faces.  Components are numbered 
 scipy.sparse.csgraph.connected_components gives.  Every output is an integer or an exactly defined float: the same inputs give
 the same bits.
 
-What follows the cut in the reference -- fill_holes, connect_two_meshes, merge_vert_around_holes, the watertight test and the
-choice among the aabb_pad trials (:589-693) -- is not here.  The reference applies find_boundary_verts and get_outlier_cc_mask
-after fill_holes; here they are primitives on whatever mesh they are given.
+The stitch that follows the cuts is here too (gsr_stitch.hip), as far as it can be defined exactly:
+
+    idx, d2 = nearest_vertices(queries, candidates)                     # knn_points(K=1) (:166, :175)
+    st = connect_two_meshes(verts1, faces1, b1, verts2, faces2, b2)     # connect_two_meshes (:158-215): StitchedMesh
+    cut = merge_vertices_around_holes(verts, faces)                     # merge_vert_around_holes (:126-155) and :201-203
+    cut = select_faces(verts, faces, face_mask, attrs)                  # update_faces + remove_unreferenced_vertices
+    ok = is_watertight(faces)                                           # trimesh is_watertight (:639)
+
+Where the stitch departs from the reference's libraries, on purpose:
+  * nearest_vertices takes the f32 coordinates to float64 and forms d2 = (dx dx + dy dy) + dz dz there, without contraction;
+    among equal distances the lowest candidate index wins.  pytorch3d's knn_points sums in f32 (:166, :175 pass .float()
+    copies), so it can rank two candidates differently only when their distances agree to f32 rounding.
+  * Vertices are grouped by position when their three coordinates compare equal as numbers (-0 equals +0, NaN equals
+    nothing).  trimesh.grouping.group_rows groups after rounding to 1e-8.
+  * A face is degenerate iff two of its three vertex indices are equal.  trimesh's nondegenerate_faces also drops faces
+    thinner than 1e-8; they are kept here, because dropping them opens a hole.
+What remains the reference's: fill_holes (:589, :617, :652; its result depends on trimesh's and networkx's cycle traversal),
+the chaining over several boxes (:660-664), the reference areas (:683-687), force_short_edge (:645-650) and the choice among
+the aabb_pad trials.  The reference applies find_boundary_verts and get_outlier_cc_mask after fill_holes; here they are
+primitives on whatever mesh they are given.
 """
 from __future__ import annotations
 
@@ -348,7 +365,7 @@ def boundary_vertices(verts: torch.Tensor, faces: torch.Tensor, box=None, cut_in
     indices.  With a box and cut_inner=True those inside the box grown by `pad` (:94-99, grown in float64); with a box and
     cut_inner=False those that belong to a face with some but not all of its vertices inside the box (:101-111).
     A primitive on the mesh it is given: the reference calls it after fill_holes (:589-600, :617-619), which is not part of
-    this module."""
+    this module (see the module docstring)."""
     lib = _lib.load()
     faces = _faces_i32(faces)
     dev, F = faces.device, int(faces.shape[0])
@@ -393,5 +410,316 @@ def outlier_component_mask(faces: torch.Tensor, face_num_threshold: Optional[flo
     return out
 
 
+# ------------------------------------------------------------------------------------------------ stitch
+def _nn_const(name: str) -> int:
+    return int(getattr(_lib.load(), name)())
+
+
+def __getattr__(name: str):
+    """NN_TILE: the candidates the nearest-vertex kernel stages in LDS at once; NN_QUERIES: the queries of one workgroup.  Read
+    from the library, so importing this module does not need it."""
+    if name == "NN_TILE":
+        return _nn_const("gsr_stitch_nn_tile")
+    if name == "NN_QUERIES":
+        return _nn_const("gsr_stitch_nn_queries")
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
+def _raise_if_stitch(err: int) -> None:
+    """The stitch kernels' err word: bit 0 = an index outside its array, bit 1 = a position that is NaN or infinite, bit 2 = an
+    index listed twice."""
+    if err & 1:
+        raise ValueError("an index lies outside the mesh")
+    if err & 4:
+        raise ValueError("a boundary list names a vertex twice")
+    if err & 2:
+        raise ValueError("a boundary position is NaN or infinite: its nearest vertex is not defined")
+
+
+def _nearest(q: torch.Tensor, c: torch.Tensor, err: torch.Tensor):
+    """q [Bq,3], c [Bc,3] f32 contiguous, Bq, Bc > 0 -> (idx [Bq] int32, d2 [Bq] f64, max_bits [1] int64).  Nothing is read."""
+    lib = _lib.load()
+    Bq, Bc = int(q.shape[0]), int(c.shape[0])
+    idx = torch.empty(Bq, dtype=torch.int32, device=q.device)
+    d2 = torch.empty(Bq, dtype=torch.float64, device=q.device)
+    mx = torch.empty(1, dtype=torch.int64, device=q.device)
+    _lib.check(lib.gsr_stitch_nearest(Bq, Bc, _p(q), _p(c), _p(idx), _p(d2), _p(mx), _p(err), _stream()), "gsr_stitch_nearest")
+    return idx, d2, mx
+
+
+@torch.no_grad()
+def nearest_vertices(queries: torch.Tensor, candidates: torch.Tensor, return_max: bool = False):
+    """(idx int32 [Bq], d2 float64 [Bq]): per query the nearest candidate and the squared distance to it, as the module
+    docstring defines them: knn_points(K=1) of refined_mesh.py:166, :175 in float64, the lowest index among equals.
+    return_max=True adds the largest d2 as a Python float (0.0 without queries).  No candidates, or a coordinate that is NaN or
+    infinite, raise ValueError.  One host read: the err word (and the maximum)."""
+    for t in (queries, candidates):
+        if t.dim() != 2 or t.shape[1] != 3 or t.dtype != torch.float32:
+            raise ValueError("queries and candidates must be [B,3] float32")
+        if t.device.type != "cuda" or t.device != queries.device:
+            raise RuntimeError("queries and candidates must be on one GPU")
+    if candidates.shape[0] == 0:
+        raise ValueError("no candidates")
+    dev = queries.device
+    if queries.shape[0] == 0:
+        out = torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.float64, device=dev)
+        return (*out, 0.0) if return_max else out
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    idx, d2, mx = _nearest(queries.detach().contiguous(), candidates.detach().contiguous(), err)
+    head = torch.cat([err.to(torch.int64), mx]).cpu().numpy()
+    _raise_if_stitch(int(head[0]))
+    return (idx, d2, float(head[1:].view(np.float64)[0])) if return_max else (idx, d2)
+
+
+def _compact(verts: torch.Tensor, faces: torch.Tensor, remap: Optional[torch.Tensor], mask: Optional[torch.Tensor],
+             attrs: Sequence[torch.Tensor], err: torch.Tensor) -> Tuple[CutMesh, torch.Tensor]:
+    """The faces rewritten by `remap`, kept by `mask` (without one: unless degenerate), their vertices renumbered in ascending
+    old index -> (CutMesh, keep_scan [F] int32).  One host read: the two totals and err."""
+    lib = _lib.load()
+    dev, F, V = faces.device, int(faces.shape[0]), int(verts.shape[0])
+    st = _stream()
+    faces_rw = torch.empty(F, 3, dtype=torch.int32, device=dev)
+    keep = torch.empty(F, dtype=torch.int32, device=dev)
+    ref = torch.empty(V, dtype=torch.int32, device=dev)
+    _lib.check(lib.gsr_stitch_mark(F, V, _p(faces), _p(remap), _p(mask), _p(faces_rw), _p(keep), _p(ref), _p(err), st),
+               "gsr_stitch_mark")
+    kscan = torch.cumsum(keep, 0, dtype=torch.int32)
+    vscan = torch.cumsum(ref, 0, dtype=torch.int32)
+    zero = torch.zeros(1, dtype=torch.int32, device=dev)
+    head = torch.cat([kscan[-1:] if F else zero, vscan[-1:] if V else zero, err]).cpu()
+    _raise_if_stitch(int(head[2]))
+    nf, nv = int(head[0]), int(head[1])
+    faces_out = torch.empty(nf, 3, dtype=torch.int32, device=dev)
+    face_mask = torch.empty(F, dtype=torch.bool, device=dev)
+    vert_map = torch.empty(V, dtype=torch.int32, device=dev)
+    old_of_new = torch.empty(nv, dtype=torch.int32, device=dev)
+    _lib.check(lib.gsr_regions_cut_emit(F, V, _p(faces_rw), _p(keep), _p(kscan), _p(ref), _p(vscan), _p(faces_out), _p(face_mask),
+                                        _p(vert_map), _p(old_of_new), st), "gsr_regions_cut_emit")
+    cut = CutMesh(verts=_gather(old_of_new, verts), faces=faces_out, face_mask=face_mask, vert_map=vert_map,
+                  attrs=tuple(_gather(old_of_new, a.detach().contiguous()) for a in attrs))
+    return cut, kscan
+
+
+@torch.no_grad()
+def select_faces(verts: torch.Tensor, faces: torch.Tensor, face_mask: torch.Tensor, attrs: Sequence[torch.Tensor] = ()) -> CutMesh:
+    """update_faces(face_mask) and remove_unreferenced_vertices (refined_mesh.py:598-599): the faces with face_mask set, in
+    their order, their vertices renumbered in ascending old index; attrs as in cut_mesh_by_box.  One host read: the totals."""
+    faces = _faces_i32(faces)
+    dev, F = faces.device, int(faces.shape[0])
+    verts = _verts_f32(verts, dev)
+    V = int(verts.shape[0])
+    mask = _mask_u8(face_mask, F, dev)
+    if mask is None:
+        raise ValueError("face_mask must be [F] bool or uint8")
+    attrs = tuple(attrs)
+    for a in attrs:
+        if a.dim() < 1 or a.shape[0] != V or a.element_size() != 4 or a.device != dev:
+            raise ValueError("attrs must be per-vertex arrays [V, ...] of a 4-byte dtype on the mesh's GPU")
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    return _compact(verts, faces, None, mask, attrs, err)[0]
+
+
+def _edge_counts(faces: torch.Tensor, err: torch.Tensor) -> Optional[torch.Tensor]:
+    return _edge_runs(faces, None, None, 0, err)[1] if faces.shape[0] else None
+
+
+def _watertight_word(faces: torch.Tensor, err: torch.Tensor) -> torch.Tensor:
+    """[1] int32 on the device: 1 where some face-edge's count is not 2."""
+    lib = _lib.load()
+    bad = torch.empty(1, dtype=torch.int32, device=faces.device)
+    _lib.check(lib.gsr_stitch_watertight(int(faces.shape[0]), _p(_edge_counts(faces, err)), _p(bad), _stream()), "gsr_stitch_watertight")
+    return bad
+
+
+@torch.no_grad()
+def is_watertight(faces: torch.Tensor) -> bool:
+    """trimesh's is_watertight (refined_mesh.py:639): F > 0 and every face-edge's vertex pair occurs exactly twice.  Reduced on
+    the device; one word is read."""
+    faces = _faces_i32(faces)
+    if faces.shape[0] == 0:
+        return False
+    err = torch.zeros(1, dtype=torch.int32, device=faces.device)
+    head = torch.cat([_watertight_word(faces, err), err]).cpu()
+    _raise_if(int(head[1]))
+    return int(head[0]) == 0
+
+
+def _merge_holes(verts: torch.Tensor, faces: torch.Tensor, max_hole_vert_num: int, err: torch.Tensor):
+    """verts [V,3] f32, faces [F,3] int32, contiguous -> (CutMesh, keep_scan, remap [V] int32): merge_vert_around_holes and the
+    degenerate pass after it.  Host reads: the hole vertices' number (torch.nonzero) and _compact's totals."""
+    lib = _lib.load()
+    dev, F, V = faces.device, int(faces.shape[0]), int(verts.shape[0])
+    st = _stream()
+    remap = torch.arange(V, dtype=torch.int32, device=dev)
+    if F == 0 or V == 0:
+        return (*_compact(verts, faces, remap, None, (), err), remap)
+    counts = _edge_counts(faces, err)
+    pairs = torch.empty(3 * F, 2, dtype=torch.int32, device=dev)
+    hole = torch.empty(V, dtype=torch.uint8, device=dev)
+    parent = torch.empty(V, dtype=torch.int32, device=dev)
+    flag = torch.empty(V, dtype=torch.int32, device=dev)
+    _lib.check(lib.gsr_stitch_hole_components(F, V, _p(faces), _p(counts), _p(pairs), _p(hole), _p(parent), _p(flag), _p(err), st),
+               "gsr_stitch_hole_components")
+    size = torch.empty(V, dtype=torch.int32, device=dev)
+    moved = torch.empty_like(verts)
+    _lib.check(lib.gsr_stitch_hole_move(V, int(max_hole_vert_num), _p(hole), _p(parent), _p(size), _p(verts), _p(moved), st),
+               "gsr_stitch_hole_move")
+    hv = torch.nonzero(hole).view(-1).to(torch.int32)
+    H = int(hv.shape[0])
+    if H:
+        kxy = torch.empty(H, dtype=torch.int64, device=dev)
+        kz = torch.empty(H, dtype=torch.int64, device=dev)
+        _lib.check(lib.gsr_stitch_pos_keys(H, _p(hv), _p(moved), _p(kxy), _p(kz), st), "gsr_stitch_pos_keys")
+        o1 = torch.sort(kz, stable=True)[1]
+        order = o1[torch.sort(kxy[o1], stable=True)[1]].contiguous()
+        head = torch.empty(H, dtype=torch.int32, device=dev)
+        _lib.check(lib.gsr_stitch_pos_heads(H, _p(order), _p(hv), _p(moved), _p(head), st), "gsr_stitch_pos_heads")
+        first = torch.cummax(head, 0)[0].contiguous()
+        _lib.check(lib.gsr_stitch_pos_remap(H, _p(order), _p(hv), _p(first), _p(remap), st), "gsr_stitch_pos_remap")
+    return (*_compact(moved, faces, remap, None, (), err), remap)
+
+
+@torch.no_grad()
+def merge_vertices_around_holes(verts: torch.Tensor, faces: torch.Tensor, max_hole_vert_num: int = 10) -> CutMesh:
+    """merge_vert_around_holes (refined_mesh.py:126-155) and the degenerate pass that follows it (:201-203).  Hole edges are the
+    face-edges whose vertex pair occurs other than exactly twice, hole vertices their ends.  Every component of the hole
+    vertices under the hole edges with at most max_hole_vert_num vertices moves to its lowest vertex's position; then ALL hole
+    vertices are grouped by equal position and every face entry is rewritten to its group's lowest vertex; faces with two
+    equal indices are dropped and the vertices renumbered.  -> CutMesh (face_mask over the input faces, vert_map with merged
+    vertices at their representative's new index).  The inputs are not modified."""
+    faces = _faces_i32(faces)
+    dev = faces.device
+    verts = _verts_f32(verts, dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    cut, _kscan, remap = _merge_holes(verts, faces, max_hole_vert_num, err)
+    V = int(verts.shape[0])
+    if V and cut.verts.shape[0]:
+        ident = torch.arange(int(cut.verts.shape[0]), dtype=torch.int32, device=dev)
+        out = torch.empty(V, dtype=torch.int32, device=dev)
+        # (remap, then the compaction's map; the second pair of maps is the identity)
+        _lib.check(_lib.load().gsr_stitch_vert_map(V, _p(remap), _p(cut.vert_map), _p(ident), _p(ident), _p(out), _stream()),
+                   "gsr_stitch_vert_map")
+        cut.vert_map = out
+    return cut
+
+
+@dataclass
+class StitchedMesh:
+    """What connect_two_meshes returns.  verts [Nv,3] f32, faces [Nf,3] int32: the stitched mesh; face_mask [F1 + F2] bool: the
+    faces of concat(mesh 1, mesh 2) kept after both degenerate passes (the reference's 'valid_face_mask', :205-206); vert_map
+    [V1 + V2] int32: old vertex (mesh 2's shifted by V1) -> new, -1 = dropped, merged vertices at their representative's new
+    index; n_faces_from_first: the kept faces that came from mesh 1 (they come first); max_dist: sqrt of the larger of the two
+    searches' largest d2, in float64 (:211); watertight: is_watertight(faces)."""
+    verts: torch.Tensor
+    faces: torch.Tensor
+    face_mask: torch.Tensor
+    vert_map: torch.Tensor
+    n_faces_from_first: int
+    max_dist: float
+    watertight: bool
+
+
+def _boundary_list(b: torch.Tensor, dev) -> torch.Tensor:
+    if b.dim() != 1 or b.dtype != torch.int32:
+        raise ValueError("a boundary list must be a 1-d int32 tensor")
+    if b.device != dev:
+        raise RuntimeError("a boundary list must be on the mesh's GPU")
+    if b.shape[0] == 0:
+        raise ValueError("a boundary list is empty: there is nothing to stitch along")
+    return b.contiguous()
+
+
+@torch.no_grad()
+def connect_two_meshes(verts1: torch.Tensor, faces1: torch.Tensor, boundary1: torch.Tensor, verts2: torch.Tensor,
+                       faces2: torch.Tensor, boundary2: torch.Tensor, max_hole_vert_num: int = 10) -> StitchedMesh:
+    """connect_two_meshes (refined_mesh.py:158-215).  The boundary vertices of mesh 2 snap to their nearest boundary vertex of
+    mesh 1 (:164-171), those of mesh 1 to their nearest of the snapped ones (:174-178); the meshes are concatenated, mesh 2's
+    faces shifted by V1 (:181-184); the listed vertices concat(boundary1, V1 + boundary2) are grouped by position and every
+    face entry naming one is rewritten to its group's earliest list entry (:188); degenerate faces go and the vertices are
+    renumbered (:193-195); merge_vertices_around_holes (:198-203).  See the module docstring for what "nearest", "equal
+    position" and "degenerate" mean here.  Boundary lists: int32, unique, in range, not empty, else ValueError; a boundary
+    position that is NaN or infinite raises ValueError.  The inputs are not modified.  Host reads: the lists' err word, the
+    two compactions' totals, the hole vertices' number, and one last read of the flags and maxima."""
+    lib = _lib.load()
+    faces1, faces2 = _faces_i32(faces1), _faces_i32(faces2)
+    dev = faces1.device
+    if faces2.device != dev:
+        raise RuntimeError("the two meshes must be on one GPU")
+    verts1, verts2 = _verts_f32(verts1, dev), _verts_f32(verts2, dev)
+    b1, b2 = _boundary_list(boundary1, dev), _boundary_list(boundary2, dev)
+    V1, V2, F1, F2 = int(verts1.shape[0]), int(verts2.shape[0]), int(faces1.shape[0]), int(faces2.shape[0])
+    B1, B2 = int(b1.shape[0]), int(b2.shape[0])
+    if V1 + V2 > 2 ** 31 - 1 or F1 + F2 > MAX_FACES:
+        raise ValueError("the two meshes together are too large for int32 indices")
+    st = _stream()
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    mark = torch.empty(max(V1, V2, 1), dtype=torch.int32, device=dev)
+    _lib.check(lib.gsr_stitch_check_list(B1, V1, _p(b1), _p(mark), _p(err), st), "gsr_stitch_check_list")
+    _lib.check(lib.gsr_stitch_check_list(B2, V2, _p(b2), _p(mark), _p(err), st), "gsr_stitch_check_list")
+    _raise_if_stitch(int(err.cpu()))                    # (before anything is gathered through the lists)
+    # the two snaps
+    pc1 = _gather(b1, verts1)
+    pc2 = _gather(b2, verts2)
+    n21, _d21, max21 = _nearest(pc2, pc1, err)
+    pc2s = _gather(n21, pc1)
+    n12, _d12, max12 = _nearest(pc1, pc2s, err)
+    verts = torch.cat([verts1, verts2])
+    verts[b1.long()] = _gather(n12, pc2s)
+    verts[b2.long() + V1] = pc2s
+    faces = torch.cat([faces1, faces2 + V1])
+    # reset_duplicate_vert over the listed vertices, the first degenerate pass
+    rep = torch.empty(B1, dtype=torch.int32, device=dev)
+    remap1 = torch.empty(V1 + V2, dtype=torch.int32, device=dev)
+    _lib.check(lib.gsr_stitch_snap_groups(B1, B2, V1, V2, _p(b1), _p(b2), _p(n21), _p(n12), _p(rep), _p(remap1), st),
+               "gsr_stitch_snap_groups")
+    cut1, kscan1 = _compact(verts, faces, remap1, None, (), err)      # (raises on NaN / a bad face index: err is read here)
+    # merge_vert_around_holes, the second degenerate pass
+    cut2, _kscan2, remap2 = _merge_holes(cut1.verts, cut1.faces, max_hole_vert_num, err)
+    F, V = F1 + F2, V1 + V2
+    face_mask = torch.empty(F, dtype=torch.bool, device=dev)
+    _lib.check(lib.gsr_stitch_compose_mask(F, _p(cut1.face_mask), _p(kscan1), _p(cut2.face_mask), int(cut2.face_mask.shape[0]),
+                                           _p(face_mask), st), "gsr_stitch_compose_mask")
+    vert_map = torch.empty(V, dtype=torch.int32, device=dev)
+    if cut1.verts.shape[0]:
+        _lib.check(lib.gsr_stitch_vert_map(V, _p(remap1), _p(cut1.vert_map), _p(remap2), _p(cut2.vert_map), _p(vert_map), st),
+                   "gsr_stitch_vert_map")
+    else:
+        vert_map.fill_(-1)
+    n_first = face_mask[:F1].sum(dtype=torch.int64).view(1)
+    if cut2.faces.shape[0]:
+        bad = _watertight_word(cut2.faces, err).to(torch.int64)
+    else:
+        bad = torch.ones(1, dtype=torch.int64, device=dev)
+    head = torch.cat([err.to(torch.int64), bad, n_first, max21, max12]).cpu().numpy()
+    _raise_if_stitch(int(head[0]))
+    d2max = head[3:5].view(np.float64)
+    return StitchedMesh(verts=cut2.verts, faces=cut2.faces, face_mask=face_mask, vert_map=vert_map, n_faces_from_first=int(head[2]),
+                        max_dist=float(np.sqrt(np.maximum(d2max[0], d2max[1]))), watertight=int(head[1]) == 0)
+
+
+def compose_face_mask(outer: torch.Tensor, inner: torch.Tensor) -> torch.Tensor:
+    """`m = outer.clone(); m[outer] = inner[:outer.sum()]` without a host read (refined_mesh.py:656-658): outer [F] bool, inner
+    [>= outer.sum()] bool."""
+    F = int(outer.shape[0])
+    out = torch.empty(F, dtype=torch.bool, device=outer.device)
+    scan = torch.cumsum(outer, 0, dtype=torch.int32)
+    outer, inner = outer.contiguous(), inner.contiguous()
+    _lib.check(_lib.load().gsr_stitch_compose_mask(F, _p(outer), _p(scan), _p(inner), int(inner.shape[0]), _p(out), _stream()),
+               "gsr_stitch_compose_mask")
+    return out
+
+
+@dataclass
+class RegionStitch:
+    """What harness.SurfaceGaussians.stitch_update_region returns for one box: stitched (StitchedMesh: the base cut, mesh 1,
+    joined with the patch, mesh 2); patch (CutMesh: the fused patch without its outlier components, colours in attrs[0]);
+    base_face_mask [F_base] bool: the faces of the UNCUT base mesh that are in the stitched mesh (refined_mesh.py:656-658)."""
+    stitched: StitchedMesh
+    patch: CutMesh
+    base_face_mask: torch.Tensor
+
+
 __all__ = ["MAX_FACES", "face_edge_counts", "face_components", "combine_overlap_aabbs", "UpdateRegions", "select_update_regions",
-           "CutMesh", "RegionCut", "cut_mesh_by_box", "boundary_vertices", "outlier_component_mask"]
+           "CutMesh", "RegionCut", "cut_mesh_by_box", "boundary_vertices", "outlier_component_mask", "NN_TILE", "NN_QUERIES",
+           "nearest_vertices", "select_faces", "is_watertight", "merge_vertices_around_holes", "StitchedMesh", "connect_two_meshes",
+           "compose_face_mask", "RegionStitch"]

@@ -628,6 +628,64 @@ int gsr_regions_boundary(int F, int V, const int* faces, const int* counts, cons
                          unsigned char* face_mark, int* err, gsr_stream_t stream);
 int gsr_regions_label_mask(int F, const int* label, const int* count, int min_count, unsigned char* out, gsr_stream_t stream);
 
+/* ---- The stitch of update_mesh_topo's back half: connect_two_meshes (gaustar_trainers/refined_mesh.py:158-215) with
+ * reset_duplicate_vert (:114-123) and merge_vert_around_holes (:126-155), the watertight test (:639) and the face-mask
+ * bookkeeping (:205-206, :656-658): gaustar_amd.regions.  fill_holes (:589, :617, :652), the chaining over boxes (:660-664) and
+ * the reference areas (:683-687) have no entry point.  Conventions as for gsr_regions_*: device pointers, asynchronous on
+ * `stream`, no float atomics, every output an integer or an exactly defined float.  err [1] int32 (zero before): bit 0 = an
+ * index outside its array, bit 1 = a coordinate that is NaN or infinite, bit 2 = an index listed twice.
+ * gsr_stitch_nn_tile / _nn_queries: the candidates staged in LDS at once and the queries of a workgroup (for the tests).
+ * gsr_stitch_nearest: replaces knn_points(K=1) (:166, :175).  queries [Bq,3], candidates [Bc,3] f32, Bc > 0.  In float64
+ *   without contraction, dx = (double) q.x - (double) c.x (dy, dz alike), d2 = (dx dx + dy dy) + dz dz; idx [Bq] int32, d2 [Bq]
+ *   f64 = the minimum of (d2, index) in lexicographic order: among equal distances the lowest index.  max_bits [1] uint64 = the
+ *   bits of the largest d2 written (cleared by the call; the doubles are not negative, so the bits' order is theirs).
+ * gsr_stitch_check_list: list [B] int32 must hold different indices in [0, V); mark [V] int32 is scratch.
+ * gsr_stitch_snap_groups: reset_duplicate_vert over concat(b1, V1 + b2) after the two snaps (:171, :178, :184-188).  n21 [B2] =
+ *   nearest(pc2 -> pc1), n12 [B1] = nearest(pc1 -> pc2 after its snap).  List entry p < B1 sits at pc1[n21[n12[p]]], entry
+ *   B1 + j at pc1[n21[j]], and n21 names a position by the lowest pc1 index holding it, so equal positions are equal source
+ *   indices.  rep [B1] int32 is scratch (per source the earliest list entry, by integer atomicMin); remap [V1 + V2] int32 =
+ *   the identity, but every listed vertex -> the earliest listed vertex at its position.
+ * gsr_stitch_mark: faces_out [F,3] = remap[faces] (faces where remap == NULL); keep [F] int32 = mask[f] where mask != NULL, else
+ *   the face's three indices differ (nondegenerate_faces, :193, :201, without trimesh's height test); referenced [V] int32 =
+ *   the vertex belongs to a kept face.  The scans of keep and referenced go to gsr_regions_cut_emit (update_faces,
+ *   remove_unreferenced_vertices, :194-195, :202-203).
+ * gsr_stitch_hole_components: merge_vert_around_holes :129-142.  counts [F,3] from gsr_regions_edge_runs.  pairs [3 F][2] int32
+ *   = the vertex pair of every face-edge of count != 2, (-1, -1) for the others; hole [V] uint8 = the vertex ends such an
+ *   edge; parent [V] int32 = the lowest vertex of its component under those edges; root_flag [V] int32 = 1 at the hole
+ *   vertices that are that lowest vertex.
+ * gsr_stitch_hole_move: :144-152.  size [V] int32 is scratch (at a lowest vertex, its component's vertices); verts_out [V,3] =
+ *   verts, with the hole vertices of components of at most max_hole_vert_num vertices at their lowest vertex's position.
+ * gsr_stitch_pos_keys / _pos_heads / _pos_remap: reset_duplicate_vert (:114-123) by true grouping.  list [H] int32: ascending
+ *   vertex indices.  key_xy, key_z [H] int64: the coordinates' bits, -0 as +0 (equal numbers, equal keys; their order means
+ *   nothing).  order [H] int64: the list entries after stable sorts by key_z, then key_xy.  head [H] int32 = i where sorted
+ *   entry i differs in position from entry i - 1 (NaN differs from everything), else 0; first = the running maximum of head.
+ *   remap [V] int32 (the identity before): every listed vertex -> the lowest listed vertex of its position.
+ * gsr_stitch_compose_mask: out [F] uint8 = outer[f] and inner[outer_scan[f] - 1] (outer_scan: the INCLUSIVE scan of outer):
+ *   `m = outer; m[outer] = inner` (:205-206, :656-658).
+ * gsr_stitch_vert_map: out [V] int32 = map2[remap2[map1[remap1[v]]]], -1 as soon as map1 says dropped.
+ * gsr_stitch_watertight: bad [1] int32 = some face-edge's count is not 2 (cleared by the call; trimesh is_watertight, :639,
+ *   also wants F > 0). */
+int gsr_stitch_nn_tile(void);
+int gsr_stitch_nn_queries(void);
+int gsr_stitch_nearest(int Bq, int Bc, const float* queries, const float* candidates, int* idx, double* d2,
+                       unsigned long long* max_bits, int* err, gsr_stream_t stream);
+int gsr_stitch_check_list(int B, int V, const int* list, int* mark, int* err, gsr_stream_t stream);
+int gsr_stitch_snap_groups(int B1, int B2, int V1, int V2, const int* b1, const int* b2, const int* n21, const int* n12, int* rep,
+                           int* remap, gsr_stream_t stream);
+int gsr_stitch_mark(int F, int V, const int* faces, const int* remap, const unsigned char* mask, int* faces_out, int* keep,
+                    int* referenced, int* err, gsr_stream_t stream);
+int gsr_stitch_hole_components(int F, int V, const int* faces, const int* counts, int* pairs, unsigned char* hole, int* parent,
+                               int* root_flag, int* err, gsr_stream_t stream);
+int gsr_stitch_hole_move(int V, int max_hole_vert_num, const unsigned char* hole, const int* parent, int* size, const float* verts,
+                         float* verts_out, gsr_stream_t stream);
+int gsr_stitch_pos_keys(int H, const int* list, const float* verts, long long* key_xy, long long* key_z, gsr_stream_t stream);
+int gsr_stitch_pos_heads(int H, const long long* order, const int* list, const float* verts, int* head, gsr_stream_t stream);
+int gsr_stitch_pos_remap(int H, const long long* order, const int* list, const int* first, int* remap, gsr_stream_t stream);
+int gsr_stitch_compose_mask(int F, const unsigned char* outer, const int* outer_scan, const unsigned char* inner, int n_inner,
+                            unsigned char* out, gsr_stream_t stream);
+int gsr_stitch_vert_map(int V, const int* remap1, const int* map1, const int* remap2, const int* map2, int* out, gsr_stream_t stream);
+int gsr_stitch_watertight(int F, const int* counts, int* bad, gsr_stream_t stream);
+
 /* Tuning aid: when device_buffer is non-NULL (4*T uint64), the two blend kernels record the start/end wall
  * clock (100 MHz) of every workgroup: forward at [2*b], backward at [2*(T+b)], b = launch index.  NULL = off. */
 int gsr_debug_set_trace(void* device_buffer);
