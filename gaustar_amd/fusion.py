@@ -10,6 +10,7 @@ FusionMesh goes to the cuts of gaustar_amd.regions (update_mesh_topo's front hal
     res = model.extract_mesh_fusion(cameras)              # the same, as a method of harness.SurfaceGaussians
     res = extract_mesh_fusion(refined_sugar, nerfmodel, voxel_size=0.008, sdf_trunc=0.02, depth_trunc=6)   # the reference's signature
     vol = TSDFVolume(lo, hi, 0.008, 0.02, device); integrate_views(vol, depth, rgb8, intrinsic, extrinsic)  # images given
+    vol = TSDFVolume.from_units(u0, nu, 0.008, 0.02, device); vol.tsdf.copy_(...)                            # a volume given
     verts, faces, colors = extract_triangle_mesh(vol)
 
 The integration follows Open3D's legacy ScalableTSDFVolume(voxel_length, sdf_trunc, RGB8) -- units of 16^3 voxels,
@@ -267,8 +268,21 @@ class TSDFVolume:
         lo, hi = np.asarray(lo, np.float64).reshape(3), np.asarray(hi, np.float64).reshape(3)
         if not (np.isfinite(lo).all() and np.isfinite(hi).all() and (hi >= lo).all()):
             raise ValueError("the box must be finite with hi >= lo")
+        self._allocate(*unit_range(lo, hi, voxel_size, sdf_trunc), voxel_size, sdf_trunc, device)
+
+    @classmethod
+    def from_units(cls, u0, nu, voxel_size: float = 0.008, sdf_trunc: float = 0.02, device="cuda") -> "TSDFVolume":
+        """The directory given itself: first unit index u0 [3] and units nu [3] along x, y, z.  (A box always comes with its
+        padding: at least 3 units per axis.)"""
+        if not (voxel_size > 0 and sdf_trunc > 0):
+            raise ValueError("voxel_size and sdf_trunc must be positive")
+        self = cls.__new__(cls)
+        self._allocate(np.asarray(u0, np.int64).reshape(3), np.asarray(nu, np.int64).reshape(3), voxel_size, sdf_trunc, device)
+        return self
+
+    def _allocate(self, u0, nu, voxel_size, sdf_trunc, device):
         self.voxel_size, self.sdf_trunc = float(voxel_size), float(sdf_trunc)
-        self.u0, self.nu = unit_range(lo, hi, voxel_size, sdf_trunc)
+        self.u0, self.nu = u0, nu
         self.grid = (ctypes.c_int * 6)(*[int(v) for v in self.u0], *[int(v) for v in self.nu])
         lib = _lib.load()
         if int(lib.gsr_fusion_volume_bytes(self.grid)) == 0:

@@ -73,18 +73,11 @@ def touch(vol, depth, intr, extr):
     return touched
 
 
-def integrate(vol, depth, rgb8, intr, extr):
-    """One view into the running means (in place); returns the touched units."""
-    fx, fy, cx, cy = (float(v) for v in intr)
-    E = np.asarray(extr, np.float64).reshape(4, 4)
-    depth = np.asarray(depth, f32)
-    H, W = depth.shape
-    touched = touch(vol, depth, intr, E)
-    voxel, truncf = vol["voxel"], f32(vol["trunc"])
+def _touched_voxels(vol, touched):
+    """Per voxel of the touched units: its global index (gx, gy, gz) and its centre (px, py, pz; f64)."""
+    voxel = vol["voxel"]
     L = float(UNIT) * voxel
     uz, uy, ux = np.nonzero(touched)
-    if len(uz) == 0:
-        return touched
     k = np.arange(UNIT)
     kz, ky, kx = np.meshgrid(k, k, k, indexing="ij")
 
@@ -96,6 +89,20 @@ def integrate(vol, depth, rgb8, intr, extr):
     gx, px = axis(ux, kx, 0)
     gy, py = axis(uy, ky, 1)
     gz, pz = axis(uz, kz, 2)
+    return gx, gy, gz, px, py, pz
+
+
+def integrate(vol, depth, rgb8, intr, extr):
+    """One view into the running means (in place); returns the touched units."""
+    fx, fy, cx, cy = (float(v) for v in intr)
+    E = np.asarray(extr, np.float64).reshape(4, 4)
+    depth = np.asarray(depth, f32)
+    H, W = depth.shape
+    touched = touch(vol, depth, intr, E)
+    truncf = f32(vol["trunc"])
+    if not touched.any():
+        return touched
+    gx, gy, gz, px, py, pz = _touched_voxels(vol, touched)
     X = E[0, 0] * px + E[0, 1] * py + E[0, 2] * pz + E[0, 3]
     Y = E[1, 0] * px + E[1, 1] * py + E[1, 2] * pz + E[1, 3]
     Z = E[2, 0] * px + E[2, 1] * py + E[2, 2] * pz + E[2, 3]
@@ -124,6 +131,74 @@ def integrate(vol, depth, rgb8, intr, extr):
     return touched
 
 
+def integration_census(vol, depth, intr, extr):
+    """Where the voxels of one view's touched units end in integrate()'s chain of tests: a dict of counts -- `behind` (Z <= 0),
+    `outside` the frame, on a `hole` (d == 0), `beyond` (sdf <= -trunc), `updated`, and of those `clamped` (t == 1) -- plus
+    `voxels`, their number: behind + outside + hole + beyond + updated.  The volume is not changed."""
+    fx, fy, cx, cy = (float(v) for v in intr)
+    E = np.asarray(extr, np.float64).reshape(4, 4)
+    depth = np.asarray(depth, f32)
+    H, W = depth.shape
+    touched = touch(vol, depth, intr, E)
+    out = dict.fromkeys(("voxels", "behind", "outside", "hole", "beyond", "clamped", "updated"), 0)
+    if not touched.any():
+        return out
+    _, _, _, px, py, pz = _touched_voxels(vol, touched)
+    X = E[0, 0] * px + E[0, 1] * py + E[0, 2] * pz + E[0, 3]
+    Y = E[1, 0] * px + E[1, 1] * py + E[1, 2] * pz + E[1, 3]
+    Z = E[2, 0] * px + E[2, 1] * py + E[2, 2] * pz + E[2, 3]
+    front = Z > 0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        uf = fx * X / Z + cx + 0.5
+        vf = fy * Y / Z + cy + 0.5
+        inside = front & (uf >= 1e-4) & (uf < W - 1e-4) & (vf >= 1e-4) & (vf < H - 1e-4)
+    Z, u, v = Z[inside], uf[inside].astype(np.int64), vf[inside].astype(np.int64)
+    d = depth[v, u]
+    seen = d > 0
+    Z, u, v, d = Z[seen], u[seen], v[seen], d[seen]
+    a = (u.astype(f32) - f32(cx)) / f32(fx)
+    c = (v.astype(f32) - f32(cy)) / f32(fy)
+    sdf = (d - Z.astype(f32)) * np.sqrt(a * a + c * c + f32(1))
+    near = sdf > -f32(vol["trunc"])
+    t = np.minimum(f32(1), sdf[near] / f32(vol["trunc"]))
+    out.update(voxels=len(px), behind=int((~front).sum()), outside=int((front & ~inside).sum()), hole=int((~seen).sum()),
+               beyond=int((~near).sum()), clamped=int((t == 1).sum()), updated=int(near.sum()))
+    return {k: int(n) for k, n in out.items()}
+
+
+def integrate_voxel_f64(centre, depth, rgb8, intr, extr, trunc):
+    """One voxel of one view into an EMPTY volume, in Python floats (f64), from the rule as include/gsr.h states it for
+    gsr_fusion_integrate -- one voxel at a time, no arrays, nothing shared with integrate() above.  centre: the voxel's centre
+    (x, y, z).  -> dict: `updated` (bool) and, as far as the chain of tests got, Z, uf, vf (the pixel coordinates before
+    truncation), d, norm (the depth-to-distance factor), sdf, and for an updated voxel tsdf (= t: the mean of one sample) and
+    color (rgb8[v, u] as a tuple)."""
+    import math
+    fx, fy, cx, cy = (float(v) for v in intr)
+    E = [[float(extr[r][c]) for c in range(4)] for r in range(3)]
+    x, y, z = (float(v) for v in centre)
+    H, W = len(depth), len(depth[0])
+    X, Y, Z = (E[r][0] * x + E[r][1] * y + E[r][2] * z + E[r][3] for r in range(3))
+    res = {"updated": False, "Z": Z}
+    if not Z > 0.0:
+        return res
+    uf, vf = fx * X / Z + cx + 0.5, fy * Y / Z + cy + 0.5
+    res.update(uf=uf, vf=vf)
+    if not (1e-4 <= uf < W - 1e-4 and 1e-4 <= vf < H - 1e-4):
+        return res
+    u, v = int(uf), int(vf)
+    d = float(depth[v][u])
+    res["d"] = d
+    if not d > 0.0:
+        return res
+    norm = math.sqrt(((u - cx) / fx) ** 2 + ((v - cy) / fy) ** 2 + 1.0)
+    sdf = (d - Z) * norm
+    res.update(norm=norm, sdf=sdf)
+    if not sdf > -float(trunc):
+        return res
+    res.update(updated=True, tsdf=min(1.0, sdf / float(trunc)), color=tuple(int(ch) for ch in rgb8[v][u]))
+    return res
+
+
 # ------------------------------------------------------------------------------------------------ marching cubes
 def _centres(vol, a):
     n = int(UNIT * vol["nu"][a])
@@ -132,8 +207,10 @@ def _centres(vol, a):
     return ((vol["u0"][a] + k // UNIT).astype(np.float64) * L + ((k % UNIT).astype(np.float64) + 0.5) * vol["voxel"]).astype(f32)
 
 
-def marching_cubes(vol, table=None):
-    """-> (verts [Nv,3] f32, faces [Nf,3] int32, colors [Nv,3] f32), in the order the kernels emit them."""
+def marching_cubes(vol, table=None, counts=False):
+    """-> (verts [Nv,3] f32, faces [Nf,3] int32, colors [Nv,3] f32), in the order the kernels emit them.  With `counts` a
+    fourth item: what gsr_fusion_count writes per voxel -- edge_mask uint8 (bit a: the edge along axis a carries a vertex),
+    vert_count and tri_count int32 [voxels] -- and, per cube, `valid` (bool) and `case` (0..255) [voxels]."""
     if table is None:
         from gaustar_amd import fusion
         table = fusion.mc_table()
@@ -210,6 +287,10 @@ def marching_cubes(vol, table=None):
     ids = vid[cube[:, None, None] + e_off[e], e_axis[e]]
     assert em[cube[:, None, None] + e_off[e], e_axis[e]][used].all()
     faces = ids[used].astype(np.int32)
+    if counts:
+        tri_count = np.where(valid.reshape(-1), ntri[cases.reshape(-1)], 0).astype(np.int32)
+        return verts, faces, colors, {"edge_mask": (em << np.arange(3)).sum(1).astype(np.uint8), "vert_count": cnt.astype(np.int32),
+                                      "tri_count": tri_count, "valid": valid.reshape(-1), "case": cases.reshape(-1)}
     return verts, faces, colors
 
 
