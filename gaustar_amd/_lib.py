@@ -171,6 +171,16 @@ SIGNATURES = {
     "gsr_stitch_compose_mask": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "gsr_stitch_vert_map": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gsr_stitch_watertight": (c_int, [c_int, c_void_p, c_void_p, c_void_p]),
+    # hole filling by the canonical rule, reference areas, mean edge length (refined_mesh.py:589, :617, :652, :683-687, :484-485):
+    # gaustar_amd.regions.fill_small_holes / update_mesh_topology
+    "gsr_splice_workspace_bytes": (c_size_t, []),
+    "gsr_splice_rim_edges": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_void_p]),
+    "gsr_splice_rim_census": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gsr_splice_rim_emit": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gsr_splice_face_areas": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gsr_splice_edge_lengths": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gsr_splice_mean": (c_int, [c_longlong, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gsr_adam_step": (c_int, [c_longlong, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_double, c_double, c_int,
                               c_void_p]),
     "gsr_adam_step_multi": (c_int, [c_int, POINTER(c_longlong), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),

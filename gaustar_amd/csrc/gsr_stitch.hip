@@ -1,6 +1,7 @@
 // gsr_stitch.hip -- the stitch of update_mesh_topo's back half (gaustar_trainers/refined_mesh.py:463-693): connect_two_meshes
 // (:158-215) with reset_duplicate_vert (:114-123) and merge_vert_around_holes (:126-155), the watertight test (:639) and the
-// face-mask bookkeeping (:656-658).  fill_holes, the chaining over boxes and the reference areas are not here.
+// face-mask bookkeeping (:656-658).  fill_holes and the reference areas are in gsr_splice.hip; the chaining over boxes is
+// gaustar_amd.regions.update_mesh_topology.
 //
 // The reference does this on the host with pytorch3d's knn_points, trimesh's group_rows / nondegenerate_faces /
 // remove_unreferenced_vertices and scipy's connected_components.  Here, over device tensors:

@@ -536,7 +536,8 @@ class SurfaceGaussians(nn.Module):
 
         Holes that fill_holes would have closed (:589, :617, :652) remain and can make `stitched.watertight` False.  What to do
         with a result that is not watertight (the reference skips the box, :639-643) is the caller's decision, and so is the
-        chaining over several boxes (:660-664): every RegionCut of cut_update_regions was cut from the uncut base mesh."""
+        chaining over several boxes (:660-664): every RegionCut of cut_update_regions was cut from the uncut base mesh.
+        update_mesh_topology below is the whole loop, with the holes filled and the boxes chained."""
         from . import regions
         patch, base = cut.fusion_patch, cut.base_cut
         if patch.verts.shape[0] == 0 or base.verts.shape[0] == 0:
@@ -552,6 +553,26 @@ class SurfaceGaussians(nn.Module):
         st = regions.connect_two_meshes(base.verts, base.faces, base_boundary, patch.verts, patch.faces, patch_boundary)
         base_face_mask = regions.compose_face_mask(base.face_mask, st.face_mask[:int(base.faces.shape[0])])
         return regions.RegionStitch(stitched=st, patch=patch, base_face_mask=base_face_mask)
+
+    def update_mesh_topology(self, res, fusion_mesh, aabb_pad: Optional[float] = None, delta_threshold: float = 0.6,
+                             cc_face_threshold: int = 80, **kw):
+        """update_mesh_topo and the choice of its pad (refined_mesh.py:463-693, :1033-1060) from detect_topology_errors' result
+        `res` and extract_mesh_fusion's `fusion_mesh`: the regions are selected once (they do not depend on the pad); with
+        aabb_pad=None the five pads are tried (regions.choose_aabb_pad) and the best one is run again, as the reference does;
+        kw goes to regions.update_mesh_topology (outlier_face_threshold, force_watertight, force_short_edge,
+        max_hole_vert_num).  -> regions.TopologyUpdate (its save() writes updated_mesh.obj and face_corr.npz), or None when
+        there is nothing to update or cc_update_num == 0 (:1041, :1054).  Unlike stitch_update_region this fills the small
+        holes (regions.fill_small_holes) and cuts every box out of what the previous box left."""
+        from . import regions
+        sel = self.topology_update_regions(res, delta_threshold=delta_threshold, cc_face_threshold=cc_face_threshold)
+        verts, faces = self._points.detach().float(), self._surface_mesh_faces.int()
+        run = lambda pad: regions.update_mesh_topology(verts, faces, sel, fusion_mesh, aabb_pad=pad, **kw)
+        if aabb_pad is None:
+            aabb_pad, _scores = regions.choose_aabb_pad(run)
+            if aabb_pad is None:
+                return None
+        out = run(aabb_pad)
+        return out if out.cc_update_num > 0 else None
 
     # -------------------------------------------------------------------------------- rendering
     def _settings(self, camera: NerfCamera, bg: torch.Tensor, sh_degree: int):

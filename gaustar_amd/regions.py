@@ -38,18 +38,31 @@ Where the stitch departs from the reference's libraries, on purpose:
     nothing).  trimesh.grouping.group_rows groups after rounding to 1e-8.
   * A face is degenerate iff two of its three vertex indices are equal.  trimesh's nondegenerate_faces also drops faces
     thinner than 1e-8; they are kept here, because dropping them opens a hole.
-What remains the reference's: fill_holes (:589, :617, :652; its result depends on trimesh's and networkx's cycle traversal),
-the chaining over several boxes (:660-664), the reference areas (:683-687), force_short_edge (:645-650) and the choice among
-the aabb_pad trials.  The reference applies find_boundary_verts and get_outlier_cc_mask after fill_holes; here they are
-primitives on whatever mesh they are given.
+  * fill_small_holes replaces trimesh's fill_holes (:589, :617, :652), whose result follows networkx's cycle_basis traversal,
+    by one canonical rule (its docstring): rims of 3 or 4 vertices are filled, the quad's diagonal passes through the rim's
+    lowest vertex, new faces come in ascending lowest vertex, and a component of boundary edges with a vertex of degree != 2
+    (two holes meeting at a vertex) is left alone, where trimesh may fill part of it.  Where trimesh's answer does not depend
+    on the traversal the two agree.
+
+The rest of update_mesh_topo is here as well (gsr_splice.hip):
+
+    filled = fill_small_holes(faces, n_verts)                           # fill_holes (:589, :617, :652): FilledMesh
+    area = face_areas(verts, faces)                                     # trimesh area_faces (:683), float64
+    upd = update_mesh_topology(verts, faces, regions, fusion_mesh)      # the loop over the boxes (:578-693): TopologyUpdate
+    pad, scores = choose_aabb_pad(run)                                  # the five aabb_pad trials (:1034-1048)
+
+The reference applies find_boundary_verts and get_outlier_cc_mask after fill_holes; boundary_vertices and
+outlier_component_mask are primitives on whatever mesh they are given, and update_mesh_topology gives them the filled one.
+Face colours are not carried through update_mesh_topology, and filled faces have none.
 """
 from __future__ import annotations
 
 import ctypes
 import itertools
 import math
+import os
 from dataclasses import dataclass
-from typing import List, Optional, Sequence, Tuple
+from typing import Callable, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -364,8 +377,8 @@ def boundary_vertices(verts: torch.Tensor, faces: torch.Tensor, box=None, cut_in
     """find_boundary_verts (refined_mesh.py:84-111): the vertices on edges that exactly one face-edge has, as ascending int32
     indices.  With a box and cut_inner=True those inside the box grown by `pad` (:94-99, grown in float64); with a box and
     cut_inner=False those that belong to a face with some but not all of its vertices inside the box (:101-111).
-    A primitive on the mesh it is given: the reference calls it after fill_holes (:589-600, :617-619), which is not part of
-    this module (see the module docstring)."""
+    A primitive on the mesh it is given: the reference calls it after fill_holes (:589-600, :617-619), and so does
+    update_mesh_topology, with fill_small_holes."""
     lib = _lib.load()
     faces = _faces_i32(faces)
     dev, F = faces.device, int(faces.shape[0])
@@ -395,8 +408,8 @@ def boundary_vertices(verts: torch.Tensor, faces: torch.Tensor, box=None, cut_in
 def outlier_component_mask(faces: torch.Tensor, face_num_threshold: Optional[float] = None) -> torch.Tensor:
     """get_outlier_cc_mask (refined_mesh.py:291-307): [F] bool, True for the faces of components with at least
     min(face_num_threshold, 0.3 max count) faces -- 0.3 max count when the threshold is None -- the product in float64 on the
-    host.  A primitive on the mesh it is given: the reference calls it after fill_holes (:589-592), which is not part of this
-    module.  One host read: the components' counts."""
+    host.  A primitive on the mesh it is given: the reference calls it after fill_holes (:589-592), and so does
+    update_mesh_topology, with fill_small_holes.  One host read: the components' counts."""
     lib = _lib.load()
     label, count = face_components(faces)
     F = int(label.shape[0])
@@ -719,7 +732,282 @@ class RegionStitch:
     base_face_mask: torch.Tensor
 
 
+# ------------------------------------------------------------------------------------------------ hole filling
+@dataclass
+class FilledMesh:
+    """What fill_small_holes returns.  faces [F + n_new,3] int32: the input faces, untouched and in their order, then the new
+    ones; n_new; rim_of_new [n_new] int32: the lowest vertex of the rim each new face closes; watertight:
+    is_watertight(faces)."""
+    faces: torch.Tensor
+    n_new: int
+    rim_of_new: torch.Tensor
+    watertight: bool
+
+
+def _fill(faces: torch.Tensor, V: int, err: torch.Tensor) -> Tuple[torch.Tensor, int, torch.Tensor]:
+    """faces [F,3] int32 contiguous -> (faces with the new ones appended, n_new, rim_of_new).  One host read: n_new and err."""
+    lib = _lib.load()
+    dev, F = faces.device, int(faces.shape[0])
+    none = torch.empty(0, dtype=torch.int32, device=dev)
+    if F == 0 or V == 0:
+        if F:
+            err.fill_(1)         # (faces without vertices: every index is outside the mesh)
+            _raise_if(1)
+        return faces, 0, none
+    st = _stream()
+    counts = _edge_runs(faces, None, None, 0, err)[1]
+    pairs = torch.empty(3 * F, 2, dtype=torch.int32, device=dev)
+    on = torch.empty(V, dtype=torch.uint8, device=dev)
+    degree = torch.empty(V, dtype=torch.int32, device=dev)
+    slots = torch.empty(V, 2, dtype=torch.int32, device=dev)
+    parent = torch.empty(V, dtype=torch.int32, device=dev)
+    flag = torch.empty(V, dtype=torch.int32, device=dev)
+    _lib.check(lib.gsr_splice_rim_edges(F, V, _p(faces), _p(counts), _p(pairs), _p(on), _p(degree), _p(slots), _p(parent), _p(flag),
+                                        _p(err), st), "gsr_splice_rim_edges")
+    size = torch.empty(V, dtype=torch.int32, device=dev)
+    bad = torch.empty(V, dtype=torch.int32, device=dev)
+    new_faces = torch.empty(V, dtype=torch.int32, device=dev)
+    _lib.check(lib.gsr_splice_rim_census(V, _p(degree), _p(parent), _p(size), _p(bad), _p(new_faces), st), "gsr_splice_rim_census")
+    scan = torch.cumsum(new_faces, 0, dtype=torch.int32)
+    head = torch.cat([scan[-1:], err]).cpu()
+    _raise_if(int(head[1]))
+    n_new = int(head[0])
+    if n_new == 0:
+        return faces, 0, none
+    out = torch.empty(n_new, 3, dtype=torch.int32, device=dev)
+    rim = torch.empty(n_new, dtype=torch.int32, device=dev)
+    _lib.check(lib.gsr_splice_rim_emit(V, n_new, _p(new_faces), _p(scan), _p(slots), _p(out), _p(rim), st), "gsr_splice_rim_emit")
+    return torch.cat([faces, out]), n_new, rim
+
+
+@torch.no_grad()
+def fill_small_holes(faces: torch.Tensor, n_verts: int) -> FilledMesh:
+    """trimesh's fill_holes (refined_mesh.py:589, :617, :652) by one canonical rule.  faces [F,3] over n_verts vertices; vertex
+    identity is the index.
+
+    Boundary face-edges are those whose vertex pair exactly one face-edge of the mesh has (face_edge_counts == 1, trimesh's
+    group_rows(edges_sorted, require_count=1)); each keeps the direction a -> b it has in its face.  Taken undirected they
+    split the vertices they touch into components.  A component is a RIM iff every one of its vertices ends exactly two
+    boundary edges; it is then a simple cycle of n vertices and n edges.  Rims with n == 3 or n == 4 are filled (trimesh's
+    hole_to_faces); every other component is left as it is: longer rims, and components with a vertex of degree != 2.
+
+    Let m be the rim's lowest vertex, x < y its two neighbours on the rim and, for a quad, o the vertex opposite m.  A triangle
+    rim gives the face (m, x, y); a quad rim the faces A = (m, x, o) and B = (o, y, m), so the diagonal always passes through
+    the lowest vertex.  A new face (a, b, c) is reversed to (a, c, b) iff the boundary face-edge between a and b runs a -> b in
+    its own face -- trimesh's winding repair, which tests the new face's first edge only: the triangle and A on the edge m-x,
+    B on the edge o-y, each on its own.  New faces are appended after the existing ones, rims in ascending m, A before B;
+    existing faces and all vertices are untouched (the reference asserts the same, :618).  No new face is dropped on geometry:
+    a rim's vertices are distinct indices, which is this project's definition of non-degenerate.
+
+    The departure from trimesh, on purpose: trimesh's result follows networkx's cycle_basis traversal, which decides the
+    diagonal of a quad, the order of the new faces, and what happens where two rims touch -- it may fill part of a component
+    with a vertex of degree != 2, which stays untouched here.  Wherever trimesh's answer does not depend on the traversal the
+    two agree.
+
+    An index outside [0, n_verts) raises ValueError.  Host reads: n_new with the err word, and the watertight word."""
+    faces = _faces_i32(faces)
+    V = int(n_verts)
+    if V < 0:
+        raise ValueError("n_verts must not be negative")
+    err = torch.zeros(1, dtype=torch.int32, device=faces.device)
+    out, n_new, rim = _fill(faces, V, err)
+    return FilledMesh(faces=out, n_new=n_new, rim_of_new=rim, watertight=is_watertight(out))
+
+
+# ------------------------------------------------------------------------------------------------ areas and means
+def _mean_f64(x: torch.Tensor) -> torch.Tensor:
+    """[1] float64 on the device: the mean of x [n > 0] float64 contiguous by the fixed-order reduction (the same bits every
+    call).  Nothing is read."""
+    lib = _lib.load()
+    ws = torch.empty(int(lib.gsr_splice_workspace_bytes()) // 8 + 1, dtype=torch.float64, device=x.device)
+    out = torch.empty(1, dtype=torch.float64, device=x.device)
+    _lib.check(lib.gsr_splice_mean(int(x.shape[0]), _p(x), _p(ws), _p(out), _stream()), "gsr_splice_mean")
+    return out
+
+
+def _areas(verts: torch.Tensor, faces: torch.Tensor, err: torch.Tensor) -> torch.Tensor:
+    F = int(faces.shape[0])
+    area = torch.empty(F, dtype=torch.float64, device=faces.device)
+    _lib.check(_lib.load().gsr_splice_face_areas(F, int(verts.shape[0]), _p(faces), _p(verts), _p(area), _p(err), _stream()),
+               "gsr_splice_face_areas")
+    return area
+
+
+@torch.no_grad()
+def face_areas(verts: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
+    """trimesh's area_faces (refined_mesh.py:683, :685): [F] float64.  On doubles converted from the f32 vertices, without
+    contraction: u = v1 - v0, w = v2 - v1, c = u x w, area = 0.5 sqrt((cx cx + cy cy) + cz cz).  One host read: the err word."""
+    faces = _faces_i32(faces)
+    verts = _verts_f32(verts, faces.device)
+    err = torch.zeros(1, dtype=torch.int32, device=faces.device)
+    area = _areas(verts, faces, err)
+    _raise_if(int(err.cpu()))
+    return area
+
+
+@torch.no_grad()
+def mean_edge_length(verts: torch.Tensor, faces: torch.Tensor) -> float:
+    """The mean length of the mesh's unique edges in float64 (refined_mesh.py:484-485): each length sqrt((dx dx + dy dy) + dz dz)
+    on the widened f32 coordinates, the mean by the fixed-order reduction.  NaN for a mesh without faces.  One host read."""
+    lib = _lib.load()
+    faces = _faces_i32(faces)
+    dev, F = faces.device, int(faces.shape[0])
+    verts = _verts_f32(verts, dev)
+    if F == 0:
+        return float("nan")
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    sel = torch.empty(F, dtype=torch.uint8, device=dev)
+    keys = torch.empty(3 * F, dtype=torch.int64, device=dev)
+    st = _stream()
+    _lib.check(lib.gsr_regions_edge_keys(F, _p(faces), None, None, 0, _p(sel), _p(keys), _p(err), st), "gsr_regions_edge_keys")
+    _raise_if(int(err.cpu()))                                 # (a negative index: its face's keys are the sentinel)
+    keys = torch.unique(keys)
+    n = int(keys.shape[0])
+    length = torch.empty(n, dtype=torch.float64, device=dev)
+    _lib.check(lib.gsr_splice_edge_lengths(n, int(verts.shape[0]), _p(keys), _p(verts), _p(length), _p(err), st), "gsr_splice_edge_lengths")
+    head = torch.cat([_mean_f64(length), err.to(torch.float64)]).cpu()
+    _raise_if(int(head[1]))
+    return float(head[0])
+
+
+# ------------------------------------------------------------------------------------------------ the loop over the boxes
+@dataclass
+class TopologyUpdate:
+    """What update_mesh_topology returns (refined_mesh.py:689-693).  verts [Nv,3] f32, faces [Nf,3] int32: the updated mesh;
+    the surviving faces of the input mesh are a prefix of `faces`, in their original order.  track_face_mask [F0] bool: the
+    input faces that survive; track_face_num: how many.  new_ref_area [Nf] f32 (:683-687): the INPUT mesh's areas for that
+    prefix, and for all the other faces the mean area of those other faces (NaN when there are none); new_area_mean: that mean
+    in float64; None when nothing_to_update.
+    cc_update_num mirrors the reference: the regions selected BEFORE merging minus the boxes that failed (an empty cut or no
+    boundary vertices, :586 / :601 / :611 / :620); a box skipped because its stitch is not watertight or too long still
+    counts; -1 when no region was selected, 0 when every box failed.  n_spliced, this project's addition: the boxes that
+    actually replaced the base mesh.  max_dist_in_connection: the running maximum of connect_two_meshes' max_dist, skipped
+    boxes included (:633).  Face colours are not carried, and filled faces have none."""
+    verts: torch.Tensor
+    faces: torch.Tensor
+    track_face_mask: torch.Tensor
+    track_face_num: int
+    new_ref_area: Optional[torch.Tensor]
+    new_area_mean: float
+    cc_update_num: int
+    n_spliced: int
+    max_dist_in_connection: float
+    nothing_to_update: bool
+
+    def save(self, directory: str) -> Tuple[str, str]:
+        """updated_mesh.obj (formats.save_obj) and face_corr.npz with the keys track_face_mask and ref_area
+        (np.savez_compressed), as refine.py:315-323 loads them (refined_mesh.py:1055-1060)."""
+        from . import formats
+        if self.new_ref_area is None:
+            raise ValueError("nothing was updated: there is no mesh to save")
+        os.makedirs(directory, exist_ok=True)
+        obj, npz = os.path.join(directory, "updated_mesh.obj"), os.path.join(directory, "face_corr.npz")
+        formats.save_obj(obj, self.verts.cpu().numpy(), self.faces.cpu().numpy())
+        np.savez_compressed(npz, track_face_mask=self.track_face_mask.cpu().numpy(), ref_area=self.new_ref_area.cpu().numpy())
+        return obj, npz
+
+    def gaussian_mask(self, G: int) -> torch.Tensor:
+        """[F0 G] bool: track_face_mask repeated G times per face (refine.py:382, pre_sh_mask)."""
+        return self.track_face_mask.repeat_interleave(int(G))
+
+
+@torch.no_grad()
+def update_mesh_topology(verts: torch.Tensor, faces: torch.Tensor, update_regions: UpdateRegions, fusion_mesh, aabb_pad: float = 0.02,
+                         outlier_face_threshold=50, force_watertight: bool = True, force_short_edge: bool = False,
+                         max_hole_vert_num: int = 10) -> TopologyUpdate:
+    """The loop of update_mesh_topo over the merged boxes (refined_mesh.py:578-693) on device tensors.  fusion_mesh: an object
+    with .verts [Vf,3] f32 and .faces [Ff,3] (fusion.FusionMesh).  Per box of update_regions.boxes(aabb_pad), in order:
+      1. the patch is cut from the WHOLE fusion mesh (:583); empty: the box fails (:586).  fill_small_holes (:589), the outlier
+         mask and select_faces (:590-599), its boundary vertices across the box (:600); none: the box fails.
+      2. the CURRENT base mesh -- what the previous boxes left -- is cut with cut_inner=True (:609); empty: fails.
+         fill_small_holes (:617), then the boundary vertices of the FILLED mesh inside the box grown by 0.02 (:619); none: fails.
+      3. connect_two_meshes (:628); max_dist joins the running maximum whatever happens next (:633).
+      4. force_watertight and a stitch that is not watertight: the box is skipped (:639-643).
+      5. force_short_edge and max_dist > 6 x the mean unique-edge length of the input mesh (:484-485, :645): skipped.
+      6. otherwise fill_small_holes on the stitch (:652), the box's mask over the current base mesh's faces from the cut's mask
+         and the stitch's mask before the base cut's filling (:656-658), base = stitched (:660), and
+         track_face_mask[track_face_mask] = that mask's first track_face_num entries (:663-664).
+    Then the reference areas (:683-687).  See TopologyUpdate for cc_update_num and n_spliced."""
+    faces = _faces_i32(faces)
+    dev, F0 = faces.device, int(faces.shape[0])
+    verts = _verts_f32(verts, dev)
+    fv, ff = _verts_f32(fusion_mesh.verts, dev), _faces_i32(fusion_mesh.faces)
+    track = torch.ones(F0, dtype=torch.bool, device=dev)
+    if update_regions.nothing_to_update:
+        return TopologyUpdate(verts, faces, track, F0, None, float("nan"), -1, 0, 0.0, True)
+    edge_len = mean_edge_length(verts, faces) if force_short_edge else None
+    base_v, base_f, track_num = verts, faces, F0
+    failed, n_spliced, max_dist = 0, 0, 0.0
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    for box in update_regions.boxes(aabb_pad):
+        patch = cut_mesh_by_box(fv, ff, box, False)
+        if patch.verts.shape[0] == 0:
+            failed += 1
+            continue
+        pf = _fill(patch.faces, int(patch.verts.shape[0]), err)[0]
+        patch = select_faces(patch.verts, pf, outlier_component_mask(pf, outlier_face_threshold))
+        pb = boundary_vertices(patch.verts, patch.faces, box, cut_inner=False)
+        if pb.shape[0] == 0:
+            failed += 1
+            continue
+        cut = cut_mesh_by_box(base_v, base_f, box, True)
+        if cut.verts.shape[0] == 0:
+            failed += 1
+            continue
+        n_cut = int(cut.faces.shape[0])
+        cf = _fill(cut.faces, int(cut.verts.shape[0]), err)[0]
+        bb = boundary_vertices(cut.verts, cf, box, cut_inner=True)
+        if bb.shape[0] == 0:
+            failed += 1
+            continue
+        st = connect_two_meshes(cut.verts, cf, bb, patch.verts, patch.faces, pb, max_hole_vert_num)
+        max_dist = max(max_dist, st.max_dist)
+        if force_watertight and not st.watertight:
+            continue
+        if force_short_edge and st.max_dist > 6 * edge_len:
+            continue
+        filled = _fill(st.faces, int(st.verts.shape[0]), err)[0]
+        mask_cc = compose_face_mask(cut.face_mask, st.face_mask[:n_cut])
+        base_v, base_f = st.verts, filled
+        track = compose_face_mask(track, mask_cc[:track_num])
+        track_num = int(track.sum().cpu())
+        n_spliced += 1
+    Fn = int(base_f.shape[0])
+    ref_area = torch.empty(Fn, dtype=torch.float32, device=dev)
+    ref_area[:track_num] = _areas(verts, faces, err)[track].to(torch.float32)
+    mean = float("nan")
+    if Fn > track_num:
+        rest = _areas(base_v, base_f, err)[track_num:].contiguous()
+        m = _mean_f64(rest)
+        ref_area[track_num:] = m.to(torch.float32)
+        head = torch.cat([m, err.to(torch.float64)]).cpu()
+        mean = float(head[0])
+        _raise_if(int(head[1]))
+    else:
+        _raise_if(int(err.cpu()))
+    return TopologyUpdate(verts=base_v, faces=base_f, track_face_mask=track, track_face_num=track_num, new_ref_area=ref_area,
+                          new_area_mean=mean, cc_update_num=update_regions.n_regions - failed, n_spliced=n_spliced,
+                          max_dist_in_connection=float(max_dist), nothing_to_update=False)
+
+
+def choose_aabb_pad(run: Callable[[float], TopologyUpdate], pads: Sequence[float] = (0.01, 0.015, 0.02, 0.025, 0.03)):
+    """The aabb_pad trials of refined_mesh.py:1034-1048.  run(pad) -> an object with cc_update_num, max_dist_in_connection and
+    nothing_to_update.  Every pad scores 100 unless its run has cc_update_num > 0, then its max_dist_in_connection; the trials
+    stop at the first run with nothing_to_update.  -> (the pad of the lowest score -- np.argmin, so the first among equals --
+    or None when there was nothing to update, the scores as a list)."""
+    pads = [float(p) for p in pads]
+    scores = [100.0] * len(pads)
+    for i, pad in enumerate(pads):
+        out = run(pad)
+        if out.nothing_to_update:
+            return None, scores
+        if out.cc_update_num > 0:
+            scores[i] = float(out.max_dist_in_connection)
+    return pads[int(np.argmin(np.asarray(scores, np.float64)))], scores
+
+
 __all__ = ["MAX_FACES", "face_edge_counts", "face_components", "combine_overlap_aabbs", "UpdateRegions", "select_update_regions",
            "CutMesh", "RegionCut", "cut_mesh_by_box", "boundary_vertices", "outlier_component_mask", "NN_TILE", "NN_QUERIES",
            "nearest_vertices", "select_faces", "is_watertight", "merge_vertices_around_holes", "StitchedMesh", "connect_two_meshes",
-           "compose_face_mask", "RegionStitch"]
+           "compose_face_mask", "RegionStitch", "FilledMesh", "fill_small_holes", "face_areas", "mean_edge_length", "TopologyUpdate",
+           "update_mesh_topology", "choose_aabb_pad"]

@@ -630,8 +630,8 @@ int gsr_regions_label_mask(int F, const int* label, const int* count, int min_co
 
 /* ---- The stitch of update_mesh_topo's back half: connect_two_meshes (gaustar_trainers/refined_mesh.py:158-215) with
  * reset_duplicate_vert (:114-123) and merge_vert_around_holes (:126-155), the watertight test (:639) and the face-mask
- * bookkeeping (:205-206, :656-658): gaustar_amd.regions.  fill_holes (:589, :617, :652), the chaining over boxes (:660-664) and
- * the reference areas (:683-687) have no entry point.  Conventions as for gsr_regions_*: device pointers, asynchronous on
+ * bookkeeping (:205-206, :656-658): gaustar_amd.regions.  fill_holes (:589, :617, :652) and the reference areas (:683-687) are
+ * gsr_splice_* below.  Conventions as for gsr_regions_*: device pointers, asynchronous on
  * `stream`, no float atomics, every output an integer or an exactly defined float.  err [1] int32 (zero before): bit 0 = an
  * index outside its array, bit 1 = a coordinate that is NaN or infinite, bit 2 = an index listed twice.
  * gsr_stitch_nn_tile / _nn_queries: the candidates staged in LDS at once and the queries of a workgroup (for the tests).
@@ -685,6 +685,50 @@ int gsr_stitch_compose_mask(int F, const unsigned char* outer, const int* outer_
                             unsigned char* out, gsr_stream_t stream);
 int gsr_stitch_vert_map(int V, const int* remap1, const int* map1, const int* remap2, const int* map2, int* out, gsr_stream_t stream);
 int gsr_stitch_watertight(int F, const int* counts, int* bad, gsr_stream_t stream);
+
+/* ---- The rest of update_mesh_topo (gaustar_trainers/refined_mesh.py:463-693): fill_holes (:589, :617, :652) by a canonical rule
+ * of this project, the reference areas (:683-687) and the mean unique-edge length of force_short_edge (:484-485):
+ * gaustar_amd.regions.fill_small_holes / update_mesh_topology.  Conventions as for gsr_regions_* and gsr_stitch_*: device
+ * pointers, asynchronous on `stream`, no host synchronisation, no float atomics.  err [1] int32 (zero before): bit 0 = a vertex
+ * index outside [0, V); such a face is left out.
+ * The rule.  Boundary face-edges are those of count exactly 1 (gsr_regions_edge_runs; trimesh's group_rows(edges_sorted,
+ *   require_count=1)), each with the direction a -> b it has in its face.  Taken undirected they split the vertices they touch
+ *   into components; a component is a rim iff every one of its vertices ends exactly two boundary edges, and is then a simple
+ *   cycle.  Rims of 3 or 4 vertices are filled (trimesh's hole_to_faces); every other component is left as it is.  With m the
+ *   rim's lowest vertex, x < y its two neighbours on the rim and o the vertex opposite m: a triangle rim gives (m, x, y), a quad
+ *   rim A = (m, x, o) and B = (o, y, m) -- the diagonal passes through the lowest vertex.  A new face (a, b, c) is reversed to
+ *   (a, c, b) iff the boundary edge between a and b runs a -> b in its own face (trimesh's winding repair, which tests the new
+ *   face's first edge only): the triangle and A on m-x, B on o-y, each on its own.  New faces are appended after the existing
+ *   ones, rims in ascending m, A before B.  No new face is dropped on geometry.  Departure from trimesh, on purpose: where its
+ *   answer depends on networkx's cycle_basis traversal (the diagonal, the order, a component with a vertex of degree != 2, which
+ *   it may fill in part) this rule decides; elsewhere the two agree.
+ * gsr_splice_workspace_bytes: the bytes of gsr_splice_mean's workspace.
+ * gsr_splice_rim_edges: counts [F,3] from gsr_regions_edge_runs.  pairs [3 F][2] int32 = the vertex pair (a, b) of every
+ *   face-edge of count 1, (-1, -1) for the others; on_rim [V] uint8 = the vertex ends such an edge; degree [V] int32 = how many
+ *   it ends; slots [V][2] uint32 = the first two of them as neighbour << 1 | (the edge leaves this vertex), in no defined order;
+ *   parent [V] int32 = the lowest vertex of its component under those edges; root_flag [V] int32 = 1 at the rim vertices that
+ *   are that lowest vertex.
+ * gsr_splice_rim_census: size, bad [V] int32 are scratch (at a lowest vertex: its component's vertices; some degree != 2);
+ *   new_faces [V] int32 = 1 / 2 at the lowest vertex of a rim of 3 / 4 vertices, 0 elsewhere.
+ * gsr_splice_rim_emit: new_scan = the INCLUSIVE scan of new_faces, n_new its total.  faces_out [n_new,3] int32 and rim_of_new
+ *   [n_new] int32 (the m of each new face), a rim's faces at new_scan[m] - new_faces[m].
+ * gsr_splice_face_areas: area [F] f64 = trimesh's area_faces: on doubles converted from the f32 vertices, without contraction,
+ *   u = v1 - v0, w = v2 - v1, c = u x w (each component two rounded products and one subtraction), s = (cx cx + cy cy) + cz cz,
+ *   area = 0.5 sqrt(s); 0 for a face left out.
+ * gsr_splice_edge_lengths: keys [n] int64 = min << 32 | max of a vertex pair (gsr_regions_edge_keys, made unique by the
+ *   caller); length [n] f64 = sqrt((dx dx + dy dy) + dz dz) on the widened coordinates.
+ * gsr_splice_mean: mean [1] f64 = (the sum of x [n] f64, n > 0) / n by a fixed-order reduction: min(ceil(n / 256), 2048)
+ *   workgroups whose threads add their elements in ascending index, a shuffle tree per wave, the waves in order, then one
+ *   workgroup's strided sums and tree.  The same bits from call to call. */
+size_t gsr_splice_workspace_bytes(void);
+int gsr_splice_rim_edges(int F, int V, const int* faces, const int* counts, int* pairs, unsigned char* on_rim, int* degree,
+                         unsigned int* slots, int* parent, int* root_flag, int* err, gsr_stream_t stream);
+int gsr_splice_rim_census(int V, const int* degree, const int* parent, int* size, int* bad, int* new_faces, gsr_stream_t stream);
+int gsr_splice_rim_emit(int V, int n_new, const int* new_faces, const int* new_scan, const unsigned int* slots, int* faces_out,
+                        int* rim_of_new, gsr_stream_t stream);
+int gsr_splice_face_areas(int F, int V, const int* faces, const float* verts, double* area, int* err, gsr_stream_t stream);
+int gsr_splice_edge_lengths(int n, int V, const long long* keys, const float* verts, double* length, int* err, gsr_stream_t stream);
+int gsr_splice_mean(long long n, const double* x, void* workspace, double* mean, gsr_stream_t stream);
 
 /* Tuning aid: when device_buffer is non-NULL (4*T uint64), the two blend kernels record the start/end wall
  * clock (100 MHz) of every workgroup: forward at [2*b], backward at [2*(T+b)], b = launch index.  NULL = off. */
