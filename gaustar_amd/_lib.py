@@ -181,6 +181,14 @@ SIGNATURES = {
     "gsr_splice_face_areas": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gsr_splice_edge_lengths": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gsr_splice_mean": (c_int, [c_longlong, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # the colours a frame hands to the next one (sugar_model.py:578-588, :235-240, :386; refined_mesh.py:183):
+    # gaustar_amd.handover
+    "gsr_handover_face_colors": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "gsr_handover_vertex_to_face": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "gsr_handover_face_to_vertex": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gsr_handover_sh_dc": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gsr_handover_gather": (c_int, [c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                    c_void_p]),
     "gsr_adam_step": (c_int, [c_longlong, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_double, c_double, c_int,
                               c_void_p]),
     "gsr_adam_step_multi": (c_int, [c_int, POINTER(c_longlong), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),

@@ -555,14 +555,16 @@ class SurfaceGaussians(nn.Module):
         return regions.RegionStitch(stitched=st, patch=patch, base_face_mask=base_face_mask)
 
     def update_mesh_topology(self, res, fusion_mesh, aabb_pad: Optional[float] = None, delta_threshold: float = 0.6,
-                             cc_face_threshold: int = 80, **kw):
+                             cc_face_threshold: int = 80, colors: bool = False, **kw):
         """update_mesh_topo and the choice of its pad (refined_mesh.py:463-693, :1033-1060) from detect_topology_errors' result
         `res` and extract_mesh_fusion's `fusion_mesh`: the regions are selected once (they do not depend on the pad); with
         aabb_pad=None the five pads are tried (regions.choose_aabb_pad) and the best one is run again, as the reference does;
         kw goes to regions.update_mesh_topology (outlier_face_threshold, force_watertight, force_short_edge,
         max_hole_vert_num).  -> regions.TopologyUpdate (its save() writes updated_mesh.obj and face_corr.npz), or None when
         there is nothing to update or cc_update_num == 0 (:1041, :1054).  Unlike stitch_update_region this fills the small
-        holes (regions.fill_small_holes) and cuts every box out of what the previous box left."""
+        holes (regions.fill_small_holes) and cuts every box out of what the previous box left.  colors=True: the result also
+        carries colour (TopologyUpdate.with_colors(self.color_mesh()[2], fusion_mesh.colors)), so that its save() writes a
+        coloured updated_mesh.obj from which from_mesh builds the re-refined model (train_seq.py:184-213)."""
         from . import regions
         sel = self.topology_update_regions(res, delta_threshold=delta_threshold, cc_face_threshold=cc_face_threshold)
         verts, faces = self._points.detach().float(), self._surface_mesh_faces.int()
@@ -572,7 +574,60 @@ class SurfaceGaussians(nn.Module):
             if aabb_pad is None:
                 return None
         out = run(aabb_pad)
-        return out if out.cc_update_num > 0 else None
+        if out.cc_update_num <= 0:
+            return None
+        return out.with_colors(self.color_mesh()[2], fusion_mesh.colors) if colors else out
+
+    # -------------------------------------------------------------------------------- the frame hand-over
+    def color_mesh(self):
+        """get_color_mesh (sugar_model.py:578-588) on the device: (verts [V,3] f32, faces [F,3] int64, face_rgba [F,4] uint8), a
+        face's colour from the mean SH dc of its Gaussians (handover.sh_face_colors), alpha 255."""
+        from . import handover
+        self._fence(self._points, self._sh_coordinates_dc)
+        rgba = handover.sh_face_colors(self._sh_coordinates_dc.detach(), self.n_gaussians_per_surface_triangle)
+        return self._points.detach(), self._surface_mesh_faces, rgba
+
+    def save_color_mesh(self, path: str) -> None:
+        """color_mesh.obj (refined_mesh.py:1223-1226): the face colours become vertex colours (handover.face_to_vertex_colors,
+        this project's statement of trimesh's conversion on OBJ export) and are written as `v x y z r g b` with u8 / 255 --
+        the file warp.warp_mesh reads and carries to warp_smooth.obj, and the reference mesh of every later frame
+        (train_seq.py:115)."""
+        from . import formats, handover
+        verts, faces, rgba = self.color_mesh()
+        vrgba = handover.face_to_vertex_colors(faces, rgba, int(verts.shape[0]))
+        formats.save_obj(path, verts.cpu().numpy(), faces.cpu().numpy(), vrgba[:, :3].cpu().numpy().astype(np.float64) / 255.0)
+
+    @classmethod
+    def from_mesh(cls, verts, faces, vertex_colors, n_gaussians_per_surface_triangle: int = 6, sh_levels: int = 4,
+                  initial_opacity: float = 0.1, **kw) -> "SurfaceGaussians":
+        """A fresh model on a coloured mesh, as the reference's constructor builds one from surface_mesh_to_bind
+        (sugar_model.py:228-240, :315, :386).  verts [V,3], faces [F,3], vertex_colors [V,>=3] in [0,1]: tensors or numpy arrays
+        of any float / integer width (formats.load_obj's float64 and int64 among them).  `_sh_coordinates_dc` is RGB2SH of the
+        barycentric blend of every face's vertex colours (handover.sh_dc_from_vertex_colors), `_sh_coordinates_rest` zero,
+        `all_densities` inverse_sigmoid(initial_opacity) -- the reference's value when opacities are learnt (:315).
+        kw: `device` (default: the tensors' GPU, else the current one) and __init__'s other arguments.  Missing colours
+        raise ValueError."""
+        from . import handover
+        if vertex_colors is None:
+            raise ValueError("from_mesh needs vertex colours: the mesh file has none")
+        dev = kw.pop("device", None)
+        if dev is None:
+            dev = verts.device if isinstance(verts, torch.Tensor) and verts.device.type == "cuda" else torch.device("cuda", torch.cuda.current_device())
+        v = torch.as_tensor(np.asarray(verts) if not isinstance(verts, torch.Tensor) else verts).to(dev, torch.float32)
+        f = torch.as_tensor(np.asarray(faces) if not isinstance(faces, torch.Tensor) else faces).to(dev, torch.long)
+        c = torch.as_tensor(np.asarray(vertex_colors) if not isinstance(vertex_colors, torch.Tensor) else vertex_colors).to(dev, torch.float32)
+        if c.dim() != 2 or c.shape[0] != v.shape[0] or c.shape[1] < 3:
+            raise ValueError(f"vertex_colors must be [V,>=3] with V = {int(v.shape[0])}, got {tuple(c.shape)}")
+        if not 0.0 < float(initial_opacity) < 1.0:
+            raise ValueError("initial_opacity must lie strictly between 0 and 1")
+        m = cls(v, f, n_gaussians_per_surface_triangle=n_gaussians_per_surface_triangle, sh_levels=sh_levels, **kw)
+        x = torch.full((1,), float(initial_opacity), dtype=torch.float32)
+        density = float(torch.log(x / (1 - x)))                  # inverse_sigmoid in f32, as the reference forms it
+        with torch.no_grad():
+            dc = handover.sh_dc_from_vertex_colors(m._surface_mesh_faces, c, m.surface_triangle_bary_coords[..., 0].contiguous())
+            m._sh_coordinates_dc.copy_(dc.view(-1, 1, 3))
+            m.all_densities.fill_(density)
+        return m
 
     # -------------------------------------------------------------------------------- rendering
     def _settings(self, camera: NerfCamera, bg: torch.Tensor, sh_degree: int):
@@ -795,3 +850,20 @@ class SurfaceGaussians(nn.Module):
         bg4 = torch.cat([bg_rgb, torch.full((1,), float(max_depth), device=dev)])   # RGB + one depth channel
         img, _ = self.render_channels(camera, bg4, sh_deg=sh_deg, depth_channels=1)
         return img[:3].permute(1, 2, 0), img[3]
+
+
+def tracked_pre_sh(pre, track_face_mask=None, G: int = 6):
+    """refine.py:379-383: the previous frame's SH coefficients a re-refined model is held to.  `pre`: a state dict (the
+    previous model's state_dict()) or a checkpoint holding one under 'state_dict'.  -> (pre_sh_dc [M,3], pre_sh [M,K,3]):
+    cat(_sh_coordinates_dc, _sh_coordinates_rest) over the Gaussians of the faces that survived the topology update
+    (track_face_mask [F0] bool, regions.TopologyUpdate.track_face_mask or regions.load_tracking; each face's G Gaussians
+    together, as TopologyUpdate.gaussian_mask(G) repeats it), all of them without a mask.  The surviving faces are the prefix of
+    the updated mesh's faces, so pre_sh_dc is ready for rgbd_step's param_reg=dict(pre_sh_dc=...)."""
+    sd = pre["state_dict"] if "state_dict" in pre else pre
+    sh = torch.cat([sd["_sh_coordinates_dc"], sd["_sh_coordinates_rest"]], dim=1).detach()
+    if track_face_mask is not None:
+        mask = torch.as_tensor(track_face_mask).to(device=sh.device, dtype=torch.bool)
+        if mask.dim() != 1 or mask.shape[0] * int(G) != sh.shape[0]:
+            raise ValueError(f"track_face_mask must be [F0] with F0 G = {int(sh.shape[0])} Gaussians, got {tuple(mask.shape)} and G = {int(G)}")
+        sh = sh[mask.repeat_interleave(int(G))]
+    return sh[:, 0].contiguous(), sh

@@ -53,7 +53,14 @@ The rest of update_mesh_topo is here as well (gsr_splice.hip):
 
 The reference applies find_boundary_verts and get_outlier_cc_mask after fill_holes; boundary_vertices and
 outlier_component_mask are primitives on whatever mesh they are given, and update_mesh_topology gives them the filled one.
-Face colours are not carried through update_mesh_topology, and filled faces have none.
+update_mesh_topology records where every face of its result came from (TopologyUpdate.face_origin), and
+TopologyUpdate.with_colors carries the colours along it (gsr_handover.hip, gaustar_amd.handover): an input face keeps its colour,
+a fusion face is coloured from its vertices, a filled face has none -- a departure from trimesh, whose fill_holes gives new faces
+a library default colour that would tint the rim vertices; the roundings of the vertex <-> face conversions are this project's
+statement of trimesh's, and parity with trimesh is not pinned (it is not a dependency).
+
+    upd = update_mesh_topology(...).with_colors(base_face_rgba, fusion_mesh.colors)    # face_colors, vertex_colors; save() writes them
+    track_face_mask, ref_area = load_tracking("face_corr.npz")          # what refine.py:315-323 reads back
 """
 from __future__ import annotations
 
@@ -882,7 +889,12 @@ class TopologyUpdate:
     boundary vertices, :586 / :601 / :611 / :620); a box skipped because its stitch is not watertight or too long still
     counts; -1 when no region was selected, 0 when every box failed.  n_spliced, this project's addition: the boxes that
     actually replaced the base mesh.  max_dist_in_connection: the running maximum of connect_two_meshes' max_dist, skipped
-    boxes included (:633).  Face colours are not carried, and filled faces have none."""
+    boxes included (:633).
+    face_origin [Nf] int32, where every face of `faces` came from: k >= 0 = face k of the input mesh (the prefix is therefore
+    nonzero(track_face_mask)); -1 - k = face k of the fusion mesh; handover.FILLED (INT32_MIN) = a face made by
+    fill_small_holes, at any of the three places it runs.  fusion_faces, fusion_n_verts: the fusion mesh face_origin indexes.
+    Face colours are not carried by update_mesh_topology itself: with_colors() fills face_colors [Nf,4] and vertex_colors
+    [Nv,4] uint8 from face_origin, and filled faces have none (0, 0, 0, 0)."""
     verts: torch.Tensor
     faces: torch.Tensor
     track_face_mask: torch.Tensor
@@ -893,16 +905,46 @@ class TopologyUpdate:
     n_spliced: int
     max_dist_in_connection: float
     nothing_to_update: bool
+    face_origin: Optional[torch.Tensor] = None
+    fusion_faces: Optional[torch.Tensor] = None
+    fusion_n_verts: int = 0
+    face_colors: Optional[torch.Tensor] = None
+    vertex_colors: Optional[torch.Tensor] = None
+
+    def with_colors(self, base_face_rgba: torch.Tensor, fusion_vertex_colors: torch.Tensor) -> "TopologyUpdate":
+        """Carry colour through the update, as the reference carries face_colors through connect_two_meshes
+        (refined_mesh.py:183).  base_face_rgba [F0,4] uint8: the input mesh's face colours
+        (harness.SurfaceGaussians.color_mesh); fusion_vertex_colors [Vf,>=3] in [0,1] (fusion.FusionMesh.colors).  Fills
+        face_colors [Nf,4] uint8 -- an input face keeps its colour, a fusion face gets handover.vertex_to_face_colors of its
+        vertices, a filled face (0, 0, 0, 0) -- and vertex_colors [Nv,4] uint8 = handover.face_to_vertex_colors of them, what
+        save() writes.  Every vertex of a filled face lies on a rim, so it has a coloured face.  -> self.
+
+        Two departures from trimesh, on purpose (handover's docstring): its fill_holes gives new faces a library default
+        colour, which would tint the rim vertices -- here filled faces carry none and are left out of the mean; and the
+        roundings of the two conversions are this project's statement of trimesh's, whose parity is not pinned (trimesh is not
+        a dependency)."""
+        from . import handover
+        if self.face_origin is None or self.fusion_faces is None:
+            raise ValueError("this TopologyUpdate has no face_origin: it was not made by update_mesh_topology")
+        if base_face_rgba.shape[0] != self.track_face_mask.shape[0]:
+            raise ValueError("base_face_rgba must have one row per face of the input mesh")
+        if fusion_vertex_colors.shape[0] != self.fusion_n_verts:
+            raise ValueError("fusion_vertex_colors must have one row per vertex of the fusion mesh")
+        self.face_colors = handover.gather_face_colors(self.face_origin, base_face_rgba, self.fusion_faces, fusion_vertex_colors)
+        self.vertex_colors = handover.face_to_vertex_colors(self.faces, self.face_colors, int(self.verts.shape[0]))
+        return self
 
     def save(self, directory: str) -> Tuple[str, str]:
         """updated_mesh.obj (formats.save_obj) and face_corr.npz with the keys track_face_mask and ref_area
-        (np.savez_compressed), as refine.py:315-323 loads them (refined_mesh.py:1055-1060)."""
+        (np.savez_compressed), as refine.py:315-323 loads them (refined_mesh.py:1055-1060).  With vertex_colors set
+        (with_colors) the vertex lines are `v x y z r g b`, the colours u8 / 255 in float64."""
         from . import formats
         if self.new_ref_area is None:
             raise ValueError("nothing was updated: there is no mesh to save")
         os.makedirs(directory, exist_ok=True)
         obj, npz = os.path.join(directory, "updated_mesh.obj"), os.path.join(directory, "face_corr.npz")
-        formats.save_obj(obj, self.verts.cpu().numpy(), self.faces.cpu().numpy())
+        colours = None if self.vertex_colors is None else self.vertex_colors[:, :3].cpu().numpy().astype(np.float64) / 255.0
+        formats.save_obj(obj, self.verts.cpu().numpy(), self.faces.cpu().numpy(), colours)
         np.savez_compressed(npz, track_face_mask=self.track_face_mask.cpu().numpy(), ref_area=self.new_ref_area.cpu().numpy())
         return obj, npz
 
@@ -933,8 +975,13 @@ def update_mesh_topology(verts: torch.Tensor, faces: torch.Tensor, update_region
     verts = _verts_f32(verts, dev)
     fv, ff = _verts_f32(fusion_mesh.verts, dev), _faces_i32(fusion_mesh.faces)
     track = torch.ones(F0, dtype=torch.bool, device=dev)
+    # face_origin follows the masks the loop has anyway: the cuts' face_mask, the outlier mask, the stitch's face_mask over the
+    # concatenation, and a run of FILLED behind every filling
+    origin = torch.arange(F0, dtype=torch.int32, device=dev)
+    Vf = int(fv.shape[0])
     if update_regions.nothing_to_update:
-        return TopologyUpdate(verts, faces, track, F0, None, float("nan"), -1, 0, 0.0, True)
+        return TopologyUpdate(verts, faces, track, F0, None, float("nan"), -1, 0, 0.0, True, origin, ff, Vf)
+    filled_run = lambda n: torch.full((n,), -2 ** 31, dtype=torch.int32, device=dev)
     edge_len = mean_edge_length(verts, faces) if force_short_edge else None
     base_v, base_f, track_num = verts, faces, F0
     failed, n_spliced, max_dist = 0, 0, 0.0
@@ -944,8 +991,11 @@ def update_mesh_topology(verts: torch.Tensor, faces: torch.Tensor, update_region
         if patch.verts.shape[0] == 0:
             failed += 1
             continue
-        pf = _fill(patch.faces, int(patch.verts.shape[0]), err)[0]
-        patch = select_faces(patch.verts, pf, outlier_component_mask(pf, outlier_face_threshold))
+        pf, p_new, _rim = _fill(patch.faces, int(patch.verts.shape[0]), err)
+        p_origin = torch.cat([-1 - torch.nonzero(patch.face_mask).view(-1).to(torch.int32), filled_run(p_new)])
+        p_keep = outlier_component_mask(pf, outlier_face_threshold)
+        patch = select_faces(patch.verts, pf, p_keep)
+        p_origin = p_origin[p_keep]
         pb = boundary_vertices(patch.verts, patch.faces, box, cut_inner=False)
         if pb.shape[0] == 0:
             failed += 1
@@ -955,7 +1005,7 @@ def update_mesh_topology(verts: torch.Tensor, faces: torch.Tensor, update_region
             failed += 1
             continue
         n_cut = int(cut.faces.shape[0])
-        cf = _fill(cut.faces, int(cut.verts.shape[0]), err)[0]
+        cf, c_new, _rim = _fill(cut.faces, int(cut.verts.shape[0]), err)
         bb = boundary_vertices(cut.verts, cf, box, cut_inner=True)
         if bb.shape[0] == 0:
             failed += 1
@@ -966,8 +1016,9 @@ def update_mesh_topology(verts: torch.Tensor, faces: torch.Tensor, update_region
             continue
         if force_short_edge and st.max_dist > 6 * edge_len:
             continue
-        filled = _fill(st.faces, int(st.verts.shape[0]), err)[0]
+        filled, s_new, _rim = _fill(st.faces, int(st.verts.shape[0]), err)
         mask_cc = compose_face_mask(cut.face_mask, st.face_mask[:n_cut])
+        origin = torch.cat([torch.cat([origin[cut.face_mask], filled_run(c_new), p_origin])[st.face_mask], filled_run(s_new)])
         base_v, base_f = st.verts, filled
         track = compose_face_mask(track, mask_cc[:track_num])
         track_num = int(track.sum().cpu())
@@ -987,7 +1038,14 @@ def update_mesh_topology(verts: torch.Tensor, faces: torch.Tensor, update_region
         _raise_if(int(err.cpu()))
     return TopologyUpdate(verts=base_v, faces=base_f, track_face_mask=track, track_face_num=track_num, new_ref_area=ref_area,
                           new_area_mean=mean, cc_update_num=update_regions.n_regions - failed, n_spliced=n_spliced,
-                          max_dist_in_connection=float(max_dist), nothing_to_update=False)
+                          max_dist_in_connection=float(max_dist), nothing_to_update=False, face_origin=origin, fusion_faces=ff,
+                          fusion_n_verts=Vf)
+
+
+def load_tracking(path: str) -> Tuple[np.ndarray, np.ndarray]:
+    """(track_face_mask [F0] bool, ref_area [Nf] f32) from the face_corr.npz TopologyUpdate.save wrote (refine.py:315-323)."""
+    with np.load(path) as z:
+        return z["track_face_mask"].astype(bool), z["ref_area"].astype(np.float32)
 
 
 def choose_aabb_pad(run: Callable[[float], TopologyUpdate], pads: Sequence[float] = (0.01, 0.015, 0.02, 0.025, 0.03)):
@@ -1010,4 +1068,4 @@ __all__ = ["MAX_FACES", "face_edge_counts", "face_components", "combine_overlap_
            "CutMesh", "RegionCut", "cut_mesh_by_box", "boundary_vertices", "outlier_component_mask", "NN_TILE", "NN_QUERIES",
            "nearest_vertices", "select_faces", "is_watertight", "merge_vertices_around_holes", "StitchedMesh", "connect_two_meshes",
            "compose_face_mask", "RegionStitch", "FilledMesh", "fill_small_holes", "face_areas", "mean_edge_length", "TopologyUpdate",
-           "update_mesh_topology", "choose_aabb_pad"]
+           "update_mesh_topology", "choose_aabb_pad", "load_tracking"]

@@ -730,6 +730,43 @@ int gsr_splice_face_areas(int F, int V, const int* faces, const float* verts, do
 int gsr_splice_edge_lengths(int n, int V, const long long* keys, const float* verts, double* length, int* err, gsr_stream_t stream);
 int gsr_splice_mean(long long n, const double* x, void* workspace, double* mean, gsr_stream_t stream);
 
+/* ---- The colours a frame hands to the next one: get_color_mesh (gaustar_scene/sugar_model.py:578-588), the face colours
+ * update_mesh_topo carries through connect_two_meshes (gaustar_trainers/refined_mesh.py:183) and the SH dc of a model built from
+ * a coloured mesh (sugar_model.py:235-240, :386): gaustar_amd.handover, regions.TopologyUpdate.with_colors,
+ * harness.SurfaceGaussians.color_mesh / from_mesh.  Conventions as for gsr_regions_* and gsr_splice_*: device pointers,
+ * asynchronous on `stream`, no host synchronisation, no float atomics.  err [1] int32 (zero before): bit 0 = an index outside
+ * its array; such an element is left out (its output is zero).  A colour is four bytes r, g, b, a; colour arrays are 4-byte
+ * aligned.  Vertex colours are rows of `stride` >= 3 floats of which the first three are r, g, b in [0,1].
+ * Two departures from trimesh, on purpose.  (1) The roundings below are this project's statement of trimesh's vertex <-> face
+ *   colour conversions; trimesh is not among this project's dependencies, so parity with it is not pinned by a test.  (2) A
+ *   face made by fill_small_holes carries (0, 0, 0, 0) and is left out of the vertex means; trimesh's fill_holes gives new
+ *   faces a library default colour, which would tint the vertices of every filled rim.
+ * gsr_handover_face_colors: sh_dc [F G,3] f32, face-major, G in {1, 3, 4, 6}; rgba [F,4].  Per face and channel, every operation
+ *   rounded to f32 and nothing contracted: m = (((x0 + x1) + ...) + x_{G-1}) / G, c = (m C0 + 0.5) 255 with
+ *   C0 = 0.28209479177387814 rounded to f32, truncated toward zero and clipped to [0, 255]; alpha 255.  numpy's result for
+ *   np.clip(np.int32(SH2RGB(np.average(dc, axis=1)) * 255), 0, 255) wherever the truncation fits an int32; beyond it (and for
+ *   NaN, 0) numpy's cast is not defined and this saturates.
+ * gsr_handover_vertex_to_face: faces [F,3] int32 over V vertices; rgba [F,4].  Per vertex u8 = clip(rint(255 c), 0, 255), the
+ *   product in f32, ties to even (NaN: 0); per face and channel floor((u0 + u1 + u2) / 3); alpha 255.
+ * gsr_handover_face_to_vertex: face_rgba [F,4]; sums [V,4] int32, 16-byte aligned, is scratch (cleared here); vert_rgba [V,4].
+ *   Per vertex and channel the floor of the integer mean over its incident faces whose alpha is not 0, alpha 255; a vertex with
+ *   no such face gets (0, 0, 0, 0).  The sums are 32-bit integer adds, so their order does not show: the same bytes every call.
+ * gsr_handover_sh_dc: bary [G,3] f32 (gaustar_amd.harness.BARY_COORDS rounded to f32); sh_dc [F G,3] f32.  Per Gaussian g of a
+ *   face (v0, v1, v2) and channel, in f32 without contraction: c = (b_g0 v0 + b_g1 v1) + b_g2 v2, dc = (c - 0.5) / C0, a true
+ *   division.
+ * gsr_handover_gather: origin [n] int32: k >= 0 = base_rgba [Fb,4] row k; -1 - k = face k of the fusion mesh (fusion_faces
+ *   [Ff,3] over Vf vertices, fusion_colors), coloured as gsr_handover_vertex_to_face colours it; INT32_MIN = a filled face,
+ *   (0, 0, 0, 0).  rgba [n,4]. */
+int gsr_handover_face_colors(int F, int G, const float* sh_dc, unsigned char* rgba, gsr_stream_t stream);
+int gsr_handover_vertex_to_face(int F, int V, const int* faces, const float* colors, int stride, unsigned char* rgba, int* err,
+                                gsr_stream_t stream);
+int gsr_handover_face_to_vertex(int F, int V, const int* faces, const unsigned char* face_rgba, int* sums, unsigned char* vert_rgba,
+                                int* err, gsr_stream_t stream);
+int gsr_handover_sh_dc(int F, int G, int V, const int* faces, const float* colors, int stride, const float* bary, float* sh_dc,
+                       int* err, gsr_stream_t stream);
+int gsr_handover_gather(int n, const int* origin, int Fb, const unsigned char* base_rgba, int Ff, int Vf, const int* fusion_faces,
+                        const float* fusion_colors, int stride, unsigned char* rgba, int* err, gsr_stream_t stream);
+
 /* Tuning aid: when device_buffer is non-NULL (4*T uint64), the two blend kernels record the start/end wall
  * clock (100 MHz) of every workgroup: forward at [2*b], backward at [2*(T+b)], b = launch index.  NULL = off. */
 int gsr_debug_set_trace(void* device_buffer);
