@@ -141,8 +141,10 @@ SIGNATURES = {
     "gsr_fusion_count": (c_int, [POINTER(c_int), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gsr_fusion_emit": (c_int, [POINTER(c_int), c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                 c_void_p, c_void_p, c_void_p]),
+    # The four mesh-surgery groups below share one err word (csrc/gsr_mesh.h: index = 1, NaN / not finite = 2, duplicate = 4),
+    # which gaustar_amd.regions._raise_if decodes, for gaustar_amd.handover too.
     # re-mesh regions at topology errors: edge multiplicity, face components, boxes, cuts (refined_mesh.py:463-693, front
-    # half): gaustar_amd.regions
+    # half): gaustar_amd.regions; gsr_regions_cut_emit is the tail of every compaction, after either mark call
     "gsr_regions_edge_keys": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gsr_regions_edge_runs": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gsr_regions_components": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -156,7 +158,8 @@ SIGNATURES = {
     "gsr_regions_gather": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gsr_regions_boundary": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gsr_regions_label_mask": (c_int, [c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
-    # the stitch of the fused patch into the cut base mesh (refined_mesh.py:114-215, :639, :656-658): gaustar_amd.regions
+    # the stitch of the fused patch into the cut base mesh (refined_mesh.py:114-215, :639, :656-658): gaustar_amd.regions;
+    # gsr_stitch_mark is select_faces' and the degenerate passes' mark call
     "gsr_stitch_nn_tile": (c_int, []),
     "gsr_stitch_nn_queries": (c_int, []),
     "gsr_stitch_nearest": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -20,6 +20,7 @@
 #include "../../include/gsr.h"
 #include "gsr_entry.h"
 #include "gsr_internal.h"
+#include "gsr_mesh.h"
 
 #pragma clang fp contract(off)
 
@@ -27,8 +28,7 @@ namespace gsr {
 
 namespace {
 
-constexpr int HO_BLOCK = 256;
-constexpr int HO_ERR_INDEX = 1;            // bit 0 of the calls' err word
+constexpr int HO_BLOCK = MESH_BLOCK;
 constexpr int HO_FILLED = -2147483647 - 1; // a face_origin entry: made by fill_small_holes
 constexpr float HO_C0 = 0.28209479177387814f;
 
@@ -72,13 +72,13 @@ __global__ void __launch_bounds__(HO_BLOCK) handover_face_color_kernel(int F, co
 
 // ---------------------------------------------------------------------------------------------------- vertex -> face
 // colors [V][stride] f32, the first three of a row are r, g, b
-__device__ __forceinline__ unsigned face_of_vertex_colors(const float* __restrict__ colors, int stride, int i0, int i1, int i2)
+__device__ __forceinline__ unsigned face_of_vertex_colors(const float* __restrict__ colors, int stride, const int (&v)[3])
 {
     int out[3];
     for (int c = 0; c < 3; ++c) {
-        const int u0 = unit_to_u8(colors[(size_t)stride * i0 + c]);
-        const int u1 = unit_to_u8(colors[(size_t)stride * i1 + c]);
-        const int u2 = unit_to_u8(colors[(size_t)stride * i2 + c]);
+        const int u0 = unit_to_u8(colors[(size_t)stride * v[0] + c]);
+        const int u1 = unit_to_u8(colors[(size_t)stride * v[1] + c]);
+        const int u2 = unit_to_u8(colors[(size_t)stride * v[2] + c]);
         out[c] = (u0 + u1 + u2) / 3;
     }
     return pack_rgba(out[0], out[1], out[2], 255);
@@ -90,13 +90,13 @@ __global__ void __launch_bounds__(HO_BLOCK) handover_vertex_to_face_kernel(int F
 {
     const int f = blockIdx.x * HO_BLOCK + threadIdx.x;
     if (f >= F) return;
-    const int i0 = faces[3 * (size_t)f], i1 = faces[3 * (size_t)f + 1], i2 = faces[3 * (size_t)f + 2];
-    if ((unsigned)i0 >= (unsigned)V || (unsigned)i1 >= (unsigned)V || (unsigned)i2 >= (unsigned)V) {
-        atomicOr(err, HO_ERR_INDEX);
+    int v[3];
+    if (!mesh_face(faces, f, V, v)) {
+        atomicOr(err, MESH_ERR_INDEX);
         rgba[f] = 0u;
         return;
     }
-    rgba[f] = face_of_vertex_colors(colors, stride, i0, i1, i2);
+    rgba[f] = face_of_vertex_colors(colors, stride, v);
 }
 
 // ---------------------------------------------------------------------------------------------------- face -> vertex
@@ -109,9 +109,8 @@ __global__ void __launch_bounds__(HO_BLOCK) handover_scatter_kernel(int F, int V
     const int f = blockIdx.x * HO_BLOCK + threadIdx.x;
     if (f >= F) return;
     int v[3];
-    for (int k = 0; k < 3; ++k) v[k] = faces[3 * (size_t)f + k];
-    if ((unsigned)v[0] >= (unsigned)V || (unsigned)v[1] >= (unsigned)V || (unsigned)v[2] >= (unsigned)V) {
-        atomicOr(err, HO_ERR_INDEX);
+    if (!mesh_face(faces, f, V, v)) {
+        atomicOr(err, MESH_ERR_INDEX);
         return;
     }
     const unsigned c = face_rgba[f];
@@ -144,18 +143,18 @@ __global__ void __launch_bounds__(HO_BLOCK) handover_sh_dc_kernel(int F, int G, 
     const long long n = (long long)blockIdx.x * HO_BLOCK + threadIdx.x;
     if (n >= (long long)F * G) return;
     const int f = (int)(n / G), g = (int)(n - (long long)f * G);
-    const int i0 = faces[3 * (size_t)f], i1 = faces[3 * (size_t)f + 1], i2 = faces[3 * (size_t)f + 2];
+    int v[3];
     float* o = sh_dc + 3 * (size_t)n;
-    if ((unsigned)i0 >= (unsigned)V || (unsigned)i1 >= (unsigned)V || (unsigned)i2 >= (unsigned)V) {
-        atomicOr(err, HO_ERR_INDEX);
+    if (!mesh_face(faces, f, V, v)) {
+        atomicOr(err, MESH_ERR_INDEX);
         o[0] = 0.f; o[1] = 0.f; o[2] = 0.f;
         return;
     }
     const float b0 = bary[3 * g], b1 = bary[3 * g + 1], b2 = bary[3 * g + 2];
     for (int c = 0; c < 3; ++c) {
-        const float p0 = b0 * colors[(size_t)stride * i0 + c];
-        const float p1 = b1 * colors[(size_t)stride * i1 + c];
-        const float p2 = b2 * colors[(size_t)stride * i2 + c];
+        const float p0 = b0 * colors[(size_t)stride * v[0] + c];
+        const float p1 = b1 * colors[(size_t)stride * v[1] + c];
+        const float p2 = b2 * colors[(size_t)stride * v[2] + c];
         const float col = (p0 + p1) + p2;
         o[c] = (col - 0.5f) / HO_C0;
     }
@@ -175,23 +174,16 @@ __global__ void __launch_bounds__(HO_BLOCK) handover_gather_kernel(int n, const 
     unsigned c = 0u;
     if (o >= 0) {
         if (o < Fb) c = base_rgba[o];
-        else atomicOr(err, HO_ERR_INDEX);
+        else atomicOr(err, MESH_ERR_INDEX);
     } else if (o != HO_FILLED) {
         const int k = -1 - o;
-        bool ok = k < Ff;
-        int i0 = 0, i1 = 0, i2 = 0;
-        if (ok) {
-            i0 = fusion_faces[3 * (size_t)k]; i1 = fusion_faces[3 * (size_t)k + 1]; i2 = fusion_faces[3 * (size_t)k + 2];
-            ok = (unsigned)i0 < (unsigned)Vf && (unsigned)i1 < (unsigned)Vf && (unsigned)i2 < (unsigned)Vf;
-        }
-        if (ok) c = face_of_vertex_colors(fusion_colors, stride, i0, i1, i2);
-        else atomicOr(err, HO_ERR_INDEX);
+        int v[3];
+        if (k < Ff && mesh_face(fusion_faces, k, Vf, v)) c = face_of_vertex_colors(fusion_colors, stride, v);
+        else atomicOr(err, MESH_ERR_INDEX);
     }
     rgba[i] = c;
 }
 
-inline unsigned blocks(long long n) { return (unsigned)((n + HO_BLOCK - 1) / HO_BLOCK); }
-bool handover_faces_ok(int F) { return F >= 0 && F <= 0x7fffffff / 3; }
 bool misaligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) != 0; }
 
 }  // namespace
@@ -206,7 +198,7 @@ extern "C" {
 int gsr_handover_face_colors(int F, int G, const float* sh_dc, unsigned char* rgba, gsr_stream_t stream)
 {
     clear_error();
-    if (!handover_faces_ok(F)) return fail_msg("gsr_handover_face_colors: negative size or too many faces");
+    if (!mesh_faces_ok(F)) return fail_msg("gsr_handover_face_colors: negative size or too many faces");
     if (G != 1 && G != 3 && G != 4 && G != 6) return fail_msg("gsr_handover_face_colors: G must be 1, 3, 4 or 6");
     if (F == 0) return 0;
     if (!sh_dc || !rgba) return fail_msg("gsr_handover_face_colors: required pointer is null");
@@ -214,10 +206,10 @@ int gsr_handover_face_colors(int F, int G, const float* sh_dc, unsigned char* rg
     hipStream_t st = (hipStream_t)stream;
     unsigned* out = reinterpret_cast<unsigned*>(rgba);
     switch (G) {
-    case 1: handover_face_color_kernel<1><<<blocks(F), HO_BLOCK, 0, st>>>(F, sh_dc, out); break;
-    case 3: handover_face_color_kernel<3><<<blocks(F), HO_BLOCK, 0, st>>>(F, sh_dc, out); break;
-    case 4: handover_face_color_kernel<4><<<blocks(F), HO_BLOCK, 0, st>>>(F, sh_dc, out); break;
-    default: handover_face_color_kernel<6><<<blocks(F), HO_BLOCK, 0, st>>>(F, sh_dc, out); break;
+    case 1: handover_face_color_kernel<1><<<mesh_blocks(F), HO_BLOCK, 0, st>>>(F, sh_dc, out); break;
+    case 3: handover_face_color_kernel<3><<<mesh_blocks(F), HO_BLOCK, 0, st>>>(F, sh_dc, out); break;
+    case 4: handover_face_color_kernel<4><<<mesh_blocks(F), HO_BLOCK, 0, st>>>(F, sh_dc, out); break;
+    default: handover_face_color_kernel<6><<<mesh_blocks(F), HO_BLOCK, 0, st>>>(F, sh_dc, out); break;
     }
     GSR_CHECK_LAUNCH("handover_face_color_kernel");
     return 0;
@@ -227,12 +219,12 @@ int gsr_handover_vertex_to_face(int F, int V, const int* faces, const float* col
                                 gsr_stream_t stream)
 {
     clear_error();
-    if (!handover_faces_ok(F) || V < 0) return fail_msg("gsr_handover_vertex_to_face: negative size or too many faces");
+    if (!mesh_faces_ok(F) || V < 0) return fail_msg("gsr_handover_vertex_to_face: negative size or too many faces");
     if (stride < 3) return fail_msg("gsr_handover_vertex_to_face: a colour row holds at least r, g, b");
     if (F == 0) return 0;
     if (!faces || !rgba || !err || (V > 0 && !colors)) return fail_msg("gsr_handover_vertex_to_face: required pointer is null");
     if (misaligned4(rgba)) return fail_msg("gsr_handover_vertex_to_face: rgba must be 4-byte aligned");
-    handover_vertex_to_face_kernel<<<blocks(F), HO_BLOCK, 0, (hipStream_t)stream>>>(F, V, faces, colors, stride,
+    handover_vertex_to_face_kernel<<<mesh_blocks(F), HO_BLOCK, 0, (hipStream_t)stream>>>(F, V, faces, colors, stride,
                                                                                      reinterpret_cast<unsigned*>(rgba), err);
     GSR_CHECK_LAUNCH("handover_vertex_to_face_kernel");
     return 0;
@@ -242,15 +234,15 @@ int gsr_handover_face_to_vertex(int F, int V, const int* faces, const unsigned c
                                 int* err, gsr_stream_t stream)
 {
     clear_error();
-    if (!handover_faces_ok(F) || V < 0 || V > 0x7fffffff / 4) return fail_msg("gsr_handover_face_to_vertex: negative size or too large a mesh");
+    if (!mesh_faces_ok(F) || V < 0 || V > 0x7fffffff / 4) return fail_msg("gsr_handover_face_to_vertex: negative size or too large a mesh");
     if (V == 0) return 0;
     if (!sums || !vert_rgba || (F > 0 && (!faces || !face_rgba || !err))) return fail_msg("gsr_handover_face_to_vertex: required pointer is null");
     if (misaligned4(vert_rgba) || (F > 0 && misaligned4(face_rgba))) return fail_msg("gsr_handover_face_to_vertex: colours must be 4-byte aligned");
     if (reinterpret_cast<uintptr_t>(sums) & 15) return fail_msg("gsr_handover_face_to_vertex: sums must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     GSR_CHECK(hipMemsetAsync(sums, 0, 4 * sizeof(int) * (size_t)V, st));
-    if (F > 0) handover_scatter_kernel<<<blocks(F), HO_BLOCK, 0, st>>>(F, V, faces, reinterpret_cast<const unsigned*>(face_rgba), sums, err);
-    handover_vertex_mean_kernel<<<blocks(V), HO_BLOCK, 0, st>>>(V, reinterpret_cast<const int4*>(sums), reinterpret_cast<unsigned*>(vert_rgba));
+    if (F > 0) handover_scatter_kernel<<<mesh_blocks(F), HO_BLOCK, 0, st>>>(F, V, faces, reinterpret_cast<const unsigned*>(face_rgba), sums, err);
+    handover_vertex_mean_kernel<<<mesh_blocks(V), HO_BLOCK, 0, st>>>(V, reinterpret_cast<const int4*>(sums), reinterpret_cast<unsigned*>(vert_rgba));
     GSR_CHECK_LAUNCH("handover face-to-vertex kernels");
     return 0;
 }
@@ -259,12 +251,12 @@ int gsr_handover_sh_dc(int F, int G, int V, const int* faces, const float* color
                        gsr_stream_t stream)
 {
     clear_error();
-    if (!handover_faces_ok(F) || V < 0) return fail_msg("gsr_handover_sh_dc: negative size or too many faces");
+    if (!mesh_faces_ok(F) || V < 0) return fail_msg("gsr_handover_sh_dc: negative size or too many faces");
     if (G != 1 && G != 3 && G != 4 && G != 6) return fail_msg("gsr_handover_sh_dc: G must be 1, 3, 4 or 6");
     if (stride < 3) return fail_msg("gsr_handover_sh_dc: a colour row holds at least r, g, b");
     if (F == 0) return 0;
     if (!faces || !bary || !sh_dc || !err || (V > 0 && !colors)) return fail_msg("gsr_handover_sh_dc: required pointer is null");
-    handover_sh_dc_kernel<<<blocks((long long)F * G), HO_BLOCK, 0, (hipStream_t)stream>>>(F, G, V, faces, colors, stride, bary, sh_dc, err);
+    handover_sh_dc_kernel<<<mesh_blocks((long long)F * G), HO_BLOCK, 0, (hipStream_t)stream>>>(F, G, V, faces, colors, stride, bary, sh_dc, err);
     GSR_CHECK_LAUNCH("handover_sh_dc_kernel");
     return 0;
 }
@@ -273,13 +265,13 @@ int gsr_handover_gather(int n, const int* origin, int Fb, const unsigned char* b
                         const float* fusion_colors, int stride, unsigned char* rgba, int* err, gsr_stream_t stream)
 {
     clear_error();
-    if (!handover_faces_ok(n) || !handover_faces_ok(Ff) || Fb < 0 || Vf < 0) return fail_msg("gsr_handover_gather: negative size or too many faces");
+    if (!mesh_faces_ok(n) || !mesh_faces_ok(Ff) || Fb < 0 || Vf < 0) return fail_msg("gsr_handover_gather: negative size or too many faces");
     if (stride < 3) return fail_msg("gsr_handover_gather: a colour row holds at least r, g, b");
     if (n == 0) return 0;
     if (!origin || !rgba || !err || (Fb > 0 && !base_rgba) || (Ff > 0 && (!fusion_faces || (Vf > 0 && !fusion_colors))))
         return fail_msg("gsr_handover_gather: required pointer is null");
     if (misaligned4(rgba) || (Fb > 0 && misaligned4(base_rgba))) return fail_msg("gsr_handover_gather: colours must be 4-byte aligned");
-    handover_gather_kernel<<<blocks(n), HO_BLOCK, 0, (hipStream_t)stream>>>(n, origin, Fb, reinterpret_cast<const unsigned*>(base_rgba), Ff, Vf,
+    handover_gather_kernel<<<mesh_blocks(n), HO_BLOCK, 0, (hipStream_t)stream>>>(n, origin, Fb, reinterpret_cast<const unsigned*>(base_rgba), Ff, Vf,
                                                                              fusion_faces, fusion_colors, stride,
                                                                              reinterpret_cast<unsigned*>(rgba), err);
     GSR_CHECK_LAUNCH("handover_gather_kernel");

@@ -26,15 +26,15 @@
 #include "../../include/gsr.h"
 #include "gsr_entry.h"
 #include "gsr_internal.h"
+#include "gsr_mesh.h"
 #include "gsr_unionfind.h"
 
 namespace gsr {
 
 namespace {
 
-constexpr int RG_BLOCK = 256;
+constexpr int RG_BLOCK = MESH_BLOCK;
 constexpr long long RG_SENTINEL = 0x7fffffffffffffffll;   // above every key: min, max <= 2^31 - 1
-constexpr int RG_ERR_INDEX = 1, RG_ERR_NAN = 2;               // bits of the calls' err word
 constexpr int RG_WALK = 8;                                 // neighbours looked at before a run's end is found by bisection
 
 struct RegionBox { double lo[3], hi[3]; };
@@ -56,7 +56,7 @@ __global__ void __launch_bounds__(RG_BLOCK) regions_edge_key_kernel(int F, const
     if (f >= F) return;
     const int a = faces[3 * (size_t)f], b = faces[3 * (size_t)f + 1], c = faces[3 * (size_t)f + 2];
     bool on = (!mask || mask[f]) && (!colour || (int)colour[f] >= cut);
-    if ((a | b | c) < 0) { atomicOr(err, RG_ERR_INDEX); on = false; }
+    if ((a | b | c) < 0) { atomicOr(err, MESH_ERR_INDEX); on = false; }
     sel[f] = on;
     long long* k = keys + 3 * (size_t)f;
     k[0] = on ? edge_key(a, b) : RG_SENTINEL;
@@ -177,10 +177,10 @@ __global__ void __launch_bounds__(RG_BLOCK) regions_box_kernel(int F, int G, int
             const int* fv = faces + 3 * (size_t)f;
             for (int k = 0; k < 3; ++k) {
                 const int v = fv[k];
-                if ((unsigned)v >= (unsigned)V) { atomicOr(err, RG_ERR_INDEX); continue; }
+                if ((unsigned)v >= (unsigned)V) { atomicOr(err, MESH_ERR_INDEX); continue; }
                 for (int a = 0; a < 3; ++a) {
                     const float x = verts[3 * (size_t)v + a];
-                    if (x != x) atomicOr(err, RG_ERR_NAN);
+                    if (x != x) atomicOr(err, MESH_ERR_NAN);
                     const unsigned u = order_bits(x);
                     lo[a] = min(lo[a], u);
                     hi[a] = max(hi[a], u);
@@ -190,7 +190,7 @@ __global__ void __launch_bounds__(RG_BLOCK) regions_box_kernel(int F, int G, int
             for (int g = 0; g < G; ++g)
                 for (int a = 0; a < 3; ++a) {
                     const float x = p[3 * g + a];
-                    if (x != x) atomicOr(err, RG_ERR_NAN);     // (numpy's min / max would give NaN; the bit order would not)
+                    if (x != x) atomicOr(err, MESH_ERR_NAN);     // (numpy's min / max would give NaN; the bit order would not)
                     const unsigned u = order_bits(x);
                     lo[a] = min(lo[a], u);
                     hi[a] = max(hi[a], u);
@@ -242,16 +242,16 @@ __global__ void __launch_bounds__(RG_BLOCK) regions_cut_mark_kernel(int F, int V
 {
     const int f = blockIdx.x * RG_BLOCK + threadIdx.x;
     if (f >= F) return;
-    const int a = faces[3 * (size_t)f], b = faces[3 * (size_t)f + 1], c = faces[3 * (size_t)f + 2];
-    if ((unsigned)a >= (unsigned)V || (unsigned)b >= (unsigned)V || (unsigned)c >= (unsigned)V) {
-        atomicOr(err, RG_ERR_INDEX);
+    int v[3];
+    if (!mesh_face(faces, f, V, v)) {
+        atomicOr(err, MESH_ERR_INDEX);
         keep[f] = 0;
         return;
     }
-    const int k = inside[a] + inside[b] + inside[c];
+    const int k = inside[v[0]] + inside[v[1]] + inside[v[2]];
     const int kp = cut_inner ? (k == 0) : (k > 0);
     keep[f] = kp;
-    if (kp) { ref[a] = 1; ref[b] = 1; ref[c] = 1; }
+    if (kp) { ref[v[0]] = 1; ref[v[1]] = 1; ref[v[2]] = 1; }
 }
 
 // kscan / vscan: the inclusive scans of keep / ref.  Kept faces keep their order; referenced vertices are renumbered in
@@ -318,8 +318,7 @@ __global__ void __launch_bounds__(RG_BLOCK) regions_boundary_kernel(int F, int V
     const int f = blockIdx.x * RG_BLOCK + threadIdx.x;
     if (f >= F) return;
     int v[3];
-    for (int k = 0; k < 3; ++k) v[k] = faces[3 * (size_t)f + k];
-    if ((unsigned)v[0] >= (unsigned)V || (unsigned)v[1] >= (unsigned)V || (unsigned)v[2] >= (unsigned)V) { atomicOr(err, RG_ERR_INDEX); return; }
+    if (!mesh_face(faces, f, V, v)) { atomicOr(err, MESH_ERR_INDEX); return; }
     for (int e = 0; e < 3; ++e)
         if (counts[3 * (size_t)f + e] == 1) { bmark[v[e]] = 1; bmark[v[(e + 1) % 3]] = 1; }
     if (inside) {
@@ -338,8 +337,6 @@ __global__ void __launch_bounds__(RG_BLOCK) regions_label_mask_kernel(int F, con
     out[f] = lab >= 0 && count[lab] >= min_count;
 }
 
-inline unsigned blocks(long long n) { return (unsigned)((n + RG_BLOCK - 1) / RG_BLOCK); }
-
 // gsr_regions_cut_mark: clears the reference flags, then marks
 hipError_t launch_regions_cut_mark(int F, int V, const int* faces, const unsigned char* inside, int cut_inner, int* keep, int* ref,
                                    int* err, hipStream_t st)
@@ -348,7 +345,7 @@ hipError_t launch_regions_cut_mark(int F, int V, const int* faces, const unsigne
         const hipError_t e = hipMemsetAsync(ref, 0, sizeof(int) * (size_t)V, st);
         if (e != hipSuccess) return e;
     }
-    if (F > 0) regions_cut_mark_kernel<<<blocks(F), RG_BLOCK, 0, st>>>(F, V, faces, inside, cut_inner, keep, ref, err);
+    if (F > 0) regions_cut_mark_kernel<<<mesh_blocks(F), RG_BLOCK, 0, st>>>(F, V, faces, inside, cut_inner, keep, ref, err);
     return hipSuccess;
 }
 
@@ -361,12 +358,9 @@ hipError_t launch_regions_boundary(int F, int V, const int* faces, const int* co
         if (e == hipSuccess && inside) e = hipMemsetAsync(fmark, 0, (size_t)V, st);
         if (e != hipSuccess) return e;
     }
-    if (F > 0) regions_boundary_kernel<<<blocks(F), RG_BLOCK, 0, st>>>(F, V, faces, counts, inside, bmark, fmark, err);
+    if (F > 0) regions_boundary_kernel<<<mesh_blocks(F), RG_BLOCK, 0, st>>>(F, V, faces, counts, inside, bmark, fmark, err);
     return hipSuccess;
 }
-
-// 3 F face-edges are counted in an int
-bool regions_faces_ok(int F) { return F >= 0 && F <= 0x7fffffff / 3; }
 
 }  // namespace
 
@@ -381,10 +375,10 @@ int gsr_regions_edge_keys(int F, const int* faces, const unsigned char* mask, co
                           unsigned char* selected, long long* keys, int* err, gsr_stream_t stream)
 {
     clear_error();
-    if (!regions_faces_ok(F)) return fail_msg("gsr_regions_edge_keys: F must be in [0, (2^31 - 1) / 3]");
+    if (!mesh_faces_ok(F)) return fail_msg("gsr_regions_edge_keys: F must be in [0, (2^31 - 1) / 3]");
     if (F == 0) return 0;
     if (!faces || !selected || !keys || !err) return fail_msg("gsr_regions_edge_keys: required pointer is null");
-    regions_edge_key_kernel<<<blocks(F), RG_BLOCK, 0, (hipStream_t)stream>>>(F, faces, mask, colour, cut, selected, keys, err);
+    regions_edge_key_kernel<<<mesh_blocks(F), RG_BLOCK, 0, (hipStream_t)stream>>>(F, faces, mask, colour, cut, selected, keys, err);
     GSR_CHECK_LAUNCH("regions_edge_key_kernel");
     return 0;
 }
@@ -392,11 +386,11 @@ int gsr_regions_edge_keys(int F, const int* faces, const unsigned char* mask, co
 int gsr_regions_edge_runs(int F, const long long* sorted_keys, const long long* order, int* counts, int* pairs, gsr_stream_t stream)
 {
     clear_error();
-    if (!regions_faces_ok(F)) return fail_msg("gsr_regions_edge_runs: F must be in [0, (2^31 - 1) / 3]");
+    if (!mesh_faces_ok(F)) return fail_msg("gsr_regions_edge_runs: F must be in [0, (2^31 - 1) / 3]");
     if (F == 0) return 0;
     if (!sorted_keys || !order || !counts || !pairs) return fail_msg("gsr_regions_edge_runs: required pointer is null");
     if (reinterpret_cast<uintptr_t>(pairs) & 7) return fail_msg("gsr_regions_edge_runs: pairs must be 8-byte aligned");
-    regions_edge_run_kernel<<<blocks(3ll * F), RG_BLOCK, 0, (hipStream_t)stream>>>(3 * F, sorted_keys, order, counts,
+    regions_edge_run_kernel<<<mesh_blocks(3ll * F), RG_BLOCK, 0, (hipStream_t)stream>>>(3 * F, sorted_keys, order, counts,
                                                                                    reinterpret_cast<int2*>(pairs));
     GSR_CHECK_LAUNCH("regions_edge_run_kernel");
     return 0;
@@ -405,7 +399,7 @@ int gsr_regions_edge_runs(int F, const long long* sorted_keys, const long long* 
 int gsr_regions_components(int F, const int* pairs, const unsigned char* selected, int* parent, int* root_flag, gsr_stream_t stream)
 {
     clear_error();
-    if (!regions_faces_ok(F)) return fail_msg("gsr_regions_components: F must be in [0, (2^31 - 1) / 3]");
+    if (!mesh_faces_ok(F)) return fail_msg("gsr_regions_components: F must be in [0, (2^31 - 1) / 3]");
     if (F == 0) return 0;
     if (!pairs || !selected || !parent || !root_flag) return fail_msg("gsr_regions_components: required pointer is null");
     if (reinterpret_cast<uintptr_t>(pairs) & 7) return fail_msg("gsr_regions_components: pairs must be 8-byte aligned");
@@ -418,10 +412,10 @@ int gsr_regions_labels(int F, const int* parent, const int* root_scan, const uns
                        gsr_stream_t stream)
 {
     clear_error();
-    if (!regions_faces_ok(F)) return fail_msg("gsr_regions_labels: F must be in [0, (2^31 - 1) / 3]");
+    if (!mesh_faces_ok(F)) return fail_msg("gsr_regions_labels: F must be in [0, (2^31 - 1) / 3]");
     if (F == 0) return 0;
     if (!parent || !root_scan || !selected || !label || !count) return fail_msg("gsr_regions_labels: required pointer is null");
-    regions_label_kernel<<<blocks(F), RG_BLOCK, 0, (hipStream_t)stream>>>(F, parent, root_scan, selected, label, count);
+    regions_label_kernel<<<mesh_blocks(F), RG_BLOCK, 0, (hipStream_t)stream>>>(F, parent, root_scan, selected, label, count);
     GSR_CHECK_LAUNCH("regions_label_kernel");
     return 0;
 }
@@ -430,12 +424,12 @@ int gsr_regions_select(int F, const int* count, int face_threshold, const int* k
                        int* kept_count, int* region, gsr_stream_t stream)
 {
     clear_error();
-    if (!regions_faces_ok(F) || cap < 0) return fail_msg("gsr_regions_select: negative size or too many faces");
+    if (!mesh_faces_ok(F) || cap < 0) return fail_msg("gsr_regions_select: negative size or too many faces");
     if (face_threshold < 0) return fail_msg("gsr_regions_select: face_threshold must not be negative");
     if (F == 0) return 0;
     if (!count || !kept_scan || !label || !region || (cap > 0 && (!kept_label || !kept_count)))
         return fail_msg("gsr_regions_select: required pointer is null");
-    regions_select_kernel<<<blocks(F), RG_BLOCK, 0, (hipStream_t)stream>>>(F, count, face_threshold, kept_scan, label, cap, kept_label,
+    regions_select_kernel<<<mesh_blocks(F), RG_BLOCK, 0, (hipStream_t)stream>>>(F, count, face_threshold, kept_scan, label, cap, kept_label,
                                                                            kept_count, region);
     GSR_CHECK_LAUNCH("regions_select_kernel");
     return 0;
@@ -445,13 +439,13 @@ int gsr_regions_boxes(int F, int G, int V, const int* faces, const float* verts,
                       unsigned int* boxes, int* err, gsr_stream_t stream)
 {
     clear_error();
-    if (!regions_faces_ok(F) || G < 0 || V < 0 || cap < 0) return fail_msg("gsr_regions_boxes: negative size or too many faces");
+    if (!mesh_faces_ok(F) || G < 0 || V < 0 || cap < 0) return fail_msg("gsr_regions_boxes: negative size or too many faces");
     if (cap == 0) return 0;
     if (!boxes || (F > 0 && (!faces || !verts || !region || !err || (G > 0 && !points))))
         return fail_msg("gsr_regions_boxes: required pointer is null");
     hipStream_t st = (hipStream_t)stream;
-    regions_box_init_kernel<<<blocks(6ll * cap), RG_BLOCK, 0, st>>>(6 * cap, boxes);
-    if (F > 0) regions_box_kernel<<<blocks(F), RG_BLOCK, 0, st>>>(F, G, V, faces, verts, points, region, cap, boxes, err);
+    regions_box_init_kernel<<<mesh_blocks(6ll * cap), RG_BLOCK, 0, st>>>(6 * cap, boxes);
+    if (F > 0) regions_box_kernel<<<mesh_blocks(F), RG_BLOCK, 0, st>>>(F, G, V, faces, verts, points, region, cap, boxes, err);
     GSR_CHECK_LAUNCH("regions box kernels");
     return 0;
 }
@@ -467,7 +461,7 @@ int gsr_regions_inside(int V, const float* verts, const double* box, unsigned ch
     if (!verts || !inside) return fail_msg("gsr_regions_inside: required pointer is null");
     RegionBox b;
     for (int a = 0; a < 3; ++a) { b.lo[a] = box[a]; b.hi[a] = box[3 + a]; }
-    regions_inside_kernel<<<blocks(V), RG_BLOCK, 0, (hipStream_t)stream>>>(V, verts, b, inside);
+    regions_inside_kernel<<<mesh_blocks(V), RG_BLOCK, 0, (hipStream_t)stream>>>(V, verts, b, inside);
     GSR_CHECK_LAUNCH("regions_inside_kernel");
     return 0;
 }
@@ -476,7 +470,7 @@ int gsr_regions_cut_mark(int F, int V, const int* faces, const unsigned char* in
                          int* err, gsr_stream_t stream)
 {
     clear_error();
-    if (!regions_faces_ok(F) || V < 0) return fail_msg("gsr_regions_cut_mark: negative size or too many faces");
+    if (!mesh_faces_ok(F) || V < 0) return fail_msg("gsr_regions_cut_mark: negative size or too many faces");
     if ((V > 0 && (!inside || !referenced)) || (F > 0 && (!faces || !keep || !err)))
         return fail_msg("gsr_regions_cut_mark: required pointer is null");
     GSR_CHECK(launch_regions_cut_mark(F, V, faces, inside, cut_inner != 0, keep, referenced, err, (hipStream_t)stream));
@@ -489,13 +483,13 @@ int gsr_regions_cut_emit(int F, int V, const int* faces, const int* keep, const 
                          gsr_stream_t stream)
 {
     clear_error();
-    if (!regions_faces_ok(F) || V < 0) return fail_msg("gsr_regions_cut_emit: negative size or too many faces");
+    if (!mesh_faces_ok(F) || V < 0) return fail_msg("gsr_regions_cut_emit: negative size or too many faces");
     // (faces_out / old_of_new may be null when the scans' totals are zero: nothing is written then)
     if ((F > 0 && (!faces || !keep || !keep_scan || !face_mask || !referenced_scan)) || (V > 0 && (!referenced || !referenced_scan || !vert_map)))
         return fail_msg("gsr_regions_cut_emit: required pointer is null");
     hipStream_t st = (hipStream_t)stream;
-    if (F > 0) regions_cut_faces_kernel<<<blocks(F), RG_BLOCK, 0, st>>>(F, faces, keep, keep_scan, referenced_scan, faces_out, face_mask);
-    if (V > 0) regions_cut_verts_kernel<<<blocks(V), RG_BLOCK, 0, st>>>(V, referenced, referenced_scan, vert_map, old_of_new);
+    if (F > 0) regions_cut_faces_kernel<<<mesh_blocks(F), RG_BLOCK, 0, st>>>(F, faces, keep, keep_scan, referenced_scan, faces_out, face_mask);
+    if (V > 0) regions_cut_verts_kernel<<<mesh_blocks(V), RG_BLOCK, 0, st>>>(V, referenced, referenced_scan, vert_map, old_of_new);
     GSR_CHECK_LAUNCH("regions cut kernels");
     return 0;
 }
@@ -510,7 +504,7 @@ int gsr_regions_gather(int n_rows, int C, const int* old_of_new, const void* src
     const long long n_el = (long long)n_rows * C;
     const int vec = ((reinterpret_cast<uintptr_t>(dst) & 15) == 0 ? 1 : 0) |
                     ((C % 4 == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0) ? 2 : 0);
-    regions_gather_kernel<<<blocks((n_el + 3) / 4), RG_BLOCK, 0, (hipStream_t)stream>>>(
+    regions_gather_kernel<<<mesh_blocks((n_el + 3) / 4), RG_BLOCK, 0, (hipStream_t)stream>>>(
         n_el, C, old_of_new, static_cast<const unsigned*>(src), static_cast<unsigned*>(dst), vec);
     GSR_CHECK_LAUNCH("regions_gather_kernel");
     return 0;
@@ -520,7 +514,7 @@ int gsr_regions_boundary(int F, int V, const int* faces, const int* counts, cons
                          unsigned char* face_mark, int* err, gsr_stream_t stream)
 {
     clear_error();
-    if (!regions_faces_ok(F) || V < 0) return fail_msg("gsr_regions_boundary: negative size or too many faces");
+    if (!mesh_faces_ok(F) || V < 0) return fail_msg("gsr_regions_boundary: negative size or too many faces");
     if ((V > 0 && (!edge_mark || (inside && !face_mark))) || (F > 0 && (!faces || !counts || !err)))
         return fail_msg("gsr_regions_boundary: required pointer is null");
     GSR_CHECK(launch_regions_boundary(F, V, faces, counts, inside, edge_mark, face_mark, err, (hipStream_t)stream));
@@ -531,10 +525,10 @@ int gsr_regions_boundary(int F, int V, const int* faces, const int* counts, cons
 int gsr_regions_label_mask(int F, const int* label, const int* count, int min_count, unsigned char* out, gsr_stream_t stream)
 {
     clear_error();
-    if (!regions_faces_ok(F)) return fail_msg("gsr_regions_label_mask: F must be in [0, (2^31 - 1) / 3]");
+    if (!mesh_faces_ok(F)) return fail_msg("gsr_regions_label_mask: F must be in [0, (2^31 - 1) / 3]");
     if (F == 0) return 0;
     if (!label || !count || !out) return fail_msg("gsr_regions_label_mask: required pointer is null");
-    regions_label_mask_kernel<<<blocks(F), RG_BLOCK, 0, (hipStream_t)stream>>>(F, label, count, min_count, out);
+    regions_label_mask_kernel<<<mesh_blocks(F), RG_BLOCK, 0, (hipStream_t)stream>>>(F, label, count, min_count, out);
     GSR_CHECK_LAUNCH("regions_label_mask_kernel");
     return 0;
 }

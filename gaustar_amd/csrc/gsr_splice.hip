@@ -29,6 +29,7 @@
 #include "../../include/gsr.h"
 #include "gsr_entry.h"
 #include "gsr_internal.h"
+#include "gsr_mesh.h"
 #include "gsr_reduce.h"
 #include "gsr_unionfind.h"
 
@@ -38,8 +39,7 @@ namespace gsr {
 
 namespace {
 
-constexpr int SP_BLOCK = 256;
-constexpr int SP_ERR_INDEX = 1;      // bit 0 of the calls' err word
+constexpr int SP_BLOCK = MESH_BLOCK;
 
 // ---------------------------------------------------------------------------------------------------- rim edges
 // pairs [3 F]; on [V], degree [V] (zero before); slots [V][2].  A third edge at a vertex only raises its degree.
@@ -51,9 +51,8 @@ __global__ void __launch_bounds__(SP_BLOCK) splice_rim_edge_kernel(int F, int V,
     const int f = blockIdx.x * SP_BLOCK + threadIdx.x;
     if (f >= F) return;
     int v[3];
-    for (int k = 0; k < 3; ++k) v[k] = faces[3 * (size_t)f + k];
-    const bool ok = (unsigned)v[0] < (unsigned)V && (unsigned)v[1] < (unsigned)V && (unsigned)v[2] < (unsigned)V;
-    if (!ok) atomicOr(err, SP_ERR_INDEX);
+    const bool ok = mesh_face(faces, f, V, v);
+    if (!ok) atomicOr(err, MESH_ERR_INDEX);
     for (int e = 0; e < 3; ++e) {
         int2 pr = make_int2(-1, -1);
         if (ok && counts[3 * (size_t)f + e] == 1) {
@@ -147,14 +146,14 @@ __global__ void __launch_bounds__(SP_BLOCK) splice_area_kernel(int F, int V, con
 {
     const int f = blockIdx.x * SP_BLOCK + threadIdx.x;
     if (f >= F) return;
-    const int i0 = faces[3 * (size_t)f], i1 = faces[3 * (size_t)f + 1], i2 = faces[3 * (size_t)f + 2];
-    if ((unsigned)i0 >= (unsigned)V || (unsigned)i1 >= (unsigned)V || (unsigned)i2 >= (unsigned)V) {
-        atomicOr(err, SP_ERR_INDEX);
+    int v[3];
+    if (!mesh_face(faces, f, V, v)) {
+        atomicOr(err, MESH_ERR_INDEX);
         area[f] = 0.0;
         return;
     }
     double p0[3], p1[3], p2[3];
-    load3(verts, i0, p0); load3(verts, i1, p1); load3(verts, i2, p2);
+    load3(verts, v[0], p0); load3(verts, v[1], p1); load3(verts, v[2], p2);
     const double ux = p1[0] - p0[0], uy = p1[1] - p0[1], uz = p1[2] - p0[2];
     const double wx = p2[0] - p1[0], wy = p2[1] - p1[1], wz = p2[2] - p1[2];
     const double cx = uy * wz - uz * wy, cy = uz * wx - ux * wz, cz = ux * wy - uy * wx;
@@ -171,7 +170,7 @@ __global__ void __launch_bounds__(SP_BLOCK) splice_edge_length_kernel(int n, int
     const long long k = keys[i];
     const long long a = k >> 32, b = k & 0xffffffffll;
     if (a < 0 || a >= V || b >= V) {
-        atomicOr(err, SP_ERR_INDEX);
+        atomicOr(err, MESH_ERR_INDEX);
         length[i] = 0.0;
         return;
     }
@@ -197,9 +196,6 @@ __global__ void __launch_bounds__(RED_BLOCK) splice_mean_kernel(int n_wg, const 
     if (threadIdx.x == 0) mean[0] = t[0] / (double)n;
 }
 
-inline unsigned blocks(long long n) { return (unsigned)((n + SP_BLOCK - 1) / SP_BLOCK); }
-bool splice_faces_ok(int F) { return F >= 0 && F <= 0x7fffffff / 3; }
-
 }  // namespace
 
 }  // namespace gsr
@@ -215,7 +211,7 @@ int gsr_splice_rim_edges(int F, int V, const int* faces, const int* counts, int*
                          unsigned int* slots, int* parent, int* root_flag, int* err, gsr_stream_t stream)
 {
     clear_error();
-    if (!splice_faces_ok(F) || V < 0) return fail_msg("gsr_splice_rim_edges: negative size or too many faces");
+    if (!mesh_faces_ok(F) || V < 0) return fail_msg("gsr_splice_rim_edges: negative size or too many faces");
     if (V == 0) return 0;
     if (!on_rim || !degree || !slots || !parent || !root_flag || (F > 0 && (!faces || !counts || !pairs || !err)))
         return fail_msg("gsr_splice_rim_edges: required pointer is null");
@@ -224,7 +220,7 @@ int gsr_splice_rim_edges(int F, int V, const int* faces, const int* counts, int*
     GSR_CHECK(hipMemsetAsync(on_rim, 0, (size_t)V, st));
     GSR_CHECK(hipMemsetAsync(degree, 0, sizeof(int) * (size_t)V, st));
     GSR_CHECK(hipMemsetAsync(slots, 0xff, 2 * sizeof(unsigned) * (size_t)V, st));
-    if (F > 0) splice_rim_edge_kernel<<<blocks(F), SP_BLOCK, 0, st>>>(F, V, faces, counts, reinterpret_cast<int2*>(pairs), on_rim, degree, slots, err);
+    if (F > 0) splice_rim_edge_kernel<<<mesh_blocks(F), SP_BLOCK, 0, st>>>(F, V, faces, counts, reinterpret_cast<int2*>(pairs), on_rim, degree, slots, err);
     launch_union_find(V, 3ll * F, reinterpret_cast<const int2*>(pairs), on_rim, parent, root_flag, st);
     GSR_CHECK_LAUNCH("splice rim-edge kernels");
     return 0;
@@ -239,8 +235,8 @@ int gsr_splice_rim_census(int V, const int* degree, const int* parent, int* size
     hipStream_t st = (hipStream_t)stream;
     GSR_CHECK(hipMemsetAsync(size, 0, sizeof(int) * (size_t)V, st));
     GSR_CHECK(hipMemsetAsync(bad, 0, sizeof(int) * (size_t)V, st));
-    splice_census_kernel<<<blocks(V), SP_BLOCK, 0, st>>>(V, degree, parent, size, bad);
-    splice_decide_kernel<<<blocks(V), SP_BLOCK, 0, st>>>(V, degree, parent, size, bad, new_faces);
+    splice_census_kernel<<<mesh_blocks(V), SP_BLOCK, 0, st>>>(V, degree, parent, size, bad);
+    splice_decide_kernel<<<mesh_blocks(V), SP_BLOCK, 0, st>>>(V, degree, parent, size, bad, new_faces);
     GSR_CHECK_LAUNCH("splice census kernels");
     return 0;
 }
@@ -252,7 +248,7 @@ int gsr_splice_rim_emit(int V, int n_new, const int* new_faces, const int* new_s
     if (V < 0 || n_new < 0 || n_new > 0x7fffffff / 3) return fail_msg("gsr_splice_rim_emit: negative size or too many faces");
     if (V == 0 || n_new == 0) return 0;
     if (!new_faces || !new_scan || !slots || !faces_out || !rim_of_new) return fail_msg("gsr_splice_rim_emit: required pointer is null");
-    splice_emit_kernel<<<blocks(V), SP_BLOCK, 0, (hipStream_t)stream>>>(V, n_new, new_faces, new_scan, slots, faces_out, rim_of_new);
+    splice_emit_kernel<<<mesh_blocks(V), SP_BLOCK, 0, (hipStream_t)stream>>>(V, n_new, new_faces, new_scan, slots, faces_out, rim_of_new);
     GSR_CHECK_LAUNCH("splice_emit_kernel");
     return 0;
 }
@@ -260,10 +256,10 @@ int gsr_splice_rim_emit(int V, int n_new, const int* new_faces, const int* new_s
 int gsr_splice_face_areas(int F, int V, const int* faces, const float* verts, double* area, int* err, gsr_stream_t stream)
 {
     clear_error();
-    if (!splice_faces_ok(F) || V < 0) return fail_msg("gsr_splice_face_areas: negative size or too many faces");
+    if (!mesh_faces_ok(F) || V < 0) return fail_msg("gsr_splice_face_areas: negative size or too many faces");
     if (F == 0) return 0;
     if (!faces || !area || !err || (V > 0 && !verts)) return fail_msg("gsr_splice_face_areas: required pointer is null");
-    splice_area_kernel<<<blocks(F), SP_BLOCK, 0, (hipStream_t)stream>>>(F, V, faces, verts, area, err);
+    splice_area_kernel<<<mesh_blocks(F), SP_BLOCK, 0, (hipStream_t)stream>>>(F, V, faces, verts, area, err);
     GSR_CHECK_LAUNCH("splice_area_kernel");
     return 0;
 }
@@ -274,7 +270,7 @@ int gsr_splice_edge_lengths(int n, int V, const long long* keys, const float* ve
     if (n < 0 || V < 0) return fail_msg("gsr_splice_edge_lengths: negative size");
     if (n == 0) return 0;
     if (!keys || !length || !err || (V > 0 && !verts)) return fail_msg("gsr_splice_edge_lengths: required pointer is null");
-    splice_edge_length_kernel<<<blocks(n), SP_BLOCK, 0, (hipStream_t)stream>>>(n, V, keys, verts, length, err);
+    splice_edge_length_kernel<<<mesh_blocks(n), SP_BLOCK, 0, (hipStream_t)stream>>>(n, V, keys, verts, length, err);
     GSR_CHECK_LAUNCH("splice_edge_length_kernel");
     return 0;
 }

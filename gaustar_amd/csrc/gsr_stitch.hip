@@ -25,6 +25,7 @@
 #include "../../include/gsr.h"
 #include "gsr_entry.h"
 #include "gsr_internal.h"
+#include "gsr_mesh.h"
 #include "gsr_unionfind.h"
 
 #pragma clang fp contract(off)
@@ -33,8 +34,7 @@ namespace gsr {
 
 namespace {
 
-constexpr int ST_BLOCK = 256;
-constexpr int ST_ERR_INDEX = 1, ST_ERR_NAN = 2, ST_ERR_DUP = 4;   // bits of the calls' err word
+constexpr int ST_BLOCK = MESH_BLOCK;
 constexpr int NN_BLOCK = 256;       // four waves
 constexpr int NN_QUERIES = 16;      // queries of a workgroup: lane & 15 of every wave
 constexpr int NN_SLICES = 16;       // shares of a tile's candidates: 4 waves x (lane >> 4); slice s takes j = s, s + 16, ...
@@ -64,7 +64,7 @@ __global__ void __launch_bounds__(NN_BLOCK) stitch_nn_kernel(int Bq, int Bc, con
     double qx = 0., qy = 0., qz = 0.;
     if (live) {
         const float x = q[3 * (size_t)qi], y = q[3 * (size_t)qi + 1], z = q[3 * (size_t)qi + 2];
-        if (slice == 0 && !finite3(x, y, z)) atomicOr(err, ST_ERR_NAN);
+        if (slice == 0 && !finite3(x, y, z)) atomicOr(err, MESH_ERR_NAN);
         qx = (double)x; qy = (double)y; qz = (double)z;
     }
     double bd = __builtin_inf();
@@ -75,7 +75,7 @@ __global__ void __launch_bounds__(NN_BLOCK) stitch_nn_kernel(int Bq, int Bc, con
         const float* src = c + 3 * (size_t)base;
         for (int e = t; e < 3 * n; e += NN_BLOCK) {
             const float v = src[e];
-            if (blockIdx.x == 0 && (v - v) != 0.f) atomicOr(err, ST_ERR_NAN);
+            if (blockIdx.x == 0 && (v - v) != 0.f) atomicOr(err, MESH_ERR_NAN);
             tile[e % 3][e / 3] = (double)v;
         }
         __syncthreads();
@@ -119,8 +119,8 @@ __global__ void __launch_bounds__(ST_BLOCK) stitch_check_list_kernel(int B, int 
     const int i = blockIdx.x * ST_BLOCK + threadIdx.x;
     if (i >= B) return;
     const int v = list[i];
-    if ((unsigned)v >= (unsigned)V) { atomicOr(err, ST_ERR_INDEX); return; }
-    if (atomicAdd(mark + v, 1) != 0) atomicOr(err, ST_ERR_DUP);
+    if ((unsigned)v >= (unsigned)V) { atomicOr(err, MESH_ERR_INDEX); return; }
+    if (atomicAdd(mark + v, 1) != 0) atomicOr(err, MESH_ERR_DUP);
 }
 
 // ---------------------------------------------------------------------------------------------------- snap groups
@@ -160,13 +160,14 @@ __global__ void __launch_bounds__(ST_BLOCK) stitch_mark_kernel(int F, int V, con
 {
     const int f = blockIdx.x * ST_BLOCK + threadIdx.x;
     if (f >= F) return;
-    int a = faces[3 * (size_t)f], b = faces[3 * (size_t)f + 1], c = faces[3 * (size_t)f + 2];
-    if ((unsigned)a >= (unsigned)V || (unsigned)b >= (unsigned)V || (unsigned)c >= (unsigned)V) {
-        atomicOr(err, ST_ERR_INDEX);
+    int v[3];
+    if (!mesh_face(faces, f, V, v)) {
+        atomicOr(err, MESH_ERR_INDEX);
         faces_rw[3 * (size_t)f] = 0; faces_rw[3 * (size_t)f + 1] = 0; faces_rw[3 * (size_t)f + 2] = 0;
         keep[f] = 0;
         return;
     }
+    int a = v[0], b = v[1], c = v[2];
     if (remap) { a = remap[a]; b = remap[b]; c = remap[c]; }
     faces_rw[3 * (size_t)f] = a; faces_rw[3 * (size_t)f + 1] = b; faces_rw[3 * (size_t)f + 2] = c;
     const int kp = mask ? (mask[f] != 0) : (a != b && b != c && c != a);
@@ -183,9 +184,8 @@ __global__ void __launch_bounds__(ST_BLOCK) stitch_hole_edge_kernel(int F, int V
     const int f = blockIdx.x * ST_BLOCK + threadIdx.x;
     if (f >= F) return;
     int v[3];
-    for (int k = 0; k < 3; ++k) v[k] = faces[3 * (size_t)f + k];
-    const bool ok = (unsigned)v[0] < (unsigned)V && (unsigned)v[1] < (unsigned)V && (unsigned)v[2] < (unsigned)V;
-    if (!ok) atomicOr(err, ST_ERR_INDEX);
+    const bool ok = mesh_face(faces, f, V, v);
+    if (!ok) atomicOr(err, MESH_ERR_INDEX);
     for (int e = 0; e < 3; ++e) {
         int2 pr = make_int2(-1, -1);
         if (ok && counts[3 * (size_t)f + e] != 2) {
@@ -289,9 +289,6 @@ __global__ void __launch_bounds__(ST_BLOCK) stitch_watertight_kernel(long long n
     if (__ballot(b) && (threadIdx.x & 63) == 0) atomicOr(bad, 1);
 }
 
-inline unsigned blocks(long long n) { return (unsigned)((n + ST_BLOCK - 1) / ST_BLOCK); }
-bool stitch_faces_ok(int F) { return F >= 0 && F <= 0x7fffffff / 3; }
-
 }  // namespace
 
 }  // namespace gsr
@@ -328,7 +325,7 @@ int gsr_stitch_check_list(int B, int V, const int* list, int* mark, int* err, gs
     if (!list || !err || (V > 0 && !mark)) return fail_msg("gsr_stitch_check_list: required pointer is null");
     hipStream_t st = (hipStream_t)stream;
     if (V > 0) GSR_CHECK(hipMemsetAsync(mark, 0, sizeof(int) * (size_t)V, st));
-    stitch_check_list_kernel<<<blocks(B), ST_BLOCK, 0, st>>>(B, V, list, mark, err);
+    stitch_check_list_kernel<<<mesh_blocks(B), ST_BLOCK, 0, st>>>(B, V, list, mark, err);
     GSR_CHECK_LAUNCH("stitch_check_list_kernel");
     return 0;
 }
@@ -342,9 +339,9 @@ int gsr_stitch_snap_groups(int B1, int B2, int V1, int V2, const int* b1, const 
     if (!b1 || !b2 || !n21 || !n12 || !rep || !remap) return fail_msg("gsr_stitch_snap_groups: required pointer is null");
     hipStream_t st = (hipStream_t)stream;
     const int V = V1 + V2, B = B1 + B2;
-    stitch_group_init_kernel<<<blocks(V > B1 ? V : B1), ST_BLOCK, 0, st>>>(B1, V, rep, remap);
-    stitch_group_min_kernel<<<blocks(B), ST_BLOCK, 0, st>>>(B1, B2, n21, n12, rep);
-    stitch_group_remap_kernel<<<blocks(B), ST_BLOCK, 0, st>>>(B1, B2, V1, b1, b2, n21, n12, rep, remap);
+    stitch_group_init_kernel<<<mesh_blocks(V > B1 ? V : B1), ST_BLOCK, 0, st>>>(B1, V, rep, remap);
+    stitch_group_min_kernel<<<mesh_blocks(B), ST_BLOCK, 0, st>>>(B1, B2, n21, n12, rep);
+    stitch_group_remap_kernel<<<mesh_blocks(B), ST_BLOCK, 0, st>>>(B1, B2, V1, b1, b2, n21, n12, rep, remap);
     GSR_CHECK_LAUNCH("stitch snap-group kernels");
     return 0;
 }
@@ -353,12 +350,12 @@ int gsr_stitch_mark(int F, int V, const int* faces, const int* remap, const unsi
                     int* referenced, int* err, gsr_stream_t stream)
 {
     clear_error();
-    if (!stitch_faces_ok(F) || V < 0) return fail_msg("gsr_stitch_mark: negative size or too many faces");
+    if (!mesh_faces_ok(F) || V < 0) return fail_msg("gsr_stitch_mark: negative size or too many faces");
     if ((V > 0 && !referenced) || (F > 0 && (!faces || !faces_out || !keep || !err)))
         return fail_msg("gsr_stitch_mark: required pointer is null");
     hipStream_t st = (hipStream_t)stream;
     if (V > 0) GSR_CHECK(hipMemsetAsync(referenced, 0, sizeof(int) * (size_t)V, st));
-    if (F > 0) stitch_mark_kernel<<<blocks(F), ST_BLOCK, 0, st>>>(F, V, faces, remap, mask, faces_out, keep, referenced, err);
+    if (F > 0) stitch_mark_kernel<<<mesh_blocks(F), ST_BLOCK, 0, st>>>(F, V, faces, remap, mask, faces_out, keep, referenced, err);
     GSR_CHECK_LAUNCH("stitch_mark_kernel");
     return 0;
 }
@@ -367,14 +364,14 @@ int gsr_stitch_hole_components(int F, int V, const int* faces, const int* counts
                                int* root_flag, int* err, gsr_stream_t stream)
 {
     clear_error();
-    if (!stitch_faces_ok(F) || V < 0) return fail_msg("gsr_stitch_hole_components: negative size or too many faces");
+    if (!mesh_faces_ok(F) || V < 0) return fail_msg("gsr_stitch_hole_components: negative size or too many faces");
     if (V == 0) return 0;
     if (!hole || !parent || !root_flag || (F > 0 && (!faces || !counts || !pairs || !err)))
         return fail_msg("gsr_stitch_hole_components: required pointer is null");
     if (reinterpret_cast<uintptr_t>(pairs) & 7) return fail_msg("gsr_stitch_hole_components: pairs must be 8-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     GSR_CHECK(hipMemsetAsync(hole, 0, (size_t)V, st));
-    if (F > 0) stitch_hole_edge_kernel<<<blocks(F), ST_BLOCK, 0, st>>>(F, V, faces, counts, reinterpret_cast<int2*>(pairs), hole, err);
+    if (F > 0) stitch_hole_edge_kernel<<<mesh_blocks(F), ST_BLOCK, 0, st>>>(F, V, faces, counts, reinterpret_cast<int2*>(pairs), hole, err);
     launch_union_find(V, 3ll * F, reinterpret_cast<const int2*>(pairs), hole, parent, root_flag, st);
     GSR_CHECK_LAUNCH("stitch hole-component kernels");
     return 0;
@@ -389,8 +386,8 @@ int gsr_stitch_hole_move(int V, int max_hole_vert_num, const unsigned char* hole
     if (!hole || !parent || !size || !verts || !verts_out) return fail_msg("gsr_stitch_hole_move: required pointer is null");
     hipStream_t st = (hipStream_t)stream;
     GSR_CHECK(hipMemsetAsync(size, 0, sizeof(int) * (size_t)V, st));
-    stitch_hole_size_kernel<<<blocks(V), ST_BLOCK, 0, st>>>(V, hole, parent, size);
-    stitch_hole_move_kernel<<<blocks(V), ST_BLOCK, 0, st>>>(V, max_hole_vert_num, hole, parent, size, verts, verts_out);
+    stitch_hole_size_kernel<<<mesh_blocks(V), ST_BLOCK, 0, st>>>(V, hole, parent, size);
+    stitch_hole_move_kernel<<<mesh_blocks(V), ST_BLOCK, 0, st>>>(V, max_hole_vert_num, hole, parent, size, verts, verts_out);
     GSR_CHECK_LAUNCH("stitch hole-move kernels");
     return 0;
 }
@@ -401,7 +398,7 @@ int gsr_stitch_pos_keys(int H, const int* list, const float* verts, long long* k
     if (H < 0) return fail_msg("gsr_stitch_pos_keys: negative size");
     if (H == 0) return 0;
     if (!list || !verts || !key_xy || !key_z) return fail_msg("gsr_stitch_pos_keys: required pointer is null");
-    stitch_pos_key_kernel<<<blocks(H), ST_BLOCK, 0, (hipStream_t)stream>>>(H, list, verts, key_xy, key_z);
+    stitch_pos_key_kernel<<<mesh_blocks(H), ST_BLOCK, 0, (hipStream_t)stream>>>(H, list, verts, key_xy, key_z);
     GSR_CHECK_LAUNCH("stitch_pos_key_kernel");
     return 0;
 }
@@ -412,7 +409,7 @@ int gsr_stitch_pos_heads(int H, const long long* order, const int* list, const f
     if (H < 0) return fail_msg("gsr_stitch_pos_heads: negative size");
     if (H == 0) return 0;
     if (!order || !list || !verts || !head) return fail_msg("gsr_stitch_pos_heads: required pointer is null");
-    stitch_pos_head_kernel<<<blocks(H), ST_BLOCK, 0, (hipStream_t)stream>>>(H, order, list, verts, head);
+    stitch_pos_head_kernel<<<mesh_blocks(H), ST_BLOCK, 0, (hipStream_t)stream>>>(H, order, list, verts, head);
     GSR_CHECK_LAUNCH("stitch_pos_head_kernel");
     return 0;
 }
@@ -423,7 +420,7 @@ int gsr_stitch_pos_remap(int H, const long long* order, const int* list, const i
     if (H < 0) return fail_msg("gsr_stitch_pos_remap: negative size");
     if (H == 0) return 0;
     if (!order || !list || !first || !remap) return fail_msg("gsr_stitch_pos_remap: required pointer is null");
-    stitch_pos_remap_kernel<<<blocks(H), ST_BLOCK, 0, (hipStream_t)stream>>>(H, order, list, first, remap);
+    stitch_pos_remap_kernel<<<mesh_blocks(H), ST_BLOCK, 0, (hipStream_t)stream>>>(H, order, list, first, remap);
     GSR_CHECK_LAUNCH("stitch_pos_remap_kernel");
     return 0;
 }
@@ -435,7 +432,7 @@ int gsr_stitch_compose_mask(int F, const unsigned char* outer, const int* outer_
     if (F < 0 || n_inner < 0) return fail_msg("gsr_stitch_compose_mask: negative size");
     if (F == 0) return 0;
     if (!outer || !outer_scan || !out || (n_inner > 0 && !inner)) return fail_msg("gsr_stitch_compose_mask: required pointer is null");
-    stitch_compose_mask_kernel<<<blocks(F), ST_BLOCK, 0, (hipStream_t)stream>>>(F, outer, outer_scan, inner, n_inner, out);
+    stitch_compose_mask_kernel<<<mesh_blocks(F), ST_BLOCK, 0, (hipStream_t)stream>>>(F, outer, outer_scan, inner, n_inner, out);
     GSR_CHECK_LAUNCH("stitch_compose_mask_kernel");
     return 0;
 }
@@ -446,7 +443,7 @@ int gsr_stitch_vert_map(int V, const int* remap1, const int* map1, const int* re
     if (V < 0) return fail_msg("gsr_stitch_vert_map: negative size");
     if (V == 0) return 0;
     if (!remap1 || !map1 || !remap2 || !map2 || !out) return fail_msg("gsr_stitch_vert_map: required pointer is null");
-    stitch_vert_map_kernel<<<blocks(V), ST_BLOCK, 0, (hipStream_t)stream>>>(V, remap1, map1, remap2, map2, out);
+    stitch_vert_map_kernel<<<mesh_blocks(V), ST_BLOCK, 0, (hipStream_t)stream>>>(V, remap1, map1, remap2, map2, out);
     GSR_CHECK_LAUNCH("stitch_vert_map_kernel");
     return 0;
 }
@@ -454,13 +451,13 @@ int gsr_stitch_vert_map(int V, const int* remap1, const int* map1, const int* re
 int gsr_stitch_watertight(int F, const int* counts, int* bad, gsr_stream_t stream)
 {
     clear_error();
-    if (!stitch_faces_ok(F)) return fail_msg("gsr_stitch_watertight: F must be in [0, (2^31 - 1) / 3]");
+    if (!mesh_faces_ok(F)) return fail_msg("gsr_stitch_watertight: F must be in [0, (2^31 - 1) / 3]");
     if (!bad) return fail_msg("gsr_stitch_watertight: required pointer is null");
     hipStream_t st = (hipStream_t)stream;
     GSR_CHECK(hipMemsetAsync(bad, 0, sizeof(int), st));
     if (F == 0) return 0;
     if (!counts) return fail_msg("gsr_stitch_watertight: required pointer is null");
-    stitch_watertight_kernel<<<blocks(3ll * F), ST_BLOCK, 0, st>>>(3ll * F, counts, bad);
+    stitch_watertight_kernel<<<mesh_blocks(3ll * F), ST_BLOCK, 0, st>>>(3ll * F, counts, bad);
     GSR_CHECK_LAUNCH("stitch_watertight_kernel");
     return 0;
 }

@@ -22,20 +22,10 @@ import torch
 
 from . import _lib
 from ._lib import ptr as _p, stream_ptr as _stream
+from .regions import _faces_i32 as _faces, _raise_if
 
 FILLED = -2 ** 31            # a face_origin entry: the face was made by fill_small_holes
 SH_C0 = 0.28209479177387814
-
-
-def _raise_if(err: torch.Tensor) -> None:
-    """One host read: the kernels' err word, bit 0 = an index outside its array."""
-    if int(err.cpu()) & 1:
-        raise ValueError("an index lies outside its array")
-
-
-def _faces(faces: torch.Tensor) -> torch.Tensor:
-    from .regions import _faces_i32
-    return _faces_i32(faces)
 
 
 def _rgba(x: torch.Tensor, dev, what: str) -> torch.Tensor:
@@ -77,7 +67,7 @@ def vertex_to_face_colors(faces: torch.Tensor, vertex_colors: torch.Tensor) -> t
     err = torch.zeros(1, dtype=torch.int32, device=faces.device)
     _lib.check(_lib.load().gsr_handover_vertex_to_face(F, int(c.shape[0]), _p(faces), _p(c), int(c.shape[1]), _p(out), _p(err), _stream()),
                "gsr_handover_vertex_to_face")
-    _raise_if(err)
+    _raise_if(int(err.cpu()))
     return out
 
 
@@ -96,8 +86,8 @@ def face_to_vertex_colors(faces: torch.Tensor, face_rgba: torch.Tensor, n_verts:
     _lib.check(_lib.load().gsr_handover_face_to_vertex(F, V, _p(faces), _p(rgba), _p(sums), _p(out), _p(err), _stream()),
                "gsr_handover_face_to_vertex")
     if V == 0 and F:
-        raise ValueError("an index lies outside its array")        # (faces without vertices)
-    _raise_if(err)
+        _raise_if(1)                                               # (faces without vertices)
+    _raise_if(int(err.cpu()))
     return out
 
 
@@ -117,7 +107,7 @@ def sh_dc_from_vertex_colors(faces: torch.Tensor, vertex_colors: torch.Tensor, b
     err = torch.zeros(1, dtype=torch.int32, device=dev)
     _lib.check(_lib.load().gsr_handover_sh_dc(F, G, int(c.shape[0]), _p(faces), _p(c), int(c.shape[1]), _p(bary), _p(out), _p(err),
                                               _stream()), "gsr_handover_sh_dc")
-    _raise_if(err)
+    _raise_if(int(err.cpu()))
     return out
 
 
@@ -139,7 +129,7 @@ def gather_face_colors(origin: torch.Tensor, base_rgba: torch.Tensor, fusion_fac
     err = torch.zeros(1, dtype=torch.int32, device=dev)
     _lib.check(_lib.load().gsr_handover_gather(n, _p(origin), int(base.shape[0]), _p(base), int(ff.shape[0]), int(c.shape[0]), _p(ff),
                                                _p(c), int(c.shape[1]), _p(out), _p(err), _stream()), "gsr_handover_gather")
-    _raise_if(err)
+    _raise_if(int(err.cpu()))
     return out
 
 

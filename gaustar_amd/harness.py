@@ -542,12 +542,10 @@ class SurfaceGaussians(nn.Module):
         patch, base = cut.fusion_patch, cut.base_cut
         if patch.verts.shape[0] == 0 or base.verts.shape[0] == 0:
             return None
-        keep = regions.outlier_component_mask(patch.faces, outlier_face_threshold)
-        patch = regions.select_faces(patch.verts, patch.faces, keep, attrs=patch.attrs)
-        patch_boundary = regions.boundary_vertices(patch.verts, patch.faces, cut.box, cut_inner=False)
+        patch, patch_boundary, _keep, _n_new = regions._patch_for_box(patch, cut.box, outlier_face_threshold, fill=False)
         if patch_boundary.shape[0] == 0:
             return None
-        base_boundary = regions.boundary_vertices(base.verts, base.faces, cut.box, cut_inner=True, pad=pad)
+        _faces, base_boundary, _n_new = regions._base_for_box(base, cut.box, pad, fill=False)
         if base_boundary.shape[0] == 0:
             return None
         st = regions.connect_two_meshes(base.verts, base.faces, base_boundary, patch.verts, patch.faces, patch_boundary)

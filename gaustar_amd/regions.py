@@ -61,6 +61,11 @@ statement of trimesh's, and parity with trimesh is not pinned (it is not a depen
 
     upd = update_mesh_topology(...).with_colors(base_face_rgba, fusion_mesh.colors)    # face_colors, vertex_colors; save() writes them
     track_face_mask, ref_area = load_tracking("face_corr.npz")          # what refine.py:315-323 reads back
+
+Stated once for all of the above: the err word of the four kernel files and its decoder (csrc/gsr_mesh.h, _raise_if; a call
+chain may pass one word through kernels of several files before it is read); a mesh's edge counts (_edge_counts); the tail of
+a compaction (_emit: cut_mesh_by_box and select_faces / the degenerate passes differ in the mark call before it); steps 1 and
+2 of one box (_patch_for_box, _base_for_box: update_mesh_topology fills holes, harness's stitch_update_region does not).
 """
 from __future__ import annotations
 
@@ -107,30 +112,49 @@ def _box6(box) -> Tuple[np.ndarray, ctypes.Array]:
     return b, (ctypes.c_double * 6)(*b.reshape(-1))
 
 
-def _raise_if(err: int) -> None:
-    """The kernels' err word: bit 0 = a vertex index outside the mesh, bit 1 = a NaN among a box's coordinates."""
+_NAN_BOX = "a vertex or Gaussian centre of a kept region is NaN: its box is not defined"
+_NAN_BOUNDARY = "a boundary position is NaN or infinite: its nearest vertex is not defined"
+
+
+def _raise_if(err: int, nan: str = _NAN_BOX) -> None:
+    """The one err word of all the mesh kernels (csrc/gsr_mesh.h): bit 0 = an index outside its array, bit 2 = a boundary list
+    names a vertex twice, bit 1 = a coordinate that is NaN or not finite; what that leaves undefined is the caller's `nan`."""
     if err & 1:
-        raise ValueError("faces hold a vertex index outside the mesh")
+        raise ValueError("a vertex index, or another index into the mesh, lies outside its array")
+    if err & 4:
+        raise ValueError("a boundary list names a vertex twice")
     if err & 2:
-        raise ValueError("a vertex or Gaussian centre of a kept region is NaN: its box is not defined")
+        raise ValueError(nan)
 
 
 # ------------------------------------------------------------------------------------------------ edges and components
+def _edge_keys(faces: torch.Tensor, mask: Optional[torch.Tensor], colour: Optional[torch.Tensor], cut: int, err: torch.Tensor, st):
+    """faces [F,3] int32 (F > 0) -> (selected [F] uint8, keys [3F] int64: min << 32 | max of every face-edge's vertex pair, a
+    sentinel for the faces not selected).  st: the caller's _stream(), which it needs for its next launch anyway."""
+    F = int(faces.shape[0])
+    sel = torch.empty(F, dtype=torch.uint8, device=faces.device)
+    keys = torch.empty(3 * F, dtype=torch.int64, device=faces.device)
+    _lib.check(_lib.load().gsr_regions_edge_keys(F, _p(faces), _p(mask), _p(colour), int(cut), _p(sel), _p(keys), _p(err), st),
+               "gsr_regions_edge_keys")
+    return sel, keys
+
+
 def _edge_runs(faces: torch.Tensor, mask: Optional[torch.Tensor], colour: Optional[torch.Tensor], cut: int, err: torch.Tensor):
     """faces [F,3] int32 (F > 0) -> (selected [F] uint8, counts [F,3] int32, pairs [3F,2] int32)."""
-    lib = _lib.load()
     dev, F = faces.device, int(faces.shape[0])
-    sel = torch.empty(F, dtype=torch.uint8, device=dev)
-    keys = torch.empty(3 * F, dtype=torch.int64, device=dev)
     st = _stream()
-    _lib.check(lib.gsr_regions_edge_keys(F, _p(faces), _p(mask), _p(colour), int(cut), _p(sel), _p(keys), _p(err), st),
-               "gsr_regions_edge_keys")
+    sel, keys = _edge_keys(faces, mask, colour, cut, err, st)
     skeys, order = torch.sort(keys, stable=True)
     del keys
     counts = torch.empty(F, 3, dtype=torch.int32, device=dev)
     pairs = torch.empty(3 * F, 2, dtype=torch.int32, device=dev)
-    _lib.check(lib.gsr_regions_edge_runs(F, _p(skeys), _p(order), _p(counts), _p(pairs), st), "gsr_regions_edge_runs")
+    _lib.check(_lib.load().gsr_regions_edge_runs(F, _p(skeys), _p(order), _p(counts), _p(pairs), st), "gsr_regions_edge_runs")
     return sel, counts, pairs
+
+
+def _edge_counts(faces: torch.Tensor, err: torch.Tensor, mask: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+    """The edge counts of a mesh: [F,3] int32 as face_edge_counts gives them, None without faces.  Nothing is read."""
+    return _edge_runs(faces, mask, None, 0, err)[1] if faces.shape[0] else None
 
 
 def _mask_u8(mask: Optional[torch.Tensor], F: int, dev) -> Optional[torch.Tensor]:
@@ -154,7 +178,7 @@ def face_edge_counts(faces: torch.Tensor, mask: Optional[torch.Tensor] = None) -
     if F == 0:
         return torch.empty(0, 3, dtype=torch.int32, device=faces.device)
     err = torch.zeros(1, dtype=torch.int32, device=faces.device)
-    _sel, counts, _pairs = _edge_runs(faces, _mask_u8(mask, F, faces.device), None, 0, err)
+    counts = _edge_counts(faces, err, _mask_u8(mask, F, faces.device))
     _raise_if(int(err.cpu()))
     return counts
 
@@ -327,6 +351,37 @@ def _gather(old_of_new: torch.Tensor, src: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def _vertex_attrs(attrs: Sequence[torch.Tensor], V: int, dev) -> Tuple[torch.Tensor, ...]:
+    attrs = tuple(attrs)
+    for a in attrs:
+        if a.dim() < 1 or a.shape[0] != V or a.element_size() != 4 or a.device != dev:
+            raise ValueError("attrs must be per-vertex arrays [V, ...] of a 4-byte dtype on the mesh's GPU")
+    return attrs
+
+
+def _emit(verts: torch.Tensor, faces: torch.Tensor, keep: torch.Tensor, ref: torch.Tensor, attrs: Sequence[torch.Tensor],
+          err: torch.Tensor, st) -> Tuple[CutMesh, torch.Tensor]:
+    """The tail of a compaction, after a mark call on stream st has written keep [F] and ref [V] int32 (0 / 1): the faces with
+    keep set, in their order, the vertices with ref set renumbered in ascending old index -> (CutMesh, keep_scan [F] int32).
+    One host read: the two totals and err."""
+    dev, F, V = faces.device, int(faces.shape[0]), int(verts.shape[0])
+    kscan = torch.cumsum(keep, 0, dtype=torch.int32)
+    vscan = torch.cumsum(ref, 0, dtype=torch.int32)
+    zero = torch.zeros(1, dtype=torch.int32, device=dev)
+    head = torch.cat([kscan[-1:] if F else zero, vscan[-1:] if V else zero, err]).cpu()
+    _raise_if(int(head[2]), _NAN_BOUNDARY)      # (bit 1 comes from connect_two_meshes' searches only)
+    nf, nv = int(head[0]), int(head[1])
+    faces_out = torch.empty(nf, 3, dtype=torch.int32, device=dev)
+    face_mask = torch.empty(F, dtype=torch.bool, device=dev)
+    vert_map = torch.empty(V, dtype=torch.int32, device=dev)
+    old_of_new = torch.empty(nv, dtype=torch.int32, device=dev)
+    _lib.check(_lib.load().gsr_regions_cut_emit(F, V, _p(faces), _p(keep), _p(kscan), _p(ref), _p(vscan), _p(faces_out), _p(face_mask),
+                                                _p(vert_map), _p(old_of_new), st), "gsr_regions_cut_emit")
+    cut = CutMesh(verts=_gather(old_of_new, verts), faces=faces_out, face_mask=face_mask, vert_map=vert_map,
+                  attrs=tuple(_gather(old_of_new, a.detach().contiguous()) for a in attrs))
+    return cut, kscan
+
+
 @torch.no_grad()
 def cut_mesh_by_box(verts: torch.Tensor, faces: torch.Tensor, box, cut_inner: bool, attrs: Sequence[torch.Tensor] = ()) -> CutMesh:
     """cut_mesh_by_boundingbox (refined_mesh.py:218-251).  box: [2,3] (lo, hi), taken as float64.  A vertex is inside iff all
@@ -341,31 +396,15 @@ def cut_mesh_by_box(verts: torch.Tensor, faces: torch.Tensor, box, cut_inner: bo
     verts = _verts_f32(verts, dev)
     V = int(verts.shape[0])
     _b, box6 = _box6(box)
-    attrs = tuple(attrs)
-    for a in attrs:
-        if a.dim() < 1 or a.shape[0] != V or a.element_size() != 4 or a.device != dev:
-            raise ValueError("attrs must be per-vertex arrays [V, ...] of a 4-byte dtype on the mesh's GPU")
-    st = _stream()
+    attrs = _vertex_attrs(attrs, V, dev)
     inside = _inside(verts, box6)
     keep = torch.empty(F, dtype=torch.int32, device=dev)
     ref = torch.empty(V, dtype=torch.int32, device=dev)
     err = torch.zeros(1, dtype=torch.int32, device=dev)
+    st = _stream()
     _lib.check(lib.gsr_regions_cut_mark(F, V, _p(faces), _p(inside), int(bool(cut_inner)), _p(keep), _p(ref), _p(err), st),
                "gsr_regions_cut_mark")
-    kscan = torch.cumsum(keep, 0, dtype=torch.int32)
-    vscan = torch.cumsum(ref, 0, dtype=torch.int32)
-    zero = torch.zeros(1, dtype=torch.int32, device=dev)
-    head = torch.cat([kscan[-1:] if F else zero, vscan[-1:] if V else zero, err]).cpu()
-    _raise_if(int(head[2]))
-    nf, nv = int(head[0]), int(head[1])
-    faces_out = torch.empty(nf, 3, dtype=torch.int32, device=dev)
-    face_mask = torch.empty(F, dtype=torch.bool, device=dev)
-    vert_map = torch.empty(V, dtype=torch.int32, device=dev)
-    old_of_new = torch.empty(nv, dtype=torch.int32, device=dev)
-    _lib.check(lib.gsr_regions_cut_emit(F, V, _p(faces), _p(keep), _p(kscan), _p(ref), _p(vscan), _p(faces_out), _p(face_mask),
-                                        _p(vert_map), _p(old_of_new), st), "gsr_regions_cut_emit")
-    return CutMesh(verts=_gather(old_of_new, verts), faces=faces_out, face_mask=face_mask, vert_map=vert_map,
-                   attrs=tuple(_gather(old_of_new, a.detach().contiguous()) for a in attrs))
+    return _emit(verts, faces, keep, ref, attrs, err, st)[0]
 
 
 @dataclass
@@ -392,7 +431,7 @@ def boundary_vertices(verts: torch.Tensor, faces: torch.Tensor, box=None, cut_in
     verts = _verts_f32(verts, dev)
     V = int(verts.shape[0])
     err = torch.zeros(1, dtype=torch.int32, device=dev)
-    counts = _edge_runs(faces, None, None, 0, err)[1] if F else None
+    counts = _edge_counts(faces, err)
     bmark = torch.empty(V, dtype=torch.uint8, device=dev)
     fmark = inside = None
     if box is not None:
@@ -445,17 +484,6 @@ def __getattr__(name: str):
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
-def _raise_if_stitch(err: int) -> None:
-    """The stitch kernels' err word: bit 0 = an index outside its array, bit 1 = a position that is NaN or infinite, bit 2 = an
-    index listed twice."""
-    if err & 1:
-        raise ValueError("an index lies outside the mesh")
-    if err & 4:
-        raise ValueError("a boundary list names a vertex twice")
-    if err & 2:
-        raise ValueError("a boundary position is NaN or infinite: its nearest vertex is not defined")
-
-
 def _nearest(q: torch.Tensor, c: torch.Tensor, err: torch.Tensor):
     """q [Bq,3], c [Bc,3] f32 contiguous, Bq, Bc > 0 -> (idx [Bq] int32, d2 [Bq] f64, max_bits [1] int64).  Nothing is read."""
     lib = _lib.load()
@@ -487,7 +515,7 @@ def nearest_vertices(queries: torch.Tensor, candidates: torch.Tensor, return_max
     err = torch.zeros(1, dtype=torch.int32, device=dev)
     idx, d2, mx = _nearest(queries.detach().contiguous(), candidates.detach().contiguous(), err)
     head = torch.cat([err.to(torch.int64), mx]).cpu().numpy()
-    _raise_if_stitch(int(head[0]))
+    _raise_if(int(head[0]), _NAN_BOUNDARY)
     return (idx, d2, float(head[1:].view(np.float64)[0])) if return_max else (idx, d2)
 
 
@@ -495,29 +523,14 @@ def _compact(verts: torch.Tensor, faces: torch.Tensor, remap: Optional[torch.Ten
              attrs: Sequence[torch.Tensor], err: torch.Tensor) -> Tuple[CutMesh, torch.Tensor]:
     """The faces rewritten by `remap`, kept by `mask` (without one: unless degenerate), their vertices renumbered in ascending
     old index -> (CutMesh, keep_scan [F] int32).  One host read: the two totals and err."""
-    lib = _lib.load()
     dev, F, V = faces.device, int(faces.shape[0]), int(verts.shape[0])
-    st = _stream()
     faces_rw = torch.empty(F, 3, dtype=torch.int32, device=dev)
     keep = torch.empty(F, dtype=torch.int32, device=dev)
     ref = torch.empty(V, dtype=torch.int32, device=dev)
-    _lib.check(lib.gsr_stitch_mark(F, V, _p(faces), _p(remap), _p(mask), _p(faces_rw), _p(keep), _p(ref), _p(err), st),
+    st = _stream()
+    _lib.check(_lib.load().gsr_stitch_mark(F, V, _p(faces), _p(remap), _p(mask), _p(faces_rw), _p(keep), _p(ref), _p(err), st),
                "gsr_stitch_mark")
-    kscan = torch.cumsum(keep, 0, dtype=torch.int32)
-    vscan = torch.cumsum(ref, 0, dtype=torch.int32)
-    zero = torch.zeros(1, dtype=torch.int32, device=dev)
-    head = torch.cat([kscan[-1:] if F else zero, vscan[-1:] if V else zero, err]).cpu()
-    _raise_if_stitch(int(head[2]))
-    nf, nv = int(head[0]), int(head[1])
-    faces_out = torch.empty(nf, 3, dtype=torch.int32, device=dev)
-    face_mask = torch.empty(F, dtype=torch.bool, device=dev)
-    vert_map = torch.empty(V, dtype=torch.int32, device=dev)
-    old_of_new = torch.empty(nv, dtype=torch.int32, device=dev)
-    _lib.check(lib.gsr_regions_cut_emit(F, V, _p(faces_rw), _p(keep), _p(kscan), _p(ref), _p(vscan), _p(faces_out), _p(face_mask),
-                                        _p(vert_map), _p(old_of_new), st), "gsr_regions_cut_emit")
-    cut = CutMesh(verts=_gather(old_of_new, verts), faces=faces_out, face_mask=face_mask, vert_map=vert_map,
-                  attrs=tuple(_gather(old_of_new, a.detach().contiguous()) for a in attrs))
-    return cut, kscan
+    return _emit(verts, faces_rw, keep, ref, attrs, err, st)
 
 
 @torch.no_grad()
@@ -531,16 +544,8 @@ def select_faces(verts: torch.Tensor, faces: torch.Tensor, face_mask: torch.Tens
     mask = _mask_u8(face_mask, F, dev)
     if mask is None:
         raise ValueError("face_mask must be [F] bool or uint8")
-    attrs = tuple(attrs)
-    for a in attrs:
-        if a.dim() < 1 or a.shape[0] != V or a.element_size() != 4 or a.device != dev:
-            raise ValueError("attrs must be per-vertex arrays [V, ...] of a 4-byte dtype on the mesh's GPU")
     err = torch.zeros(1, dtype=torch.int32, device=dev)
-    return _compact(verts, faces, None, mask, attrs, err)[0]
-
-
-def _edge_counts(faces: torch.Tensor, err: torch.Tensor) -> Optional[torch.Tensor]:
-    return _edge_runs(faces, None, None, 0, err)[1] if faces.shape[0] else None
+    return _compact(verts, faces, None, mask, _vertex_attrs(attrs, V, dev), err)[0]
 
 
 def _watertight_word(faces: torch.Tensor, err: torch.Tensor) -> torch.Tensor:
@@ -676,7 +681,7 @@ def connect_two_meshes(verts1: torch.Tensor, faces1: torch.Tensor, boundary1: to
     mark = torch.empty(max(V1, V2, 1), dtype=torch.int32, device=dev)
     _lib.check(lib.gsr_stitch_check_list(B1, V1, _p(b1), _p(mark), _p(err), st), "gsr_stitch_check_list")
     _lib.check(lib.gsr_stitch_check_list(B2, V2, _p(b2), _p(mark), _p(err), st), "gsr_stitch_check_list")
-    _raise_if_stitch(int(err.cpu()))                    # (before anything is gathered through the lists)
+    _raise_if(int(err.cpu()), _NAN_BOUNDARY)            # (before anything is gathered through the lists)
     # the two snaps
     pc1 = _gather(b1, verts1)
     pc2 = _gather(b2, verts2)
@@ -711,7 +716,7 @@ def connect_two_meshes(verts1: torch.Tensor, faces1: torch.Tensor, boundary1: to
     else:
         bad = torch.ones(1, dtype=torch.int64, device=dev)
     head = torch.cat([err.to(torch.int64), bad, n_first, max21, max12]).cpu().numpy()
-    _raise_if_stitch(int(head[0]))
+    _raise_if(int(head[0]), _NAN_BOUNDARY)
     d2max = head[3:5].view(np.float64)
     return StitchedMesh(verts=cut2.verts, faces=cut2.faces, face_mask=face_mask, vert_map=vert_map, n_faces_from_first=int(head[2]),
                         max_dist=float(np.sqrt(np.maximum(d2max[0], d2max[1]))), watertight=int(head[1]) == 0)
@@ -756,13 +761,12 @@ def _fill(faces: torch.Tensor, V: int, err: torch.Tensor) -> Tuple[torch.Tensor,
     lib = _lib.load()
     dev, F = faces.device, int(faces.shape[0])
     none = torch.empty(0, dtype=torch.int32, device=dev)
-    if F == 0 or V == 0:
-        if F:
-            err.fill_(1)         # (faces without vertices: every index is outside the mesh)
-            _raise_if(1)
+    if F and V == 0:
+        _raise_if(1)             # (faces without vertices: every index is outside the mesh)
+    if F == 0:
         return faces, 0, none
     st = _stream()
-    counts = _edge_runs(faces, None, None, 0, err)[1]
+    counts = _edge_counts(faces, err)
     pairs = torch.empty(3 * F, 2, dtype=torch.int32, device=dev)
     on = torch.empty(V, dtype=torch.uint8, device=dev)
     degree = torch.empty(V, dtype=torch.int32, device=dev)
@@ -863,10 +867,8 @@ def mean_edge_length(verts: torch.Tensor, faces: torch.Tensor) -> float:
     if F == 0:
         return float("nan")
     err = torch.zeros(1, dtype=torch.int32, device=dev)
-    sel = torch.empty(F, dtype=torch.uint8, device=dev)
-    keys = torch.empty(3 * F, dtype=torch.int64, device=dev)
     st = _stream()
-    _lib.check(lib.gsr_regions_edge_keys(F, _p(faces), None, None, 0, _p(sel), _p(keys), _p(err), st), "gsr_regions_edge_keys")
+    keys = _edge_keys(faces, None, None, 0, err, st)[1]
     _raise_if(int(err.cpu()))                                 # (a negative index: its face's keys are the sentinel)
     keys = torch.unique(keys)
     n = int(keys.shape[0])
@@ -953,6 +955,23 @@ class TopologyUpdate:
         return self.track_face_mask.repeat_interleave(int(G))
 
 
+def _patch_for_box(patch: CutMesh, box, outlier_face_threshold, fill: bool, err: Optional[torch.Tensor] = None):
+    """Step 1 of update_mesh_topology's docstring after the cut, on a patch that is not empty: with `fill` fill_small_holes (err:
+    its word), the outlier mask, select_faces (patch.attrs follow), the boundary vertices across the box.  -> (the selected
+    patch, its boundary -- none: the box fails --, the outlier mask over the patch's faces and the n_new filled ones, n_new)."""
+    pf, n_new, _rim = _fill(patch.faces, int(patch.verts.shape[0]), err) if fill else (patch.faces, 0, None)
+    keep = outlier_component_mask(pf, outlier_face_threshold)
+    patch = select_faces(patch.verts, pf, keep, attrs=patch.attrs)
+    return patch, boundary_vertices(patch.verts, patch.faces, box, cut_inner=False), keep, n_new
+
+
+def _base_for_box(cut: CutMesh, box, pad: float, fill: bool, err: Optional[torch.Tensor] = None):
+    """Step 2 after the cut, on a base cut that is not empty: with `fill` fill_small_holes, the boundary vertices inside the box
+    grown by `pad`.  -> (the cut's faces and the n_new filled ones, the boundary -- none: the box fails --, n_new)."""
+    cf, n_new, _rim = _fill(cut.faces, int(cut.verts.shape[0]), err) if fill else (cut.faces, 0, None)
+    return cf, boundary_vertices(cut.verts, cf, box, cut_inner=True, pad=pad), n_new
+
+
 @torch.no_grad()
 def update_mesh_topology(verts: torch.Tensor, faces: torch.Tensor, update_regions: UpdateRegions, fusion_mesh, aabb_pad: float = 0.02,
                          outlier_face_threshold=50, force_watertight: bool = True, force_short_edge: bool = False,
@@ -991,12 +1010,9 @@ def update_mesh_topology(verts: torch.Tensor, faces: torch.Tensor, update_region
         if patch.verts.shape[0] == 0:
             failed += 1
             continue
-        pf, p_new, _rim = _fill(patch.faces, int(patch.verts.shape[0]), err)
-        p_origin = torch.cat([-1 - torch.nonzero(patch.face_mask).view(-1).to(torch.int32), filled_run(p_new)])
-        p_keep = outlier_component_mask(pf, outlier_face_threshold)
-        patch = select_faces(patch.verts, pf, p_keep)
-        p_origin = p_origin[p_keep]
-        pb = boundary_vertices(patch.verts, patch.faces, box, cut_inner=False)
+        p_cut = -1 - torch.nonzero(patch.face_mask).view(-1).to(torch.int32)
+        patch, pb, p_keep, p_new = _patch_for_box(patch, box, outlier_face_threshold, True, err)
+        p_origin = torch.cat([p_cut, filled_run(p_new)])[p_keep]
         if pb.shape[0] == 0:
             failed += 1
             continue
@@ -1005,8 +1021,7 @@ def update_mesh_topology(verts: torch.Tensor, faces: torch.Tensor, update_region
             failed += 1
             continue
         n_cut = int(cut.faces.shape[0])
-        cf, c_new, _rim = _fill(cut.faces, int(cut.verts.shape[0]), err)
-        bb = boundary_vertices(cut.verts, cf, box, cut_inner=True)
+        cf, bb, c_new = _base_for_box(cut, box, 0.02, True, err)
         if bb.shape[0] == 0:
             failed += 1
             continue

@@ -144,6 +144,28 @@ def test_bad_index_empty_and_closed():
     assert got.n_new == 0 and got.watertight and np.array_equal(_n(got.faces), CUBE)
 
 
+def test_one_err_word_through_every_entry():
+    """A vertex index equal to V on a 2-quad grid (4 faces, 6 vertices): every entry that shares the err word (csrc/gsr_mesh.h)
+    raises the decoder's ValueError, and the same call with the valid faces then succeeds on the same stream.  Each kernel
+    tests the index before it indexes anything with it, so nothing here faults the device."""
+    from gaustar_amd import handover, regions
+    v, f = rr.quad_grid(2, 1)
+    bad = f.copy()
+    bad[3, 2] = len(v)
+    box = np.array([[-1.0] * 3, [3.0] * 3])
+    tv, colours = _t(v), _t(np.full((len(v), 3), 0.5, np.float32))
+    every = torch.ones(len(f), dtype=torch.bool, device=DEV)
+    calls = dict(cut_mesh_by_box=lambda m: regions.cut_mesh_by_box(tv, m, box, False).faces,
+                 select_faces=lambda m: regions.select_faces(tv, m, every).faces,
+                 fill_small_holes=lambda m: regions.fill_small_holes(m, len(v)).faces,
+                 face_areas=lambda m: regions.face_areas(tv, m),
+                 vertex_to_face_colors=lambda m: handover.vertex_to_face_colors(m, colours))
+    for name, call in calls.items():
+        with pytest.raises(ValueError, match="outside"):
+            call(_t(bad))
+        assert call(_t(f)).shape[0] == len(f), name
+
+
 # ---------------------------------------------------------------------------------------------------- areas
 def test_face_areas_and_mean_are_reproducible():
     from gaustar_amd import regions
@@ -223,6 +245,28 @@ def test_chain():
     assert regions.is_watertight(got.faces)
     g = got.gaussian_mask(2)
     assert np.array_equal(_n(g), np.repeat(want["track_face_mask"], 2))
+
+
+# update_mesh_topology's calls of Tensor.cpu for one spliced box of the chain case, counted by this test at the commit
+# "Carry colours through the frame hand-over: colour mesh, update, re-bind" (32c4fe4), before the wrappers were shared: the
+# two cuts 1 + 1, the three fillings 1 + 1 + 1, the outlier mask 2, select_faces 1, the two boundaries 1 + 1,
+# connect_two_meshes 4, the surviving faces' number 1, the areas 1.
+HOST_READS_ONE_BOX = 16
+
+
+def test_update_host_reads(monkeypatch):
+    """A host read is a discrete event: sharing code between the wrappers may not add one.  No margin."""
+    from gaustar_amd import regions
+    bv, bf, fv, ff, raw = chain_case()
+    args = (_t(bv), _t(bf), _regions_of(raw[:1]), _Mesh(fv, ff))
+    calls = []
+    real = torch.Tensor.cpu
+    monkeypatch.setattr(torch.Tensor, "cpu", lambda self, *a, **kw: calls.append(1) or real(self, *a, **kw))
+    got = regions.update_mesh_topology(*args)
+    monkeypatch.undo()
+    print("Tensor.cpu calls in update_mesh_topology, one box:", len(calls))
+    assert got.n_spliced == 1 and got.cc_update_num == 1
+    assert len(calls) == HOST_READS_ONE_BOX
 
 
 def test_nothing_to_update_and_failed_boxes():

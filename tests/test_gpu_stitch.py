@@ -315,6 +315,29 @@ def test_stitch_update_region():
     assert empty.fusion_patch.faces.shape[0] == 0 and model.stitch_update_region(empty) is None
 
 
+def test_stitch_update_region_is_the_public_primitives():
+    """stitch_update_region equals, bit for bit, the sequence of public calls its docstring names -- whatever private helpers
+    the harness and update_mesh_topology share to state one box."""
+    from gaustar_amd import harness, regions
+    v, f, vp, fp, box, _bound = _torus_case()
+    model = harness.SurfaceGaussians(_t(v), _t(f, torch.long), n_gaussians_per_surface_triangle=1, sh_levels=1)
+    colours = np.random.default_rng(8).uniform(0, 1, (len(vp), 3)).astype(np.float32)
+    cut = regions.RegionCut(box=box, fusion_patch=regions.cut_mesh_by_box(_t(vp), _t(fp), box, False, attrs=(_t(colours),)),
+                            base_cut=regions.cut_mesh_by_box(_t(v), _t(f), box, True))
+    out = model.stitch_update_region(cut, pad=1.0)
+    patch, base = cut.fusion_patch, cut.base_cut
+    keep = regions.outlier_component_mask(patch.faces, 50)
+    patch = regions.select_faces(patch.verts, patch.faces, keep, attrs=patch.attrs)
+    b2 = regions.boundary_vertices(patch.verts, patch.faces, box, cut_inner=False)
+    b1 = regions.boundary_vertices(base.verts, base.faces, box, cut_inner=True, pad=1.0)
+    assert b1.shape[0] > 16 and b2.shape[0] > 16
+    st = regions.connect_two_meshes(base.verts, base.faces, b1, patch.verts, patch.faces, b2)
+    mask = regions.compose_face_mask(base.face_mask, st.face_mask[:int(base.faces.shape[0])])
+    assert torch.equal(out.stitched.faces, st.faces) and _same_bits(_n(out.stitched.verts), _n(st.verts))
+    assert torch.equal(out.stitched.face_mask, st.face_mask) and torch.equal(out.base_face_mask, mask)
+    assert torch.equal(out.patch.faces, patch.faces) and _same_bits(_n(out.patch.attrs[0]), _n(patch.attrs[0]))
+
+
 # ---------------------------------------------------------------------------------------------------- errors
 def test_errors():
     """Bad lists are caught by the err word before anything is gathered through them: nothing here faults the device."""
