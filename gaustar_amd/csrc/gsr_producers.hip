@@ -15,6 +15,20 @@
 
 namespace gsr {
 
+// The wave's 64 coefficient rows into its LDS rows (coalesced, see gsr_internal.h), from one array [P, M, 3] or from the
+// dc / rest pair -- both layouts land in the same rows.  (The wave's first row, idx - lane, is formed inside each branch:
+// taken as an argument it stays live across both and costs the two kernels 2 VGPRs each.)
+__device__ __forceinline__ void sh_stage_rows(float* __restrict__ wave_rows, const float* __restrict__ shs,
+                                              const float* __restrict__ shs_rest, int idx, int P, int M, int lane)
+{
+    if (shs_rest == nullptr) {
+        sh_stage_load(wave_rows, shs, (size_t)(idx - lane), P, M, lane);
+    } else {
+        sh_stage_load_cols(wave_rows, shs, (size_t)(idx - lane), P, 3, sh_row_stride(M), 0, lane);
+        sh_stage_load_cols(wave_rows, shs_rest, (size_t)(idx - lane), P, 3 * (M - 1), sh_row_stride(M), 3, lane);
+    }
+}
+
 __global__ void __launch_bounds__(256)
 sh_to_rgb_kernel(int P, int D, int M, const float* __restrict__ positions, const float* __restrict__ campos,
                  const float* __restrict__ shs, const float* __restrict__ shs_rest, const float* __restrict__ view,
@@ -28,12 +42,7 @@ sh_to_rgb_kernel(int P, int D, int M, const float* __restrict__ positions, const
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     const int lane = threadIdx.x & 63;
     float* wave_rows = sh_lds + (size_t)(threadIdx.x >> 6) * 64 * sh_row_stride(M);
-    if (shs_rest == nullptr) {
-        sh_stage_load(wave_rows, shs, (size_t)(idx - lane), P, M, lane);   // coalesced, see gsr_internal.h
-    } else {
-        sh_stage_load_cols(wave_rows, shs, (size_t)(idx - lane), P, 3, sh_row_stride(M), 0, lane);
-        sh_stage_load_cols(wave_rows, shs_rest, (size_t)(idx - lane), P, 3 * (M - 1), sh_row_stride(M), 3, lane);
-    }
+    sh_stage_rows(wave_rows, shs, shs_rest, idx, P, M, lane);
     __builtin_amdgcn_wave_barrier();
     if (idx >= P) return;
     const size_t i = (size_t)idx;
@@ -71,12 +80,7 @@ sh_to_rgb_bwd_kernel(int P, int D, int M, const float* __restrict__ positions, c
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     const int lane = threadIdx.x & 63;
     float* wave_rows = sh_lds + (size_t)(threadIdx.x >> 6) * 64 * sh_row_stride(M);
-    if (shs_rest == nullptr) {
-        sh_stage_load(wave_rows, shs, (size_t)(idx - lane), P, M, lane);
-    } else {
-        sh_stage_load_cols(wave_rows, shs, (size_t)(idx - lane), P, 3, sh_row_stride(M), 0, lane);
-        sh_stage_load_cols(wave_rows, shs_rest, (size_t)(idx - lane), P, 3 * (M - 1), sh_row_stride(M), 3, lane);
-    }
+    sh_stage_rows(wave_rows, shs, shs_rest, idx, P, M, lane);
     __builtin_amdgcn_wave_barrier();
     if (idx < P) {
         const size_t i = (size_t)idx;
@@ -248,6 +252,74 @@ mesh_gaussians_fwd_kernel(int F, int G, const float* __restrict__ verts, const l
     }
 }
 
+// ---- the backward's per-Gaussian body, shared by the per-face and the lane-per-Gaussian kernel below
+// scales: exp, then clamp_max, clamp_min masks (x <= max, y >= min)
+__device__ __forceinline__ float scale_grad(float raw, float g, float min_scale, float max_scale)
+{
+    const float e = __expf(raw);
+    const bool pass = e <= max_scale && fminf(e, max_scale) >= min_scale;
+    return pass ? g * e : 0.f;
+}
+
+// Sums of products that are fused by hand, the way the lane-per-Gaussian kernel had them before both kernels shared this
+// body.  Left to -ffp-contract=fast, which product of a sum stays a plain multiply depends on the kernel the body is inlined
+// into (same opcodes, another pairing), and dL_draw_complex and dL_dverts move in their last bit.
+__device__ __forceinline__ float dot_zxy(V3 a, V3 b) { return fmaf(a.z, b.z, fmaf(a.x, b.x, a.y * b.y)); }
+__device__ __forceinline__ V3 fma3(float s, V3 a, V3 b) { return v3(fmaf(s, a.x, b.x), fmaf(s, a.y, b.y), fmaf(s, a.z, b.z)); }
+
+// One Gaussian's rotation: dL/dq -> rotation vector -> dL/dR -> delta_r and the raw complex number (both stored here);
+// returns what is left for the face frame, to be summed over the face's Gaussians.
+struct FrameGrad { V3 R0, bR1, bR2; };
+__device__ __forceinline__ FrameGrad rotation_backward(const FaceFrame& Ff, const GaussFrame& Gf, float4 gq, size_t n,
+                                                       float* __restrict__ dL_draw_complex, float* __restrict__ dL_ddelta_r)
+{
+    float q[4];
+    matrix_to_unit_quaternion(Gf.R, q);
+    const V3 qv = v3(q[1], q[2], q[3]), gqv = v3(gq.y, gq.z, gq.w);
+    const V3 Gw = 0.5f * (((-gq.x) * qv + q[0] * gqv) + cross(qv, gqv));           // dL/d(rotation vector)
+    // dL/dR = 1/2 [G]x R, column by column
+    V3 A[3];
+#pragma unroll
+    for (int c = 0; c < 3; c++) A[c] = 0.5f * cross(Gw, v3(Gf.R[0][c], Gf.R[1][c], Gf.R[2][c]));
+    V3 gB[3];
+    if (Gf.loose) {
+        // delta_r: dphi = 2 vec(dd^ (x) conj(d^)), dd^ = (I - d^ d^T) dd / |d|
+        const float hw = -2.0f * dot(Gw, Gf.dv);
+        const V3 hv = 2.0f * (Gf.dw * Gw - cross(Gf.dv, Gw));
+        const float il = 1.0f / Gf.ld;
+        if (dL_ddelta_r) reinterpret_cast<float4*>(dL_ddelta_r)[n] = make_float4(hw * il, hv.x * il, hv.y * il, hv.z * il);
+#pragma unroll
+        for (int c = 0; c < 3; c++)   // dL/dB = D^T dL/dR
+            gB[c] = v3(Gf.D[0][0] * A[c].x + Gf.D[1][0] * A[c].y + Gf.D[2][0] * A[c].z,
+                       Gf.D[0][1] * A[c].x + Gf.D[1][1] * A[c].y + Gf.D[2][1] * A[c].z,
+                       Gf.D[0][2] * A[c].x + Gf.D[1][2] * A[c].y + Gf.D[2][2] * A[c].z);
+    } else {
+#pragma unroll
+        for (int c = 0; c < 3; c++) gB[c] = A[c];
+    }
+    const float g_qc = dot_zxy(gB[1], Ff.bR1) + dot_zxy(gB[2], Ff.bR2), g_qs = dot_zxy(gB[1], Ff.bR2) - dot_zxy(gB[2], Ff.bR1);
+    // through the normalisation of the raw complex number (:493)
+    const float inv = 1.0f / fmaxf(Gf.lq, 1e-12f);
+    const float d = g_qc * Gf.qc + g_qs * Gf.qs;
+    const bool reg = Gf.lq > 1e-12f;
+    dL_draw_complex[2 * n] = reg ? inv * (g_qc - d * Gf.qc) : inv * g_qc;
+    dL_draw_complex[2 * n + 1] = reg ? inv * (g_qs - d * Gf.qs) : inv * g_qs;
+    return FrameGrad{gB[0], Gf.qc * gB[1] - Gf.qs * gB[2], fma3(Gf.qs, gB[1], Gf.qc * gB[2])};
+}
+
+// face frame -> vertices: the summed frame gradients go on top of the three vertex gradients
+__device__ __forceinline__ void frame_backward(const FaceFrame& Ff, V3 gR0, V3 gbR1, V3 gbR2, V3& gv0, V3& gv1, V3& gv2)
+{
+    const V3 gcr = normalize_bwd(Ff.bR2, Ff.lc, 1e-12f, gbR2);       // bR2 = normalize(R0 x bR1)
+    gR0 = gR0 + cross(Ff.bR1, gcr);
+    gbR1 = gbR1 + cross(gcr, Ff.R0);
+    const V3 ga = normalize_bwd(Ff.bR1, Ff.la, 1e-12f, gbR1);        // bR1 = normalize(v0 - v1)
+    gv0 = gv0 + ga; gv1 = gv1 - ga;
+    const V3 gn = normalize_bwd(Ff.R0, Ff.len, 1e-6f, gR0);          // R0 = normalize((e1 x e2) / max(|.|, 1e-6))
+    const V3 ge1 = cross(Ff.e2, gn), ge2 = cross(gn, Ff.e1);
+    gv1 = gv1 + ge1; gv2 = gv2 + ge2; gv0 = gv0 - (ge1 + ge2);
+}
+
 __global__ void __launch_bounds__(128)
 mesh_gaussians_bwd_kernel(int F, int G, const float* __restrict__ verts, const long long* __restrict__ faces,
                           const float* __restrict__ bary, const float* __restrict__ raw_scales,
@@ -268,61 +340,18 @@ mesh_gaussians_bwd_kernel(int F, int G, const float* __restrict__ verts, const l
         const V3 gm = dL_dpoints ? ld3(dL_dpoints, n) : v3(0, 0, 0);
         gv0 = gv0 + bary[3 * g] * gm; gv1 = gv1 + bary[3 * g + 1] * gm; gv2 = gv2 + bary[3 * g + 2] * gm;
         if (dL_ddelta_t) st3(dL_ddelta_t, n, gm);
-        // scales: exp, then clamp_max, clamp_min masks (x <= max, y >= min)
+        // scales
 #pragma unroll
-        for (int j = 0; j < 2; j++) {
-            const float e = __expf(raw_scales[2 * n + j]);
-            const bool pass = e <= max_scale && fminf(e, max_scale) >= min_scale;
-            dL_draw_scales[2 * n + j] = (dL_dscaling && pass) ? dL_dscaling[3 * n + 1 + j] * e : 0.f;
-        }
+        for (int j = 0; j < 2; j++)
+            dL_draw_scales[2 * n + j] =
+                dL_dscaling ? scale_grad(raw_scales[2 * n + j], dL_dscaling[3 * n + 1 + j], min_scale, max_scale) : 0.f;
         // rotation
         const GaussFrame Gf = gauss_frame(Ff, raw_complex, delta_r, n);
-        float q[4];
-        matrix_to_unit_quaternion(Gf.R, q);
         const float4 gq = dL_dquats ? reinterpret_cast<const float4*>(dL_dquats)[n] : make_float4(0.f, 0.f, 0.f, 0.f);
-        const V3 qv = v3(q[1], q[2], q[3]), gqv = v3(gq.y, gq.z, gq.w);
-        const V3 Gw = 0.5f * (((-gq.x) * qv + q[0] * gqv) + cross(qv, gqv));           // dL/d(rotation vector)
-        // dL/dR = 1/2 [G]x R, column by column
-        V3 A[3];
-#pragma unroll
-        for (int c = 0; c < 3; c++) A[c] = 0.5f * cross(Gw, v3(Gf.R[0][c], Gf.R[1][c], Gf.R[2][c]));
-        V3 gB[3];
-        if (Gf.loose) {
-            // delta_r: dphi = 2 vec(dd^ (x) conj(d^)), dd^ = (I - d^ d^T) dd / |d|
-            const float hw = -2.0f * dot(Gw, Gf.dv);
-            const V3 hv = 2.0f * (Gf.dw * Gw - cross(Gf.dv, Gw));
-            const float il = 1.0f / Gf.ld;
-            if (dL_ddelta_r) reinterpret_cast<float4*>(dL_ddelta_r)[n] = make_float4(hw * il, hv.x * il, hv.y * il, hv.z * il);
-#pragma unroll
-            for (int c = 0; c < 3; c++)   // dL/dB = D^T dL/dR
-                gB[c] = v3(Gf.D[0][0] * A[c].x + Gf.D[1][0] * A[c].y + Gf.D[2][0] * A[c].z,
-                           Gf.D[0][1] * A[c].x + Gf.D[1][1] * A[c].y + Gf.D[2][1] * A[c].z,
-                           Gf.D[0][2] * A[c].x + Gf.D[1][2] * A[c].y + Gf.D[2][2] * A[c].z);
-        } else {
-#pragma unroll
-            for (int c = 0; c < 3; c++) gB[c] = A[c];
-        }
-        gR0 = gR0 + gB[0];
-        const float g_qc = dot(gB[1], Ff.bR1) + dot(gB[2], Ff.bR2), g_qs = dot(gB[1], Ff.bR2) - dot(gB[2], Ff.bR1);
-        gbR1 = gbR1 + (Gf.qc * gB[1] - Gf.qs * gB[2]);
-        gbR2 = gbR2 + (Gf.qs * gB[1] + Gf.qc * gB[2]);
-        {   // through the normalisation of the raw complex number (:493)
-            const float inv = 1.0f / fmaxf(Gf.lq, 1e-12f);
-            const float d = g_qc * Gf.qc + g_qs * Gf.qs;
-            const bool reg = Gf.lq > 1e-12f;
-            dL_draw_complex[2 * n] = reg ? inv * (g_qc - d * Gf.qc) : inv * g_qc;
-            dL_draw_complex[2 * n + 1] = reg ? inv * (g_qs - d * Gf.qs) : inv * g_qs;
-        }
+        const FrameGrad fg = rotation_backward(Ff, Gf, gq, n, dL_draw_complex, dL_ddelta_r);
+        gR0 = gR0 + fg.R0; gbR1 = gbR1 + fg.bR1; gbR2 = gbR2 + fg.bR2;
     }
-    // face frame -> vertices
-    const V3 gcr = normalize_bwd(Ff.bR2, Ff.lc, 1e-12f, gbR2);       // bR2 = normalize(R0 x bR1)
-    gR0 = gR0 + cross(Ff.bR1, gcr);
-    gbR1 = gbR1 + cross(gcr, Ff.R0);
-    const V3 ga = normalize_bwd(Ff.bR1, Ff.la, 1e-12f, gbR1);        // bR1 = normalize(v0 - v1)
-    gv0 = gv0 + ga; gv1 = gv1 - ga;
-    const V3 gn = normalize_bwd(Ff.R0, Ff.len, 1e-6f, gR0);          // R0 = normalize((e1 x e2) / max(|.|, 1e-6))
-    const V3 ge1 = cross(Ff.e2, gn), ge2 = cross(gn, Ff.e1);
-    gv1 = gv1 + ge1; gv2 = gv2 + ge2; gv0 = gv0 - (ge1 + ge2);
+    frame_backward(Ff, gR0, gbR1, gbR2, gv0, gv1, gv2);
     const size_t i0 = (size_t)faces[3 * (size_t)f], i1 = (size_t)faces[3 * (size_t)f + 1], i2 = (size_t)faces[3 * (size_t)f + 2];
     atomicAdd(dL_dverts + 3 * i0, gv0.x); atomicAdd(dL_dverts + 3 * i0 + 1, gv0.y); atomicAdd(dL_dverts + 3 * i0 + 2, gv0.z);
     atomicAdd(dL_dverts + 3 * i1, gv1.x); atomicAdd(dL_dverts + 3 * i1 + 1, gv1.y); atomicAdd(dL_dverts + 3 * i1 + 2, gv1.z);
@@ -421,55 +450,16 @@ mesh_gaussians_bwd8_kernel(int F, int G, const float* __restrict__ verts, const 
         const GaussFrame Gf = gauss_frame(Ff, raw_complex, delta_r, n);
         gv0 = b0 * gm; gv1 = b1 * gm; gv2 = b2 * gm;
         if (dL_ddelta_t) st3(dL_ddelta_t, n, gm);
-        {   // scales: exp, then clamp_max, clamp_min masks (x <= max, y >= min)
-            const float e0 = __expf(rs.x), e1 = __expf(rs.y);
-            const bool p0 = e0 <= max_scale && fminf(e0, max_scale) >= min_scale, p1 = e1 <= max_scale && fminf(e1, max_scale) >= min_scale;
-            reinterpret_cast<float2*>(dL_draw_scales)[n] = make_float2(p0 ? gs[0] * e0 : 0.f, p1 ? gs[1] * e1 : 0.f);
-        }
-        float q[4];
-        matrix_to_unit_quaternion(Gf.R, q);
-        const V3 qv = v3(q[1], q[2], q[3]), gqv = v3(gq.y, gq.z, gq.w);
-        const V3 Gw = 0.5f * (((-gq.x) * qv + q[0] * gqv) + cross(qv, gqv));           // dL/d(rotation vector)
-        V3 A[3];
-#pragma unroll
-        for (int c = 0; c < 3; c++) A[c] = 0.5f * cross(Gw, v3(Gf.R[0][c], Gf.R[1][c], Gf.R[2][c]));   // dL/dR = 1/2 [G]x R
-        V3 gB[3];
-        if (Gf.loose) {
-            const float hw = -2.0f * dot(Gw, Gf.dv);
-            const V3 hv = 2.0f * (Gf.dw * Gw - cross(Gf.dv, Gw));
-            const float il = 1.0f / Gf.ld;
-            if (dL_ddelta_r) reinterpret_cast<float4*>(dL_ddelta_r)[n] = make_float4(hw * il, hv.x * il, hv.y * il, hv.z * il);
-#pragma unroll
-            for (int c = 0; c < 3; c++)   // dL/dB = D^T dL/dR
-                gB[c] = v3(Gf.D[0][0] * A[c].x + Gf.D[1][0] * A[c].y + Gf.D[2][0] * A[c].z,
-                           Gf.D[0][1] * A[c].x + Gf.D[1][1] * A[c].y + Gf.D[2][1] * A[c].z,
-                           Gf.D[0][2] * A[c].x + Gf.D[1][2] * A[c].y + Gf.D[2][2] * A[c].z);
-        } else {
-#pragma unroll
-            for (int c = 0; c < 3; c++) gB[c] = A[c];
-        }
-        gR0 = gB[0];
-        const float g_qc = dot(gB[1], Ff.bR1) + dot(gB[2], Ff.bR2), g_qs = dot(gB[1], Ff.bR2) - dot(gB[2], Ff.bR1);
-        gbR1 = Gf.qc * gB[1] - Gf.qs * gB[2];
-        gbR2 = Gf.qs * gB[1] + Gf.qc * gB[2];
-        const float inv = 1.0f / fmaxf(Gf.lq, 1e-12f);   // through the normalisation of the raw complex number (:493)
-        const float d = g_qc * Gf.qc + g_qs * Gf.qs;
-        const bool reg = Gf.lq > 1e-12f;
-        dL_draw_complex[2 * n] = reg ? inv * (g_qc - d * Gf.qc) : inv * g_qc;
-        dL_draw_complex[2 * n + 1] = reg ? inv * (g_qs - d * Gf.qs) : inv * g_qs;
+        reinterpret_cast<float2*>(dL_draw_scales)[n] = make_float2(scale_grad(rs.x, gs[0], min_scale, max_scale),
+                                                                   scale_grad(rs.y, gs[1], min_scale, max_scale));
+        const FrameGrad fg = rotation_backward(Ff, Gf, gq, n, dL_draw_complex, dL_ddelta_r);
+        gR0 = fg.R0; gbR1 = fg.bR1; gbR2 = fg.bR2;
     }
     // sum over the face's lanes (all 64 lanes take part in the exchanges), then face frame -> vertices on lane 0
     gv0 = face_sum(gv0); gv1 = face_sum(gv1); gv2 = face_sum(gv2);
     gR0 = face_sum(gR0); gbR1 = face_sum(gbR1); gbR2 = face_sum(gbR2);
     if (face_ok && g == 0) {
-        const V3 gcr = normalize_bwd(Ff.bR2, Ff.lc, 1e-12f, gbR2);       // bR2 = normalize(R0 x bR1)
-        gR0 = gR0 + cross(Ff.bR1, gcr);
-        gbR1 = gbR1 + cross(gcr, Ff.R0);
-        const V3 ga = normalize_bwd(Ff.bR1, Ff.la, 1e-12f, gbR1);        // bR1 = normalize(v0 - v1)
-        gv0 = gv0 + ga; gv1 = gv1 - ga;
-        const V3 gn = normalize_bwd(Ff.R0, Ff.len, 1e-6f, gR0);          // R0 = normalize((e1 x e2) / max(|.|, 1e-6))
-        const V3 ge1 = cross(Ff.e2, gn), ge2 = cross(gn, Ff.e1);
-        gv1 = gv1 + ge1; gv2 = gv2 + ge2; gv0 = gv0 - (ge1 + ge2);
+        frame_backward(Ff, gR0, gbR1, gbR2, gv0, gv1, gv2);
         const uint32_t vi[3] = {(uint32_t)faces[3 * (size_t)f], (uint32_t)faces[3 * (size_t)f + 1], (uint32_t)faces[3 * (size_t)f + 2]};
         const V3 gv[3] = {gv0, gv1, gv2};
 #pragma unroll

@@ -6,23 +6,47 @@ normalised view direction) and to the coefficients.  One kernel forward, one bac
 kernels each way.  No CPU path."""
 from __future__ import annotations
 
-import ctypes
-
 import torch
 
 from . import _host, _lib
+from ._lib import ptr as _p
 
 
 def _stream():
     return _host.raw_stream(torch._C._cuda_getDevice())
 
 
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr())
+def _as_f32(t, dev):
+    return None if t is None else t.detach().to(dev, torch.float32).contiguous()
 
 
-def _op(t):
-    return None if t is None else _p(t)
+def _check_sh_args(positions, camera_center, sh, sh_rest, sh_levels, view, depth_channels):
+    """The argument check of both colour producers -> (D, M).  sh_rest None: sh is [P, M, 3]; otherwise sh is the dc array
+    [P, 1, 3] and sh_rest holds the other M - 1 coefficients."""
+    if not positions.is_cuda:
+        raise RuntimeError("gaustar_amd.producers: positions must live on a HIP (cuda) device -- there is no CPU path")
+    if positions.dim() != 2 or positions.size(1) != 3:
+        raise RuntimeError("positions must have dimensions (num_points, 3)")
+    P = int(positions.size(0))
+    if sh_rest is None:
+        if sh.dim() != 3 or sh.size(2) != 3 or sh.size(0) != P:
+            raise RuntimeError("sh_coordinates must have dimensions (num_points, n_coeffs, 3)")
+        M = int(sh.size(1))
+    else:
+        if tuple(sh.shape) != (P, 1, 3) or sh_rest.dim() != 3 or sh_rest.size(0) != P or sh_rest.size(2) != 3:
+            raise RuntimeError("sh_dc must be (num_points, 1, 3) and sh_rest (num_points, n_coeffs - 1, 3)")
+        M = 1 + int(sh_rest.size(1))
+    D = int(sh_levels) - 1
+    if D < 0 or D > 4 or (D + 1) ** 2 > M:   # eval_sh asserts deg <= 4 (spherical_harmonics.py:130)
+        raise RuntimeError(f"sh_levels must be 1..5 and sh_levels**2 <= n_coeffs ({M})")
+    if camera_center.numel() != 3:
+        raise RuntimeError("camera_center must hold one 3-vector (shape (3,) or (1, 3))")
+    if view is not None:
+        if tuple(view.shape) != (4, 4):
+            raise RuntimeError("viewmatrix must be (4, 4), as handed to the rasterizer")
+        if depth_channels not in (1, 3):
+            raise RuntimeError("depth_channels must be 1 (colours [P,4]) or 3 (colours [P,6])")
+    return D, M
 
 
 def _sh_forward_raw(pos, cam, sh, sh_rest, D, M, view, depth_channels, densities=None):
@@ -43,9 +67,9 @@ def _sh_forward_raw(pos, cam, sh, sh_rest, D, M, view, depth_channels, densities
         else:
             if sh_rest is None and M != 1:
                 raise RuntimeError("opacities ride along only with the two-array coefficient layout")
-            _lib.check(lib.gsr_sh_colors_split(P, D, M, _p(pos), _p(cam), _p(sh), _op(sh_rest if M > 1 else None), _op(view),
-                                               int(depth_channels) if view is not None else 0, _op(densities), _p(colors),
-                                               _op(opacity), _stream()), "gsr_sh_colors_split")
+            _lib.check(lib.gsr_sh_colors_split(P, D, M, _p(pos), _p(cam), _p(sh), _p(sh_rest if M > 1 else None), _p(view),
+                                               int(depth_channels) if view is not None else 0, _p(densities), _p(colors),
+                                               _p(opacity), _stream()), "gsr_sh_colors_split")
     return colors, opacity
 
 
@@ -72,9 +96,9 @@ def _sh_backward_raw(pos, cam, sh, sh_rest, D, M, view, depth_channels, g, opaci
             if sh_rest is None and M != 1:
                 raise RuntimeError("the fused backward takes the two-array coefficient layout")
             _lib.check(lib.gsr_sh_colors_split_backward(
-                P, D, M, _p(pos), _p(cam), _p(sh), _op(sh_rest if M > 1 else None), _op(view),
-                int(depth_channels) if view is not None else 0, _p(g), _op(opacity), _op(dL_dopacity), _p(dsh),
-                _op(drest if M > 1 else None), _p(dpos), int(dpos_inout is not None), _op(ddens), _stream()),
+                P, D, M, _p(pos), _p(cam), _p(sh), _p(sh_rest if M > 1 else None), _p(view),
+                int(depth_channels) if view is not None else 0, _p(g), _p(opacity), _p(dL_dopacity), _p(dsh),
+                _p(drest if M > 1 else None), _p(dpos), int(dpos_inout is not None), _p(ddens), _stream()),
                 "gsr_sh_colors_split_backward")
     return dsh, drest, dpos, ddens
 
@@ -84,30 +108,10 @@ class _PointsRGB(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, positions, camera_center, sh_coordinates, sh_levels, view=None, depth_channels=3):
-        lib = _lib.load()
-        if not positions.is_cuda:
-            raise RuntimeError("gaustar_amd.producers: positions must live on a HIP (cuda) device -- there is no CPU path")
-        if positions.dim() != 2 or positions.size(1) != 3:
-            raise RuntimeError("positions must have dimensions (num_points, 3)")
-        if sh_coordinates.dim() != 3 or sh_coordinates.size(2) != 3 or sh_coordinates.size(0) != positions.size(0):
-            raise RuntimeError("sh_coordinates must have dimensions (num_points, n_coeffs, 3)")
-        D = int(sh_levels) - 1
-        M = int(sh_coordinates.size(1))
-        if D < 0 or D > 4 or (D + 1) ** 2 > M:   # eval_sh asserts deg <= 4 (spherical_harmonics.py:130)
-            raise RuntimeError(f"sh_levels must be 1..5 and sh_levels**2 <= n_coeffs ({M})")
+        D, M = _check_sh_args(positions, camera_center, sh_coordinates, None, sh_levels, view, depth_channels)
         dev = positions.device
-        pos = positions.detach().to(torch.float32).contiguous()
-        cam = camera_center.detach().to(dev, torch.float32).reshape(-1)[:3].contiguous()
-        if camera_center.numel() != 3:
-            raise RuntimeError("camera_center must hold one 3-vector (shape (3,) or (1, 3))")
-        sh = sh_coordinates.detach().to(torch.float32).contiguous()
-        P = int(pos.size(0))
-        if view is not None:
-            if tuple(view.shape) != (4, 4):
-                raise RuntimeError("viewmatrix must be (4, 4), as handed to the rasterizer")
-            view = view.detach().to(dev, torch.float32).contiguous()
-        if view is not None and depth_channels not in (1, 3):
-            raise RuntimeError("depth_channels must be 1 (colours [P,4]) or 3 (colours [P,6])")
+        pos, sh, view = _as_f32(positions, dev), _as_f32(sh_coordinates, dev), _as_f32(view, dev)
+        cam = _as_f32(camera_center, dev).reshape(-1)
         rgb, _ = _sh_forward_raw(pos, cam, sh, None, D, M, view, depth_channels)
         ctx.save_for_backward(pos, cam, sh, view)
         ctx.D = D
@@ -145,26 +149,12 @@ def points_rgb_depth(positions: torch.Tensor, camera_centers: torch.Tensor, sh_c
 class _PointsColorsSplit(torch.autograd.Function):
     @staticmethod
     def forward(ctx, positions, camera_center, sh_dc, sh_rest, sh_levels, view, depth_channels, densities):
-        if not positions.is_cuda:
-            raise RuntimeError("gaustar_amd.producers: positions must live on a HIP (cuda) device -- there is no CPU path")
-        P = int(positions.size(0)) if positions.dim() == 2 else -1
-        if positions.dim() != 2 or positions.size(1) != 3:
-            raise RuntimeError("positions must have dimensions (num_points, 3)")
-        if tuple(sh_dc.shape) != (P, 1, 3) or sh_rest.dim() != 3 or sh_rest.size(0) != P or sh_rest.size(2) != 3:
-            raise RuntimeError("sh_dc must be (num_points, 1, 3) and sh_rest (num_points, n_coeffs - 1, 3)")
-        D, M = int(sh_levels) - 1, 1 + int(sh_rest.size(1))
-        if D < 0 or D > 4 or (D + 1) ** 2 > M:
-            raise RuntimeError(f"sh_levels must be 1..5 and sh_levels**2 <= n_coeffs ({M})")
-        if camera_center.numel() != 3:
-            raise RuntimeError("camera_center must hold one 3-vector (shape (3,) or (1, 3))")
-        if view is not None and (tuple(view.shape) != (4, 4) or depth_channels not in (1, 3)):
-            raise RuntimeError("viewmatrix must be (4, 4) and depth_channels 1 or 3")
-        if densities is not None and densities.numel() != P:
+        D, M = _check_sh_args(positions, camera_center, sh_dc, sh_rest, sh_levels, view, depth_channels)
+        if densities is not None and densities.numel() != positions.size(0):
             raise RuntimeError("densities must hold one value per point")
         dev = positions.device
-        f32 = lambda t: None if t is None else t.detach().to(dev, torch.float32).contiguous()
-        pos, dc, rest, view, dens = f32(positions), f32(sh_dc), f32(sh_rest), f32(view), f32(densities)
-        cam = camera_center.detach().to(dev, torch.float32).reshape(-1).contiguous()
+        pos, dc, rest, view, dens = (_as_f32(t, dev) for t in (positions, sh_dc, sh_rest, view, densities))
+        cam = _as_f32(camera_center, dev).reshape(-1)
         colors, opacity = _sh_forward_raw(pos, cam, dc, rest, D, M, view, depth_channels if view is not None else 0, dens)
         ctx.save_for_backward(pos, cam, dc, rest, view, opacity)
         ctx.cfg = (D, M, int(depth_channels) if view is not None else 0)
@@ -209,8 +199,8 @@ def _mesh_forward_raw(v, fc, bc, rs, rc, thickness, lo, hi, dt, dr, clear=None):
     scaling = torch.empty(N, 3, dtype=torch.float32, device=dev)
     quats = torch.empty(N, 4, dtype=torch.float32, device=dev)
     with _host.on_device(dev):
-        _lib.check(lib.gsr_mesh_gaussians(F, G, _p(v), _p(fc), _p(bc), _p(rs), _p(rc), float(thickness), lo, hi, _op(dt),
-                                          _op(dr), _p(points), _p(scaling), _p(quats), _op(clear), int(v.size(0)), _stream()),
+        _lib.check(lib.gsr_mesh_gaussians(F, G, _p(v), _p(fc), _p(bc), _p(rs), _p(rc), float(thickness), lo, hi, _p(dt),
+                                          _p(dr), _p(points), _p(scaling), _p(quats), _p(clear), int(v.size(0)), _stream()),
                    "gsr_mesh_gaussians")
     return points, scaling, quats
 
@@ -228,8 +218,8 @@ def _mesh_backward_raw(v, fc, bc, rs, rc, dr, lo, hi, has_dt, g_points, g_scalin
     d_dr = pick(out[4], lambda: torch.empty_like(dr)) if dr is not None else None
     with _host.on_device(dev):
         _lib.check(lib.gsr_mesh_gaussians_backward(
-            F, G, V, _p(v), _p(fc), _p(bc), _p(rs), _p(rc), lo, hi, _op(dr), _op(g_points), _op(g_scaling), _op(g_quats),
-            _p(d_verts), _p(d_rs), _p(d_rc), _op(d_dt), _op(d_dr), int(bool(verts_cleared and out[0] is not None)), _stream()),
+            F, G, V, _p(v), _p(fc), _p(bc), _p(rs), _p(rc), lo, hi, _p(dr), _p(g_points), _p(g_scaling), _p(g_quats),
+            _p(d_verts), _p(d_rs), _p(d_rc), _p(d_dt), _p(d_dr), int(bool(verts_cleared and out[0] is not None)), _stream()),
             "gsr_mesh_gaussians_backward")
     return d_verts, d_rs, d_rc, d_dt, d_dr
 
@@ -240,10 +230,9 @@ class _MeshGaussians(torch.autograd.Function):
         if not verts.is_cuda:
             raise RuntimeError("gaustar_amd.producers: verts must live on a HIP (cuda) device -- there is no CPU path")
         dev = verts.device
-        f32 = lambda t: None if t is None else t.detach().to(dev, torch.float32).contiguous()
-        v, rs, rc, dt, dr = f32(verts), f32(raw_scales), f32(raw_complex), f32(delta_t), f32(delta_r)
+        v, rs, rc, dt, dr = (_as_f32(t, dev) for t in (verts, raw_scales, raw_complex, delta_t, delta_r))
         fc = faces.detach().to(dev, torch.int64).contiguous()
-        bc = f32(bary).reshape(-1, 3)
+        bc = _as_f32(bary, dev).reshape(-1, 3)
         F, G = int(fc.size(0)), int(bc.size(0))
         N = F * G
         if v.dim() != 2 or v.size(1) != 3 or fc.dim() != 2 or fc.size(1) != 3:

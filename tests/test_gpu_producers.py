@@ -343,3 +343,82 @@ def test_mesh_producer_backward_twice_over_one_graph(hip_lib):
     g3 = torch.autograd.grad((pts * wp).sum() + (sc * ws).sum() + (qu * wq).sum(), (verts, rs, rc))
     for a, b in zip(g1, g3):
         assert torch.allclose(a, b, rtol=1e-5, atol=1e-7)
+
+
+# ------------------------------------------------------------------ the backward's ragged last workgroup and table overflow
+def _mesh_params(F, G, loose, g):
+    """Per-Gaussian parameters and loss weights of test_mesh_bound_gaussians_other_counts_per_face for F faces."""
+    N = F * G
+    bary = torch.rand(G, 3, generator=g) + 0.1
+    bary = bary / bary.sum(-1, keepdim=True)
+    rs, rc = torch.randn(N, 2, generator=g) * 0.4 - 4.0, torch.randn(N, 2, generator=g)
+    dt, dr = 0.01 * torch.randn(N, 3, generator=g), torch.randn(N, 4, generator=g) * 0.3 + torch.tensor([1.0, 0, 0, 0])
+    w = (torch.randn(N, 3, generator=g), torch.randn(N, 3, generator=g), torch.randn(3, 3, generator=g))
+    return bary, rs, rc, (dt if loose else None), (dr if loose else None), w
+
+
+def _mesh_run(fn, dev, v, f, bary, rs, rc, dt, dr, w, lo=None, hi=None):
+    """-> points, scaling, gradients w.r.t. (verts, raw_scales, raw_complex[, delta_t, delta_r]) under that test's loss."""
+    a = [t.clone().to(dev).requires_grad_(True) for t in (v, rs, rc, dt, dr) if t is not None]
+    p, s, q = fn(a[0], f.to(dev), bary.to(dev), a[1], a[2], 3e-6, lo, hi, *(a[3:] if dt is not None else (None, None)))
+    r, i, j, k = q.unbind(-1)
+    R = torch.stack((1 - 2 * (j * j + k * k), 2 * (i * j - k * r), 2 * (i * k + j * r), 2 * (i * j + k * r),
+                     1 - 2 * (i * i + k * k), 2 * (j * k - i * r), 2 * (i * k - j * r), 2 * (j * k + i * r),
+                     1 - 2 * (i * i + j * j)), -1).reshape(-1, 3, 3)
+    wp, wq, W3 = (t.to(dev) for t in w)
+    ((p * wp).sum() + (s ** 2).sum() + ((R @ W3) * wq[:, :, None]).sum()).backward()
+    return p.detach().cpu(), s.detach().cpu(), [t.grad.cpu() for t in a]
+
+
+def _mesh_check_against_oracle(case, ref, got):
+    (p0, s0, g0), (p1, s1, g1) = ref, got
+    np.testing.assert_allclose(p1.numpy(), p0.numpy(), rtol=1e-6, atol=1e-6)
+    np.testing.assert_allclose(s1.numpy(), s0.numpy(), rtol=2e-6, atol=0)
+    for name, a, b in zip(("verts", "raw_scales", "raw_complex", "delta_t", "delta_r"), g1, g0):
+        err = np.abs(a.numpy().astype(np.float64) - b.numpy()).max() / max(np.abs(b.numpy()).max(), 1e-30)
+        print(f"{case} {name}: normalised max error {err:.3e}")
+        assert err < 2e-4, f"{case} {name}: normalised max error {err:.3e}"
+
+
+@pytest.mark.parametrize("F,G,loose", [(1, 1, True), (1, 6, True), (33, 6, True), (33, 8, True), (129, 3, True), (1, 9, True),
+                                       (129, 9, True), (33, 6, False)])
+def test_mesh_bound_gaussians_ragged_face_counts(F, G, loose, hip_lib):
+    """Face counts that are no multiple of a workgroup's faces (32 for the lane-per-Gaussian backward, 128 for the per-face
+    one): a lone face, a second workgroup with one live face, a ragged tail behind full workgroups.  The mesh is a triangle
+    strip, so neighbouring faces share vertices across the workgroup boundary; the strictly bound case clamps the scales.
+    With one face every accumulator takes one add, so two runs must agree bit for bit."""
+    from gaustar_amd import producers
+    from oracle import producers_oracle
+    g = torch.Generator().manual_seed(1000 * F + 10 * G + int(loose))
+    i = torch.arange(F + 2)
+    v = torch.stack((0.1 * i, 0.1 * (i % 2), 0.02 * torch.randn(F + 2, generator=g)), -1).float() + torch.tensor([0.0, 1.2, 0.0])
+    f = torch.stack((i[:F], i[:F] + 1, i[:F] + 2), -1)
+    f[1::2, :2] = f[1::2, :2].flip(-1)
+    args = (v, f, *_mesh_params(F, G, loose, g)) + ((None, None) if loose else (0.012, 0.03))
+    ref = _mesh_run(producers_oracle.mesh_bound_gaussians, "cpu", *args)
+    got = _mesh_run(producers.mesh_bound_gaussians, "cuda", *args)
+    _mesh_check_against_oracle(f"F={F} G={G}", ref, got)
+    if F == 1:
+        again = _mesh_run(producers.mesh_bound_gaussians, "cuda", *args)
+        assert len(got[2]) == 5 and all(torch.equal(a, b) for a, b in zip(got[2], again[2]))
+
+
+def test_mesh_bound_gaussians_vertex_table_overflow(hip_lib):
+    """Twelve vertices whose hash is the same slot of the backward's LDS vertex table: eight probes place eight of them, four
+    take the fallback of atomics to memory.  (Only at the default GSR_MESH_BWD_BLOCK of 256, a table of 128 slots, does the
+    case reach the fallback; at any other value it still has to pass.)"""
+    from gaustar_amd import producers
+    from oracle import producers_oracle
+    V, F, G = 1164, 4, 6
+    used = [x for x in range(V) if (((x * 2654435761) % 2 ** 32) >> 16) & 127 == 5][:12]
+    assert len(used) == 12
+    g = torch.Generator().manual_seed(77)
+    v = torch.rand(V, 3, generator=g)
+    f = torch.tensor(used).reshape(F, 3)
+    args = (v, f, *_mesh_params(F, G, True, g))
+    ref = _mesh_run(producers_oracle.mesh_bound_gaussians, "cpu", *args)
+    got = _mesh_run(producers.mesh_bound_gaussians, "cuda", *args)
+    _mesh_check_against_oracle("overflow", ref, got)
+    unused = torch.ones(V, dtype=torch.bool)
+    unused[used] = False
+    assert int(unused.sum()) == V - 12 and (got[2][0][unused] == 0).all()
