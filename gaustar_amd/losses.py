@@ -78,7 +78,7 @@ class _L1DSSIM(torch.autograd.Function):
                 ctypes.c_void_p(ws.data_ptr()), ctypes.c_void_p(out.data_ptr()), None, 0, 0, 0, _stream()), "gsr_l1_ssim")
         if ctx.needs_input_grad[0]:
             ctx.save_for_backward(p_full, g_full, ws)
-        ctx.cfg = (float(dssim_factor), margin, pred.shape)
+        ctx.cfg = (float(dssim_factor), margin, pred.shape, pred.dtype)
         ctx.mark_non_differentiable(out)
         ctx.set_materialize_grads(False)   # no zero-filled "gradient" of the parts vector per backward (one fill kernel)
         return out[0], out
@@ -89,7 +89,7 @@ class _L1DSSIM(torch.autograd.Function):
             return None, None, None, None
         lib = _lib.load()
         p_full, g_full, ws = ctx.saved_tensors
-        f, margin, pred_shape = ctx.cfg
+        f, margin, pred_shape, in_dtype = ctx.cfg
         p, g = _crop(p_full, margin), _crop(g_full, margin)
         C, H, W = (int(v) for v in p.shape)
         dev = p.device
@@ -102,7 +102,7 @@ class _L1DSSIM(torch.autograd.Function):
                 C, H, W, ctypes.c_void_p(p.data_ptr()), p.stride(0), p.stride(1), p.stride(2),
                 ctypes.c_void_p(g.data_ptr()), g.stride(0), g.stride(1), g.stride(2), f, ctypes.c_void_p(ws.data_ptr()), sp,
                 ctypes.c_void_p(gv.data_ptr()), gv.stride(0), gv.stride(1), gv.stride(2), _stream()), "gsr_l1_ssim_backward")
-        return grad_full.reshape(pred_shape), None, None, None
+        return grad_full.reshape(pred_shape).to(in_dtype), None, None, None
 
 
 def l1_dssim_loss(pred: torch.Tensor, gt: torch.Tensor, dssim_factor: float = 0.2,
