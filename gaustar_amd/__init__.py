@@ -7,8 +7,9 @@ hand-written HIP for gfx950 behind the C ABI of include/gsr.h.  `scene` (numpy o
 synthetic cameras / mesh-bound Gaussians used by tests and bench.py; `dist` is the view-parallel
 gradient all-reduce.  Either side of the rasterizer: `producers` (SH -> RGB, mesh-bound
 means / scales / quaternions), `losses` (l1 + dssim, masked depth L1, surface-mesh regularisers), `meshes` (single-mesh
-stand-ins for pytorch3d's `Meshes` / `mesh_normal_consistency`), `sweep` (forward-only camera sweeps) and
-`formats` (cameras.json, 3DGS PLY, SuGaR .pt) -- import them as submodules.
+stand-ins for pytorch3d's `Meshes` / `mesh_normal_consistency`), `sweep` (forward-only camera sweeps),
+`mesh_depth` (a mesh's depth maps, masks and visible faces over the rig: the inputs of a tracked sequence) and
+`formats` (cameras.json, 3DGS PLY, SuGaR .pt, OBJ, grey PNG) -- import them as submodules.
 """
 from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, rasterize_gaussians  # noqa: F401
 

@@ -131,6 +131,10 @@ SIGNATURES = {
                               POINTER(c_double), POINTER(c_double), c_void_p, c_void_p, c_void_p]),
     "gsr_warp_aggregate": (c_int, [c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gsr_warp_smooth": (c_int, [c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # a mesh's depth map, mask and visible face per camera (render_depth_from_mesh.py:13-101): gaustar_amd.mesh_depth
+    "gsr_mesh_depth_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "gsr_mesh_depth_view": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, POINTER(c_double), c_double, c_float, c_int,
+                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     # TSDF fusion of the rig's renders and mesh extraction (refined_mesh.py:311-459): gaustar_amd.fusion
     "gsr_fusion_prep_workspace_bytes": (c_size_t, [c_int, c_int]),
     "gsr_fusion_volume_bytes": (c_size_t, [POINTER(c_int)]),

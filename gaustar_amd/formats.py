@@ -9,6 +9,8 @@ SuGaR / GauSTAR `{iter}.pt` checkpoints -- enough to render a real checkpoint wi
   f_rest is stored channel-major ([P,3,K] flattened); opacity is a logit, scales are logs, rot is unnormalised.
 * OBJ: the meshes gaustar_tools/warp_mesh.py:230 loads with trimesh (process=False, maintain_order=True) and :364-397
   exports: `v x y z [r g b]` and triangular `f` lines, vertex order kept (load_obj / save_obj).
+* PNG: the 8-bit grey masks `img_{c:04d}_alpha.png` that data_process/render_depth_from_mesh.py:93 writes with cv2.imwrite and
+  gaustar_scene/cameras.py:97-106 reads (save_png_gray8 / load_png_gray8; zlib and struct only, neither cv2 nor PIL).
 * .pt: sugar_model.py:1313-1318 (`save_model`): {'state_dict': ..., extra keys}; state-dict entries `_points`,
   `_surface_mesh_faces`, `_scales`, `_quaternions`, `all_densities`, `_sh_coordinates_dc`, `_sh_coordinates_rest`,
   `surface_mesh_thickness`, `_delta_t`, `_delta_r`.
@@ -17,6 +19,8 @@ from __future__ import annotations
 
 import json
 import math
+import struct
+import zlib
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence
 
@@ -278,3 +282,86 @@ def save_obj(path: str, verts, faces, colours=None) -> None:
     lines += [f"f {a + 1} {b + 1} {c + 1}" for a, b, c in f.tolist()]
     with open(path, "w") as fh:
         fh.write("\n".join(lines) + "\n")
+
+
+# ---------------------------------------------------------------------------------------------- PNG (8-bit grey)
+_PNG_MAGIC = b"\x89PNG\r\n\x1a\n"
+
+
+def _png_chunk(tag: bytes, data: bytes) -> bytes:
+    return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
+
+
+def save_png_gray8(path: str, array) -> None:
+    """array [H,W] uint8 -> an 8-bit greyscale PNG (colour type 0, no interlace, filter 0 on every row)."""
+    a = np.asarray(array)
+    if a.ndim != 2 or a.dtype != np.uint8 or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError(f"save_png_gray8 takes a non-empty [H,W] uint8 array, got {a.dtype} {a.shape}")
+    H, W = a.shape
+    rows = np.zeros((H, W + 1), np.uint8)      # (one filter byte in front of every row)
+    rows[:, 1:] = a
+    data = _PNG_MAGIC + _png_chunk(b"IHDR", struct.pack(">IIBBBBB", W, H, 8, 0, 0, 0, 0)) + \
+        _png_chunk(b"IDAT", zlib.compress(rows.tobytes(), 6)) + _png_chunk(b"IEND", b"")
+    with open(path, "wb") as fh:
+        fh.write(data)
+
+
+def load_png_gray8(path: str) -> np.ndarray:
+    """An 8-bit greyscale, non-interlaced PNG -> [H,W] uint8 (all five row filters; chunk CRCs are checked).  Any other PNG
+    raises ValueError."""
+    with open(path, "rb") as fh:
+        blob = fh.read()
+    if blob[:8] != _PNG_MAGIC:
+        raise ValueError(f"{path}: not a PNG file")
+    pos, head, idat, ended = 8, None, [], False
+    while pos + 12 <= len(blob) and not ended:
+        n, tag = struct.unpack(">I4s", blob[pos:pos + 8])
+        data = blob[pos + 8:pos + 8 + n]
+        if len(data) != n or pos + 12 + n > len(blob):
+            raise ValueError(f"{path}: truncated {tag!r} chunk")
+        if struct.unpack(">I", blob[pos + 8 + n:pos + 12 + n])[0] != (zlib.crc32(tag + data) & 0xFFFFFFFF):
+            raise ValueError(f"{path}: bad CRC in {tag!r} chunk")
+        if tag == b"IHDR":
+            head = struct.unpack(">IIBBBBB", data)
+        elif tag == b"IDAT":
+            idat.append(data)
+        ended = tag == b"IEND"
+        pos += 12 + n
+    if head is None or not ended:
+        raise ValueError(f"{path}: truncated PNG")
+    W, H, depth, colour, comp, filt, interlace = head
+    if (depth, colour, comp, filt, interlace) != (8, 0, 0, 0, 0) or W < 1 or H < 1:
+        raise ValueError(f"{path}: not an 8-bit greyscale, non-interlaced PNG (depth {depth}, colour type {colour}, interlace {interlace})")
+    raw = zlib.decompress(b"".join(idat))
+    if len(raw) != H * (W + 1):
+        raise ValueError(f"{path}: {len(raw)} bytes of image data for a {W} x {H} image")
+    rows = np.frombuffer(raw, np.uint8).reshape(H, W + 1)
+    out = np.zeros((H, W), np.uint8)
+    prev = np.zeros(W, np.int64)
+    for r in range(H):
+        kind, x = int(rows[r, 0]), rows[r, 1:].astype(np.int64)
+        if kind == 0:
+            cur = x
+        elif kind == 2:                                  # up
+            cur = (x + prev) & 255
+        elif kind in (1, 3, 4):                          # sub, average, Paeth: each byte needs its left neighbour
+            cur = np.zeros(W, np.int64)
+            left = upleft = 0
+            for c in range(W):
+                up = int(prev[c])
+                if kind == 1:
+                    pred = left
+                elif kind == 3:
+                    pred = (left + up) // 2
+                else:
+                    p = left + up - upleft
+                    pa, pb, pc = abs(p - left), abs(p - up), abs(p - upleft)
+                    pred = left if pa <= pb and pa <= pc else (up if pb <= pc else upleft)
+                left = (int(x[c]) + pred) & 255
+                upleft = up
+                cur[c] = left
+        else:
+            raise ValueError(f"{path}: row {r} has filter type {kind}")
+        out[r] = cur
+        prev = cur
+    return out

@@ -494,6 +494,20 @@ class SurfaceGaussians(nn.Module):
         rig = kw.pop("rig", None) or topology.rig_from_cameras(cameras)
         return warp.warp_mesh(self._points.detach(), self._surface_mesh_faces, rig, frames, **kw)
 
+    def render_mesh_depth(self, camera_or_index, cameras=None, **kw):
+        """The surface mesh's own depth map, mask and (return_faces=True) visible face per pixel for one camera
+        (render_depth_from_mesh.py:13-101 on the model's mesh): mesh_depth.mesh_depth_view(vertices, faces, ...) with the
+        camera's row of topology.rig_from_cameras -> mesh_depth.MeshDepthView.  camera_or_index: a NerfCamera, or an index into
+        `cameras`.  use_principal_point=True (in kw) reads the camera's principal point instead of (W / 2, H / 2)."""
+        from . import mesh_depth, topology
+        cam = cameras[int(camera_or_index)] if isinstance(camera_or_index, (int, np.integer)) else camera_or_index
+        rig = topology.rig_from_cameras([cam])
+        H, W = (int(x) for x in rig["shape"][0])
+        if kw.pop("use_principal_point", False):
+            kw["principal_point"] = (rig["intrinsics"][0][0, 2], rig["intrinsics"][0][1, 2])
+        return mesh_depth.mesh_depth_view(self._points.detach(), self._surface_mesh_faces, rig["extrinsics"][0], rig["intrinsics"][0],
+                                          H, W, **kw)
+
     def extract_mesh_fusion(self, cameras, **kw):
         """The surface the renders of `cameras` (and of the 60 sampled cameras around them) agree on, by TSDF fusion and
         marching cubes (refined_mesh.py:311-459): fusion.fuse_mesh(self, cameras, **kw) -> fusion.FusionMesh."""

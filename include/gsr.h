@@ -522,6 +522,28 @@ int gsr_warp_aggregate(int C, int V, const double* table, int min_observe, doubl
 int gsr_warp_smooth(int V, const int* nbr_offsets, const int* nbr, int sweeps, const double* value_in, double* value_out,
                     double* value_tmp, gsr_stream_t stream);
 
+/* ---- A mesh's depth map, mask and visible face for one camera of the rig (data_process/render_depth_from_mesh.py:13-101
+ * `render_mesh_depth_w_aitviewer`, which renders them with OpenGL): the `img_{c:04d}_depth.npz` / `_alpha.png` inputs of the
+ * depth and mask losses, of detect_topo_err and of warp_mesh_using_flow.  A depth-only triangle rasterizer by the rules
+ * restated in tests/meshdepth_ref.py (aitviewer was not available: parity with it is not pinned), all in double:
+ *   cam16: [host] 16 doubles = gsr_warp_view's 14 (rotation row-major, translation, fx, fy) and the principal point cx, cy.
+ *   local = R p + t, x = fx (lx / lz) + cx, y = fy (ly / lz) + cy; the centre of pixel (row r, column c) is at (x, y) = (c, r),
+ *   the convention of gsr_topo_view / gsr_warp_view's lookups.  verts [V,3] double, faces [F,3] int32.  Skipped: a face with
+ *   an index outside [0, V), with any vertex at lz <= znear (these are counted in n_clipped; nothing is clipped against the
+ *   near plane) or with a zero or non-finite signed screen area.  A pixel is covered iff its three edge functions have the
+ *   area's sign or are zero (inclusive edges, no culling); depth is perspective-correct, z = (float)(1 / sum_i w_i / z_i), kept
+ *   iff finite and > 0; per pixel the smallest (bits(z) << 32 | face) wins: the nearest depth, ties to the lower face.
+ *   Writes depth [H,W] f32 (z, or `background`), mask [H,W] uint8 (255 / 0), face_or_null [H,W] int32 (the face, or -1) and
+ *   n_clipped [1] int32.  small_max: a face whose pixel range holds at most this many pixels is walked by 8 lanes, a larger
+ *   one by a wave, beyond 4096 pixels by a wave per 64th of its rows (<= 0: the default, 256); the result does not depend on
+ *   it.  No float atomics: the
+ *   outputs are bitwise reproducible.  workspace: gsr_mesh_depth_workspace_bytes(H, W, F) bytes (8 H W + 4 F + counters), 16-byte
+ *   aligned, one per view in flight.  Asynchronous on `stream`, no host read.  F == 0 yields the background image. */
+size_t gsr_mesh_depth_workspace_bytes(int H, int W, int F);
+int gsr_mesh_depth_view(int H, int W, int V, int F, const double* verts, const int* faces, const double* cam16, double znear,
+                        float background, int small_max, void* workspace, float* depth, unsigned char* mask, int* face_or_null,
+                        int* n_clipped, gsr_stream_t stream);
+
 /* ---- TSDF fusion of the rig's renders and mesh extraction (gaustar_trainers/refined_mesh.py:311-459 `extract_mesh_fusion`).
  * The volume follows Open3D's legacy ScalableTSDFVolume(voxel_length, sdf_trunc, RGB8) -- units of 16^3 voxels,
  * depth_sampling_stride 4 -- by the rules restated in tests/fusion_ref.py (Open3D itself was not available: parity with it
