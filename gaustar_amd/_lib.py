@@ -210,6 +210,18 @@ SIGNATURES = {
     "gsr_debug_host_wait": (c_int, [POINTER(c_longlong), POINTER(c_longlong), c_int]),
 }
 
+
+
+class PlanInfo(ctypes.Structure):
+    """gsr_plan_info of include/gsr.h, field for field: what the GSR_PLAN_INFO_INTS ints of a plan_info block mean."""
+    _fields_ = [("state", c_int), ("R_cap", c_int), ("U_cap", c_int), ("max_cap", c_int), ("level", c_int), ("half", c_int),
+                ("pending_half", c_int), ("reserved0", c_int), ("header", c_int * 8), ("arrived", c_int), ("pending", c_int),
+                ("diag", c_int * 4), ("reserved1", c_int * 10)]
+
+
+PLAN_INFO_INTS = 32
+PH_VALID, PH_T, PH_R_CAP, PH_U_CAP, PH_MAX_CAP, PH_NONEMPTY, PH_ENTRIES, PH_LONGEST = range(8)   # words of PlanInfo.header
+
 _lib = None
 
 

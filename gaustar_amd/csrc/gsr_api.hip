@@ -33,14 +33,25 @@ thread_local struct { int R, maxc, nseg, parts; } g_last_stage1 = {-1, -1, -1, -
 // words of the pad: [0..3] stage-1 totals, [4] their sequence number (tile_scan); [8] verdict of a planned preprocess, [9] its
 // sequence number
 constexpr int PAD_WORDS = 64, PAD_VERDICT = 8;
-// ints of a plan_info block (include/gsr.h): [0..4] = {state, R_cap, U_cap, max_cap, slack level}; [PI_HEADER .. +7] the header of
-// a plan as its builder wrote it, [PI_ARRIVED] the builder's sequence number (written behind the header), [PI_PENDING] the
-// sequence number the host expects there (0: no plan under way)
-constexpr int PI_HEADER = 8, PI_ARRIVED = 16, PI_PENDING = 17;
-// [PI_HALF] which half of the caller's plan buffer holds the plan in use (gsr_internal.h carve_plan), [PI_PENDING_HALF] the half
-// the builder on its way writes
-constexpr int PI_HALF = 5, PI_PENDING_HALF = 6;
-static_assert(PI_PENDING < GSR_PLAN_INFO_INTS, "plan_info block");
+// ---- one helper per small rule of the drivers below
+inline int nonneg(int x) { return x > 0 ? x : 0; }
+// the next value of a sequence counter that never yields 0 (0 = "nothing yet" wherever such a number is waited for)
+template <class Counter> uint32_t next_nonzero(Counter& c)
+{
+    const uint32_t x = ++c;
+    return x ? x : ++c;
+}
+// Environment switches the driver reads; each is ON unless its value starts with '0'.  Per call (tools/ab_env.py flips them inside
+// one process):   GSR_OWN_COUNTERS   the library's self-cleaning counter block (off: the image buffer's counters, a fill per view)
+//                 GSR_SORT_IN_BLEND  short lists are sorted inside the forward blend (off: a separate sort kernel)
+//                 GSR_REPLAN         a planned view builds the next view's plan (off: a plan lives until a view outgrows it)
+// Once per process: GSR_SYNC_SPIN      stage 1 polls the pinned pad for its totals (off: hipStreamSynchronize)
+//                   GSR_EARLY_SCATTER  the fused forward queues scatter behind the scan before the host has the totals
+bool env_on(const char* name)
+{
+    const char* e = getenv(name);
+    return !(e && e[0] == '0');
+}
 std::atomic<long long> g_wait_ns{0}, g_waits{0};   // gsr_debug_host_wait
 
 const char* const kStageNames[ST_COUNT] = {"preprocess_kernel", "tile_scan_kernel", "scatter_kernel",
@@ -98,15 +109,14 @@ int gsr_abi_version(void) { return 16; }
 
 const char* gsr_last_error(void) { return g_err.c_str(); }
 
-size_t gsr_geom_bytes(int P) { return carve_geom(nullptr, P > 0 ? P : 0).bytes; }
+size_t gsr_geom_bytes(int P) { return carve_geom(nullptr, nonneg(P)).bytes; }
 size_t gsr_image_bytes(int W, int H) { return carve_image(nullptr, W, H).bytes; }
 size_t gsr_binning_bytes_mt(int R, int num_segments, int num_channels)
 {
-    return carve_bin(nullptr, R > 0 ? R : 0, num_segments > 0 ? num_segments : 0,
-                     channels_ok(num_channels) ? num_channels : 3).bytes;
+    return carve_bin(nullptr, nonneg(R), nonneg(num_segments), channels_ok(num_channels) ? num_channels : 3).bytes;
 }
 size_t gsr_binning_bytes(int R, int num_segments) { return gsr_binning_bytes_mt(R, num_segments, 3); }
-size_t gsr_grad_scratch_bytes(int P) { return (size_t)48 * (size_t)(P > 0 ? P : 0) + 256; }
+size_t gsr_grad_scratch_bytes(int P) { return (size_t)48 * (size_t)nonneg(P) + 256; }
 size_t gsr_plan_bytes(int W, int H) { return (W > 0 && H > 0) ? carve_plan(nullptr, W, H).bytes : 0; }
 
 // plan_info blocks: GSR_PLAN_INFO_INTS ints of pinned, device-mapped host memory each (the device writes a plan's header there),
@@ -165,6 +175,23 @@ struct Counters {
     uint32_t* sync() const { return base; }
     uint32_t* cnt() const { return base ? base + PLAN_SYNC_WORDS : nullptr; }
     uint32_t* cursors(int b) const { return base ? base + PLAN_SYNC_WORDS + cnt_words + (b ? cur_words : 0) : nullptr; }
+    // *blk = the cursor block a planned view claims on: one that is all zero (block 0 is filled if neither is)
+    int claim_clean_cursors(hipStream_t st, int* blk)
+    {
+        *blk = cur_dirty[0] == 0 ? 0 : cur_dirty[1] == 0 ? 1 : -1;
+        if (*blk >= 0) return 0;
+        *blk = 0;
+        GSR_CHECK(hipMemsetAsync(cursors(0), 0, 4 * cur_dirty[0] * PLAN_CURSOR_STRIDE, st));
+        cur_dirty[0] = 0;
+        return 0;
+    }
+    // a planned view of T tiles has claimed on block blk: its counts stand there, its forward blend hands the other block's
+    // first T cursors back zeroed
+    void settle_cursors(int blk, size_t T)
+    {
+        cur_dirty[blk] = T;
+        if (cur_dirty[blk ^ 1] <= T) cur_dirty[blk ^ 1] = 0;
+    }
 };
 std::mutex g_cnt_mu;
 std::map<std::pair<int, hipStream_t>, Counters> g_cnt;
@@ -178,10 +205,8 @@ struct CountersLease {   // releases the block on every way out of gsr_forward_f
 // marked in flight and busy; nullptr: use the image buffer
 Counters* acquire_counters(hipStream_t st, size_t cnt_words, size_t cur_words)
 {
-    const char* e_own = getenv("GSR_OWN_COUNTERS");   // read per call: tools/ab_env.py flips it inside one process
-    const bool off = e_own && e_own[0] == '0';
     int dev = 0;
-    if (off || hipGetDevice(&dev) != hipSuccess) return nullptr;
+    if (!env_on("GSR_OWN_COUNTERS") || hipGetDevice(&dev) != hipSuccess) return nullptr;
     Counters* c;
     {
         // (the lease is taken under the lock: gsr_release_stream_state tests `busy` under the same lock before it frees
@@ -235,6 +260,19 @@ int wait_pad_word(const volatile uint32_t* flag, uint32_t seq, hipStream_t st, b
     return 0;
 }
 
+// The same, for a word whose value also lies in device memory: when the stream retired without the store into the pad showing
+// up (never observed, but a platform where device stores to mapped host memory are not coherent must not yield stale values),
+// `bytes` from `dev_src` are fetched into `host_dst` with an ordinary copy and the stream is synchronised.
+int wait_or_copy_back(const volatile uint32_t* flag, uint32_t seq, hipStream_t st, void* host_dst, const void* dev_src, size_t bytes,
+                      bool* seen)
+{
+    if (const int bad = wait_pad_word(flag, seq, st, seen)) return bad;
+    if (*seen) return 0;
+    GSR_CHECK(hipMemcpyAsync(host_dst, dev_src, bytes, hipMemcpyDeviceToHost, st));
+    GSR_CHECK(hipStreamSynchronize(st));
+    return 0;
+}
+
 int ensure_pad()
 {
     if (!g_pinned) {
@@ -243,17 +281,42 @@ int ensure_pad()
     }
     return 0;
 }
-uint32_t next_seq() { return ++g_pinned_seq ? g_pinned_seq : ++g_pinned_seq; }   // never 0 (the pad's initial value)
+uint32_t next_seq() { return next_nonzero(g_pinned_seq); }   // (0 is the pad's initial value)
 uint32_t next_view_token()
 {
     // Token of a view (never 0, unique in the process): a preprocess workgroup that cannot record all of its instances
     // stores it in totals[4], the scan stores it in totals[5], and scatter walks the tiles again iff the two are equal.
     // No word has to be cleared between views, and a stale or uninitialised totals[4] can only select the slower path.
     static std::atomic<uint32_t> g_view_token{0};
-    uint32_t view_token = ++g_view_token;
-    if (view_token == 0) view_token = ++g_view_token;
-    return view_token;
+    return next_nonzero(g_view_token);
 }
+
+// One view's inputs as the entry points receive them, by field name (gsr_internal.h ViewArgs)
+ViewArgs view_args(int P, int D, int M, const float* means3D, const float* shs, const float* colors_precomp, const float* opacities,
+                   const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                   const float* viewmatrix, const float* projmatrix, const float* campos, int W, int H, float tan_fovx,
+                   float tan_fovy, int* radii)
+{
+    ViewArgs v;
+    v.P = P; v.D = D; v.M = M;
+    v.means3D = means3D; v.shs = shs; v.colors_precomp = colors_precomp; v.opacities = opacities;
+    v.scales = scales; v.scale_modifier = scale_modifier; v.rotations = rotations; v.cov3D_precomp = cov3D_precomp;
+    v.viewmatrix = viewmatrix; v.projmatrix = projmatrix; v.campos = campos;
+    v.W = W; v.H = H; v.tan_fovx = tan_fovx; v.tan_fovy = tan_fovy; v.radii = radii;
+    return v;
+}
+// the image buffer's state, with the library's counter block (already zero: acquire_counters; nullptr: none) in place of its own
+ImageState carve_image_with(void* image_buffer, int W, int H, uint32_t* counters)
+{
+    ImageState im = carve_image(image_buffer, W, H);
+    if (counters) {
+        im.tile_count = counters;
+        im.tile_cursor = counters + (size_t)shard_stride(tiles_of(W, H).T) * NSHARD;
+    }
+    return im;
+}
+// what the blends read as a Gaussian's colours
+const float* features_of(const float* colors_precomp, const GeomState& g) { return colors_precomp ? colors_precomp : g.rgb; }
 
 int check_stage1_args(const ViewArgs& v, const void* geom_buffer, const void* image_buffer)
 {
@@ -290,12 +353,8 @@ int forward_stage1_impl(const ViewArgs& v, void* geom_buffer, void* image_buffer
     const int P = v.P, W = v.W, H = v.H;
     hipStream_t st = (hipStream_t)stream;
     const Tiles t = tiles_of(W, H);
-    ImageState im = carve_image(image_buffer, W, H);
-    if (counters) {   // library-owned, already zero (acquire_counters)
-        im.tile_count = counters;
-        im.tile_cursor = counters + (size_t)shard_stride(t.T) * NSHARD;
-    } else {
-        // counters and cursors are adjacent in the image buffer: one fill covers both
+    ImageState im = carve_image_with(image_buffer, W, H, counters);
+    if (!counters) {   // counters and cursors are adjacent in the image buffer: one fill covers both
         GSR_CHECK(hipMemsetAsync(im.tile_count, 0,
                                  (size_t)((char*)(im.tile_cursor + shard_stride(t.T) * NSHARD) - (char*)im.tile_count), st));
     }
@@ -313,7 +372,7 @@ int forward_stage1_impl(const ViewArgs& v, void* geom_buffer, void* image_buffer
     // interrupt wake-up costs tens of microseconds of idle GPU per view); every few thousand polls it asks the stream
     // whether it finished or faulted, so a failed kernel ends the wait with its error.  GSR_SYNC_SPIN=0 -> plain sync.
     if (const int bad = ensure_pad()) return bad;
-    static const bool spin = !(getenv("GSR_SYNC_SPIN") && atoi(getenv("GSR_SYNC_SPIN")) == 0);
+    static const bool spin = env_on("GSR_SYNC_SPIN");
     const uint32_t seq = next_seq();
     {
         Scope sc(ST_TILE_SCAN, st);
@@ -331,15 +390,8 @@ int forward_stage1_impl(const ViewArgs& v, void* geom_buffer, void* image_buffer
     }
     if (spin) {
         bool seen = false;
-        if (const int bad = wait_pad_word(g_pinned + 4, seq, st, &seen)) return bad;
-        if (!seen) {
-            // The stream reports the kernel retired but its store into the pad has not shown up: never observed, but a
-            // platform where device stores to mapped host memory are not coherent must not yield stale totals -- fetch
-            // them with an ordinary copy.
-            GSR_CHECK(hipMemcpyAsync(g_pinned, im.totals, 16, hipMemcpyDeviceToHost, st));
-            g_pinned[5] = 0xffffffffu;   // (the number of parts did not arrive either: -1 = let stage 2 decide from the sizes)
-            GSR_CHECK(hipStreamSynchronize(st));
-        }
+        if (const int bad = wait_or_copy_back(g_pinned + 4, seq, st, g_pinned, im.totals, 16, &seen)) return bad;
+        if (!seen) g_pinned[5] = 0xffffffffu;   // (the number of parts did not arrive either: -1 = let stage 2 decide from the sizes)
     } else {
         GSR_CHECK(hipStreamSynchronize(st));   // the forward's single host sync (cf. rasterizer_impl.cu:281)
     }
@@ -350,6 +402,19 @@ int forward_stage1_impl(const ViewArgs& v, void* geom_buffer, void* image_buffer
     return 0;
 }
 
+// what stage 2 asks of its arguments, whichever driver launches the forward blend
+int check_stage2_args(int R, int num_channels, int W, int H, const float* background, const float* colors_precomp,
+                      const void* geom_buffer, const void* binning_buffer, const void* image_buffer, const float* out_color)
+{
+    if (W <= 0 || H <= 0) return fail_msg("gsr_forward_stage2: image size must be positive");
+    if (!background || !out_color || !image_buffer) return fail_msg("gsr_forward_stage2: required pointer is null");
+    if (R > 0 && (!binning_buffer || !geom_buffer)) return fail_msg("gsr_forward_stage2: scratch buffer is null");
+    if (!channels_ok(num_channels)) return fail_msg("gsr_forward_stage2: num_channels must be 3, 4 or 6");
+    if (num_channels != 3 && !colors_precomp)
+        return fail_msg("gsr_forward_stage2: multi-target renders need precomputed colours [P, num_channels]");
+    return 0;
+}
+
 // grad_scratch != nullptr: the backward's accumulation table, cleared by the forward blend on the side (gsr_forward_fused)
 int forward_stage2_impl(int P, int R, int max_tile_instances, int num_segments, int num_channels, int W, int H,
                         const float* background, const float* colors_precomp, void* geom_buffer, void* binning_buffer,
@@ -357,251 +422,261 @@ int forward_stage2_impl(int P, int R, int max_tile_instances, int num_segments, 
                         bool scattered, const PlanJob* job = nullptr, bool* job_rides = nullptr)
 {
     g_err.clear();
-    if (W <= 0 || H <= 0) return fail_msg("gsr_forward_stage2: image size must be positive");
-    if (!background || !out_color || !image_buffer) return fail_msg("gsr_forward_stage2: required pointer is null");
-    if (R > 0 && (!binning_buffer || !geom_buffer)) return fail_msg("gsr_forward_stage2: scratch buffer is null");
-    if (!channels_ok(num_channels)) return fail_msg("gsr_forward_stage2: num_channels must be 3, 4 or 6");
-    if (num_channels != 3 && !colors_precomp)
-        return fail_msg("gsr_forward_stage2: multi-target renders need precomputed colours [P, num_channels]");
+    if (const int bad = check_stage2_args(R, num_channels, W, H, background, colors_precomp, geom_buffer, binning_buffer, image_buffer,
+                                          out_color))
+        return bad;
     const int C = num_channels;
     hipStream_t st = (hipStream_t)stream;
-    ImageState im = carve_image(image_buffer, W, H);
-    if (counters) {   // library-owned counters of the fused forward; the blend hands them back zeroed
-        im.tile_count = counters;
-        im.tile_cursor = counters + (size_t)shard_stride(tiles_of(W, H).T) * NSHARD;
-    }
-    GeomState g = carve_geom(geom_buffer, P > 0 ? P : 0);
+    const uint32_t max_count = (uint32_t)nonneg(max_tile_instances);
+    ImageState im = carve_image_with(image_buffer, W, H, counters);   // (the blend hands the library's counters back zeroed)
+    GeomState g = carve_geom(geom_buffer, nonneg(P));
     // num_segments < 0: forward-only render (same buffer size as for |num_segments|; the blended-instance words the
     // backward would replay are not written back)
     const bool forward_only = num_segments < 0;
     if (num_segments < 0) num_segments = -num_segments;
     if (R > 0 && num_segments == 0) return fail_msg("gsr_forward_stage2: num_segments of stage 1 is required (it sizes the binning buffer)");
-    BinState b = carve_bin(binning_buffer, R > 0 ? R : 0, num_segments, C);
+    BinState b = carve_bin(binning_buffer, nonneg(R), num_segments, C);
     bool sort_in_blend = false;
     if (R > 0) {
         if (!scattered) {   // (the fused forward has launched it behind the scan already)
             Scope sc(ST_SCATTER, st);
-            launch_scatter(P, W, H, R, (uint32_t)(max_tile_instances > 0 ? max_tile_instances : 0), g, im, b, st);
+            launch_scatter(P, W, H, R, max_count, g, im, b, st);
             GSR_CHECK_LAUNCH("scatter_kernel");
         }
         {
-            const char* e_fuse = getenv("GSR_SORT_IN_BLEND");   // read per call (tools/ab_env.py); "0": separate sort kernel
-            const bool fuse = !(e_fuse && e_fuse[0] == '0');
+            const bool fuse = env_on("GSR_SORT_IN_BLEND");
             // (no event bracket around a stage that launches nothing -- every list of a typical view is sorted inside the
             // forward blend; two back-to-back event records read as ~5 us of "kernel")
-            const bool launches = tile_sort_launches(R, (uint32_t)(max_tile_instances > 0 ? max_tile_instances : 0), fuse);
-            Scope sc(launches ? ST_TILE_SORT : -1, st);
-            sort_in_blend = launch_tile_sort(W, H, R, num_segments, (uint32_t)(max_tile_instances > 0 ? max_tile_instances : 0), im, b, fuse, st);
+            Scope sc(tile_sort_launches(R, max_count, fuse) ? ST_TILE_SORT : -1, st);
+            sort_in_blend = launch_tile_sort(W, H, R, num_segments, max_count, im, b, fuse, st);
         }
         GSR_CHECK_LAUNCH("tile_sort_kernel");
     }
-    const float* feats = colors_precomp ? colors_precomp : g.rgb;
     const int num_parts = (g_last_stage1.R == R && g_last_stage1.maxc == max_tile_instances && g_last_stage1.nseg == num_segments)
                               ? g_last_stage1.parts : -1;   // (-1: stage 1 of another view, or of another thread)
     {
         Scope sc(ST_BLEND_FWD, st);
-        launch_blend_fwd(C, W, H, R > 0 ? R : 0, num_segments, (uint32_t)(max_tile_instances > 0 ? max_tile_instances : 0), background, feats, g, im, b,
-                         out_color, !forward_only, grad_scratch,
-                         grad_scratch ? gsr_grad_scratch_bytes(P > 0 ? P : 0) : 0, counters, sort_in_blend, st, job, job_rides, num_parts);
+        launch_blend_fwd(C, W, H, nonneg(R), num_segments, max_count, background, features_of(colors_precomp, g), g, im, b, out_color,
+                         !forward_only, grad_scratch, grad_scratch ? gsr_grad_scratch_bytes(P) : 0, counters, sort_in_blend, st, job,
+                         job_rides, num_parts);
     }
     GSR_CHECK_LAUNCH("blend_fwd_kernel");
     return 0;
 }
 
-// One planned attempt (gsr_internal.h "planned binning"): preprocess claims bucket slots and writes the keys, the forward blend
-// is queued right behind it, and the host waits for preprocess's verdict only.  *fit = 0: the view did not fit the plan --
-// nothing was blended, the library's counter block is clean again once the queued blend has passed, and the caller takes the
-// exact path.
-int forward_planned_attempt(const ViewArgs& v, int C, int need_backward, const float* background, void* geom_buffer,
-                            void* image_buffer, void* binning_buffer, void* grad_scratch, float* out_color, void* plan_buffer,
-                            const int* plan_info, uint32_t* cursors, uint32_t* cursors_other, uint32_t* sync_words,
-                            hipStream_t st, int* fit, const PlanJob* job)
-{
-    *fit = 0;
-    g_err.clear();
-    if (const int bad = check_stage1_args(v, geom_buffer, image_buffer)) return bad;
-    if (!background || !out_color) return fail_msg("gsr_forward_stage2: required pointer is null");
-    if (C != 3 && !v.colors_precomp)
-        return fail_msg("gsr_forward_stage2: multi-target renders need precomputed colours [P, num_channels]");
-    if (const int bad = ensure_pad()) return bad;
-    const int P = v.P, W = v.W, H = v.H;
-    ImageState im = carve_image(image_buffer, W, H);
-    GeomState g = carve_geom(geom_buffer, P);
-    BinState b = carve_bin(binning_buffer, plan_info[1], plan_info[2], C);
-    const PlanState pl = carve_plan(plan_buffer, W, H, plan_info[PI_HALF] & 1);
-    PlanRun run;
-    run.ranges = pl.ranges; run.seg_off = pl.seg_off; run.order = pl.order;
-    run.cursor = cursors; run.cursor_other = cursors_other; run.sync = sync_words;
-    run.keys = b.keys; run.unit_info = b.unit_info; run.im_ranges = im.ranges; run.im_seg_off = im.seg_off;
-    run.host_pad = g_pinned + PAD_VERDICT; run.host_seq = next_seq(); run.token = next_view_token();
+// ---- gsr_forward_fused / gsr_forward_planned: one call's arguments and what its steps share.  forward_fused_impl (below) reads
+// as the sequence of the steps: adopt_arrived_plan, planned_view (plan_job + planned_attempt), exact_view (plan_job, and
+// hand_back_counters when the guess was too small).
+struct FusedCall {
+    const ViewArgs& v; int C, need_backward; const float* background;
+    void *geom_buffer, *image_buffer, *binning_buffer; size_t binning_capacity; void* grad_scratch; float* out_color;
+    int *num_rendered, *max_tile_instances, *num_segments, *blended;
+    void* plan_buffer; gsr_plan_info* pi; int* planned;   // pi: the caller's plan_info block (nullptr: gsr_forward_fused)
+    gsr_stream_t stream; hipStream_t st; bool sane, keeps_plan; size_t cnt_words;
+    Counters* own;   // the library's counter block, leased to this call (nullptr: the image buffer's counters)
+
+    int level() const { return std::min(std::max(pi->level, 0), 3); }
+    // the builder of `job` is on its way: the camera's next call waits for its sequence number in pi->arrived
+    void expect(const PlanJob& job, int half) const { pi->pending = (int)job.host_seq; pi->pending_half = half; }
+
+    // The plan an earlier view of this camera left behind: its header arrives in pi->header some tens of microseconds into that
+    // view's forward blend; nobody waited for it then.  Normally it is long there.
+    int adopt_arrived_plan() const
     {
-        Scope sc(ST_PREPROCESS, st);
-        launch_preprocess_planned(v, g, im, run, st);
-    }
-    GSR_CHECK_LAUNCH("preprocess_kernel");
-    const float* feats = v.colors_precomp ? v.colors_precomp : g.rgb;
-    {
-        Scope sc(ST_BLEND_FWD, st);
-        launch_blend_fwd_planned(C, W, H, background, feats, g, im, b, out_color, need_backward != 0,
-                                 need_backward ? grad_scratch : nullptr,
-                                 need_backward && grad_scratch ? gsr_grad_scratch_bytes(P) : 0, run, st, job);
-    }
-    GSR_CHECK_LAUNCH("blend_fwd_kernel");
-    bool seen = false;
-    if (const int bad = wait_pad_word(g_pinned + PAD_VERDICT + 1, run.host_seq, st, &seen)) return bad;
-    if (!seen) {   // (see forward_stage1_impl: never observed; the stream has retired, so a plain read-back is final)
-        uint32_t flag = 0;
-        GSR_CHECK(hipMemcpyAsync(&flag, run.sync + 9 * PLAN_SYNC_STRIDE, 4, hipMemcpyDeviceToHost, st));
-        GSR_CHECK(hipStreamSynchronize(st));
-        *fit = flag != run.token;
+        bool seen = false;
+        if (const int bad = wait_pad_word(reinterpret_cast<volatile uint32_t*>(&pi->arrived), (uint32_t)pi->pending, st, &seen))
+            return bad;
+        const uint32_t* h = reinterpret_cast<const uint32_t*>(pi->header);
+        // (a header that is not this image's -- another size's, or not a header at all -- is no plan)
+        if (seen && (h[PH_T] != (uint32_t)v.tiles().T || h[PH_U_CAP] != h[PH_R_CAP] >> 6 || (h[PH_R_CAP] & 63u) != 0u)) seen = false;
+        pi->state = seen ? (h[PH_VALID] == 1u ? 1 : -1) : 0;
+        if (seen) {
+            pi->R_cap = (int)h[PH_R_CAP]; pi->U_cap = (int)h[PH_U_CAP]; pi->max_cap = (int)h[PH_MAX_CAP];
+            pi->half = pi->pending_half & 1;
+        }
+        pi->pending = 0;
         return 0;
     }
-    *fit = g_pinned[PAD_VERDICT] == 1u;
-    return 0;
-}
+
+    // The plan workgroup of THIS view (exact or planned) writes the half of the plan buffer that is not in use (-> that half); its
+    // header lands in pi->header and is adopted by the camera's next call (above).
+    int plan_job(PlanJob& job) const
+    {
+        const Tiles t = v.tiles();
+        const int half = (pi->half & 1) ^ 1;
+        const PlanState pl = carve_plan(plan_buffer, v.W, v.H, half);
+        job.enabled = 1u; job.T = t.T; job.gx = t.gx; job.gy = t.gy;
+        job.header = pl.header; job.ranges = pl.ranges; job.seg_off = pl.seg_off; job.order = pl.order;
+        job.split_from_word = split_from();
+        job.level = (uint32_t)level();
+        job.host_pad = reinterpret_cast<uint32_t*>(pi->header);
+        // (the sequence number belongs to the PLAN, not to the calling thread: a plan_info block may be used from several
+        // host threads, and a thread-local counter that happens to equal the block's stale `arrived` would make the next
+        // call adopt the OLD header while the device holds the new plan)
+        uint32_t seq = (uint32_t)pi->arrived;
+        job.host_seq = next_nonzero(seq);
+        job.cursor = nullptr;
+        // (GSR_PLAN_DIAG builds: the plan being replaced, if the buffer has held one)
+        job.prev_ranges = pi->R_cap > 0 ? carve_plan(plan_buffer, v.W, v.H, half ^ 1).ranges : nullptr;
+        return half;
+    }
+
+    // One planned attempt (gsr_internal.h "planned binning") on cursor block blk: preprocess claims bucket slots and writes the
+    // keys, the forward blend is queued right behind it, and the host waits for preprocess's verdict only.  *fit = 0: the view did
+    // not fit the plan -- nothing was blended, and the library's counter block is clean again once the queued blend has passed.
+    int planned_attempt(int blk, const PlanJob* job, int* fit) const
+    {
+        *fit = 0;
+        g_err.clear();
+        if (const int bad = check_stage1_args(v, geom_buffer, image_buffer)) return bad;
+        if (const int bad = check_stage2_args(pi->R_cap, C, v.W, v.H, background, v.colors_precomp, geom_buffer, binning_buffer,
+                                              image_buffer, out_color))
+            return bad;
+        if (const int bad = ensure_pad()) return bad;
+        ImageState im = carve_image(image_buffer, v.W, v.H);
+        GeomState g = carve_geom(geom_buffer, v.P);
+        BinState b = carve_bin(binning_buffer, pi->R_cap, pi->U_cap, C);
+        const PlanState pl = carve_plan(plan_buffer, v.W, v.H, pi->half & 1);
+        PlanRun run;
+        run.ranges = pl.ranges; run.seg_off = pl.seg_off; run.order = pl.order;
+        run.cursor = own->cursors(blk); run.cursor_other = own->cursors(blk ^ 1); run.sync = own->sync();
+        run.keys = b.keys; run.unit_info = b.unit_info; run.im_ranges = im.ranges; run.im_seg_off = im.seg_off;
+        run.host_pad = g_pinned + PAD_VERDICT; run.host_seq = next_seq(); run.token = next_view_token();
+        {
+            Scope sc(ST_PREPROCESS, st);
+            launch_preprocess_planned(v, g, im, run, st);
+        }
+        GSR_CHECK_LAUNCH("preprocess_kernel");
+        {
+            Scope sc(ST_BLEND_FWD, st);
+            launch_blend_fwd_planned(C, v.W, v.H, background, features_of(v.colors_precomp, g), g, im, b, out_color, need_backward != 0,
+                                     need_backward ? grad_scratch : nullptr,
+                                     need_backward && grad_scratch ? gsr_grad_scratch_bytes(v.P) : 0, run, st, job);
+        }
+        GSR_CHECK_LAUNCH("blend_fwd_kernel");
+        bool seen = false;
+        uint32_t flag = 0;   // (the stream has retired when this is read back, so it is final)
+        if (const int bad = wait_or_copy_back(g_pinned + PAD_VERDICT + 1, run.host_seq, st, &flag, run.sync + 9 * PLAN_SYNC_STRIDE, 4, &seen))
+            return bad;
+        *fit = seen ? g_pinned[PAD_VERDICT] == 1u : flag != run.token;
+        return 0;
+    }
+
+    bool has_usable_plan() const
+    {
+        return keeps_plan && own && pi->state == 1 && pi->R_cap > 0 && pi->U_cap > 0 && binning_buffer && num_rendered &&
+               max_tile_instances && num_segments && (split_from() & 0x80000000u) == 0u &&
+               gsr_binning_bytes_mt(pi->R_cap, pi->U_cap, C) <= binning_capacity;
+    }
+
+    // Bin and blend the view by its camera's plan.  *blended stays 0: it outgrew the plan, and the exact path renders it (the queued
+    // blend leaves the counter block clean) and re-plans, with twice the slack.
+    int planned_view() const
+    {
+        const bool replan = env_on("GSR_REPLAN");
+        // the cursor block this view claims on must be all zero; the other one is handed back zeroed by this view's forward blend
+        int blk = 0, half = 0, fit = 0;
+        if (const int bad = own->claim_clean_cursors(st, &blk)) return bad;
+        PlanJob job{};
+        if (replan) {
+            half = plan_job(job);
+            job.cursor = own->cursors(blk);
+        }
+        if (const int bad = planned_attempt(blk, replan ? &job : nullptr, &fit)) return bad;   // (own stays marked dirty: everything is re-filled on its next use)
+        own->settle_cursors(blk, (size_t)v.tiles().T);
+        if (!fit) {
+            pi->state = 0;
+            pi->level = std::min(level() + 1, 3);
+            if (planned) *planned = -1;
+            return 0;
+        }
+        if (replan) expect(job, half);
+        *num_rendered = pi->R_cap;
+        *num_segments = pi->U_cap;
+        *max_tile_instances = pi->max_cap;
+        *blended = 1;
+        if (planned) *planned = 1;
+        own->clean = true;   // (the exact path's counters were not touched; the cursor blocks are accounted for above)
+        return 0;
+    }
+
+    // The guess was too small: the caller allocates exactly and runs stage 2 itself -- over the image buffer's own counters, so
+    // they get this call's counts (cursors are still zero) and the library's block is filled again.
+    int hand_back_counters() const
+    {
+        if (!own) return 0;
+        ImageState im = carve_image(image_buffer, v.W, v.H);
+        GSR_CHECK(hipMemcpyAsync(im.tile_count, own->cnt(), 4 * cnt_words / 2, hipMemcpyDeviceToDevice, st));
+        GSR_CHECK(hipMemsetAsync(im.tile_cursor, 0, 4 * cnt_words / 2, st));
+        GSR_CHECK(hipMemsetAsync(own->cnt(), 0, 4 * cnt_words / 2, st));
+        own->clean = true;
+        return 0;
+    }
+
+    // Scan + scatter: stage 1, then stage 2 right away if the caller's binning buffer holds the view.
+    int exact_view() const
+    {
+        static const bool early_ok = env_on("GSR_EARLY_SCATTER");
+        const bool early = early_ok && sane && binning_buffer != nullptr && binning_capacity > 0;
+        uint32_t* const counters = own ? own->cnt() : nullptr;
+        const int rc = forward_stage1_impl(v, geom_buffer, image_buffer, num_rendered, max_tile_instances, num_segments, counters, stream,
+                                           early ? binning_buffer : nullptr, binning_capacity, C);
+        if (rc != 0) return rc;   // (own stays marked dirty: re-filled on its next use)
+        // The plan this view leaves behind is built by one extra workgroup of its forward blend (gsr_plan.h).  Nobody waits for
+        // it: the header lands in the caller's pinned plan_info block and is adopted by the next call with this plan.  Not built
+        // when a plan exists (state 1 was tried first; a misfit has reset it to 0), when the camera is known to be unplannable (-1:
+        // the caller asks again by resetting it to 0), when this view's longest list cannot be planned, or when stage 2 is left to
+        // the caller.
+        PlanJob job{};
+        bool job_rides = false;
+        int half = 0;
+        if (keeps_plan && pi->state == 0) {
+            if ((uint32_t)*max_tile_instances + 16u > PLAN_MAX_LIST) pi->state = -1;
+            else if (*num_rendered > 0) half = plan_job(job);
+        }
+        if (gsr_binning_bytes_mt(*num_rendered, *num_segments, C) > binning_capacity || (*num_rendered > 0 && !binning_buffer))
+            return hand_back_counters();
+        const int rc2 = forward_stage2_impl(v.P, *num_rendered, *max_tile_instances, need_backward ? *num_segments : -*num_segments, C,
+                                            v.W, v.H, background, v.colors_precomp, geom_buffer, binning_buffer, image_buffer, out_color,
+                                            need_backward ? grad_scratch : nullptr, counters, stream, early, job.enabled ? &job : nullptr,
+                                            &job_rides);
+        if (rc2 != 0) return rc2;
+        *blended = 1;
+        if (own) own->clean = true;   // the forward blend zeroes every tile's counters and cursors
+        if (job_rides) expect(job, half);
+        return 0;
+    }
+};
 
 int forward_fused_impl(const ViewArgs& v, int num_channels, int need_backward, const float* background, void* geom_buffer,
                        void* image_buffer, void* binning_buffer, size_t binning_capacity, void* grad_scratch, float* out_color,
                        int* num_rendered, int* max_tile_instances, int* num_segments, int* blended, void* plan_buffer,
                        int* plan_info, int* planned, gsr_stream_t stream)
 {
-    const int P = v.P, W = v.W, H = v.H;
     if (!blended) { g_err.clear(); return fail_msg("gsr_forward_fused: null output pointer"); }
     *blended = 0;
     if (planned) *planned = 0;
     if (!channels_ok(num_channels)) { g_err.clear(); return fail_msg("gsr_forward_fused: num_channels must be 3, 4 or 6"); }
     hipStream_t st = (hipStream_t)stream;
-    const bool sane = W > 0 && H > 0 && (long long)tiles_of(W > 0 ? W : 1, H > 0 ? H : 1).T <= 256ll * 1024 && image_buffer && P > 0;
-    const size_t cnt_words = sane ? 2 * (size_t)shard_stride(tiles_of(W, H).T) * NSHARD : 0;
+    const int T = v.W > 0 && v.H > 0 ? v.tiles().T : 0;
+    const bool sane = T > 0 && (long long)T <= 256ll * 1024 && image_buffer && v.P > 0;
     const bool keeps_plan = plan_buffer != nullptr && plan_info != nullptr && sane;
-    // (a caller that keeps plans: two blocks of one cursor per tile, PLAN_CURSOR_STRIDE words apart, behind the exact counters)
-    const size_t cur_words = keeps_plan ? (size_t)tiles_of(W, H).T * PLAN_CURSOR_STRIDE : 0;
+    // the exact path's counters and cursors; a caller that keeps plans: two blocks of one cursor per tile, PLAN_CURSOR_STRIDE words
+    // apart, behind them
+    const size_t cnt_words = sane ? 2 * (size_t)shard_stride(T) * NSHARD : 0;
+    const size_t cur_words = keeps_plan ? (size_t)T * PLAN_CURSOR_STRIDE : 0;
     Counters* own = sane ? acquire_counters(st, cnt_words, cur_words) : nullptr;
     CountersLease lease{own};
-    if (keeps_plan && plan_info[PI_PENDING] != 0) {
-        // The plan an earlier view of this camera left behind: its header arrives in the caller's pinned words [PI_HEADER ..]
-        // some tens of microseconds into that view's forward blend; nobody waited for it then.  Normally it is long there.
-        bool seen = false;
-        if (const int bad = wait_pad_word(reinterpret_cast<volatile uint32_t*>(plan_info) + PI_ARRIVED, (uint32_t)plan_info[PI_PENDING],
-                                          st, &seen))
-            return bad;
-        const uint32_t* h = reinterpret_cast<const uint32_t*>(plan_info) + PI_HEADER;
-        // (a header that is not this image's -- another size's, or not a header at all -- is no plan)
-        if (seen && (h[1] != (uint32_t)tiles_of(W, H).T || h[3] != h[2] >> 6 || (h[2] & 63u) != 0u)) seen = false;
-        plan_info[0] = seen ? (h[0] == 1u ? 1 : -1) : 0;
-        if (seen) {
-            plan_info[1] = (int)h[2]; plan_info[2] = (int)h[3]; plan_info[3] = (int)h[4];
-            plan_info[PI_HALF] = plan_info[PI_PENDING_HALF] & 1;
-        }
-        plan_info[PI_PENDING] = 0;
+    const FusedCall c{v, num_channels, need_backward, background, geom_buffer, image_buffer, binning_buffer, binning_capacity,
+                      grad_scratch, out_color, num_rendered, max_tile_instances, num_segments, blended, plan_buffer,
+                      reinterpret_cast<gsr_plan_info*>(plan_info), planned, stream, st, sane, keeps_plan, cnt_words, own};
+    if (keeps_plan && c.pi->pending != 0)
+        if (const int bad = c.adopt_arrived_plan()) return bad;
+    if (c.has_usable_plan()) {
+        if (const int bad = c.planned_view()) return bad;
+        if (*blended) return 0;
     }
-    // The plan workgroup of THIS view (exact or planned) writes the half of the plan buffer that is not in use; its header
-    // lands in the caller's pinned words and is adopted by the camera's next call (above).
-    const auto plan_job = [&](PlanJob& job) {
-        const Tiles t = tiles_of(W, H);
-        const int half = (plan_info[PI_HALF] & 1) ^ 1;
-        const PlanState pl = carve_plan(plan_buffer, W, H, half);
-        job.enabled = 1u; job.T = t.T; job.gx = t.gx; job.gy = t.gy;
-        job.header = pl.header; job.ranges = pl.ranges; job.seg_off = pl.seg_off; job.order = pl.order;
-        job.split_from_word = split_from();
-        job.level = (uint32_t)(plan_info[4] < 0 ? 0 : plan_info[4] > 3 ? 3 : plan_info[4]);
-        job.host_pad = reinterpret_cast<uint32_t*>(plan_info) + PI_HEADER;
-        // (the sequence number belongs to the PLAN, not to the calling thread: a plan_info block may be used from several
-        // host threads, and a thread-local counter that happens to equal the block's stale ARRIVED word would make the next
-        // call adopt the OLD header while the device holds the new plan)
-        job.host_seq = (uint32_t)plan_info[PI_ARRIVED] + 1u;
-        if (job.host_seq == 0u) job.host_seq = 1u;
-        job.cursor = nullptr;
-        // (GSR_PLAN_DIAG builds: the plan being replaced, if the buffer has held one)
-        job.prev_ranges = plan_info[1] > 0 ? carve_plan(plan_buffer, W, H, half ^ 1).ranges : nullptr;
-        return half;
-    };
-    const char* e_rp = getenv("GSR_REPLAN");   // (0: round 5's behaviour; read per call: tools/ab_env.py flips it inside one process)
-    const bool replan = !(e_rp && e_rp[0] == '0');
-    if (keeps_plan && own && plan_info[0] == 1 && plan_info[1] > 0 && plan_info[2] > 0 && binning_buffer &&
-        num_rendered && max_tile_instances && num_segments && (split_from() & 0x80000000u) == 0u &&
-        gsr_binning_bytes_mt(plan_info[1], plan_info[2], num_channels) <= binning_capacity) {
-        int fit = 0;
-        // the cursor block this view claims on must be all zero; the other one is handed back zeroed by this view's forward blend
-        const size_t Tn = (size_t)tiles_of(W, H).T;
-        int blk = own->cur_dirty[0] == 0 ? 0 : own->cur_dirty[1] == 0 ? 1 : -1;
-        if (blk < 0) {
-            blk = 0;
-            GSR_CHECK(hipMemsetAsync(own->cursors(0), 0, 4 * own->cur_dirty[0] * PLAN_CURSOR_STRIDE, st));
-            own->cur_dirty[0] = 0;
-        }
-        PlanJob pjob{};
-        int pjob_half = 0;
-        if (replan) {
-            pjob_half = plan_job(pjob);
-            pjob.cursor = own->cursors(blk);
-        }
-        const int rc = forward_planned_attempt(v, num_channels, need_backward, background, geom_buffer, image_buffer, binning_buffer,
-                                               grad_scratch, out_color, plan_buffer, plan_info, own->cursors(blk),
-                                               own->cursors(blk ^ 1), own->sync(), st, &fit, replan ? &pjob : nullptr);
-        if (rc != 0) return rc;   // (own stays marked dirty: everything is re-filled on its next use)
-        own->cur_dirty[blk] = Tn;
-        if (own->cur_dirty[blk ^ 1] <= Tn) own->cur_dirty[blk ^ 1] = 0;
-        if (fit) {
-            if (replan) { plan_info[PI_PENDING] = (int)pjob.host_seq; plan_info[PI_PENDING_HALF] = pjob_half; }
-            *num_rendered = plan_info[1];
-            *num_segments = plan_info[2];
-            *max_tile_instances = plan_info[3];
-            *blended = 1;
-            if (planned) *planned = 1;
-            own->clean = true;   // (the exact path's counters were not touched; the cursor blocks are accounted for above)
-            return 0;
-        }
-        // the view outgrew its plan: the exact path below renders it (the queued blend leaves the block clean) and re-plans, with
-        // twice the slack
-        plan_info[0] = 0;
-        plan_info[4] = plan_info[4] < 3 ? (plan_info[4] < 0 ? 0 : plan_info[4]) + 1 : 3;
-        if (planned) *planned = -1;
-    }
-    static const bool early_ok = !(getenv("GSR_EARLY_SCATTER") && atoi(getenv("GSR_EARLY_SCATTER")) == 0);
-    const bool early = early_ok && sane && binning_buffer != nullptr && binning_capacity > 0;
-    const int rc = forward_stage1_impl(v, geom_buffer, image_buffer, num_rendered, max_tile_instances, num_segments,
-                                       own ? own->cnt() : nullptr, stream, early ? binning_buffer : nullptr, binning_capacity,
-                                       num_channels);
-    if (rc != 0) return rc;   // (own stays marked dirty: re-filled on its next use)
-    // The plan this view leaves behind is built by one extra workgroup of its forward blend (gsr_plan.h).  Nobody waits for
-    // it: the header lands in the caller's pinned plan_info words and is adopted by the next call with this plan (above).
-    // Not built when a plan exists (plan_info[0] == 1 was handled above; a misfit has reset it to 0), when the camera is known
-    // to be unplannable (-1: the caller asks again by resetting it to 0), when this view's longest list cannot be planned, or
-    // when stage 2 is left to the caller.
-    PlanJob job{};
-    bool job_rides = false;
-    int job_half = 0;
-    if (keeps_plan && plan_info[0] == 0) {
-        if ((uint32_t)*max_tile_instances + 16u > PLAN_MAX_LIST) {
-            plan_info[0] = -1;
-        } else if (*num_rendered > 0) {
-            job_half = plan_job(job);
-        }
-    }
-    if (gsr_binning_bytes_mt(*num_rendered, *num_segments, num_channels) > binning_capacity || (*num_rendered > 0 && !binning_buffer)) {
-        // the guess was too small: the caller allocates exactly and runs stage 2 itself -- over the image buffer's own
-        // counters, so they get this call's counts (cursors are still zero) and the library's block is filled again
-        if (own) {
-            ImageState im = carve_image(image_buffer, W, H);
-            GSR_CHECK(hipMemcpyAsync(im.tile_count, own->cnt(), 4 * cnt_words / 2, hipMemcpyDeviceToDevice, st));
-            GSR_CHECK(hipMemsetAsync(im.tile_cursor, 0, 4 * cnt_words / 2, st));
-            GSR_CHECK(hipMemsetAsync(own->cnt(), 0, 4 * cnt_words / 2, st));
-            own->clean = true;
-        }
-        return 0;
-    }
-    const int rc2 = forward_stage2_impl(P, *num_rendered, *max_tile_instances, need_backward ? *num_segments : -*num_segments,
-                                        num_channels, W, H, background, v.colors_precomp, geom_buffer, binning_buffer,
-                                        image_buffer, out_color, need_backward ? grad_scratch : nullptr,
-                                        own ? own->cnt() : nullptr, stream, early, job.enabled ? &job : nullptr, &job_rides);
-    if (rc2 == 0) {
-        *blended = 1;
-        if (own) own->clean = true;   // the forward blend zeroes every tile's counters and cursors
-    }
-    if (rc2 != 0) return rc2;
-    if (job_rides) { plan_info[PI_PENDING] = (int)job.host_seq; plan_info[PI_PENDING_HALF] = job_half; }
-    return 0;
+    return c.exact_view();
 }
 }  // namespace
 
@@ -621,12 +696,8 @@ int gsr_forward_stage1(int P, int D, int M, const float* means3D, const float* s
                        int* num_segments, gsr_stream_t stream)
 {
     (void)prefiltered;
-    ViewArgs v;
-    v.P = P; v.D = D; v.M = M;
-    v.means3D = means3D; v.shs = shs; v.colors_precomp = colors_precomp; v.opacities = opacities;
-    v.scales = scales; v.scale_modifier = scale_modifier; v.rotations = rotations; v.cov3D_precomp = cov3D_precomp;
-    v.viewmatrix = viewmatrix; v.projmatrix = projmatrix; v.campos = campos;
-    v.W = W; v.H = H; v.tan_fovx = tan_fovx; v.tan_fovy = tan_fovy; v.radii = radii;
+    const ViewArgs v = view_args(P, D, M, means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp,
+                                 viewmatrix, projmatrix, campos, W, H, tan_fovx, tan_fovy, radii);
     return forward_stage1_impl(v, geom_buffer, image_buffer, num_rendered, max_tile_instances, num_segments, nullptr, stream);
 }
 
@@ -639,12 +710,8 @@ int gsr_forward_fused(int P, int D, int M, int num_channels, int need_backward, 
                       int* num_rendered, int* max_tile_instances, int* num_segments, int* blended, gsr_stream_t stream)
 {
     (void)prefiltered;
-    ViewArgs v;
-    v.P = P; v.D = D; v.M = M;
-    v.means3D = means3D; v.shs = shs; v.colors_precomp = colors_precomp; v.opacities = opacities;
-    v.scales = scales; v.scale_modifier = scale_modifier; v.rotations = rotations; v.cov3D_precomp = cov3D_precomp;
-    v.viewmatrix = viewmatrix; v.projmatrix = projmatrix; v.campos = campos;
-    v.W = W; v.H = H; v.tan_fovx = tan_fovx; v.tan_fovy = tan_fovy; v.radii = radii;
+    const ViewArgs v = view_args(P, D, M, means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp,
+                                 viewmatrix, projmatrix, campos, W, H, tan_fovx, tan_fovy, radii);
     return forward_fused_impl(v, num_channels, need_backward, background, geom_buffer, image_buffer, binning_buffer, binning_capacity,
                               grad_scratch, out_color, num_rendered, max_tile_instances, num_segments, blended, nullptr, nullptr,
                               nullptr, stream);
@@ -661,12 +728,8 @@ int gsr_forward_planned(int P, int D, int M, int num_channels, int need_backward
 {
     if (!plan_buffer || !plan_info || !planned) { g_err.clear(); return fail_msg("gsr_forward_planned: null plan pointer"); }
     (void)prefiltered;
-    ViewArgs v;
-    v.P = P; v.D = D; v.M = M;
-    v.means3D = means3D; v.shs = shs; v.colors_precomp = colors_precomp; v.opacities = opacities;
-    v.scales = scales; v.scale_modifier = scale_modifier; v.rotations = rotations; v.cov3D_precomp = cov3D_precomp;
-    v.viewmatrix = viewmatrix; v.projmatrix = projmatrix; v.campos = campos;
-    v.W = W; v.H = H; v.tan_fovx = tan_fovx; v.tan_fovy = tan_fovy; v.radii = radii;
+    const ViewArgs v = view_args(P, D, M, means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp,
+                                 viewmatrix, projmatrix, campos, W, H, tan_fovx, tan_fovy, radii);
     return forward_fused_impl(v, num_channels, need_backward, background, geom_buffer, image_buffer, binning_buffer, binning_capacity,
                               grad_scratch, out_color, num_rendered, max_tile_instances, num_segments, blended, plan_buffer, plan_info,
                               planned, stream);
@@ -757,7 +820,7 @@ int gsr_backward_mt(int P, int D, int M, int R, int num_segments, int num_channe
     hipStream_t st = (hipStream_t)stream;
     ImageState im = carve_image(const_cast<void*>(image_buffer), W, H);
     GeomState g = carve_geom(const_cast<void*>(geom_buffer), P);
-    BinState b = carve_bin(const_cast<void*>(binning_buffer), R > 0 ? R : 0, num_segments > 0 ? num_segments : 0, C);
+    BinState b = carve_bin(const_cast<void*>(binning_buffer), nonneg(R), nonneg(num_segments), C);
     // Zero the packed moment records (the only atomic targets); every output tensor is written outright
     // by geom_bwd (cf. the nine zeroed tensors of rasterize_points.cu:151-159).
     float* grad_acc = static_cast<float*>(grad_scratch);
@@ -765,24 +828,19 @@ int gsr_backward_mt(int P, int D, int M, int R, int num_segments, int num_channe
         Scope sc(ST_ZERO_FILL, st);
         GSR_CHECK(hipMemsetAsync(grad_acc, 0, gsr_grad_scratch_bytes(P), st));
     }
-    const float* feats = colors_precomp ? colors_precomp : g.rgb;
     if (R > 0) {
         {
             Scope sc(ST_BLEND_BWD, st);
-            launch_blend_bwd(C, W, H, num_segments, background, feats, g, im, b, dL_dpix, grad_acc, st);
+            launch_blend_bwd(C, W, H, num_segments, background, features_of(colors_precomp, g), g, im, b, dL_dpix, grad_acc, st);
         }
         GSR_CHECK_LAUNCH("blend_bwd_kernel");
     }
     {
         Scope sc(ST_GEOM_BWD, st);
-        ViewArgs v;
-        v.P = P; v.D = D; v.M = M;
-        v.means3D = means3D; v.shs = shs; v.colors_precomp = colors_precomp; v.opacities = nullptr;
-        v.scales = cov3D_precomp ? nullptr : scales; v.scale_modifier = scale_modifier;
-        v.rotations = cov3D_precomp ? nullptr : rotations; v.cov3D_precomp = cov3D_precomp;
-        v.viewmatrix = viewmatrix; v.projmatrix = projmatrix; v.campos = campos;
-        v.W = W; v.H = H; v.tan_fovx = tan_fovx; v.tan_fovy = tan_fovy;
-        v.radii = const_cast<int*>(radii);   // (the backward only reads them)
+        // (no opacities, and no scales / rotations under cov3D_precomp: launch_geom_bwd; the backward only reads the radii)
+        const ViewArgs v = view_args(P, D, M, means3D, shs, colors_precomp, nullptr, cov3D_precomp ? nullptr : scales, scale_modifier,
+                                     cov3D_precomp ? nullptr : rotations, cov3D_precomp, viewmatrix, projmatrix, campos, W, H,
+                                     tan_fovx, tan_fovy, const_cast<int*>(radii));
         launch_geom_bwd(v, g, C, grad_acc, dL_dmean2D, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, shs ? dL_dsh : nullptr,
                         cov3D_precomp ? nullptr : dL_dscale, cov3D_precomp ? nullptr : dL_drot, st);
     }
@@ -979,7 +1037,7 @@ int gsr_debug_export(int P, int R, int num_segments, int W, int H, const void* g
         if (n_contrib) GSR_CHECK(hipMemcpyAsync(n_contrib, im.n_contrib, 4 * N, hipMemcpyDeviceToDevice, st));
     }
     if (R > 0 && binning_buffer && point_list) {
-        BinState b = carve_bin(const_cast<void*>(binning_buffer), R, num_segments > 0 ? num_segments : 0);
+        BinState b = carve_bin(const_cast<void*>(binning_buffer), R, nonneg(num_segments));
         GSR_CHECK(hipMemcpyAsync(point_list, b.point_list, 4 * (size_t)R, hipMemcpyDeviceToDevice, st));
     }
     return 0;

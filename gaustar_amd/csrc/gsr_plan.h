@@ -7,7 +7,9 @@
 // move between its visits.  Also home of the wave64 DPP scans
 // the tile-offset scan (gsr_binning.hip) shares with it.
 #pragma once
+#include "../../include/gsr.h"
 #include "gsr_internal.h"
+#include <cstddef>
 #include <type_traits>
 #include <utility>
 
@@ -51,6 +53,15 @@ __device__ __forceinline__ uint32_t wave_max_to_lane63(uint32_t x)
     return v;
 }
 
+// The eight words of a plan's header (PlanState::header, gsr_plan_info::header), as plan_build_block writes them
+enum PlanHeaderWord { PH_VALID = 0, PH_T, PH_R_CAP, PH_U_CAP, PH_MAX_CAP, PH_NONEMPTY, PH_ENTRIES, PH_LONGEST };
+// Where the builder's words lie in PlanJob::host_pad, which points at the header of the caller's gsr_plan_info (include/gsr.h)
+constexpr int PLAN_PAD_SEQ = 8, PLAN_PAD_DIAG = 10;
+static_assert(sizeof(gsr_plan_info) == sizeof(int) * GSR_PLAN_INFO_INTS, "gsr_plan_info is the whole block");
+static_assert(offsetof(gsr_plan_info, arrived) == offsetof(gsr_plan_info, header) + 4 * PLAN_PAD_SEQ, "host_seq lands in `arrived`");
+static_assert(offsetof(gsr_plan_info, diag) == offsetof(gsr_plan_info, header) + 4 * PLAN_PAD_DIAG, "the diagnosis lands in `diag`");
+static_assert(offsetof(gsr_plan_info, header) % 16 == 0, "the header is stored as two uint4");
+
 // What the plan-building workgroup needs (by value in the forward blend's arguments); enabled == 0: no job in this launch.
 struct PlanJob {
     uint32_t enabled;
@@ -60,7 +71,7 @@ struct PlanJob {
     uint32_t* seg_off;
     uint32_t* order;
     uint32_t split_from_word, level;
-    uint32_t* host_pad;      // pinned, device-mapped: header words [0..7], then host_seq at [8]
+    uint32_t* host_pad;      // pinned, device-mapped: &gsr_plan_info::header -- the header's eight words, then host_seq at [PLAN_PAD_SEQ]
     uint32_t host_seq;
     const uint32_t* cursor;  // (a PLANNED view re-plans, round 6) the view's tile counts = its cursors, PLAN_CURSOR_STRIDE words apart,
                              // left standing by the forward blend; nullptr: an exact view, counts from its ranges
@@ -196,14 +207,14 @@ __device__ __forceinline__ void plan_build_block(const PlanJob& job, const uint2
         const bool in = t < T;
         const uint32_t cap = !in ? 0u : staged ? cnt_lds[t] >> 16 : cap_of(t);
         const uint32_t incl = wave_incl_scan(cap, lane);
-#ifdef GSR_PLAN_DIAG   // (devtool build) how this view's counts sit in the plan being replaced: host pad words 10 .. 13 =
+#ifdef GSR_PLAN_DIAG   // (devtool build) how this view's counts sit in the plan being replaced: gsr_plan_info::diag =
                        // tiles over a zero bucket, tiles over a non-zero bucket, entries over, the worst count / capacity in 1/64
         if (in && job.host_pad && job.prev_ranges) {
             const uint32_t old = job.prev_ranges[t].y, n = count_of(t);
             if (n > old) {
-                atomicAdd(&job.host_pad[old == 0u ? 10 : 11], 1u);
-                atomicAdd(&job.host_pad[12], n - old);
-                if (old) atomicMax(&job.host_pad[13], n * 64u / old);
+                atomicAdd(&job.host_pad[PLAN_PAD_DIAG + (old == 0u ? 0 : 1)], 1u);
+                atomicAdd(&job.host_pad[PLAN_PAD_DIAG + 2], n - old);
+                if (old) atomicMax(&job.host_pad[PLAN_PAD_DIAG + 3], n * 64u / old);
             }
         }
 #endif
@@ -227,7 +238,7 @@ __device__ __forceinline__ void plan_build_block(const PlanJob& job, const uint2
         if (job.host_pad) {
             reinterpret_cast<uint4*>(job.host_pad)[0] = h0;
             reinterpret_cast<uint4*>(job.host_pad)[1] = h1;
-            __hip_atomic_store(&job.host_pad[8], job.host_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+            __hip_atomic_store(&job.host_pad[PLAN_PAD_SEQ], job.host_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
         }
     }
 }

@@ -104,7 +104,10 @@ def _require_gpu(t: torch.Tensor, what: str):
 # Binding-level functions: same positional signatures as the reference's `_C` module
 # (DGR/rasterize_points.h:17-66), implemented over the C ABI.
 # --------------------------------------------------------------------------------------------
-# device index -> bytes of binning scratch to hand gsr_forward_fused up front (1.25x the largest need seen so far)
+# device index -> bytes of binning scratch to hand gsr_forward_fused up front (_next_hint).  The scratch is sized BEFORE num_rendered
+# is known, from what earlier views on this device needed: the library then goes from the stage-1 read-back straight into the
+# stage-2 launches, and the GPU does not idle while Python allocates and re-enters.  First view, or a guess that turns out too
+# small: blended = 0, and stage 2 runs over an exactly sized buffer (the reference's order of events, rasterize_points.cu:82-112).
 _BINNING_HINT: dict = {}
 _HINT_LOCK = threading.Lock()   # trainer thread + evaluation thread may render on one device
 _FUSED = os.environ.get("GSR_FUSED_FORWARD", "1") != "0"   # 0: always stage 1, allocate exactly, stage 2
@@ -136,23 +139,48 @@ PLAN_STATS = {"planned": 0, "exact": 0, "misfit": 0}            # views binned b
 
 
 class _Plan:
-    """One camera's plan: the device buffer, the pinned plan_info block the library reads and writes (include/gsr.h), and the
-    binding's own bookkeeping (views to render without asking, misfits in a row, views seen while unplannable)."""
-    __slots__ = ("buf", "info", "skip", "misfits", "idle", "_lib")
+    """One camera's plan: the device buffer, the pinned plan_info block the library reads and writes (`info`: the pointer it takes;
+    `pi`: the same memory by field name, _lib.PlanInfo), and the binding's own bookkeeping (views to render without asking, misfits
+    in a row, views seen while unplannable).  `free`: what takes the block back."""
+    __slots__ = ("buf", "info", "pi", "skip", "misfits", "idle", "_free")
 
-    def __init__(self, lib, nbytes, byte_opts, level):
-        self.buf = torch.empty(nbytes, **byte_opts)
-        self.info = lib.gsr_plan_info_new()
-        if not self.info:
-            raise RuntimeError("gsr_plan_info_new failed")
-        self.skip, self.misfits, self.idle, self._lib = 0, 0, 0, lib
-        self.info[4] = level
+    def __init__(self, info, buf=None, free=None, level=0):
+        self.buf, self.info, self._free = buf, info, free
+        self.pi = ctypes.cast(info, ctypes.POINTER(_lib.PlanInfo)).contents
+        self.skip, self.misfits, self.idle = 0, 0, 0
+        self.pi.level = level
 
     def __del__(self):
         try:
-            self._lib.gsr_plan_info_free(self.info)
+            self._free(self.info)
         except Exception:
             pass
+
+    def after_view(self, planned, need_backward=True):
+        """What gsr_forward_planned's `planned` (1 by the plan, 0 exact, -1 outgrew its plan) means for the camera's next views."""
+        pi = self.pi
+        if planned == 1:
+            PLAN_STATS["planned"] += 1
+            self.misfits = 0
+            return
+        PLAN_STATS["exact"] += 1
+        if planned == -1:
+            # the view outgrew its plan (the library has raised the slack level and re-plans).  Misfits in a row -- a close-up whose
+            # workgroups run out of table space misfits under ANY plan -- pause planning for this camera: 2, 4, .. 64 views
+            PLAN_STATS["misfit"] += 1
+            self.misfits += 1
+            if _PLAN_DIAG:    # (devtool: -DGSR_PLAN_DIAG build) how the view sat in the plan it outgrew
+                torch.cuda.synchronize()
+                d = pi.diag
+                print(f"[plan] misfit grad={need_backward} level={pi.level} tiles over empty buckets {d[0]}, over "
+                      f"non-empty {d[1]}, entries over {d[2]}, worst count/capacity {d[3] / 64:.2f}", file=sys.stderr)
+                d[0] = d[1] = d[2] = d[3] = 0
+            if self.misfits >= 2:
+                self.skip = min(64, 1 << (self.misfits - 1))
+        if pi.state == -1:     # unplannable (longest list above the in-kernel sort): ask again after _PLAN_RETRY views
+            self.idle += 1
+            if self.idle >= _PLAN_RETRY:
+                pi.state, self.idle = 0, 0
 
 
 # Plans that left the table while a builder of theirs may still be on its way to their pinned block: (event recorded on the
@@ -175,6 +203,7 @@ def _retire(key, ent):
 
 
 def _plan_entry(key, lib, nbytes, byte_opts, level):
+    """The plan kept under `key`, made anew when there is none or the image size has changed; the oldest leave a full table."""
     with _HINT_LOCK:
         ent = _PLANS.get(key)
         if ent is not None and ent.buf.numel() == nbytes:
@@ -184,7 +213,10 @@ def _plan_entry(key, lib, nbytes, byte_opts, level):
             _PLAN_GRAVE[:] = [(ev, e) for ev, e in _PLAN_GRAVE if ev is None or not ev.query()]
         if ent is not None:
             _retire(key, ent)
-        ent = _Plan(lib, nbytes, byte_opts, level)
+        info = lib.gsr_plan_info_new()
+        if not info:
+            raise RuntimeError("gsr_plan_info_new failed")
+        ent = _Plan(info, torch.empty(nbytes, **byte_opts), lib.gsr_plan_info_free, level)
         _PLANS[key] = ent
         while len(_PLANS) > _PLAN_SLOTS:
             _retire(*_PLANS.popitem(last=False))
@@ -215,7 +247,8 @@ _PENDING = object()
 def _camera_key_begin(lib, vm, dev):
     """First half of _camera_key: -> the key if it is known without the device (a tensor seen before, a host matrix, None for a
     matrix this binding cannot name), or _PENDING with the read launched (gsr_camera_key_begin) -- _camera_key_end then completes
-    it; the caller's own host work in between hides the round trip."""
+    it; the caller's own host work (its allocations) in between hides the round trip.  `vm` is the caller's own tensor, which is
+    final; a .contiguous() copy of it would be a kernel queued on the caller's stream."""
     ent = _CAM_KEYS.get(id(vm))
     if ent is not None and ent[0]() is vm and ent[1] == vm._version and ent[2] == vm.data_ptr():
         CAMERA_KEY_STATS["known_tensor"] += 1
@@ -258,6 +291,60 @@ def _camera_key(lib, vm, dev):
     return _camera_key_end(lib, vm) if k is _PENDING else k
 
 
+def _choose_plan(lib, cam_key, dev, st, W, H, need_backward, tan_fovx, tan_fovy):
+    """-> the _Plan this view of camera `cam_key` is rendered with; None: a camera whose views keep outgrowing their plans, left
+    alone for this view.  A camera's differentiable renders and its forward-only ones -- ground-truth / evaluation sweeps, often of
+    another model -- keep separate plans; the field of view is part of the camera."""
+    key = (dev.index, int(st or 0), W, H, bool(need_backward), float(tan_fovx), float(tan_fovy), cam_key)
+    level = int(_PLAN_LEVEL_ENV) if _PLAN_LEVEL_ENV is not None else (1 if need_backward else 0)
+    plan = _plan_entry(key, lib, int(lib.gsr_plan_bytes(W, H)), dict(dtype=torch.uint8, device=dev), level)
+    if plan.skip > 0:
+        plan.skip -= 1
+        return None
+    return plan
+
+
+def _view_buffers(lib, dev, P, C, W, H, want_scratch):
+    """-> (out_color, radii, geom, img, binning, its size = this device's hint, scratch).  scratch: the backward's accumulation
+    table rides along (callers that will run a backward pass a list as scratch_box) -- the forward blend clears it on the side,
+    and the backward skips its own fill; None without a hint (stage 2 is the caller's then)."""
+    byte_opts = dict(dtype=torch.uint8, device=dev)
+    with _HINT_LOCK:
+        hint = _BINNING_HINT.get(dev.index, 0) if _FUSED else 0
+    return (torch.empty(C, H, W, dtype=torch.float32, device=dev), torch.empty(P, dtype=torch.int32, device=dev),
+            torch.empty(lib.gsr_geom_bytes(P), **byte_opts), torch.empty(lib.gsr_image_bytes(W, H), **byte_opts),
+            torch.empty(hint, **byte_opts), hint,
+            torch.empty(lib.gsr_grad_scratch_bytes(P), **byte_opts) if want_scratch and hint > 0 else None)
+
+
+def _need_bytes(binning_bytes, C, R, nseg, pi=None):
+    """Bytes of binning scratch the next view of this camera may ask for: what this view took and, with a valid plan `pi`, room for
+    the plan's capacities -- and for those of the plan this view's forward blend is building, if its header has landed already.
+    binning_bytes(R, U, C) -> bytes (gsr_binning_bytes_mt)."""
+    need = int(binning_bytes(R, nseg, C))
+    if pi is not None and pi.state == 1:
+        need = max(need, int(binning_bytes(pi.R_cap, pi.U_cap, C)))
+        h = pi.header
+        if pi.pending != 0 and pi.arrived == pi.pending and h[_lib.PH_VALID] == 1 and 0 < h[_lib.PH_R_CAP] < (1 << 30):
+            need = max(need, int(binning_bytes(h[_lib.PH_R_CAP], h[_lib.PH_U_CAP], C)))
+    return need
+
+
+def _next_hint(cur, need):
+    """The binning hint after a view that needed `need` bytes.  It only moves in steps of 32 MB and only comes down when a view
+    needs less than a QUARTER of it (then it halves): every change of the size is a new block for the caching allocator -- a
+    hipMalloc of a few hundred MB costs tens of milliseconds -- and a hint that shrank by 10 % whenever a view needed less than
+    half of it made a rig of near and far cameras oscillate between shrinking and the exact-size fallback (82 ms iterations in the
+    windowed refinement loop).  288 GB of HBM make a generous buffer the cheap side of this trade."""
+    step = 32 << 20
+    grown = (need * 5 // 4 + step - 1) // step * step
+    if need > cur:
+        return grown
+    if need * 4 < cur:
+        return max(grown, (cur // 2 + step - 1) // step * step)
+    return cur
+
+
 def rasterize_gaussians_native(background, means3D, colors, opacity, scales, rotations, scale_modifier,
                                cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height,
                                image_width, sh, degree, campos, prefiltered, debug, need_backward=True,
@@ -272,16 +359,12 @@ def rasterize_gaussians_native(background, means3D, colors, opacity, scales, rot
     dev = means3D.device
     P, H, W = int(means3D.size(0)), int(image_height), int(image_width)
     with _on_device(dev):
-        byte_opts = dict(dtype=torch.uint8, device=dev)
-        if P == 0:
-            # rasterize_points.cu:68-81: zero-filled image, no rasterization at all
+        if P == 0:   # rasterize_points.cu:68-81: zero-filled image, no rasterization at all
+            none = torch.empty(0, dtype=torch.uint8, device=dev)
             return (0, torch.zeros(_num_channels(colors, background), H, W, dtype=torch.float32, device=dev),
-                    torch.zeros(0, dtype=torch.int32, device=dev), torch.empty(0, **byte_opts),
-                    torch.empty(0, **byte_opts), torch.empty(0, **byte_opts), 0, 0)
+                    torch.zeros(0, dtype=torch.int32, device=dev), none, none.clone(), none.clone(), 0, 0)
         means3D = _dev_f32(means3D, dev)
-        # (the camera's identity is read from the caller's own tensor -- the .contiguous() copy below is a kernel queued on the
-        # caller's stream, the caller's tensor is final -- and the read is launched first thing: the allocations below hide it)
-        vm_in = viewmatrix
+        vm_in = viewmatrix   # (the camera's identity is read from the caller's own tensor, first thing: _camera_key_begin)
         want_plan = (_PLANNED if use_plan is None else use_plan) and _FUSED and not debug
         cam_key = plan_key if (plan_key is not None or not want_plan) else _camera_key_begin(lib, vm_in, dev)
         background, viewmatrix, projmatrix, campos = (_dev_f32(x, dev) for x in (background, viewmatrix, projmatrix, campos))
@@ -289,99 +372,35 @@ def rasterize_gaussians_native(background, means3D, colors, opacity, scales, rot
             _dev_f32(x, dev) for x in (colors, opacity, scales, rotations, cov3D_precomp, sh))
         M = int(sh.size(1)) if sh is not None and sh.numel() != 0 else 0
         C = _num_channels(colors, background)
-        out_color = torch.empty(C, H, W, dtype=torch.float32, device=dev)
-        radii = torch.empty(P, dtype=torch.int32, device=dev)
-        geom = torch.empty(lib.gsr_geom_bytes(P), **byte_opts)
-        img = torch.empty(lib.gsr_image_bytes(W, H), **byte_opts)
+        out_color, radii, geom, img, binning, hint, scratch = _view_buffers(lib, dev, P, C, W, H,
+                                                                            need_backward and scratch_box is not None)
         R, maxc, nseg, blended = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
         st = _stream(dev.index)
-        # The binning scratch is sized BEFORE num_rendered is known, from what earlier views on this device needed
-        # (x1.25): the library then goes from the stage-1 read-back straight into the stage-2 launches, and the GPU does
-        # not idle while Python allocates and re-enters.  First view, or a guess that turns out too small: blended = 0,
-        # and stage 2 runs below over an exactly sized buffer (the reference's order of events, rasterize_points.cu:82-112).
-        with _HINT_LOCK:
-            hint = _BINNING_HINT.get(dev.index, 0) if _FUSED else 0
-        binning = torch.empty(hint, **byte_opts)
-        # The backward's accumulation table rides along (callers that will run a backward pass a list as scratch_box):
-        # the forward blend clears it on the side, and the backward skips its own fill.
-        scratch = None
-        if need_backward and scratch_box is not None and hint > 0:
-            scratch = torch.empty(lib.gsr_grad_scratch_bytes(P), **byte_opts)
         head = (P, int(degree), M, C, int(bool(need_backward)), _ptr(means3D), _ptr(sh), _ptr(colors), _ptr(opacity),
                 _ptr(scales), float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp), _ptr(viewmatrix), _ptr(projmatrix),
                 _ptr(campos), W, H, float(tan_fovx), float(tan_fovy), int(bool(prefiltered)), _ptr(background), _ptr(radii),
                 _ptr(geom), _ptr(img), _ptr(binning), hint, _ptr(scratch), _ptr(out_color), ctypes.byref(R),
                 ctypes.byref(maxc), ctypes.byref(nseg), ctypes.byref(blended))
-        plan = None
-        if cam_key is _PENDING:
-            cam_key = _camera_key_end(lib, vm_in)
-        if want_plan:
-            if cam_key is not None:
-                # (a camera's differentiable renders and its forward-only ones -- ground-truth / evaluation sweeps, often of
-                # another model -- keep separate plans; the field of view is part of the camera)
-                key = (dev.index, int(st or 0), W, H, bool(need_backward), float(tan_fovx), float(tan_fovy), cam_key)
-                plan = _plan_entry(key, lib, int(lib.gsr_plan_bytes(W, H)), byte_opts,
-                                   int(_PLAN_LEVEL_ENV) if _PLAN_LEVEL_ENV is not None else (1 if need_backward else 0))
-                if plan.skip > 0:         # (a camera whose views keep outgrowing their plans: left alone for a while)
-                    plan.skip -= 1
-                    plan = None
+        cam_key = _camera_key_end(lib, vm_in) if cam_key is _PENDING else cam_key
+        plan = _choose_plan(lib, cam_key, dev, st, W, H, need_backward, tan_fovx, tan_fovy) if want_plan and cam_key is not None else None
         if plan is None:
             _lib.check(lib.gsr_forward_fused(*head, st), "gsr_forward_fused")
         else:
             planned = ctypes.c_int(0)
-            info = plan.info
-            _lib.check(lib.gsr_forward_planned(*head, _ptr(plan.buf), info, ctypes.byref(planned), st), "gsr_forward_planned")
-            if planned.value == 1:
-                PLAN_STATS["planned"] += 1
-                plan.misfits = 0
-            else:
-                PLAN_STATS["exact"] += 1
-                if planned.value == -1:
-                    # the view outgrew its plan (the library has raised the slack level and re-plans).  Misfits in a row -- a
-                    # close-up whose workgroups run out of table space misfits under ANY plan -- pause planning for this
-                    # camera: 2, 4, .. 64 views
-                    PLAN_STATS["misfit"] += 1
-                    plan.misfits += 1
-                    if _PLAN_DIAG:    # (devtool: -DGSR_PLAN_DIAG build) how the view sat in the plan it outgrew
-                        torch.cuda.synchronize()
-                        print(f"[plan] misfit grad={need_backward} level={info[4]} tiles over empty buckets {info[18]}, over "
-                              f"non-empty {info[19]}, entries over {info[20]}, worst count/capacity {info[21] / 64:.2f}", file=sys.stderr)
-                        info[18] = info[19] = info[20] = info[21] = 0
-                    if plan.misfits >= 2:
-                        plan.skip = min(64, 1 << (plan.misfits - 1))
-                if info[0] == -1:     # unplannable (longest list above the in-kernel sort): ask again after _PLAN_RETRY views
-                    plan.idle += 1
-                    if plan.idle >= _PLAN_RETRY:
-                        info[0], plan.idle = 0, 0
+            _lib.check(lib.gsr_forward_planned(*head, _ptr(plan.buf), plan.info, ctypes.byref(planned), st), "gsr_forward_planned")
+            plan.after_view(planned.value, need_backward)
         if scratch is not None and blended.value:
             scratch_box.append(scratch)   # cleared by the forward blend: good for exactly one backward
-        need = int(lib.gsr_binning_bytes_mt(R.value, nseg.value, C))
-        if plan is not None and plan.info[0] == 1:   # room for the plan's capacities, so that the next view of this camera can use it
-            need = max(need, int(lib.gsr_binning_bytes_mt(plan.info[1], plan.info[2], C)))
-            # (and for the plan this view's forward blend is building for that next view, if its header has landed already:
-            # info[8..15] = the header, [16] / [17] = the builder's sequence number arrived / awaited, include/gsr.h)
-            if plan.info[17] != 0 and plan.info[16] == plan.info[17] and plan.info[8] == 1 and 0 < plan.info[10] < (1 << 30):
-                need = max(need, int(lib.gsr_binning_bytes_mt(plan.info[10], plan.info[11], C)))
-        # The hint only moves in steps of 32 MB and only comes down when a view needs less than a QUARTER of it (then it
-        # halves): every change of the size is a new block for the caching allocator -- a hipMalloc of a few hundred MB costs
-        # tens of milliseconds -- and a hint that shrank by 10 % whenever a view needed less than half of it made a rig of
-        # near and far cameras oscillate between shrinking and the exact-size fallback (82 ms iterations in the windowed
-        # refinement loop).  288 GB of HBM make a generous buffer the cheap side of this trade.
+        need = _need_bytes(lib.gsr_binning_bytes_mt, C, R.value, nseg.value, plan.pi if plan is not None else None)
         if need > hint or need * 4 < hint:
             with _HINT_LOCK:
-                cur = _BINNING_HINT.get(dev.index, 0)
-                step = 32 << 20
-                if need > cur:
-                    _BINNING_HINT[dev.index] = (need * 5 // 4 + step - 1) // step * step
-                elif need * 4 < cur:
-                    _BINNING_HINT[dev.index] = max((need * 5 // 4 + step - 1) // step * step, (cur // 2 + step - 1) // step * step)
+                _BINNING_HINT[dev.index] = _next_hint(_BINNING_HINT.get(dev.index, 0), need)
         if not blended.value:
             # forward-only renders hand stage 2 the NEGATED segment count: no per-segment snapshots are written (gsr.h)
-            nseg2 = nseg.value if need_backward else -nseg.value
-            binning = torch.empty(need, **byte_opts)
+            binning = torch.empty(need, dtype=torch.uint8, device=dev)
             _lib.check(lib.gsr_forward_stage2_mt(
-                P, R.value, maxc.value, nseg2, C, W, H, _ptr(background), _ptr(colors), _ptr(geom), _ptr(binning),
-                _ptr(img), _ptr(out_color), st), "gsr_forward_stage2_mt")
+                P, R.value, maxc.value, nseg.value if need_backward else -nseg.value, C, W, H, _ptr(background), _ptr(colors),
+                _ptr(geom), _ptr(binning), _ptr(img), _ptr(out_color), st), "gsr_forward_stage2_mt")
         if debug:
             torch.cuda.synchronize(dev)   # surface asynchronous faults here, like CHECK_CUDA(..., debug)
     return R.value, out_color, radii, geom, binning, img, maxc.value, (nseg.value if need_backward else 0)

@@ -120,12 +120,12 @@ int gsr_forward_fused(int P, int D, int M, int num_channels, int need_backward, 
 
 /* PLANNED forward (ABI 13): gsr_forward_fused for a camera that is rendered again and again (a training rig: every camera
  * once per epoch, gaustar_trainers/refine.py:534-548).  The caller keeps, per camera, a device buffer of gsr_plan_bytes(W, H)
- * bytes (ABI 16: room for TWO plans -- the one in use and the one being built for the next view) and a plan_info block from gsr_plan_info_new() = {state, R_cap, U_cap, max_cap, slack level, ...} (all zero at first).  A call with plan_info[0] == 0
+ * bytes (ABI 16: room for TWO plans -- the one in use and the one being built for the next view) and a plan_info block from gsr_plan_info_new() = a gsr_plan_info (below; all zero at first).  A call with state == 0
  * renders the exact way (as gsr_forward_fused) and leaves a PLAN behind (built by one extra workgroup of that view's forward
  * blend; nobody waits for it: the next call with this plan_info adopts it): per tile the place and capacity of its bucket of
  * instances (this view's count + (1/8 of it, at least 16, + 1/8 of what the largest of the tile's eight neighbours holds more -- the
  * tiles that outgrow a bucket are the few on the surface's silhouette, whose counts jump when it moves a few pixels their way) times
- * 2^level, rounded up to whole 64-entry units), the tile's first unit and a launch order; plan_info is updated.  A call with plan_info[0] == 1 bins BY THE PLAN: preprocess claims bucket slots and writes the
+ * 2^level, rounded up to whole 64-entry units), the tile's first unit and a launch order; plan_info is updated.  A call with state == 1 bins BY THE PLAN: preprocess claims bucket slots and writes the
  * sort keys itself, the forward blend is queued right behind it, and the host only waits for preprocess's verdict -- no
  * tile-offset scan, no scatter pass and no host round trip between the stages; (ABI 16) such a view also RE-PLANS: the same extra
  * workgroup rides in its forward blend and builds the next view's plan from this view's own tile counts into the other half of the
@@ -140,15 +140,31 @@ int gsr_forward_fused(int P, int D, int M, int num_channels, int need_backward, 
  * the same sorted list; only where it lies differs).  A view that does not fit its plan (a bucket overflows: the Gaussians
  * have moved since the plan was made) is detected by preprocess before anything is blended; the same call then renders it the
  * exact way and re-plans with the slack level raised by one, at most 3 (*planned = -1; 0: no plan was tried).  Only views whose longest list stays within the forward blend's own sort (2 048
- * entries incl. slack) and that would not be split are planned (plan_info[0] stays 0 otherwise).  A plan is a HINT: any plan of
+ * entries incl. slack) and that would not be split are planned (state stays 0 otherwise).  A plan is a HINT: any plan of
  * the right image size is safe for any view -- a bad one costs the fallback, never a wrong pixel.  Needs the library's
  * per-stream counter block (gsr_forward_fused's), otherwise exact.  All other arguments as gsr_forward_fused. */
 #define GSR_PLAN_INFO_INTS 32
 size_t gsr_plan_bytes(int W, int H);
 /* A plan_info block: GSR_PLAN_INFO_INTS ints of pinned, device-mapped host memory, zeroed (the builder of a plan writes its
- * header there from the device; ordinary host memory will not do).  [0] state: 0 no plan, 1 valid, -1 this camera's views cannot
- * be planned (reset to 0 to have the next view try again); [1..3] R_cap, U_cap, max_cap of a valid plan; [4] slack level
- * (0..3); the rest belongs to the library ([5] / [6]: the half of the plan buffer in use / being written, [8..17] the arriving header).  Free with gsr_plan_info_free once no call using it is in flight. */
+ * header there from the device; ordinary host memory will not do), laid out as this struct.  The caller reads and writes the
+ * first five fields; the rest belongs to the library.  Free with gsr_plan_info_free once no call using it is in flight. */
+typedef struct gsr_plan_info {
+    int state;         /* 0 no plan, 1 valid, -1 this camera's views cannot be planned (reset to 0 to have the next view try again) */
+    int R_cap;         /* of a valid plan: entries, */
+    int U_cap;         /*   64-entry units (R_cap / 64) */
+    int max_cap;       /*   and the largest bucket */
+    int level;         /* slack level (0..3) */
+    int half;          /* the half of the plan buffer in use */
+    int pending_half;  /*   and the one the builder on its way writes */
+    int reserved0;
+    int header[8];     /* of the arriving plan, as its builder wrote it: valid, T, R_cap, U_cap, max_cap, non-empty tiles, entries,
+                        * longest list of its source view */
+    int arrived;       /* the builder's sequence number, written behind the header */
+    int pending;       /* the sequence number the host expects there (0: no plan under way) */
+    int diag[4];       /* (GSR_PLAN_DIAG builds) how a view sat in the plan it replaces: tiles over an empty bucket, over a non-empty
+                        * one, entries over, worst count / capacity in 1/64 */
+    int reserved1[10];
+} gsr_plan_info;
 int* gsr_plan_info_new(void);
 void gsr_plan_info_free(int* plan_info);
 int gsr_forward_planned(int P, int D, int M, int num_channels, int need_backward, const float* means3D, const float* shs,

@@ -395,3 +395,41 @@ def test_camera_key_is_a_function_of_the_contents():
     a.copy_(_t(cams[1].viewmatrix, dev))     # written in place: the version counter moves, the contents are read again
     k2 = rz._camera_key(lib, a, dev)
     assert k2 != k0 and k2 == rz._camera_key(lib, _t(cams[1].viewmatrix, dev), dev)
+
+
+def test_plan_info_fields_name_what_the_library_does():
+    """The smallest view a plan exists for -- 64 x 64 pixels = 16 tiles, 500 Gaussians -- three times on one stream: the fields of
+    the plan_info block (_lib.PlanInfo, include/gsr.h gsr_plan_info) hold what the calls return and what the device wrote."""
+    from gaustar_amd import _lib, scene
+    from gaustar_amd import rasterizer as rz
+    dev = torch.device("cuda:0")
+    gs = scene.random_gaussians(500, np.random.default_rng(3))
+    cam = scene.look_at_camera((0.0, 0.0, -4.0), (0.0, 0.0, 0.0), 64, 64, fovx=0.9, znear=0.01)
+    ps, cam_t, bg_t, _ = _inputs(dev, gs, cam, np.zeros(3, np.float32))
+    e = torch.Tensor([])
+
+    def view(**kw):
+        before = rz.PLAN_STATS["planned"]
+        out = rz.rasterize_gaussians_native(bg_t, ps["means3D"], ps["colors"], ps["opacities"], ps["scales"], ps["rotations"], 1.0, e,
+                                            cam_t["view"], cam_t["proj"], cam.tanfovx, cam.tanfovy, cam.H, cam.W, e, 0, cam_t["campos"],
+                                            False, False, **kw)
+        torch.cuda.synchronize(dev)
+        return out, rz.PLAN_STATS["planned"] - before
+
+    rz.drop_plans()
+    # (not a view of the camera's plan: it gives the device a binning hint -- without one a first view leaves stage 2, and with it
+    # the plan, to the caller)
+    view(use_plan=False)
+    assert not rz._PLANS
+    first, planned = view()
+    assert planned == 0 and len(rz._PLANS) == 1
+    pi = next(iter(rz._PLANS.values())).pi
+    assert first[0] > 0 and pi.state == 0 and pi.pending != 0 and pi.arrived == pi.pending   # exact, and its plan has landed
+    for _ in range(2):
+        (R, color, _radii, _geom, _bin, _img, maxc, nseg), planned = view()
+        assert planned == 1 and pi.state == 1
+        assert (R, nseg, maxc) == (pi.R_cap, pi.U_cap, pi.max_cap)
+        assert pi.U_cap * 64 == pi.R_cap >= first[0]
+        assert pi.header[_lib.PH_T] == pi.header[1] == 16
+        assert pi.arrived == pi.pending or pi.pending == 0
+        assert torch.equal(color, first[1])
