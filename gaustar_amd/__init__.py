@@ -8,9 +8,12 @@ synthetic cameras / mesh-bound Gaussians used by tests and bench.py; `dist` is t
 gradient all-reduce.  Either side of the rasterizer: `producers` (SH -> RGB, mesh-bound
 means / scales / quaternions), `losses` (l1 + dssim, masked depth L1, surface-mesh regularisers), `meshes` (single-mesh
 stand-ins for pytorch3d's `Meshes` / `mesh_normal_consistency`), `sweep` (forward-only camera sweeps),
-`mesh_depth` (a mesh's depth maps, masks and visible faces over the rig: the inputs of a tracked sequence) and
+`mesh_depth` (a mesh's depth maps, masks and visible faces over the rig: the inputs of a tracked sequence),
+`tracking` (points followed on the surface through topology updates: SurfaceTracker, track_faces) and
 `formats` (cameras.json, 3DGS PLY, SuGaR .pt, OBJ, grey PNG) -- import them as submodules.
 """
 from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, rasterize_gaussians  # noqa: F401
+from .tracking import RebindStats, SurfaceTracker, bind_points, track_faces  # noqa: F401
 
-__all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians"]
+__all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "RebindStats", "SurfaceTracker",
+           "bind_points", "track_faces"]

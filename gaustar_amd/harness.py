@@ -508,6 +508,11 @@ class SurfaceGaussians(nn.Module):
         return mesh_depth.mesh_depth_view(self._points.detach(), self._surface_mesh_faces, rig["extrinsics"][0], rig["intrinsics"][0],
                                           H, W, **kw)
 
+    def track(self, tracker):
+        """Where a tracking.SurfaceTracker's points sit on the model's own mesh (tracking_util.py:70): tracker.positions(vertices,
+        faces) -> [K,3] f64, the f32 vertices widened."""
+        return tracker.positions(self._points.detach(), self._surface_mesh_faces)
+
     def extract_mesh_fusion(self, cameras, **kw):
         """The surface the renders of `cameras` (and of the 60 sampled cameras around them) agree on, by TSDF fusion and
         marching cubes (refined_mesh.py:311-459): fusion.fuse_mesh(self, cameras, **kw) -> fusion.FusionMesh."""

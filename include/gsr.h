@@ -805,6 +805,59 @@ int gsr_handover_sh_dc(int F, int G, int V, const int* faces, const float* color
 int gsr_handover_gather(int n, const int* origin, int Fb, const unsigned char* base_rgba, int Ff, int Vf, const int* fusion_faces,
                         const float* fusion_colors, int stride, unsigned char* rgba, int* err, gsr_stream_t stream);
 
+/* ---- Points followed on the surface from frame to frame: tracking_face (gaustar_tools/tracking_util.py:34-148) and the binding
+ * step of find_face_of_tags (:20-27): gaustar_amd.tracking.  Conventions as for gsr_stitch_* and gsr_splice_*: device pointers,
+ * asynchronous on `stream`, no host synchronisation, no float atomics, no scratch, every output an integer or a float defined
+ * operation by operation.  All arithmetic is float64 without contraction: verts [V,3] f64, faces [F,3] int32, ids [K] int32,
+ * bary [K,3] f64, pos [K,3] f64.  err [1] int32 (zero before): bit 0 = an id, a rank, a list entry or a face's vertex index
+ * outside its array; bit 1 = a vertex or position coordinate that is not finite; bit 3 = a re-bound barycentric that is not
+ * >= 0 (the reference's `assert np.all(face_bary >= 0)`, :125: a degenerate nearest face).  An element err speaks of is left out:
+ * its float outputs are NaN, its id is unchanged (0 from gsr_track_rebind_displaced).
+ * Definitions (tests/tracking_ref.py restates them in numpy).
+ *   dot(a,b) = (a.x b.x + a.y b.y) + a.z b.z.
+ *   bary_to_point(t0,t1,t2,b): per coordinate (b0 t0 + b1 t1) + b2 t2 -- trimesh's barycentric_to_points,
+ *     (triangles * b[:, :, None]).sum(axis=1).
+ *   point_to_bary(t0,t1,t2,p), the "cramer" method: e0 = t1 - t0, e1 = t2 - t0, w = p - t0; d00 = dot(e0,e0), d01 = dot(e0,e1),
+ *     d02 = dot(e0,w), d11 = dot(e1,e1), d12 = dot(e1,w); inv = 1.0 / (d00 d11 - d01 d01); b2 = (d00 d12 - d01 d02) inv;
+ *     b1 = (d11 d02 - d01 d12) inv; b0 = (1 - b1) - b2.  This is the project's statement of trimesh's points_to_barycentric:
+ *     trimesh forms its dots through a BLAS product whose order is not defined, and trimesh is not among this project's
+ *     dependencies, so parity with it is not pinned by a test.
+ *   centre(f) = ((t0 + t1) + t2) / 3.0 per coordinate -- np.average(verts[faces], axis=-2) (:87).
+ *   nearest(p): with dx = p.x - centre_j.x (dy, dz alike) and s_j = sqrt((dx dx + dy dy) + dz dz), the lowest j among those
+ *     with the smallest s_j -- np.argmin(np.linalg.norm(p - centres, axis=-1)) (:110-112).  The comparison is on the ROUNDED
+ *     square root, as numpy's is: two different squared distances can share a square root, and then the lower index wins even
+ *     if its squared distance is the larger one.
+ * gsr_track_nn_tile / _nn_queries: the centres staged in LDS at once and the queries of a workgroup (for the tests).
+ * gsr_track_positions: pos[k] = bary_to_point(verts[faces[ids[k]]], bary[k]) (:70).
+ * gsr_track_centres: centres [F,3] f64 = centre(f).
+ * gsr_track_rebind_survivors: mask [F0] uint8 = track_face_mask, rank [F0] int32 = its EXCLUSIVE scan (np.sum(mask[:i]), :94),
+ *   new mesh of F1 faces over V1 vertices.  For point k with mask[ids[k]]: j = rank[ids[k]], nb = point_to_bary(new face j,
+ *   pos[k]); if all three components are >= 0 (NaN fails, as in numpy) ids[k] = j, bary[k] = nb, in place (:102-107).  flag [K]
+ *   int32 = 1 for every other point, and for a point whose face did not survive.  stats [3] int32 (cleared by the call):
+ *   points kept / moved off their face / lost, by integer atomics.
+ * gsr_track_todo: flag_scan = the INCLUSIVE scan of flag.  todo = the flagged k, ascending; n_todo [1] int32 = their number.
+ * gsr_track_nearest: idx [slot] int32 = nearest(queries[k]) over centres [F1,3], F1 > 0, for slot < n = min(K, *n_live) (K where
+ *   n_live == NULL) and k = list[slot] (slot where list == NULL).  The grid is sized for K; its surplus workgroups exit on
+ *   *n_live, so there is no host read between the passes.  A square root per pair (csrc/gsr_track.hip's header says why).
+ * gsr_track_rebind_displaced: for slot < n and k as above, j = idx[slot]: ids[k] = j, bary[k] = nb = point_to_bary(new face j,
+ *   pos[k]) (:115-117; with list == NULL and clamp == 0 this is find_face_of_tags' :24-27, unclamped as the reference leaves it).
+ *   clamp != 0: if any component is < 0, a component < 0 becomes 0 and nb = nb / ((nb0 + nb1) + nb2) (:118-120); a component
+ *   that is then still not >= 0 sets err bit 3. */
+int gsr_track_nn_tile(void);
+int gsr_track_nn_queries(void);
+int gsr_track_positions(int K, int F, int V, const int* faces, const double* verts, const int* ids, const double* bary, double* pos,
+                        int* err, gsr_stream_t stream);
+int gsr_track_centres(int F, int V, const int* faces, const double* verts, double* centres, int* err, gsr_stream_t stream);
+int gsr_track_rebind_survivors(int K, int F0, int F1, int V1, const unsigned char* mask, const int* rank, const int* new_faces,
+                               const double* new_verts, const double* pos, int* ids, double* bary, int* flag, int* stats, int* err,
+                               gsr_stream_t stream);
+int gsr_track_todo(int K, const int* flag, const int* flag_scan, int* todo, int* n_todo, gsr_stream_t stream);
+int gsr_track_nearest(int K, const int* list, const int* n_live, int F1, const double* queries, const double* centres, int* idx,
+                      gsr_stream_t stream);
+int gsr_track_rebind_displaced(int K, const int* list, const int* n_live, const int* idx, int F1, int V1, const int* new_faces,
+                               const double* new_verts, const double* pos, int* ids, double* bary, int clamp, int* err,
+                               gsr_stream_t stream);
+
 /* Tuning aid: when device_buffer is non-NULL (4*T uint64), the two blend kernels record the start/end wall
  * clock (100 MHz) of every workgroup: forward at [2*b], backward at [2*(T+b)], b = launch index.  NULL = off. */
 int gsr_debug_set_trace(void* device_buffer);
