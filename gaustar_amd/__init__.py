@@ -9,7 +9,8 @@ gradient all-reduce.  Either side of the rasterizer: `pro
 means / scales / quaternions), `losses` (l1 + dssim, masked depth L1, surface-mesh regularisers), `meshes` (single-mesh
 stand-ins for pytorch3d's `Meshes` / `mesh_normal_consistency`), `sweep` (forward-only camera sweeps),
 `mesh_depth` (a mesh's depth maps, masks and visible faces over the rig: the inputs of a tracked sequence),
-`tracking` (points followed on the surface through topology updates: SurfaceTracker, track_faces) and
+`tracking` (points followed on the surface through topology updates: SurfaceTracker, track_faces),
+`evaluate` (how good a result is: point-to-mesh distance, Chamfer distance and F-score of two meshes, PSNR and SSIM of renders) and
 `formats` (cameras.json, 3DGS PLY, SuGaR .pt, OBJ, grey PNG) -- import them as submodules.
 """
 from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, rasterize_gaussians  # noqa: F401

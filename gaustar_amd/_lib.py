@@ -208,6 +208,21 @@ SIGNATURES = {
     "gsr_track_nearest": (c_int, [c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gsr_track_rebind_displaced": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                            c_void_p, c_int, c_void_p, c_void_p]),
+    # scoring a result: point-to-mesh distance, surface samples, distance statistics, image SSE: gaustar_amd.evaluate; the
+    # err word has the mesh kernels' bits and bit 3 = sampling weights that are not usable
+    "gsr_eval_tile": (c_int, []),
+    "gsr_eval_queries": (c_int, []),
+    "gsr_eval_max_thresholds": (c_int, []),
+    "gsr_eval_workspace_bytes": (c_size_t, []),
+    "gsr_eval_gather": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gsr_eval_closest": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_void_p]),
+    "gsr_eval_areas": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gsr_eval_sample": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, ctypes.c_ulonglong, c_void_p, c_void_p, c_void_p,
+                                c_void_p, c_void_p]),
+    "gsr_eval_distance_stats": (c_int, [c_longlong, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gsr_eval_image_sse": (c_int, [c_int, c_int, c_int, c_void_p, c_longlong, c_longlong, c_longlong, c_void_p, c_longlong,
+                                   c_longlong, c_longlong, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "gsr_adam_step": (c_int, [c_longlong, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_double, c_double, c_int,
                               c_void_p]),
     "gsr_adam_step_multi": (c_int, [c_int, POINTER(c_longlong), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),

@@ -1,5 +1,5 @@
-// gsr_mesh.h -- what the mesh-surgery kernels (gsr_regions.hip, gsr_stitch.hip, gsr_splice.hip, gsr_handover.hip, gsr_track.hip)
-// share.
+// gsr_mesh.h -- what the mesh-surgery kernels (gsr_regions.hip, gsr_stitch.hip, gsr_splice.hip, gsr_handover.hip, gsr_track.hip,
+// gsr_eval.hip) share.
 // Every call of those files that takes `int* err` ORs into one word, which gaustar_amd.regions may pass through calls of
 // several files before its one decoder (regions._raise_if) reads it: the bits are defined here and nowhere else.
 #pragma once
@@ -9,7 +9,8 @@ namespace gsr {
 constexpr int MESH_ERR_INDEX = 1;   // an index outside its array: a face's vertex, a list entry, a face_origin entry
 constexpr int MESH_ERR_NAN = 2;     // a coordinate that is NaN (a region's box) or not finite (a nearest-vertex search)
 constexpr int MESH_ERR_DUP = 4;     // a boundary list names a vertex twice
-constexpr int MESH_ERR_DEGENERATE = 8;   // gsr_track.hip: a re-bound barycentric that is not >= 0 (a degenerate nearest face)
+constexpr int MESH_ERR_DEGENERATE = 8;   // gsr_track.hip: a re-bound barycentric that is not >= 0 (a degenerate nearest face);
+                                         // gsr_eval.hip: sampling weights that are not usable (no face with a positive, finite area)
 constexpr int MESH_BLOCK = 256;     // the workgroup of every one-thread-per-element kernel of these files
 
 inline unsigned mesh_blocks(long long n) { return (unsigned)((n + MESH_BLOCK - 1) / MESH_BLOCK); }

@@ -12,7 +12,8 @@
 //                                                  queries, f64 centres and the rounded square root as the key
 //   rebind, displaced   track_displaced_kernel     the nearest face's barycentrics, clamped and renormalised (:115-121)
 // All arithmetic is float64 without contraction, every operation in the order include/gsr.h states.  No float atomics, no
-// scratch: the counts are integer atomics, the search combines by the lexicographic (key, index) minimum.
+// scratch: the counts are integer atomics, the search combines by the lexicographic (key, index) minimum.  The point type, the dot
+// product, bary_to_point, a face's vertices and that minimum are gsr_surface.h's, shared with gsr_eval.hip.
 //
 // The square root.  numpy's argmin compares sqrt(d2), and two different d2 can share a rounded square root, so the minimum of
 // (d2, index) is not the answer: the search takes the square root of every pair and keeps the (s, index) minimum.  The other
@@ -26,7 +27,7 @@
 // bring back.
 #include "../../include/gsr.h"
 #include "gsr_entry.h"
-#include "gsr_mesh.h"
+#include "gsr_surface.h"
 
 #pragma clang fp contract(off)
 
@@ -35,25 +36,7 @@ namespace gsr {
 namespace {
 
 constexpr int TR_BLOCK = MESH_BLOCK;
-constexpr int TNN_BLOCK = 256;      // four waves
-constexpr int TNN_QUERIES = 16;     // queries of a workgroup: lane & 15 of every wave
-constexpr int TNN_SLICES = 16;      // shares of a tile's centres: 4 waves x (lane >> 4); slice s takes j = s, s + 16, ...
 constexpr int TNN_TILE = 1024;      // centres staged in LDS at once: 3 x 1024 doubles = 24 KiB
-
-struct D3 { double x, y, z; };
-
-__device__ __forceinline__ D3 load3(const double* __restrict__ p, size_t i) { return {p[3 * i], p[3 * i + 1], p[3 * i + 2]}; }
-__device__ __forceinline__ void store3(double* __restrict__ p, size_t i, D3 v) { p[3 * i] = v.x; p[3 * i + 1] = v.y; p[3 * i + 2] = v.z; }
-__device__ __forceinline__ D3 sub3(D3 a, D3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ double dot3(D3 a, D3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-__device__ __forceinline__ bool finite1(double x) { return (x - x) == 0.; }
-__device__ __forceinline__ bool finite3(D3 a) { return finite1(a.x) && finite1(a.y) && finite1(a.z); }
-
-// trimesh's barycentric_to_points: per coordinate (b0 t0 + b1 t1) + b2 t2
-__device__ __forceinline__ D3 bary_to_point(D3 t0, D3 t1, D3 t2, D3 b)
-{
-    return {(b.x * t0.x + b.y * t1.x) + b.z * t2.x, (b.x * t0.y + b.y * t1.y) + b.z * t2.y, (b.x * t0.z + b.y * t1.z) + b.z * t2.z};
-}
 
 // trimesh's points_to_barycentric, method "cramer", as include/gsr.h states it
 __device__ __forceinline__ D3 point_to_bary(D3 t0, D3 t1, D3 t2, D3 p)
@@ -64,17 +47,6 @@ __device__ __forceinline__ D3 point_to_bary(D3 t0, D3 t1, D3 t2, D3 p)
     const double b2 = (d00 * d12 - d01 * d02) * inv;
     const double b1 = (d11 * d02 - d01 * d12) * inv;
     return {(1.0 - b1) - b2, b1, b2};
-}
-
-// the three vertices of face f of a mesh of V vertices; false (and err) when an index is outside or a coordinate not finite
-__device__ __forceinline__ bool face_verts(const int* __restrict__ faces, const double* __restrict__ verts, int f, int V,
-                                           D3& t0, D3& t1, D3& t2, int* __restrict__ err)
-{
-    int v[3];
-    if (!mesh_face(faces, f, V, v)) { atomicOr(err, MESH_ERR_INDEX); return false; }
-    t0 = load3(verts, (size_t)v[0]); t1 = load3(verts, (size_t)v[1]); t2 = load3(verts, (size_t)v[2]);
-    if (!(finite3(t0) && finite3(t1) && finite3(t2))) { atomicOr(err, MESH_ERR_NAN); return false; }
-    return true;
 }
 
 __device__ __forceinline__ void wave_count(bool mine, int* __restrict__ word)
@@ -158,28 +130,6 @@ __global__ void __launch_bounds__(TR_BLOCK) track_todo_kernel(int K, const int* 
     const int s = scan[k];
     if (flag[k] && s >= 1 && s <= K) todo[s - 1] = k;
     if (k == K - 1) *n_todo = s < 0 ? 0 : (s > K ? K : s);
-}
-
-// the lexicographic (key, index) minimum: the same whatever the order the parts are combined in
-__device__ __forceinline__ void tnn_take(double& bd, int& bi, double od, int oi)
-{
-    if (od < bd || (od == bd && oi < bi)) { bd = od; bi = oi; }
-}
-
-// the (key, index) minimum of a query's 16 slices -> lanes < 16 of every wave (lane = the query)
-__device__ __forceinline__ void tnn_combine(double& bd, int& bi, double (*part_d)[TNN_QUERIES], int (*part_i)[TNN_QUERIES])
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int m = 16; m < 64; m <<= 1) {                      // the four slices of this wave
-        const double od = __shfl_xor(bd, m);
-        const int oi = __shfl_xor(bi, m);
-        tnn_take(bd, bi, od, oi);
-    }
-    if (lane < TNN_QUERIES) { part_d[wave][lane] = bd; part_i[wave][lane] = bi; }
-    __syncthreads();
-    if (lane < TNN_QUERIES)
-        for (int w = 0; w < TNN_BLOCK / 64; ++w) tnn_take(bd, bi, part_d[w][lane], part_i[w][lane]);
 }
 
 __device__ __forceinline__ void tnn_stage(double (*tile)[TNN_TILE], const double* __restrict__ c, int base, int n)

@@ -513,6 +513,18 @@ class SurfaceGaussians(nn.Module):
         faces) -> [K,3] f64, the f32 vertices widened."""
         return tracker.positions(self._points.detach(), self._surface_mesh_faces)
 
+    def surface_distance(self, points):
+        """The closest point of the model's own mesh for every point of points [K,3] f64: evaluate.surface_distance(points,
+        vertices, faces) -> evaluate.SurfaceHit, the f32 vertices widened."""
+        from . import evaluate
+        return evaluate.surface_distance(points, self._points.detach(), self._surface_mesh_faces)
+
+    def mesh_distance_to(self, verts, faces, **kw):
+        """The model's own mesh, as the result, against a ground-truth mesh: evaluate.mesh_distance((vertices, faces), (verts,
+        faces), **kw) -> evaluate.MeshDistance (Chamfer distance, precision, recall and F-score)."""
+        from . import evaluate
+        return evaluate.mesh_distance((self._points.detach(), self._surface_mesh_faces), (verts, faces), **kw)
+
     def extract_mesh_fusion(self, cameras, **kw):
         """The surface the renders of `cameras` (and of the 60 sampled cameras around them) agree on, by TSDF fusion and
         marching cubes (refined_mesh.py:311-459): fusion.fuse_mesh(self, cameras, **kw) -> fusion.FusionMesh."""

@@ -192,10 +192,16 @@ class SurfaceTracker:
 
 
 @torch.no_grad()
-def bind_points(verts: torch.Tensor, faces: torch.Tensor, points: torch.Tensor):
+def bind_points(verts: torch.Tensor, faces: torch.Tensor, points: torch.Tensor, exact: bool = False):
     """(face_ids [K] int32, face_bary [K,3] f64) for any points [K,3] f64: per point the face of the nearest centre (np.argmin
     of np.linalg.norm, the lowest index among equals) and point_to_bary on it, UNCLAMPED as find_face_of_tags leaves it
-    (:20-27): a point beside its face has a negative weight.  One host read: the err word."""
+    (:20-27): a point beside its face has a negative weight.  One host read: the err word.
+    exact=True: a true projection instead of the reference's approximation -- the face and the barycentrics (all >= 0) of the
+    closest point of the SURFACE, evaluate.surface_distance's."""
+    if exact:
+        from . import evaluate
+        hit = evaluate.surface_distance(points, verts, faces)
+        return hit.face, hit.bary
     verts, faces = _mesh_f64(verts, faces)
     dev = faces.device
     pts = _points_f64(points, dev, "points")

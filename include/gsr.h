@@ -858,6 +858,81 @@ int gsr_track_rebind_displaced(int K, const int* list, const int* n_live, const 
                                const double* new_verts, const double* pos, int* ids, double* bary, int clamp, int* err,
                                gsr_stream_t stream);
 
+/* ---- Scoring a result: the distance from points to a mesh, surface samples, distance statistics, an image pair's squared
+ * error: gaustar_amd.evaluate.  It takes the place of the reference's scorer (gaussian_splatting/metrics.py,
+ * utils/image_utils.py), which reads PNG directories through torchvision and lpips and has no geometric score; LPIPS is not
+ * offered.  Conventions as for gsr_track_*: device pointers, asynchronous on `stream`, no host synchronisation, no float atomics,
+ * no scratch; verts [V,3] f64, faces [F,3] int32; all geometry is float64 without contraction, in the order written here.  err
+ * [1] int32 (zero before): bit 0 = a face's vertex index or a list entry outside its array; bit 1 = a coordinate that is not
+ * finite, or a query for which no face ranks; bit 3 = the sampling weights are not usable (gaustar_amd.evaluate also sets it
+ * when no face has a positive, finite area).  tests/eval_ref.py restates all of it in numpy.
+ * Definitions.
+ *   dot, bary_to_point: as for gsr_track_*.
+ *   closest(p; a,b,c), the region test of Ericson, Real-Time Collision Detection, 5.1.5, with one reciprocal and no branch:
+ *     ab = b - a, ac = c - a, ap = p - a, bp = p - b, cp = p - c;
+ *     d1 = dot(ab,ap), d2 = dot(ac,ap), d3 = dot(ab,bp), d4 = dot(ac,bp), d5 = dot(ab,cp), d6 = dot(ac,cp);
+ *     vc = d1 d4 - d3 d2, vb = d5 d2 - d1 d6, va = d3 d6 - d5 d4, e = d4 - d3, g = d5 - d6;
+ *     the first that holds gives (nv, nw, den):
+ *       A   d1 <= 0 and d2 <= 0               (0, 0, 1)
+ *       B   d3 >= 0 and d4 <= d3              (1, 0, 1)
+ *       AB  vc <= 0 and d1 >= 0 and d3 <= 0   (d1, 0, d1 - d3)
+ *       C   d6 >= 0 and d5 <= d6              (0, 1, 1)
+ *       AC  vb <= 0 and d2 >= 0 and d6 <= 0   (0, d2, d2 - d6)
+ *       BC  va <= 0 and e >= 0 and g >= 0     (-, e, e + g)
+ *       inside, otherwise                     (vb, vc, (va + vb) + vc)
+ *     r = 1.0 / den; w = nw r; v = nv r, on BC v = 1.0 - w; u = (1.0 - v) - w, and 0 if that is < 0;
+ *     q = a + (ab v + ac w) per coordinate; d = p - q; dist2 = dot(d,d).
+ *     A face of repeated or collinear vertices falls into a vertex or an edge region and gives the distance to that point or
+ *     segment, except where den is 0 (a == b with p beside them): dist2 is then NaN.  A pair whose dist2 is NaN ranks nothing.
+ *   nearest face of p: the lowest j among those with the smallest dist2 -- the lexicographic minimum of (dist2, j).  The
+ *     square root is taken once, of the winner's dist2.
+ *   area(f): u = t1 - t0, w = t2 - t1, c = u x w (each component two rounded products and one subtraction),
+ *     0.5 sqrt((cx cx + cy cy) + cz cz) -- gsr_splice_face_areas' statement on f64 vertices; 0 for a face left out.
+ *   sampling weights (formed by the caller in integers): m = max area = mu 2^e with mu in [0.5, 1); w_f = (int64) floor(area_f
+ *     2^(32-e)), so max w lies in [2^31, 2^32); cum = the inclusive int64 scan of w.
+ *   sample k of n: W = cum[F-1], q = W div n, r = W mod n, t_k = k q + min(k, r) + q div 2; face = the lowest f with cum[f] > t_k
+ *     (a face of weight 0 is never taken, the faces are non-decreasing in k).  z = mix(seed + (k + 1) 0x9E3779B97F4A7C15) mod
+ *     2^64 with mix(z): z = (z ^ (z >> 30)) 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) 0x94D049BB133111EB; z ^ (z >> 31)
+ *     (splitmix64's finaliser).  s = ((z >> 32) + 0.5) 2^-32, t = ((z & 0xffffffff) + 0.5) 2^-32; if s + t > 1: s = 1 - s, t =
+ *     1 - t; bary = ((1 - s) - t, s, t): every step exact, the weights >= 0 and of sum exactly 1.  point = bary_to_point.
+ *   scores (gaustar_amd.evaluate.mesh_distance, A the result, B the ground truth, n samples of each, d_AB the distances of A's
+ *     samples to B): mean = sum d / n, mean of squares = sum d d / n, max; chamfer = mean_AB + mean_BA, chamfer_sq the same of
+ *     the means of squares; per threshold tau: precision = #(d_AB < tau) / n, recall = #(d_BA < tau) / n, fscore = 2 P R / (P
+ *     + R), 0 where P + R = 0.  mse = SSE / count, psnr = 20 log10(1 / sqrt(mse)) in f64 (the reference takes the mean and the
+ *     logarithm in f32).
+ * gsr_eval_tile / _queries / _max_thresholds: the faces staged in LDS at once, the queries of a workgroup, the most thresholds
+ *   of one gsr_eval_distance_stats call.  gsr_eval_workspace_bytes: the workspace of the two reducing calls.
+ * gsr_eval_gather: tri [9,F] f64, row 3 i + k = coordinate k of vertex i of every face; NaN for a face left out.
+ * gsr_eval_closest: slot s < n = min(S, *n_live) (S where n_live == NULL) is query k = list[s] (s where list == NULL) of
+ *   queries [K,3]; a k outside [0, K) sets err bit 0.  Per slot: face [S] int32 = the nearest face over tri (F > 0), bary [S,3]
+ *   = (u, v, w), closest [S,3] = q, dist [S] = sqrt(dist2).  No face ranks: face -1, dist +inf, bary and closest NaN, err bit 1.
+ *   The grid is sized for S; its surplus workgroups exit on *n_live.
+ * gsr_eval_areas: area [F] f64 = area(f).
+ * gsr_eval_sample: cum [F] int64; n > 0 samples: face_ids [n] int32, bary [n,3], points [n,3]; cum[F-1] < n sets err bit 3.
+ * gsr_eval_distance_stats: dist [K] f64 >= 0, thresholds [T], T <= 8.  out, 3 + T words of 64 bits (cleared by the call): f64
+ *   sum d; f64 sum of (d d); the largest d (non-negative doubles order as their bit patterns: an integer max); then per
+ *   threshold the int64 count of d < tau.  The sums by the fixed-order reduction of gsr_splice_mean, the rest by integer atomics:
+ *   the same bits from call to call.
+ * gsr_eval_image_sse: pred, gt [C,H,W] f32 with element strides; mask [H,W] bytes, contiguous, or NULL (a pixel counts where its
+ *   byte is not 0).  Per element p = pred, with clamp01 != 0 p = (pred < 0 ? 0 : pred > 1 ? 1 : pred) (NaN stays NaN, as
+ *   torch.clamp leaves it); e = p - gt and e e in f32, as torch computes (a - b) ** 2; the square widened to f64 and summed in
+ *   that fixed order.  out, 2 words (cleared by the call): f64 SSE, int64 count of elements. */
+int gsr_eval_tile(void);
+int gsr_eval_queries(void);
+int gsr_eval_max_thresholds(void);
+size_t gsr_eval_workspace_bytes(void);
+int gsr_eval_gather(int F, int V, const int* faces, const double* verts, double* tri, int* err, gsr_stream_t stream);
+int gsr_eval_closest(int S, const int* list, const int* n_live, int K, int F, const double* queries, const double* tri, int* face,
+                     double* bary, double* closest, double* dist, int* err, gsr_stream_t stream);
+int gsr_eval_areas(int F, int V, const int* faces, const double* verts, double* area, int* err, gsr_stream_t stream);
+int gsr_eval_sample(int n, int F, int V, const int* faces, const double* verts, const long long* cum, unsigned long long seed,
+                    int* face_ids, double* bary, double* points, int* err, gsr_stream_t stream);
+int gsr_eval_distance_stats(long long K, const double* dist, int T, const double* thresholds, void* workspace, void* out,
+                            gsr_stream_t stream);
+int gsr_eval_image_sse(int C, int H, int W, const float* pred, long long ps0, long long ps1, long long ps2, const float* gt,
+                       long long gs0, long long gs1, long long gs2, const unsigned char* mask, int clamp01, void* workspace, void* out,
+                       gsr_stream_t stream);
+
 /* Tuning aid: when device_buffer is non-NULL (4*T uint64), the two blend kernels record the start/end wall
  * clock (100 MHz) of every workgroup: forward at [2*b], backward at [2*(T+b)], b = launch index.  NULL = off. */
 int gsr_debug_set_trace(void* device_buffer);
