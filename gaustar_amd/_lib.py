@@ -223,6 +223,23 @@ SIGNATURES = {
     "gsr_eval_distance_stats": (c_int, [c_longlong, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gsr_eval_image_sse": (c_int, [c_int, c_int, c_int, c_void_p, c_longlong, c_longlong, c_longlong, c_void_p, c_longlong,
                                    c_longlong, c_longlong, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    # quadric decimation and Laplacian / Taubin smoothing (refined_mesh.py:451-458, cmr_convert.py:262-266): gaustar_amd.remesh;
+    # the err word is the mesh kernels'
+    "gsr_remesh_setup": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gsr_remesh_keys": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gsr_remesh_vertex_quadrics": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gsr_remesh_edge_heads": (c_int, [c_int, c_void_p, c_void_p, c_void_p]),
+    "gsr_remesh_edges": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gsr_remesh_candidates": (c_int, [c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gsr_remesh_select": (c_int, [c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gsr_remesh_cap": (c_int, [c_int, c_int, c_int, POINTER(c_int)]),
+    "gsr_remesh_apply": (c_int, [c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gsr_remesh_apply_attr": (c_int, [c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gsr_remesh_narrow": (c_int, [c_longlong, c_void_p, c_void_p, c_void_p]),
+    "gsr_remesh_smooth": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_double, c_double, c_int, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_void_p]),
     "gsr_adam_step": (c_int, [c_longlong, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_double, c_double, c_int,
                               c_void_p]),
     "gsr_adam_step_multi": (c_int, [c_int, POINTER(c_longlong), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),

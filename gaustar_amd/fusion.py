@@ -23,7 +23,10 @@ Views are integrated in list order (sampled cameras first, then the rig), so the
 renders of the next `views_in_flight - 1` views run ahead on their own streams.  Host synchronisation: the rasterizer's own
 per render, the bounding box once, the two totals of the extraction.
 
-Not implemented (ValueError in the adapter): save_dir (no cv2), smooth, simplify_face_num > 0.
+fuse_mesh(..., smooth_iterations=K, simplify_face_num=N) smooths, then decimates the extracted mesh and its colours as the
+reference does with Open3D (refined_mesh.py:451-458), by gaustar_amd.remesh's rules; both default to 0 = off.
+Not implemented (ValueError in the adapter): save_dir (no cv2); the adapter also keeps refusing smooth and
+simplify_face_num > 0, which the native route (fuse_mesh, SurfaceGaussians.extract_mesh_fusion) offers.
 """
 from __future__ import annotations
 
@@ -462,11 +465,17 @@ _side_streams.cache = {}
 @torch.no_grad()
 def fuse_mesh(model, cameras: Sequence, voxel_size: float = 0.008, sdf_trunc: float = 0.02, depth_trunc: float = 6.0,
               mask_background: bool = True, remove_depth_edge: bool = True, sample_cameras: bool = True, views_in_flight: int = 2,
-              return_volume: bool = False, sample_dist: float = 3.0, sample_look_at_y: float = 1.2) -> FusionMesh:
+              return_volume: bool = False, sample_dist: float = 3.0, sample_look_at_y: float = 1.2, smooth_iterations: int = 0,
+              simplify_face_num: int = 0) -> FusionMesh:
     """extract_mesh_fusion for a harness.SurfaceGaussians `model` seen by `cameras` (NerfCameras): with sample_cameras the 60
     cameras of sample_cam (intrinsics of cameras[0], refined_mesh.py:339-345) come first, then the rig.  Defaults are the
     reference's.  views_in_flight: 1 = everything on the calling stream; n > 1 = the renders and the image preparation of
-    the next n - 1 views run on side streams while a view is integrated (the integration itself stays in list order)."""
+    the next n - 1 views run on side streams while a view is integrated (the integration itself stays in list order).
+    smooth_iterations > 0: that many Laplacian sweeps (remesh.smooth_laplacian, positions only); simplify_face_num > 0: quadric
+    decimation to that many faces (remesh.simplify_mesh, the colours as its attribute); smoothing first, the reference's order
+    (refined_mesh.py:451-458).  Both 0: the extracted mesh as it is."""
+    if int(smooth_iterations) < 0 or int(simplify_face_num) < 0:
+        raise ValueError("smooth_iterations and simplify_face_num must not be negative")
     dev = model.device
     if dev.type != "cuda":
         raise RuntimeError("fuse_mesh needs the model on a GPU")
@@ -526,6 +535,12 @@ def fuse_mesh(model, cameras: Sequence, voxel_size: float = 0.008, sdf_trunc: fl
             main.wait_stream(s)
 
     verts, faces, colors = extract_triangle_mesh(volume)
+    from . import remesh         # (here: remesh imports regions, which nothing else of this module needs)
+    if int(smooth_iterations) > 0 and verts.shape[0]:
+        verts = remesh.smooth_laplacian(verts, faces, iterations=int(smooth_iterations))
+    if int(simplify_face_num) > 0 and faces.shape[0]:
+        small = remesh.simplify_mesh(verts, faces, int(simplify_face_num), attrs=(colors,))
+        verts, faces, colors = small.verts, small.faces, small.attrs[0]
     res = FusionMesh(verts=verts, faces=faces, colors=colors, n_blocks=int(seen.count_nonzero()), n_views=volume.n_views)
     if return_volume:
         res.tsdf, res.weight, res.color, res.origin, res.dims = volume.tsdf, volume.weight, volume.color, volume.origin, volume.dims
@@ -538,7 +553,9 @@ def extract_mesh_fusion(refined_sugar, nerfmodel, voxel_size=0.008, sdf_trunc=0.
     returns a FusionMesh where the reference returns an open3d mesh.  `refined_sugar` is a harness.SurfaceGaussians;
     `nerfmodel` needs its camera list as `cameras` (harness.NerfCamera).  Raises ValueError for what is not implemented:
     save_dir (the reference's debug images need cv2), smooth (Laplacian smoothing; the reference's call passes False) and
-    simplify_face_num > 0 (quadric decimation)."""
+    simplify_face_num > 0 (quadric decimation).  The native route offers both: fuse_mesh(..., smooth_iterations=K,
+    simplify_face_num=N) and SurfaceGaussians.extract_mesh_fusion(cameras, ...), by gaustar_amd.remesh's rules, whose parity
+    with Open3D is not pinned -- which is why this adapter, the reference's signature, keeps refusing them."""
     if save_dir:
         raise ValueError("extract_mesh_fusion: save_dir is not implemented (no image writer)")
     if smooth:

@@ -527,7 +527,8 @@ class SurfaceGaussians(nn.Module):
 
     def extract_mesh_fusion(self, cameras, **kw):
         """The surface the renders of `cameras` (and of the 60 sampled cameras around them) agree on, by TSDF fusion and
-        marching cubes (refined_mesh.py:311-459): fusion.fuse_mesh(self, cameras, **kw) -> fusion.FusionMesh."""
+        marching cubes (refined_mesh.py:311-459): fusion.fuse_mesh(self, cameras, **kw) -> fusion.FusionMesh.  smooth_iterations=K
+        and simplify_face_num=N smooth and decimate it (refined_mesh.py:451-458, gaustar_amd.remesh)."""
         from . import fusion
         return fusion.fuse_mesh(self, cameras, **kw)
 

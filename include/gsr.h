@@ -933,6 +933,67 @@ int gsr_eval_image_sse(int C, int H, int W, const float* pred, long long ps0, lo
                        long long gs0, long long gs1, long long gs2, const unsigned char* mask, int clamp01, void* workspace, void* out,
                        gsr_stream_t stream);
 
+/* ---- Quadric mesh decimation and Laplacian / Taubin smoothing: extract_mesh_fusion's `simplify_face_num` and `smooth`
+ * (gaustar_trainers/refined_mesh.py:451-458, Open3D's simplify_quadric_decimation and filter_smooth_laplacian), the Taubin filter
+ * of the reference's tools (gaustar_tools/internal_use_tools/fusion_depth.py:80-84) and the decimation that makes a sequence's
+ * init_mesh_100k.obj (gaustar_tools/cmr_convert.py:262-266, pyfqmr's simplify_mesh): gaustar_amd.remesh, which states the rules
+ * and the departures from those libraries.  This is the project's own round-based parallel statement of Garland-Heckbert
+ * decimation; parity with Open3D or pyfqmr is not pinned.  Conventions as for gsr_regions_*: device pointers unless marked
+ * [host], asynchronous on `stream`, no host synchronisation, no float atomics; geometry in f64 without contraction, every sum in
+ * one stated order.  err [1] int32 (zero before): bit 0 = a face with a vertex index outside [0, V); such a face is not live.
+ * All keys are int64, not negative, 2^63 - 1 where there is none.
+ * gsr_remesh_setup: verts [V,3] f32, faces [F,3] int32 -> pos [V,3] f64 (widened), live [F] int32 (1 / 0), face_quadric [F,10]
+ *   f64 = A p p^T for p = (n / |n|, -(n / |n|) . x0), n = (x1 - x0) x (x2 - x0), A = |n| / 2, as aa ab ac ad bb bc bd cc cd dd;
+ *   zeros where |n| is not > 0.
+ * gsr_remesh_keys: per live face-edge (a, b), (b, c), (c, a) edge_keys [3 F] = min << 32 | max; per live corner corner_keys
+ *   [3 F] = vertex 3F + (3 face + corner); degree [V] int32 (cleared by the call) = the live corners of every vertex.  With the
+ *   sorted corner keys and offsets = the exclusive scan of degree [V + 1], vertex v's faces are corners[offsets[v] ..
+ *   offsets[v + 1]) in ascending face order (MeshTopology.vertex_face_csr's order): `vf_offsets`, `corners` below.
+ * gsr_remesh_vertex_quadrics: quadric [V,10] = the sum of face_quadric over the vertex's list in that order, from 0.
+ * gsr_remesh_edge_heads: head [n] int32 = 1 at the first of every run of equal sorted keys (n = 3 live faces: the rest of the
+ *   sorted array holds no key).  With head_scan its inclusive scan an edge's id is head_scan - 1 and head_scan[n - 1] the number
+ *   of edges (`n_edges` below, read on the device).
+ * gsr_remesh_edges: edge_verts [n,2] int32 (u < v), manifold [n] uint8 = exactly two face-edges of two different faces have the
+ *   edge; fixed [V] uint8 (the caller's locked mask before) gets 1 at both ends of every edge that is not manifold.
+ * gsr_remesh_candidates: key [cap] = f32(cost) bits << 32 | edge id where the edge is a candidate (both ends free, manifold,
+ *   link condition, a finite f32 cost, no face turned over or flattened), placement [cap,3] f64 = where the merged vertex goes.
+ *   With Q = Q_u + Q_v: Cramer's rule on the 3x3 (cofactors along the first row) where |det| > 1e-10 s^3, s = the largest
+ *   |entry|; else the cheapest of P_u, P_v, 0.5 (P_u + P_v), the earlier on ties.  cost = max(x^T Q x, 0).
+ * gsr_remesh_select: m1, m2 [V] int64 scratch.  m1[v] = min key over the candidate edges at v; m2[v] = min over ALL edges
+ *   (v, w) of min(m1[v], m1[w]); selected [cap] = key where m2[u] == m2[v] == key: no face touches two selected edges.
+ * gsr_remesh_cap: [host] n_apply = min(n_selected, (live_faces - target_faces + 1) / 2), 0 where live_faces <= target_faces.
+ * gsr_remesh_apply: for every selected edge with key <= *threshold (the n_apply-th smallest selected key): pos[u] = placement,
+ *   quadric[u] = quadric[u] + quadric[v], the edge's two faces die, v becomes u in v's other faces.
+ * gsr_remesh_apply_attr: attr [V,C] f32, attr[u] = (attr[u] + attr[v]) * 0.5f for the same edges.
+ * gsr_remesh_narrow: out [n] f32 = in [n] f64 rounded to nearest.
+ * gsr_remesh_smooth: verts [V,3] f32 -> out [V,3] f32 after `steps` sweeps in f64, step s with lambda_even / lambda_odd by the
+ *   parity of s (Laplacian: both lambda; Taubin: lambda, mu).  new = prev + lambda (sum w_n prev_n / sum w_n - prev) over the
+ *   neighbours in list order, w_n = 1 / (|prev - prev_n| + 1e-12) or, with uniform != 0, 1.  A vertex without neighbours or
+ *   with locked[v] (NULL: none) keeps its position.  work_a, work_b [V,3] f64 are scratch. */
+int gsr_remesh_setup(int F, int V, const float* verts, const int* faces, double* pos, int* live, double* face_quadric, int* err,
+                     gsr_stream_t stream);
+int gsr_remesh_keys(int F, int V, const int* faces, const int* live, long long* edge_keys, long long* corner_keys, int* degree,
+                    gsr_stream_t stream);
+int gsr_remesh_vertex_quadrics(int F, int V, const int* vf_offsets, const long long* corners, const double* face_quadric, double* quadric,
+                               gsr_stream_t stream);
+int gsr_remesh_edge_heads(int n, const long long* sorted_keys, int* head, gsr_stream_t stream);
+int gsr_remesh_edges(int n, int V, const long long* sorted_keys, const long long* order, const int* head_scan, int* edge_verts,
+                     unsigned char* manifold, unsigned char* fixed, gsr_stream_t stream);
+int gsr_remesh_candidates(int cap, const int* n_edges, int F, int V, const int* edge_verts, const unsigned char* manifold,
+                          const unsigned char* fixed, const int* vf_offsets, const long long* corners, const int* faces, const double* pos,
+                          const double* quadric, long long* key, double* placement, gsr_stream_t stream);
+int gsr_remesh_select(int cap, const int* n_edges, int V, const int* edge_verts, const long long* key, long long* m1, long long* m2,
+                      long long* selected, gsr_stream_t stream);
+int gsr_remesh_cap(int live_faces, int target_faces, int n_selected, int* n_apply);
+int gsr_remesh_apply(int cap, const int* n_edges, int F, int V, const long long* selected, const long long* threshold, const int* edge_verts,
+                     const double* placement, const int* vf_offsets, const long long* corners, int* faces, int* live, double* pos,
+                     double* quadric, gsr_stream_t stream);
+int gsr_remesh_apply_attr(int cap, const int* n_edges, int V, int C, const long long* selected, const long long* threshold,
+                          const int* edge_verts, float* attr, gsr_stream_t stream);
+int gsr_remesh_narrow(long long n, const double* in, float* out, gsr_stream_t stream);
+int gsr_remesh_smooth(int V, const int* nbr_offsets, const int* nbr, const unsigned char* locked, int steps, double lambda_even,
+                      double lambda_odd, int uniform, const float* verts, double* work_a, double* work_b, float* out, gsr_stream_t stream);
+
 /* Tuning aid: when device_buffer is non-NULL (4*T uint64), the two blend kernels record the start/end wall
  * clock (100 MHz) of every workgroup: forward at [2*b], backward at [2*(T+b)], b = launch index.  NULL = off. */
 int gsr_debug_set_trace(void* device_buffer);
