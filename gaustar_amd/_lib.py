@@ -104,6 +104,12 @@ SIGNATURES = {
                                      c_float, c_float, c_float, c_void_p, c_void_p, c_void_p]),
     "gsr_mesh_reg_backward": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_float, c_float, c_float, c_void_p, c_void_p, c_int, c_void_p]),
+    # mesh Laplacian-smoothing loss and small-area regulariser (refine.py:681-683, :713-718): losses.mesh_smoothness_loss
+    "gsr_mesh_lap_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "gsr_mesh_lap_forward": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float,
+                                     c_float, c_void_p, c_void_p, c_void_p]),
+    "gsr_mesh_lap_backward": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float,
+                                      c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     # regularisers on the Gaussians' own parameters (refine.py:739-748, :663-669): losses.gaussian_param_loss
     "gsr_param_reg_workspace_bytes": (c_size_t, [c_int]),
     "gsr_param_reg_forward": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_longlong, c_longlong, c_float, c_float,

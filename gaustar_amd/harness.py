@@ -793,7 +793,12 @@ class SurfaceGaussians(nn.Module):
         (nc_factor, ref_edge_len, edge_factor, ref_area, area_factor; `topology` defaults to mesh_topology()): their forward
         and backward run in the same step, their vertex gradient is added to the mesh producer's in its own buffer, and the
         returned loss is the image losses + their total -- what `(rgb_depth_loss(...) + surface_mesh_loss(...)).backward()`
-        gives.  None (default): the image losses alone, as before.
+        gives.  None (default): the image losses alone, as before.  The same dict also takes the keyword arguments of
+        losses.mesh_smoothness_loss -- laplacian_factor, laplacian_method ("uniform" by default, "cot" or "cotcurv":
+        refine.py:681-683) and area_reg_factor (refine.py:713-718): when one of the two factors is non-zero their forward runs
+        in the same step, their vertex gradient is added to the same buffer after the other regularisers', and their total is
+        added to the returned loss last -- `(rgb_depth_loss + surface_mesh_loss + mesh_smoothness_loss).backward()`.  Without
+        these keys the step is bit for bit what it was.
         param_reg: the regularisers on the Gaussians' own parameters (refine.py:739-748, :663-669) as the scalar keyword
         arguments of losses.gaussian_param_loss (factor_t, factor_r, min_opacity -- None switches the opacity term off --,
         sh_factor) plus optional `pre_sh_dc` (without it there is no SH term) and `weight` (default: unbind_loss_weight).  The
@@ -814,6 +819,14 @@ class SurfaceGaussians(nn.Module):
                 reg_total, _reg_parts = _losses._SurfaceMeshLoss.forward(
                     mctx, self._points, topo, float(kw.pop("nc_factor")), kw.pop("ref_edge_len", None), float(kw.pop("edge_factor", 0.0)),
                     kw.pop("ref_area", None), float(kw.pop("area_factor", 0.0)))
+                lap_f, lap_m = float(kw.pop("laplacian_factor", 0.0)), kw.pop("laplacian_method", "uniform")
+                areg_f = float(kw.pop("area_reg_factor", 0.0))
+                sctx = None
+                if lap_f != 0.0 or areg_f != 0.0:
+                    if lap_m not in _losses._LAP_METHODS:
+                        raise ValueError("Method should be one of {uniform, cot, cotcurv}")
+                    sctx = _PlainCtx((self._points.requires_grad,) + (False,) * 4)
+                    smooth_total, _smooth_parts = _losses._MeshSmoothnessLoss.forward(sctx, self._points, topo, lap_f, lap_m, areg_f)
                 if kw:
                     raise TypeError(f"mesh_reg: unexpected keys {sorted(kw)}")
             if param_reg is not None:
@@ -843,8 +856,13 @@ class SurfaceGaussians(nn.Module):
                 grad_scale = one
             if mesh_reg is not None:
                 loss = loss + reg_total
-                if mctx.saved_tensors:
-                    cfg["verts_grad_hook"] = lambda dv: _losses._SurfaceMeshLoss.grad_into(mctx, grad_scale, dv, 1)
+                if sctx is not None:
+                    loss = loss + smooth_total
+                nodes = [(_losses._SurfaceMeshLoss, mctx)] if mctx.saved_tensors else []
+                if sctx is not None and sctx.saved_tensors:
+                    nodes.append((_losses._MeshSmoothnessLoss, sctx))
+                if nodes:
+                    cfg["verts_grad_hook"] = lambda dv: [fn.grad_into(c, grad_scale, dv, 1) for fn, c in nodes]
             if param_reg is not None:
                 loss = loss + preg_total
                 if pctx.saved_tensors:

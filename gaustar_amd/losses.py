@@ -368,6 +368,84 @@ def surface_mesh_loss(verts: torch.Tensor, topology, nc_factor: float, ref_edge_
     return (loss, parts) if return_parts else loss
 
 
+_LAP_METHODS = {"uniform": 0, "cot": 1, "cotcurv": 2}
+
+
+class _MeshSmoothnessLoss(torch.autograd.Function):
+    """The Laplacian-smoothing loss of refine.py:681-683 and the small-area regulariser of :713-718 as ONE autograd node over
+    the vertices.  Forward: gsr_mesh_lap_forward -> {laplacian, area_reg, total} on the device, each already multiplied by
+    its factor.  Backward: gsr_mesh_lap_backward, one vertex-major launch over the workspace the forward left, scaled by the
+    incoming gradient on the device."""
+
+    @staticmethod
+    def forward(ctx, verts, topo, laplacian_factor, method, area_reg_factor):
+        if not verts.is_cuda:
+            raise RuntimeError("gaustar_amd.losses: verts must live on a HIP (cuda) device -- there is no CPU path")
+        lib = _lib.load()
+        if verts.dim() != 2 or verts.size(1) != 3 or int(verts.size(0)) != topo.V:
+            raise RuntimeError(f"verts must have dimensions ({topo.V}, 3), got {tuple(verts.shape)}")
+        dev = verts.device
+        if topo.device != dev:
+            raise RuntimeError("the mesh topology lives on another device than the vertices")
+        v = verts.detach()
+        if v.dtype != torch.float32 or not v.is_contiguous():
+            v = v.float().contiguous()
+        cfg = (_LAP_METHODS[method], float(laplacian_factor), float(area_reg_factor))
+        lists = (*topo.vertex_neighbours, *topo.vertex_face_csr)
+        with _host.on_device(dev):
+            ws = torch.empty(lib.gsr_mesh_lap_workspace_bytes(topo.V, topo.F), dtype=torch.uint8, device=dev)
+            out = torch.empty(3, dtype=torch.float32, device=dev)
+            _lib.check(lib.gsr_mesh_lap_forward(
+                topo.V, topo.F, _vp(v), _vp(topo.faces), *[_vp(t) for t in lists], *cfg, _vp(ws), _vp(out), _stream()),
+                "gsr_mesh_lap_forward")
+        ctx.topo, ctx.cfg, ctx.in_dtype = topo, cfg, verts.dtype
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(v, ws)
+        ctx.mark_non_differentiable(out)
+        ctx.set_materialize_grads(False)
+        return out[2], out
+
+    @staticmethod
+    def grad_into(ctx, g_loss, dL_dverts, accumulate):
+        """gsr_mesh_lap_backward into dL_dverts [V,3] f32 (accumulate = 1: added to what is there, one rounding per element)."""
+        lib = _lib.load()
+        v, ws = ctx.saved_tensors
+        topo = ctx.topo
+        dev = v.device
+        if dL_dverts.dtype != torch.float32 or not dL_dverts.is_contiguous() or tuple(dL_dverts.shape) != tuple(v.shape) \
+                or dL_dverts.device != dev:
+            raise RuntimeError(f"dL_dverts must be a contiguous float32 ({topo.V}, 3) tensor on {dev}")
+        lists = (*topo.vertex_neighbours, *topo.vertex_face_csr)
+        with _host.on_device(dev):
+            keep, sp = _scale_ptr(g_loss, dev)
+            _lib.check(lib.gsr_mesh_lap_backward(
+                topo.V, topo.F, _vp(v), _vp(topo.faces), *[_vp(t) for t in lists], *ctx.cfg, _vp(ws), sp, _vp(dL_dverts),
+                int(accumulate), _stream()), "gsr_mesh_lap_backward")
+        return dL_dverts
+
+    @staticmethod
+    def backward(ctx, g_loss, _g_parts):
+        if not ctx.saved_tensors or g_loss is None:
+            return (None,) * 5
+        v = ctx.saved_tensors[0]
+        grad = _MeshSmoothnessLoss.grad_into(ctx, g_loss, torch.empty_like(v), 0)
+        return grad.to(ctx.in_dtype), None, None, None, None
+
+
+def mesh_smoothness_loss(verts: torch.Tensor, topology, laplacian_factor: float = 1.0, method: str = "uniform",
+                         area_reg_factor: float = 0.0, return_parts: bool = False):
+    """laplacian_factor * mesh_laplacian_smoothing(mesh, method) + area_reg_factor * relu(mean_area / face_area - 2).mean()
+    (refine.py:681-683, :713-718; mean_area a constant) on verts [V,3] with the faces of `topology`
+    (gaustar_amd.meshes.MeshTopology).  method: "uniform", "cot" or "cotcurv", as pytorch3d names them; the rules are restated
+    in include/gsr.h (parity with pytorch3d itself is not pinned).  The weights are constants.  A term whose factor is 0 is left
+    out.  A face of area exactly 0 makes the area regulariser +inf and contributes no gradient.  One fused HIP op each way, no
+    host synchronisation, bit-reproducible; parts = the device vector {laplacian, area_reg, total}, each times its factor."""
+    if method not in _LAP_METHODS:
+        raise ValueError("Method should be one of {uniform, cot, cotcurv}")
+    loss, parts = _MeshSmoothnessLoss.apply(verts, topology, float(laplacian_factor), method, float(area_reg_factor))
+    return (loss, parts) if return_parts else loss
+
+
 def _flat_f32(t, dev, n_cols, what):
     """Detached contiguous float32 view (copy only if needed) of a parameter-like tensor holding n_cols floats per Gaussian."""
     if t is None:

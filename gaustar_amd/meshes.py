@@ -1,10 +1,11 @@
 """Surface-mesh side of a refinement iteration (gaustar_trainers/refine.py:676-706) without pytorch3d.
 
-GauSTAR's trainer reads three things of pytorch3d on its mesh: `Meshes(verts=[v], faces=[f])` with `verts_packed`,
-`edges_packed` and `faces_areas_packed`, and `pytorch3d.loss.mesh_normal_consistency`.  This module restates them for ONE
-mesh, so that refine.py:681-706 runs unchanged after swapping two imports:
+GauSTAR's trainer reads four things of pytorch3d on its mesh: `Meshes(verts=[v], faces=[f])` with `verts_packed`,
+`edges_packed` and `faces_areas_packed`, `pytorch3d.loss.mesh_normal_consistency` and
+`pytorch3d.loss.mesh_laplacian_smoothing`.  This module restates them for ONE mesh, so that refine.py:681-706 runs unchanged
+after swapping two imports:
 
-    from gaustar_amd.meshes import Meshes, mesh_normal_consistency
+    from gaustar_amd.meshes import Meshes, mesh_laplacian_smoothing, mesh_normal_consistency
 
 `MeshTopology` holds what depends only on the faces -- pytorch3d's edge order, the face pairs of every edge and a
 vertex-major incidence list -- built once per face tensor with torch operations on its device; the per-iteration work
@@ -171,4 +172,12 @@ def mesh_normal_consistency(meshes: Meshes) -> torch.Tensor:
     return losses.surface_mesh_loss(meshes.verts_packed(), meshes.topology(), 1.0)
 
 
-__all__ = ["MeshTopology", "Meshes", "mesh_normal_consistency"]
+def mesh_laplacian_smoothing(meshes: Meshes, method: str = "uniform") -> torch.Tensor:
+    """pytorch3d.loss.mesh_laplacian_smoothing of one mesh: the mean over the vertices of |L v| with the uniform, cotangent or
+    cotangent-curvature Laplacian (include/gsr.h restates the rules; parity with pytorch3d itself is not pinned), the weights
+    constants.  One fused HIP op each way (losses.mesh_smoothness_loss with only the Laplacian term)."""
+    from . import losses
+    return losses.mesh_smoothness_loss(meshes.verts_packed(), meshes.topology(), 1.0, method)
+
+
+__all__ = ["MeshTopology", "Meshes", "mesh_laplacian_smoothing", "mesh_normal_consistency"]

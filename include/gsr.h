@@ -420,6 +420,43 @@ int gsr_mesh_reg_backward(int V, int F, int E, int Q, const float* verts, const 
                           float nc_factor, float edge_factor, float area_factor, const float* grad_scale, float* dL_dverts,
                           int accumulate, gsr_stream_t stream);
 
+/* ---- Mesh Laplacian-smoothing loss and small-area regulariser of a refinement iteration, fused.  Replaces
+ *   laplacian_factor * pytorch3d.loss.mesh_laplacian_smoothing(mesh, method)                    (refine.py:681-683)
+ * + area_reg_factor * relu(mean_area / Meshes.faces_areas_packed() - 2).mean()                  (refine.py:713-718)
+ * on ONE mesh: verts [V,3] f32, faces [F,3] int32.  The rules restate pytorch3d/loss/mesh_laplacian_smoothing.py and
+ * pytorch3d/ops/laplacian_matrices.py (`laplacian`, `cot_laplacian`; 0.7) from memory of those sources; parity with pytorch3d
+ * itself is not pinned.  The topology comes from the caller (gaustar_amd/meshes.py MeshTopology), int32 and contiguous:
+ *   nbr_offsets [V+1], nbr: every vertex's edge neighbours, ascending (vertex_neighbours);
+ *   vf_offsets [V+1], vf_entries [3F]: every vertex's incidences face * 3 + corner, ascending (vertex_face_csr).
+ * Laplacian loss = (1 / V) sum_i |l_i| (Euclidean norm), N(i) the neighbours of i, method 0 / 1 / 2:
+ *   0 uniform  l_i = (1 / |N(i)|) sum_{j in N(i)} v_j - v_i; a vertex without an edge has l_i = -v_i (pytorch3d's matrix has -1
+ *              on the whole diagonal: such a vertex is pulled to the origin);
+ *   1 cot      per face (a, b, c): A = |v_b - v_c|, B = |v_a - v_c|, C = |v_a - v_b|, s = (A + B + C) / 2,
+ *              area = sqrt(max(s (s-A) (s-B) (s-C), 1e-12)), cot_a = (B^2 + C^2 - A^2) / area / 4 and cyclically; the face adds
+ *              cot_a to w_bc and w_cb, cot_b to w_ca and w_ac, cot_c to w_ab and w_ba.  S_i = sum_j w_ij, n_i = 1 / S_i if
+ *              S_i > 0, otherwise n_i = S_i (pytorch3d leaves a non-positive row sum as it is), l_i = n_i sum_j w_ij v_j - v_i;
+ *   2 cotcurv  a_i = 0.25 / (sum of area over the faces at i) if that sum is > 0, otherwise 0; l_i = a_i (sum_j w_ij v_j - S_i v_i).
+ * The weights are constants (no gradient through the degrees, the cotangents, the areas or the mean area); d|l|/dl = l / |l|,
+ * 0 at l = 0.  Differences, cotangents and per-vertex sums are f64 from the f32 positions, rounded to f32 once at the end.
+ * Area regulariser: area_f = 0.5 |(v_b - v_a) x (v_c - v_a)|, m = mean_f area_f (a constant), mean_f max(m / area_f - 2, 0), f32
+ * with f64 sums.  A face of area exactly 0 makes the value +inf, as the torch composition does; its gradient contribution is
+ * defined as 0 (torch gives NaN).
+ * A term whose factor is 0 is skipped entirely: its passes do not run and its part is 0.
+ * gsr_mesh_lap_forward: loss_out [3] device floats = {laplacian_factor * laplacian, area_reg_factor * area_reg, total};
+ *   workspace: gsr_mesh_lap_workspace_bytes(V, F) bytes, 8-byte aligned; it keeps what the backward reads.  No host
+ *   synchronisation.
+ * gsr_mesh_lap_backward: ONE vertex-major launch over the forward's workspace (unmodified, same arguments): dL_dverts [V,3]
+ *   receives grad_scale[0] * d total / d verts (grad_scale a DEVICE scalar, NULL = 1) -- written, or with accumulate = 1 added
+ *   to what is there with one rounding per element (= torch's X + fresh), as gsr_mesh_reg_backward.
+ * No float atomics, fixed summation orders (gsr_reduce.h for the totals): results are bitwise reproducible. */
+size_t gsr_mesh_lap_workspace_bytes(int V, int F);
+int gsr_mesh_lap_forward(int V, int F, const float* verts, const int* faces, const int* nbr_offsets, const int* nbr,
+                         const int* vf_offsets, const int* vf_entries, int method, float laplacian_factor, float area_reg_factor,
+                         void* workspace, float* loss_out, gsr_stream_t stream);
+int gsr_mesh_lap_backward(int V, int F, const float* verts, const int* faces, const int* nbr_offsets, const int* nbr,
+                          const int* vf_offsets, const int* vf_entries, int method, float laplacian_factor, float area_reg_factor,
+                          void* workspace, const float* grad_scale, float* dL_dverts, int accumulate, gsr_stream_t stream);
+
 /* ---- Regularisers on the Gaussians' own parameters (gaustar_trainers/refine.py:739-740, :743-748, :663-669), fused.  Replaces
  *   factor_t * (unbind_loss_weight * delta_t.abs()).mean()                                     (refine.py:739)
  * + factor_r * (unbind_loss_weight * delta_r[..., 1:].abs()).mean()                            (refine.py:740)

@@ -11,6 +11,8 @@ frame, train_seq.py:101-244 / gaustar_trainers/refine.py:529-841) assembled from
 With --mesh-reg every iteration also carries the surface-mesh regularisers of refine.py:676-706 (normal consistency, edge
 and area isometry against the frame-0 mesh, train_seq.py:108-110's factors) through losses.surface_mesh_loss -- or, with
 --fused-step, through rgbd_step(mesh_reg=...).  Off by default.
+With --mesh-reg --mesh-lap the uniform Laplacian-smoothing term of refine.py:681-683 (factor 5, refine.py:118-122) is added
+to them through losses.mesh_smoothness_loss / the same rgbd_step dict.  Off by default.
 With --loose-bind the model is loose-bound before the timed region (weight 1 on every other face) and every iteration carries
 the regularisers on the Gaussians' parameters (refine.py:739-748, :663-669): rgbd_step(param_reg=...) with --fused-step, the
 autograd composition of the reference's four torch lines otherwise.  Off by default.
@@ -72,6 +74,8 @@ def run(a):
         mesh_reg = dict(topology=model.mesh_topology(), nc_factor=0.5, ref_edge_len=(ve[:, 0] - ve[:, 1]).norm(dim=1),
                         edge_factor=1000.0, ref_area=ref.faces_areas_packed().detach(), area_factor=5000.0)
         reg_kw = {k: v_ for k, v_ in mesh_reg.items() if k != "topology"}
+        if getattr(a, "mesh_lap", False):   # refine.py:118-122, :681-683: the uniform Laplacian term beside them
+            mesh_reg.update(laplacian_factor=5.0, laplacian_method="uniform")
     param_reg, loose_groups = None, False
     if getattr(a, "loose_bind", False):   # (bench.py builds the namespace without this flag: off)
         w = (torch.arange(N // 6, device=dev) % 2).float().repeat_interleave(6)[:, None].expand(-1, 3)
@@ -130,6 +134,9 @@ def run(a):
                     loss = losses.rgb_depth_loss(img, gts[ci][0], gts[ci][1], MAX_DEPTH, 0.2, 1.0, 0.5)
                     if mesh_reg is not None:
                         loss = loss + losses.surface_mesh_loss(model._points, mesh_reg["topology"], **reg_kw)
+                        if "laplacian_factor" in mesh_reg:
+                            loss = loss + losses.mesh_smoothness_loss(model._points, mesh_reg["topology"], mesh_reg["laplacian_factor"],
+                                                                      mesh_reg["laplacian_method"])
                     if param_reg is not None:     # refine.py:739-740, :743-748, :669 as the reference writes them
                         loss = loss + 100.0 * (model.unbind_loss_weight * model._delta_t.abs()).mean()
                         loss = loss + 1.0 * (model.unbind_loss_weight * model._delta_r[..., 1:].abs()).mean()
@@ -176,6 +183,8 @@ def run(a):
         extra["fused_step"] = True
     if mesh_reg is not None:
         extra["mesh_reg"] = True
+        if "laplacian_factor" in mesh_reg:
+            extra["mesh_lap"] = True
     if loose_groups:
         extra["loose_bind"], extra["param_reg"] = True, param_reg is not None
     return {**extra, "gaussians": N, "image": [a.width, a.height], "cameras": len(ncams), "frames": frames, "iterations": n_it,
@@ -201,6 +210,8 @@ def main():
                     help="render + losses + backward through SurfaceGaussians.rgbd_step (no autograd graph) instead of loss.backward()")
     ap.add_argument("--mesh-reg", dest="mesh_reg", action="store_true",
                     help="add the surface-mesh regularisers of refine.py:676-706 (normal consistency, edge / area isometry)")
+    ap.add_argument("--mesh-lap", dest="mesh_lap", action="store_true",
+                    help="with --mesh-reg: add the uniform Laplacian-smoothing term of refine.py:681-683 (factor 5)")
     ap.add_argument("--loose-bind", dest="loose_bind", action="store_true",
                     help="loose-bind the model and add the regularisers on the Gaussians' parameters (refine.py:739-748, :663-669)")
     r = run(ap.parse_args())
