@@ -489,9 +489,12 @@ struct FusedCall {
         const uint32_t* h = reinterpret_cast<const uint32_t*>(pi->header);
         // (a header that is not this image's -- another size's, or not a header at all -- is no plan)
         if (seen && (h[PH_T] != (uint32_t)v.tiles().T || h[PH_U_CAP] != h[PH_R_CAP] >> 6 || (h[PH_R_CAP] & 63u) != 0u)) seen = false;
+        // (nor is one that claims more light tiles than the image has tiles: the forward blend's grid is sized by that count)
+        if (seen && h[PLAN_PAD_LIGHT] > h[PH_T]) seen = false;
         pi->state = seen ? (h[PH_VALID] == 1u ? 1 : -1) : 0;
         if (seen) {
             pi->R_cap = (int)h[PH_R_CAP]; pi->U_cap = (int)h[PH_U_CAP]; pi->max_cap = (int)h[PH_MAX_CAP];
+            pi->reserved1[PI_LIGHT] = (int)h[PLAN_PAD_LIGHT];   // (the arriving count's own word is the next builder's to write)
             pi->half = pi->pending_half & 1;
         }
         pi->pending = 0;
@@ -542,6 +545,7 @@ struct FusedCall {
         run.cursor = own->cursors(blk); run.cursor_other = own->cursors(blk ^ 1); run.sync = own->sync();
         run.keys = b.keys; run.unit_info = b.unit_info; run.im_ranges = im.ranges; run.im_seg_off = im.seg_off;
         run.host_pad = g_pinned + PAD_VERDICT; run.host_seq = next_seq(); run.token = next_view_token();
+        run.n_light = (uint32_t)std::min(std::max(pi->reserved1[PI_LIGHT], 0), v.tiles().T);
         {
             Scope sc(ST_PREPROCESS, st);
             launch_preprocess_planned(v, g, im, run, st);

@@ -39,6 +39,12 @@
 
 namespace gsr {
 
+// Light tiles of a planned view (below) per workgroup.
+#ifndef GSR_FWD_LIGHT_TILES
+#define GSR_FWD_LIGHT_TILES 16
+#endif
+constexpr int FWD_LIGHT_TILES = GSR_FWD_LIGHT_TILES;
+static_assert(FWD_LIGHT_TILES >= 1 && FWD_LIGHT_TILES <= 64, "a wave's lanes hold the group's tiles");
 
 // MODE 0: one workgroup per tile (launch order = `order`): the list is sorted and walked here, front to back.  That is every
 // view whose longest list stays below SPLIT_FROM entries.  A longer list -- a surface seen edge-on stacks thousands of thin
@@ -60,6 +66,8 @@ namespace gsr {
 // workgroup also writes the backward's unit table for ALL units of the bucket (a unit past the list's end is an empty work
 // item there), leaves {first, first + count} in the image state like the exact path's scan, and hands the cursor back zeroed.
 // A view that did not fit its plan (flag word == this view's token) is left alone: the host renders it the exact way.
+// The plan's LIGHT tiles (capacity 0; the last plan.n_light places of its order) get no workgroup each: FWD_LIGHT_TILES of them
+// share one, which does an empty tile's bookkeeping and background pixels for each of its tiles and nothing else.
 template <int C, int CH, int MODE, bool PLANNED = false>
 __global__ void __launch_bounds__(256)
 blend_fwd_kernel(int W, int H, int gx, const uint2* __restrict__ ranges, const uint32_t* __restrict__ order,
@@ -87,11 +95,24 @@ blend_fwd_kernel(int W, int H, int gx, const uint2* __restrict__ ranges, const u
     // Side job: the backward's accumulation table (48 B per Gaussian) has to be zero before blend_bwd runs.  When the
     // caller hands it over at forward time every workgroup clears its slice here instead of a separate fill (a 5 us blit
     // plus its dispatch) in front of the backward.
-    if (MODE != 1 && zero_ptr != nullptr) {
-        const uint32_t per = (zero_n + gridDim.x - 1u) / gridDim.x;
-        const uint32_t i0 = blockIdx.x * per, i1 = min(zero_n, i0 + per);
-        for (uint32_t i = i0 + threadIdx.x; i < i1; i += 256u) zero_ptr[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    // (PLANNED: a workgroup of light tiles, below, clears one slice per tile it stands for -- shares by workgroup would move most
+    // of the clearing from the empty tiles at the launch's end to the start of its longest tiles: + 3 us on the launch alone)
+    // (such a workgroup clears them once its index loads are on their way: a wait for a load is also one for the stores before it)
+    [[maybe_unused]] uint32_t n_tiles = 0, n_front = 0;
+    bool light_group = false;
+    if constexpr (PLANNED) {
+        n_tiles = (uint32_t)gx * (uint32_t)((H + TILE - 1) / TILE);
+        n_front = n_tiles - min(plan.n_light, n_tiles);
+        light_group = blockIdx.x >= n_front + (has_job ? 1u : 0u);
     }
+    // slices [s0, s1) of `slices`
+    const auto clear_slices = [&](uint32_t slices, uint32_t s0, uint32_t s1) {
+        const uint32_t per = (zero_n + slices - 1u) / slices;
+        const uint32_t i0 = min(zero_n, s0 * per), i1 = min(zero_n, s1 * per);
+        for (uint32_t i = i0 + threadIdx.x; i < i1; i += 256u) zero_ptr[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    };
+    if (MODE != 1 && zero_ptr != nullptr && !light_group)
+        clear_slices(PLANNED ? n_tiles + (has_job ? 1u : 0u) : gridDim.x, blockIdx.x, blockIdx.x + 1u);
     constexpr int NH = CH / 32;                                       // 32-bit mask words per lane and chunk
     constexpr int PT = CH / 256;                                      // list positions per thread and chunk
     static_assert(CH % 256 == 0 && NH <= 32, "a chunk is a whole number of 256-thread fetch rounds; nz is one dword");
@@ -120,6 +141,69 @@ blend_fwd_kernel(int W, int H, int gx, const uint2* __restrict__ ranges, const u
                 if (misfit) return;
             }
             plan_build_block<256>(job, ranges, order, reinterpret_cast<uint32_t*>(smem));
+            return;
+        }
+    }
+    if constexpr (PLANNED) {
+        // LIGHT tiles (gsr_plan.h: capacity 0 -- empty in the plan's source view, and so were all eight neighbours; the last
+        // plan.n_light places of the launch order): a view that fits its plan has nothing on them, so all there is to do is the
+        // bookkeeping of an empty tile and 256 background pixels.  As a tile workgroup of its own each held 35 KB of LDS and four
+        // waves of the full kernel's registers through a chain of dependent loads and two barriers -- nothing while the launch
+        // has the chip to itself, a quarter of a CU each next to another view's backward.  Here LT of them share a workgroup that
+        // touches neither LDS nor a barrier: one trip to memory for the LT tile ids, one for their buckets, then stores.
+        const uint32_t T = n_tiles;
+        if (light_group) {
+            constexpr int LT = FWD_LIGHT_TILES;
+            const uint32_t p0 = n_front + (tile_block - n_front) * (uint32_t)LT;
+            const int lane = threadIdx.x & 63;
+            const bool misfit = plan.sync[9 * PLAN_SYNC_STRIDE] == plan.token;
+            // lane k of every wave holds the group's k-th tile
+            const bool mine = lane < LT && p0 + (uint32_t)lane < T;
+            const uint32_t tl = mine ? order[p0 + (uint32_t)lane] : 0xffffffffu;
+            float bgv[C];
+#pragma unroll
+            for (int ch = 0; ch < C; ch++) bgv[ch] = bg[ch];
+            if (zero_ptr != nullptr) {   // one slice per tile of the group, the plan job's in front of all tiles'
+                const uint32_t lead = has_job ? 1u : 0u;
+                clear_slices(T + lead, lead + p0, lead + min(p0 + (uint32_t)LT, T));
+            }
+            const bool ok = mine && tl < T;
+            uint2 bucket = make_uint2(0u, 0u);
+            uint32_t unit_first = 0;
+            if (ok) { bucket = ranges[tl]; unit_first = seg_off[tl]; }
+            if (blockIdx.x == 0 && threadIdx.x == 0) {   // (a launch without the plan job whose every tile is light)
+                plan.host_pad[0] = misfit ? 2u : 1u;
+                __hip_atomic_store(&plan.host_pad[1], plan.host_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+            }
+            // what every tile's workgroup leaves behind, misfit or not: the cursor of the other block zeroed (a view that did not
+            // fit may have claimed on a light tile) and the image state's {first, first + count}, first unit
+            if (ok && threadIdx.x < 64) {
+                plan.cursor_other[(size_t)tl * PLAN_CURSOR_STRIDE] = 0u;
+                plan.im_ranges[tl] = make_uint2(bucket.x, bucket.x);
+                plan.im_seg_off[tl] = unit_first;
+            }
+            if (misfit) return;
+            // 16 consecutive lanes write one 64-byte row of a tile
+            const uint32_t where = ok ? ((tl / (uint32_t)gx) << 16) | (tl % (uint32_t)gx) : 0xffffffffu;
+            const int col = threadIdx.x & 15, row = threadIdx.x >> 4;
+            const size_t HW = (size_t)H * W;
+#pragma unroll
+            for (int k = 0; k < LT; k++) {
+                // (a place past the end of the order -- the last group may be partial -- holds no tile: its pixels lie outside)
+                const uint32_t xy = (uint32_t)__builtin_amdgcn_readlane((int)where, k);
+                const int px = (int)(xy & 0xffffu) * TILE + col, py = (int)(xy >> 16) * TILE + row;
+                if (px < W && py < H) {
+                    const size_t pix = (size_t)W * py + px;
+                    final_T[pix] = 1.0f;
+                    n_contrib[pix] = 0u;
+#pragma unroll
+                    for (int ch = 0; ch < C; ch++) out_color[ch * HW + pix] = 0.0f + 1.0f * bgv[ch];   // (C + T bg of a pixel nothing reached)
+                }
+            }
+            if (trace && lane == 0) {
+                if (threadIdx.x == 0) trace[2 * tile_block] = t_start;
+                atomicMax((unsigned long long*)&trace[2 * tile_block + 1], (unsigned long long)wall_clock64());
+            }
             return;
         }
     }
@@ -815,7 +899,10 @@ static void launch_fwd_planned_c(int W, int H, const float* bg, const float* fea
     const Tiles t = tiles_of(W, H);
     static const int pad = getenv("GSR_FWD_LDS_PAD") ? atoi(getenv("GSR_FWD_LDS_PAD")) : 0;
     const bool rides = job != nullptr && job->enabled != 0u;
-    blend_fwd_kernel<C, FWD_CHUNK, 0, true><<<(unsigned)t.T + (rides ? 1u : 0u), 256, pad, st>>>(
+    // one workgroup per tile in front of the plan's light tiles, one per FWD_LIGHT_TILES of those
+    const unsigned n_light = std::min<unsigned>(plan.n_light, (unsigned)t.T);
+    const unsigned grid = (rides ? 1u : 0u) + ((unsigned)t.T - n_light) + (n_light + FWD_LIGHT_TILES - 1u) / FWD_LIGHT_TILES;
+    blend_fwd_kernel<C, FWD_CHUNK, 0, true><<<grid, 256, pad, st>>>(
         W, H, t.gx, plan.ranges, plan.order, b.point_list, b.keys, g.g0, g.g1, feats, bg, out_color, im.final_T, im.n_contrib,
         plan.seg_off, b.masks, b.snap, b.rec_a, b.rec_b, static_cast<RecTail<C>*>(b.rec_c), b.part_list, im.totals, b.part_fin,
         b.part_last, b.part_ticket, 0u, false, 0xffffffffu, keep_masks, static_cast<float4*>(zero_ptr), (uint32_t)(zero_bytes / 16),

@@ -288,6 +288,7 @@ struct PlanRun {             // what the planned kernels get besides the exact p
     uint32_t* host_pad;      // pinned, device-mapped: {verdict (1 fits, 2 does not), sequence number}, written by the forward blend
     uint32_t host_seq;
     uint32_t token;          // this view's token
+    uint32_t n_light;        // the last n_light tiles of `order` have capacity 0 (gsr_plan.h): the forward blend fills them in bulk
 };
 
 // Optional per-workgroup timeline for tuning (gsr_debug_set_trace): when non-null, the blend kernels store

@@ -56,10 +56,13 @@ __device__ __forceinline__ uint32_t wave_max_to_lane63(uint32_t x)
 // The eight words of a plan's header (PlanState::header, gsr_plan_info::header), as plan_build_block writes them
 enum PlanHeaderWord { PH_VALID = 0, PH_T, PH_R_CAP, PH_U_CAP, PH_MAX_CAP, PH_NONEMPTY, PH_ENTRIES, PH_LONGEST };
 // Where the builder's words lie in PlanJob::host_pad, which points at the header of the caller's gsr_plan_info (include/gsr.h)
-constexpr int PLAN_PAD_SEQ = 8, PLAN_PAD_DIAG = 10;
+// ([PLAN_PAD_LIGHT] = reserved1[0]: the number of light tiles at the end of the arriving plan's launch order)
+constexpr int PLAN_PAD_SEQ = 8, PLAN_PAD_DIAG = 10, PLAN_PAD_LIGHT = 14;
+constexpr int PI_LIGHT = 1;   // gsr_plan_info::reserved1[PI_LIGHT]: that count of the plan in use, kept beside R_cap / U_cap / max_cap
 static_assert(sizeof(gsr_plan_info) == sizeof(int) * GSR_PLAN_INFO_INTS, "gsr_plan_info is the whole block");
 static_assert(offsetof(gsr_plan_info, arrived) == offsetof(gsr_plan_info, header) + 4 * PLAN_PAD_SEQ, "host_seq lands in `arrived`");
 static_assert(offsetof(gsr_plan_info, diag) == offsetof(gsr_plan_info, header) + 4 * PLAN_PAD_DIAG, "the diagnosis lands in `diag`");
+static_assert(offsetof(gsr_plan_info, reserved1) == offsetof(gsr_plan_info, header) + 4 * PLAN_PAD_LIGHT, "the light-tile count lands in reserved1[0]");
 static_assert(offsetof(gsr_plan_info, header) % 16 == 0, "the header is stored as two uint4");
 
 // What the plan-building workgroup needs (by value in the forward blend's arguments); enabled == 0: no job in this launch.
@@ -118,7 +121,7 @@ __device__ __forceinline__ void plan_build_block(const PlanJob& job, const uint2
 {
     static_assert(NT % 64 == 0 && NT <= 1024, "whole waves");
     constexpr int NW = NT / 64;
-    __shared__ uint32_t ws_cap[NW], ws_max[NW], ws_ne[NW], ws_n[NW];
+    __shared__ uint32_t ws_cap[NW], ws_max[NW], ws_ne[NW], ws_n[NW], ws_light[NW], ws_front[NW];
     const int T = job.T, gx = job.gx, gy = job.gy;
     const uint32_t level = job.level;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -178,27 +181,74 @@ __device__ __forceinline__ void plan_build_block(const PlanJob& job, const uint2
     const int r0 = wave * rpw, r1 = min(rows, r0 + rpw);
     // pass 1: this wave's capacities (kept in the upper half of the staged word: a neighbour's look-up reads the lower half,
     // which the store does not change) and their sum
-    uint32_t sum_cap = 0;
+    uint32_t sum_cap = 0, light = 0;
     for (int r = r0; r < r1; r++) {
         const int t = 64 * r + lane;
         if (t < T) {
             const uint32_t c = cap_of(t);
             if (staged) cnt_lds[t] = (cnt_lds[t] & 0xffffu) | (c << 16);
             sum_cap += c;
+            light += staged && c == 0u ? 1u : 0u;
         }
     }
-    const uint32_t incl_cap = wave_incl_scan(sum_cap, lane);
+    const uint32_t incl_cap = wave_incl_scan(sum_cap, lane), incl_light = wave_incl_scan(light, lane);
     const uint32_t incl_n = wave_incl_scan(sum_n, lane), incl_ne = wave_incl_scan(ne, lane);
     vmax = wave_max_to_lane63(vmax);
-    if (lane == 63) { ws_cap[wave] = incl_cap; ws_max[wave] = vmax; ws_ne[wave] = incl_ne; ws_n[wave] = incl_n; }
+    if (lane == 63) { ws_cap[wave] = incl_cap; ws_max[wave] = vmax; ws_ne[wave] = incl_ne; ws_n[wave] = incl_n; ws_light[wave] = incl_light; }
     __syncthreads();
-    uint32_t woff = 0, total_cap = 0, gmax = 0, total_ne = 0, total_n = 0;
+    uint32_t woff = 0, total_cap = 0, gmax = 0, total_ne = 0, total_n = 0, n_light = 0;
     for (int w = 0; w < NW; w++) {
         if (w < wave) woff += ws_cap[w];
         total_cap += ws_cap[w];
         gmax = max(gmax, ws_max[w]);
         total_ne += ws_ne[w];
         total_n += ws_n[w];
+        n_light += ws_light[w];
+    }
+    // The launch order of the plan: the source's, with the LIGHT tiles -- capacity 0: empty, and so are all eight neighbours; a
+    // view that fits the plan has nothing on them -- moved behind all others (a stable partition: the order of the others
+    // stays what it was).  The planned forward blend fills them with the background many to a workgroup (gsr_blend_fwd.hip).
+    // A wave owns rows of 64 launch positions; two sweeps over them: count the tiles that stay in front, then place.
+    // (unstaged -- above 8 192 tiles --: the order is copied and no tile is reported light)
+    constexpr int OB = 8;   // rows of the order in flight per wave
+    const auto sweep_order = [&](auto&& row) {
+        for (int rb = r0; rb < r1; rb += OB) {
+            uint32_t tl[OB];
+#pragma unroll
+            for (int q = 0; q < OB; q++) {
+                const int p = 64 * (rb + q) + lane;
+                tl[q] = rb + q < r1 && p < T ? order_in[p] : 0xffffffffu;
+            }
+#pragma unroll
+            for (int q = 0; q < OB; q++) {
+                if (rb + q >= r1) break;
+                const bool in = tl[q] < (uint32_t)T;   // (an order is a permutation of the tiles; anything else is dropped)
+                const bool is_light = in && staged && (cnt_lds[tl[q]] >> 16) == 0u;
+                row(64 * (rb + q) + lane, tl[q], in, is_light);
+            }
+        }
+    };
+    uint32_t front = 0;   // tiles of this wave's positions that stay in front (wave-uniform)
+    if (staged) {
+        sweep_order([&](int, uint32_t, bool in, bool is_light) { front += (uint32_t)__popcll(__ballot(in && !is_light)); });
+        if (lane == 0) ws_front[wave] = front;
+        __syncthreads();
+        uint32_t before = 0;
+        for (int w = 0; w < wave; w++) before += ws_front[w];
+        // next free place in front / among the light tiles: the positions ahead of this wave hold `before` tiles that stay
+        uint32_t at_front = before, at_light = (uint32_t)T - n_light + ((uint32_t)min(64 * r0, T) - before);
+        const unsigned long long below = (1ull << lane) - 1ull;
+        sweep_order([&](int, uint32_t t, bool in, bool is_light) {
+            const unsigned long long mf = __ballot(in && !is_light), ml = __ballot(is_light);
+            if (in) {
+                const uint32_t to = is_light ? at_light + (uint32_t)__popcll(ml & below) : at_front + (uint32_t)__popcll(mf & below);
+                if (to < (uint32_t)T) job.order[to] = t;
+            }
+            at_front += (uint32_t)__popcll(mf);
+            at_light += (uint32_t)__popcll(ml);
+        });
+    } else {
+        for (int t = tid; t < T; t += NT) job.order[t] = order_in[t];
     }
     // pass 2: one wave scan per row, the running base carried in a scalar
     uint32_t run = woff;
@@ -222,7 +272,6 @@ __device__ __forceinline__ void plan_build_block(const PlanJob& job, const uint2
             const uint32_t first = run + incl - cap;
             job.ranges[t] = make_uint2(first, cap);
             job.seg_off[t] = first >> 6;     // (capacities are whole units: the unit prefix is the entry prefix / 64)
-            job.order[t] = order_in[t];
         }
         run += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
     }
@@ -238,6 +287,7 @@ __device__ __forceinline__ void plan_build_block(const PlanJob& job, const uint2
         if (job.host_pad) {
             reinterpret_cast<uint4*>(job.host_pad)[0] = h0;
             reinterpret_cast<uint4*>(job.host_pad)[1] = h1;
+            job.host_pad[PLAN_PAD_LIGHT] = n_light;   // (the eight header words are taken: the count travels beside them)
             __hip_atomic_store(&job.host_pad[PLAN_PAD_SEQ], job.host_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
         }
     }

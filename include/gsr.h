@@ -163,7 +163,9 @@ typedef struct gsr_plan_info {
     int pending;       /* the sequence number the host expects there (0: no plan under way) */
     int diag[4];       /* (GSR_PLAN_DIAG builds) how a view sat in the plan it replaces: tiles over an empty bucket, over a non-empty
                         * one, entries over, worst count / capacity in 1/64 */
-    int reserved1[10];
+    int reserved1[10]; /* [0]: behind the arriving header, the number of LIGHT tiles at the end of that plan's launch order (capacity 0:
+                        * empty with eight empty neighbours; the planned forward blend fills them many to a workgroup); [1]: that
+                        * count of the plan in use; the rest is unused */
 } gsr_plan_info;
 int* gsr_plan_info_new(void);
 void gsr_plan_info_free(int* plan_info);
