@@ -11,12 +11,15 @@ stand-ins for pytorch3d's `Meshes` / `mesh_normal_consistency`), `sweep` (forwar
 `mesh_depth` (a mesh's depth maps, masks and visible faces over the rig: the inputs of a tracked sequence),
 `tracking` (points followed on the surface through topology updates: SurfaceTracker, track_faces),
 `remesh` (quadric mesh decimation and Laplacian / Taubin smoothing: how an init_mesh_100k.obj is made),
+`knn` (exact K-nearest neighbours with spatial culling: pytorch3d's knn_points, simple-knn's distCUDA2),
 `evaluate` (how good a result is: point-to-mesh distance, Chamfer distance and F-score of two meshes, PSNR and SSIM of renders) and
 `formats` (cameras.json, 3DGS PLY, SuGaR .pt, OBJ, grey PNG) -- import them as submodules.
 """
 from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, rasterize_gaussians  # noqa: F401
 from .tracking import RebindStats, SurfaceTracker, bind_points, track_faces  # noqa: F401
 from .remesh import SimplifiedMesh, simplify_mesh, smooth_laplacian, smooth_taubin  # noqa: F401
+from .knn import dist_cuda2, knn_points, nearest_neighbors  # noqa: F401
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "RebindStats", "SurfaceTracker",
-           "bind_points", "track_faces", "SimplifiedMesh", "simplify_mesh", "smooth_laplacian", "smooth_taubin"]
+           "bind_points", "track_faces", "SimplifiedMesh", "simplify_mesh", "smooth_laplacian", "smooth_taubin", "nearest_neighbors",
+           "knn_points", "dist_cuda2"]

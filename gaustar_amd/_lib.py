@@ -246,6 +246,19 @@ SIGNATURES = {
     "gsr_remesh_narrow": (c_int, [c_longlong, c_void_p, c_void_p, c_void_p]),
     "gsr_remesh_smooth": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_double, c_double, c_int, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_void_p]),
+    # exact K-nearest-neighbour search with spatial culling (pytorch3d knn_points, simple-knn distCUDA2) and the rows' uses:
+    # gaustar_amd.knn
+    "gsr_knn_tile": (c_int, []),
+    "gsr_knn_seed": (c_int, []),
+    "gsr_knn_queries": (c_int, []),
+    "gsr_knn_max_k": (c_int, []),
+    "gsr_knn_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "gsr_knn_prepare": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gsr_knn_search": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                               c_void_p]),
+    "gsr_knn_mean_d2": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "gsr_knn_segment_mean": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gsr_knn_weighted_mean": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_void_p]),
     "gsr_adam_step": (c_int, [c_longlong, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_double, c_double, c_int,
                               c_void_p]),
     "gsr_adam_step_multi": (c_int, [c_int, POINTER(c_longlong), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),

@@ -487,6 +487,28 @@ class SurfaceGaussians(nn.Module):
         from . import topology
         return topology.detect_topology_errors(self, cameras, gt_depth, **kw)
 
+    def reset_neighbors(self, knn_to_track: Optional[int] = None, force: bool = False) -> None:
+        """sugar_model.py:847-864: `knn_idx` [n_points, K] int64 and `knn_dists` [n_points, K] f32 of the current Gaussian
+        centres among themselves (knn.knn_points; every row starts with the point itself, or a duplicate of it at a lower
+        index, at distance 0).  K = knn_to_track, else the last one used, else 16.  The reference skips the call for a
+        model bound to a mesh unless force is set, with a warning; every model here is bound, so the neighbours are always
+        computed and `force` is accepted for the signature only."""
+        from . import knn
+        if knn_to_track is None:
+            knn_to_track = getattr(self, "knn_to_track", 16)
+        self.knn_to_track = int(knn_to_track)
+        with torch.no_grad():
+            pts = self.points.detach().float().contiguous()
+            res = knn.knn_points(pts[None], pts[None], K=self.knn_to_track)
+        self.knn_dists, self.knn_idx = res.dists[0], res.idx[0]
+
+    def get_neighbors_of_random_points(self, num_samples: int) -> torch.Tensor:
+        """sugar_model.py:804-809: the rows of `knn_idx` (reset_neighbors) of `num_samples` random points, all rows in
+        order for a negative count."""
+        if num_samples >= 0:
+            return self.knn_idx[torch.randperm(self.n_points, device=self.device)[:num_samples]]
+        return self.knn_idx
+
     def warp_mesh(self, cameras, frames, **kw):
         """The surface mesh moved to the next frame along the optical flow of `cameras` (warp_mesh.py:216-401):
         warp.warp_mesh(vertices, faces, topology.rig_from_cameras(cameras), frames, **kw) (`rig` may be passed in kw)."""

@@ -18,9 +18,15 @@ cameras start and each pipeline waits for its stream once its cameras are done (
 calling stream without a wait), and warp_mesh waits for its stream once at the end.  The mesh's topology, neighbour lists and
 vertex-face lists are built (with host reads) on first use and kept on the faces tensor, as meshes.MeshTopology.of does.
 
-Only post_processing = 'mesh' (the reference's default) is implemented; 'voxel' and save_inter raise ValueError.  An isolated
-vertex (no neighbours) keeps its move through propagation and becomes NaN in smoothing, as np.average of an empty selection
-makes it; the reference raises IndexError there (its empty neighbour list is a float array).
+post_processing = 'mesh' (the reference's default) is the above.  With 'voxel' (warp_mesh.py:368-376) the propagation is not
+run: the vertices with count >= min_observe are binned into voxels of cfg.voxel_size (Open3D's VoxelGrid rule, gsr_topo.hip's
+keys), each voxel takes the mean move of its vertices, and every vertex takes the distance-weighted mean of its cfg.knn_K
+nearest voxel centres (gaustar_amd.knn, gsr_knn.hip), which is then smoothed.  Departures: the voxels stand in ascending key
+order (Open3D's order is its hash map's and unspecified; it decides only which of two equidistant centres comes first); the
+vertices enter the keys and the search rounded to f32 (Open3D bins the f64 vertices); the weights are f64 (the reference's
+are f32).  No observed vertex raises ValueError (the reference crashes in Open3D).  save_inter raises ValueError.  An
+isolated vertex (no neighbours) keeps its move through propagation and becomes NaN in smoothing, as np.average of an empty
+selection makes it; the reference raises IndexError there (its empty neighbour list is a float array).
 """
 from __future__ import annotations
 
@@ -77,17 +83,21 @@ class MeshWarp:
     """move_raw [V,3] f64: the rig mean after outlier removal, 0 where count < min_observe (warp_{f:04d}.obj);
     move_propagated (warp_mesh_prop.obj) and move_smoothed (warp_smooth.obj) [V,3] f64; verts_raw / verts_propagated /
     verts_smoothed = verts + the move; observed [V] int32: cameras that see the vertex; count [V] int32: after outlier
-    removal (the one :384 uses).  With return_stages: table [C,V,3] f64 (NaN = not visible) and normals [V,3] f64."""
+    removal (the one :384 uses).  With return_stages: table [C,V,3] f64 (NaN = not visible) and normals [V,3] f64.
+    post_processing = 'voxel': move_voxel / verts_voxel [V,3] f64 (warp_voxel.obj) is what gets smoothed, and
+    move_propagated / verts_propagated are None; in 'mesh' mode move_voxel / verts_voxel are None."""
     move_raw: torch.Tensor
-    move_propagated: torch.Tensor
+    move_propagated: Optional[torch.Tensor]
     move_smoothed: torch.Tensor
     verts_raw: torch.Tensor
-    verts_propagated: torch.Tensor
+    verts_propagated: Optional[torch.Tensor]
     verts_smoothed: torch.Tensor
     observed: torch.Tensor
     count: torch.Tensor
     table: Optional[torch.Tensor] = None
     normals: Optional[torch.Tensor] = None
+    move_voxel: Optional[torch.Tensor] = None
+    verts_voxel: Optional[torch.Tensor] = None
 
 
 def vertex_face_csr(topo):
@@ -111,8 +121,8 @@ def warp_mesh(verts, faces, rig: dict, frames: Callable[[int], tuple], cfg: Warp
     (H, W)).  frames(i) -> (flow_f, flow_b, depth_cur, depth_next) for camera i, on any device: the raw RAFT flows [h,w,2]
     in (x, y) order and the depth maps [H,W] of frames f and f + interval; called once per camera of this rank's shard.
     pad: (top, bottom, left, right) of the flows (pad.txt), or None."""
-    if cfg.post_processing != "mesh":
-        raise ValueError(f"warp_mesh: post_processing={cfg.post_processing!r} is not implemented (only 'mesh')")
+    if cfg.post_processing not in ("mesh", "voxel"):
+        raise ValueError(f"warp_mesh: post_processing={cfg.post_processing!r} is not implemented (only 'mesh' and 'voxel')")
     lib = _lib.load()
     if device is None:
         device = verts.device if isinstance(verts, torch.Tensor) and verts.is_cuda else torch.device("cuda", torch.cuda.current_device())
@@ -175,24 +185,65 @@ def warp_mesh(verts, faces, rig: dict, frames: Callable[[int], tuple], cfg: Warp
     _lib.check(lib.gsr_warp_aggregate(C, V, _p(table.contiguous()), int(cfg.min_observe), _p(move), _p(observed), _p(count),
                                       _p(valid), stream), "gsr_warp_aggregate")
     off, nbr = topo.vertex_neighbours
-    # propagation: the valid set evolves independently of the values, so one scalar call per component is the vector result
-    comp = move.t().contiguous()
-    prop_c = torch.empty_like(comp)
-    tmp = torch.empty(V, dtype=torch.float64, device=dev)
-    va, vb = torch.empty_like(valid), torch.empty_like(valid)
-    for k in range(3):
-        _lib.check(lib.gsr_topo_propagate(V, _p(off), _p(nbr), PROP_SWEEPS, _p(comp[k]), _p(valid), _p(prop_c[k]), _p(tmp), _p(va),
-                                          _p(vb), stream), "gsr_topo_propagate")
-    prop = prop_c.t().contiguous()
-    smooth = torch.empty_like(prop)
-    stmp = torch.empty_like(prop)
-    _lib.check(lib.gsr_warp_smooth(V, _p(off), _p(nbr), SMOOTH_SWEEPS, _p(prop), _p(smooth), _p(stmp), stream), "gsr_warp_smooth")
-    res = MeshWarp(move_raw=move, move_propagated=prop, move_smoothed=smooth, verts_raw=v + move, verts_propagated=v + prop,
-                   verts_smoothed=v + smooth, observed=observed, count=count)
+    prop = vox = None
+    if cfg.post_processing == "voxel":
+        vox = _voxel_interpolate(lib, v, move, valid, cfg, stream)
+    else:
+        # propagation: the valid set evolves independently of the values, so one scalar call per component is the vector result
+        comp = move.t().contiguous()
+        prop_c = torch.empty_like(comp)
+        tmp = torch.empty(V, dtype=torch.float64, device=dev)
+        va, vb = torch.empty_like(valid), torch.empty_like(valid)
+        for k in range(3):
+            _lib.check(lib.gsr_topo_propagate(V, _p(off), _p(nbr), PROP_SWEEPS, _p(comp[k]), _p(valid), _p(prop_c[k]), _p(tmp),
+                                              _p(va), _p(vb), stream), "gsr_topo_propagate")
+        prop = prop_c.t().contiguous()
+    pre = vox if prop is None else prop
+    smooth = torch.empty_like(pre)
+    stmp = torch.empty_like(pre)
+    _lib.check(lib.gsr_warp_smooth(V, _p(off), _p(nbr), SMOOTH_SWEEPS, _p(pre), _p(smooth), _p(stmp), stream), "gsr_warp_smooth")
+    res = MeshWarp(move_raw=move, move_propagated=prop, move_smoothed=smooth, verts_raw=v + move,
+                   verts_propagated=None if prop is None else v + prop, verts_smoothed=v + smooth, observed=observed, count=count,
+                   move_voxel=vox, verts_voxel=None if vox is None else v + vox)
     if return_stages:
         res.table, res.normals = table.view(C, V, 3), normals
     torch.cuda.current_stream().synchronize()
     return res
+
+
+VOXEL_BITS = 21      # gsr_topo_voxel_keys: voxel index bits per axis of a key
+
+
+def _voxel_interpolate(lib, v, move, valid, cfg: WarpConfig, stream) -> torch.Tensor:
+    """warp_mesh.py:368-371: build_voxel_from_pc over the observed vertices and interpolate_in_voxel for every vertex ->
+    [V,3] f64.  Reads the device twice (the observed vertices, the number of voxels)."""
+    from . import knn
+    dev = v.device
+    vs = float(cfg.voxel_size)
+    sel = torch.nonzero(valid).reshape(-1)
+    n = int(sel.shape[0])
+    if n == 0:
+        raise ValueError("warp_mesh: post_processing='voxel' found no vertex seen by min_observe cameras: there is no voxel")
+    v32 = v.float().contiguous()
+    pts = v32[sel].contiguous()
+    vmin = pts.amin(0).contiguous()
+    keys = torch.empty(n, dtype=torch.int64, device=dev)
+    flags = torch.zeros(1, dtype=torch.int32, device=dev)
+    _lib.check(lib.gsr_topo_voxel_keys(n, _p(pts), _p(vmin), vs, _p(keys), _p(flags), stream), "gsr_topo_voxel_keys")
+    skeys, order = torch.sort(keys, stable=True)
+    head = torch.ones(n, dtype=torch.bool, device=dev)
+    head[1:] = skeys[1:] != skeys[:-1]
+    vid = torch.cumsum(head.long(), 0) - 1
+    n_vox, overflow = (int(x) for x in torch.stack([vid[-1] + 1, flags[0].long()]).cpu())
+    if overflow:
+        raise ValueError(f"the observed vertices span more than 2^{VOXEL_BITS} voxels of {vs} along an axis")
+    vox_move, _ = knn.segment_mean(vid, order, move[sel].contiguous(), n_vox)
+    ukeys = skeys[head]
+    mask = (1 << VOXEL_BITS) - 1
+    index = torch.stack([ukeys >> (2 * VOXEL_BITS), (ukeys >> VOXEL_BITS) & mask, ukeys & mask], 1).double()
+    centre = ((vmin.double() - vs * 0.5) + (index + 0.5) * vs).float().contiguous()
+    idx, d2, _ = knn._search(v32, centre, int(cfg.knn_K), False, True, False)
+    return knn.weighted_mean(idx, d2, vox_move, 1.0 / (vs * vs))
 
 
 class _Prefetch:
@@ -224,20 +275,22 @@ class _Prefetch:
 
 
 def warp_mesh_using_flow(mesh_path, data_root, work_root, f_idx, interval=1, cmr=None, save_inter=False, from_humanrf=False,
-                         views_in_flight: int = 2, prefetch_threads: int = MAX_PREFETCH_THREADS) -> MeshWarp:
+                         views_in_flight: int = 2, prefetch_threads: int = MAX_PREFETCH_THREADS,
+                         cfg: Optional[WarpConfig] = None) -> MeshWarp:
     """warp_mesh.py:216-401 with the reference's signature, files and errors.  Paths are joined by concatenation as in the
     reference (data_root and work_root end with '/').  Reads rgb_cameras.npz (unless cmr is given), the mesh (OBJ, vertex
     order kept), {f:04d}/{flow_dir}/pad.txt and {c:04d}_{f,b}.npz ('flow'), {f:04d}/depth[_humanrf]/img_{c:04d}_depth.npz and
     the same for f + interval ('depth').  Writes config.json, warp_{f:04d}.obj, warp_mesh_prop.obj and warp_smooth.obj
     under {f+interval:04d}/coarse_mesh/ (the last two with the input's vertex colours).  Every input is checked before the
-    first launch.  save_inter=True raises ValueError."""
+    first launch.  save_inter=True raises ValueError.  cfg: the warp_config to use (the reference builds its default inside
+    the function); with cfg.post_processing = 'voxel' warp_voxel.obj is written instead of warp_mesh_prop.obj (:373-376)."""
     if save_inter:
         raise ValueError("warp_mesh_using_flow: save_inter=True is not implemented")
     if cmr is None:
         cmr = np.load(data_root + "rgb_cameras.npz")
     rig = {k: np.asarray(cmr[k]) for k in ("intrinsics", "extrinsics", "shape")}
     C = int(rig["shape"].shape[0])
-    cfg = WarpConfig()
+    cfg = WarpConfig() if cfg is None else cfg
     out_dir = work_root + f"{(f_idx + interval):04d}/coarse_mesh/"
     os.makedirs(out_dir, exist_ok=True)
     cfg.save_cfg(out_dir)
@@ -269,7 +322,10 @@ def warp_mesh_using_flow(mesh_path, data_root, work_root, f_idx, interval=1, cmr
     finally:
         pre.close()
     formats.save_obj(out_dir + f"warp_{f_idx:04d}.obj", res.verts_raw.cpu().numpy(), faces)
-    formats.save_obj(out_dir + "warp_mesh_prop.obj", res.verts_propagated.cpu().numpy(), faces, colours)
+    if res.verts_voxel is not None:
+        formats.save_obj(out_dir + "warp_voxel.obj", res.verts_voxel.cpu().numpy(), faces, colours)
+    else:
+        formats.save_obj(out_dir + "warp_mesh_prop.obj", res.verts_propagated.cpu().numpy(), faces, colours)
     formats.save_obj(out_dir + "warp_smooth.obj", res.verts_smoothed.cpu().numpy(), faces, colours)
     return res
 

@@ -1033,6 +1033,59 @@ int gsr_remesh_narrow(long long n, const double* in, float* out, gsr_stream_t st
 int gsr_remesh_smooth(int V, const int* nbr_offsets, const int* nbr, const unsigned char* locked, int steps, double lambda_even,
                       double lambda_odd, int uniform, const float* verts, double* work_a, double* work_b, float* out, gsr_stream_t stream);
 
+/* ---- Exact K-nearest-neighbour search of f32 points (pytorch3d's knn_points as gaustar_scene/sugar_model.py:49, :253, :862,
+ * :877, :1014 and gaustar_tools/warp_mesh.py:199-213 call it; simple-knn's distCUDA2, simple_knn.cu:147-183) and what the
+ * callers make of the rows: gaustar_amd.knn.  The rules, restated in tests/knn_ref.py: queries [N,3] and candidates [M,3] are
+ * f32; with d = query - candidate, d2 = (dx dx + dy dy) + dz dz in f32 without contraction; a row holds the K smallest pairs in
+ * ascending (d2, candidate index) order, the lower index first among equals; 1 <= K <= gsr_knn_max_k() = 32; slots beyond the
+ * number of eligible candidates hold idx = -1, d2 = +inf; a point with a non-finite coordinate is never returned as a
+ * neighbour and has, as a query, an empty row; with exclude_self (N == M: the queries are the candidates) candidate j == i is
+ * skipped for query i, a duplicate of it at another index is not (boxMeanDist, simple_knn.cu:158, :177).  The result is the
+ * exhaustive search's bit for bit: it does not depend on the two orders below, on the tiles or on the call.  All device
+ * pointers; every call is asynchronous on `stream`, none synchronises the host, none uses float atomics.
+ * gsr_knn_tile / _seed / _queries: T = candidates per tile, S = the seed looks at the 2 S + 1 sorted candidates around a
+ *   query's position, Q = queries per (one-wave) workgroup.
+ * gsr_knn_workspace_bytes(N, M, K): the candidates' copy, padded to whole tiles, and the tile boxes (N and K do not enter: the
+ *   lists are registers); 16-byte aligned.
+ * gsr_knn_prepare: order [M] int64 = a permutation of the candidates along a space-filling curve, non-finite ones last (a
+ *   30-bit Morton code over the finite candidates' box, gaustar_amd/knn.py; it only orders the work).  Writes the workspace:
+ *   the candidates in that order as float4 (xyz, the index as bits; NaN for a non-finite one) and, per tile of T consecutive
+ *   ones, the box of its finite points.
+ * gsr_knn_search: query_order [N] int64 = a permutation of the queries along the same curve; workgroup w takes the Q queries
+ *   query_order[w Q ..].  query_pos [N] int64, by sorted query: where the query would stand among the sorted candidates (its
+ *   own position when the queries are the candidates); read only with cull != 0.  cull != 0: per query the K best of the
+ *   candidates at sorted positions [pos - S, pos + S] give tau, an upper bound of its K-th distance; a tile is skipped iff the
+ *   lower bound of its box -- d2's operations in d2's order, 0 for an axis inside the box -- is > the current bound min(tau, the
+ *   list's K-th) of every query of the workgroup.  cull == 0: every tile is visited and there is no seed: the exhaustive mode.
+ *   idx [N,K] int32 and d2 [N,K] f32 in the caller's query order.  stats: NULL, or 2 uint64 cleared by the call: pairs
+ *   evaluated (seed windows included; N M with cull == 0) and tiles skipped, one integer atomic per workgroup and counter.
+ *   M == 0 leaves every row empty; N == 0 is a no-op.
+ * gsr_knn_mean_d2: out [N] f32 = ((r0 + r1) + r2) / 3.0f over the first three slots of every row of d2 [N,K], K >= 3, the
+ *   expression of simple_knn.cu:182; an empty slot counts as FLT_MAX, the reference's initial `best`, so fewer than three
+ *   neighbours give inf (one missing: FLT_MAX / 3 after rounding).
+ * gsr_knn_segment_mean: segment_ids [n] int64 ascending, dense in [0, S); order [n] int64 = the element each sorted position
+ *   came from; values [n,C] double by element.  out [S,C] double = per run of equal ids the sum over the run in sorted order,
+ *   from 0, divided by its length; count [S] int32 = the length (a voxel's mean, gsr_topo_voxel_interp's rule; no atomics).
+ * gsr_knn_weighted_mean: interpolate_in_voxel's average (warp_mesh.py:204-211) over the rows idx, d2 [N,K] of a search among M
+ *   candidates with values [M,C] double: w_k = exp(-(double) d2_k inv_scale) + 1e-8, out [N,C] double = (sum_k v[idx_k] w_k) /
+ *   (sum_k w_k), both sums from 0 for k ascending.  An empty slot counts as (index 0, distance 0), as pytorch3d pads its rows.
+ *   The weights are double (the reference's are f32, numpy's exp of an f32 array); exp is evaluated from IEEE operations in a
+ *   fixed order (tests/knn_ref.py::exp_neg, within 2 ulp), so the result is reproducible to the bit on any machine. */
+int gsr_knn_tile(void);
+int gsr_knn_seed(void);
+int gsr_knn_queries(void);
+int gsr_knn_max_k(void);
+size_t gsr_knn_workspace_bytes(int N, int M, int K);
+int gsr_knn_prepare(int M, const float* candidates, const long long* order, void* workspace, gsr_stream_t stream);
+int gsr_knn_search(int N, int M, int K, const float* queries, const long long* query_order, const long long* query_pos,
+                   const void* workspace, int exclude_self, int cull, int* idx, float* d2, unsigned long long* stats,
+                   gsr_stream_t stream);
+int gsr_knn_mean_d2(int N, int K, const float* d2, float* out, gsr_stream_t stream);
+int gsr_knn_segment_mean(int n, int S, int C, const long long* segment_ids, const long long* order, const double* values,
+                         double* out, int* count, gsr_stream_t stream);
+int gsr_knn_weighted_mean(int N, int K, int C, int M, const int* idx, const float* d2, const double* values, double inv_scale,
+                          double* out, gsr_stream_t stream);
+
 /* Tuning aid: when device_buffer is non-NULL (4*T uint64), the two blend kernels record the start/end wall
  * clock (100 MHz) of every workgroup: forward at [2*b], backward at [2*(T+b)], b = launch index.  NULL = off. */
 int gsr_debug_set_trace(void* device_buffer);
