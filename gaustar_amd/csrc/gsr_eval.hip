@@ -3,7 +3,7 @@
 // F-score, PSNR).  The reference scores from PNG directories with torchvision and lpips (gaussian_splatting/metrics.py,
 // utils/image_utils.py) and has no geometric score; nothing here mirrors a library, the definitions are include/gsr.h's own.
 //   face records        eval_gather_kernel         tri [9,F] f64: a, b, c of every face, coordinate-major, NaN for a face left out
-//   closest point       eval_closest_kernel        the one O(K F) step: track_nn_kernel's shape -- 256 threads, 16 queries per
+//   closest point       eval_closest_kernel        the one O(K F) step: gsr_surface.h's tnn_search -- 256 threads, 16 queries per
 //                                                  workgroup, the records staged through LDS in tiles of 512 faces (9 x 512
 //                                                  doubles = 36 KiB) and split 16 ways among the lanes -- with the region test
 //                                                  written as selects, so lanes that hold different faces do not diverge, one
@@ -27,7 +27,6 @@ namespace {
 constexpr int EV_BLOCK = MESH_BLOCK;
 constexpr int EV_TILE = 512;        // faces staged in LDS at once: 9 x 512 doubles = 36 KiB
 constexpr int EV_MAX_THR = 8;       // thresholds of one gsr_eval_distance_stats call
-constexpr int EV_NONE = 0x7fffffff;
 
 // The closest point of triangle (a, b, c) to p, as include/gsr.h states it -> the squared distance; v, w its barycentrics on
 // b and c (u is formed by the caller), q the point.  Every region's (nv, nw, den) is chosen by selects.
@@ -74,16 +73,6 @@ __global__ void __launch_bounds__(EV_BLOCK) eval_gather_kernel(int F, int V, con
     tri[6 * n + f] = t2.x; tri[7 * n + f] = t2.y; tri[8 * n + f] = t2.z;
 }
 
-__device__ __forceinline__ void eval_stage(double (*tile)[EV_TILE], const double* __restrict__ tri, int F, int base, int n)
-{
-    __syncthreads();                                         // (the tile before is read to its end)
-    for (int e = threadIdx.x; e < 9 * n; e += TNN_BLOCK) {
-        const int row = e / n, j = e - row * n;
-        tile[row][j] = tri[(size_t)row * F + base + j];
-    }
-    __syncthreads();
-}
-
 // slot s < n = min(S, *n_live) (S where n_live == NULL) is query k = list ? list[s] : s, k in [0, K).  Per slot: face = the
 // lowest j among those with the smallest d2, bary (u, v, w), closest q, dist = sqrt(d2).  grid = ceil(S / 16): the surplus
 // workgroups exit on n.  A pair whose d2 is NaN ranks nothing; a slot for which no face ranks gets face -1, dist +inf, NaN
@@ -94,44 +83,39 @@ __global__ void __launch_bounds__(TNN_BLOCK) eval_closest_kernel(int S, const in
                                                                  double* __restrict__ closest, double* __restrict__ dist,
                                                                  int* __restrict__ err)
 {
-    __shared__ double tile[9][EV_TILE];
-    __shared__ double part_d[TNN_BLOCK / 64][TNN_QUERIES];
-    __shared__ int part_i[TNN_BLOCK / 64][TNN_QUERIES];
     int n = n_live ? *n_live : S;
     n = n < S ? n : S;
-    if (blockIdx.x * TNN_QUERIES >= n) return;               // (the whole workgroup)
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int ql = lane & (TNN_QUERIES - 1), slice = wave * 4 + (lane >> 4);
-    const int slot = blockIdx.x * TNN_QUERIES + ql;
+    if (blockIdx.x * TNN_QUERIES >= n) return;               // (the whole workgroup, ahead of tnn_search's barriers)
+    const int slot = blockIdx.x * TNN_QUERIES + tnn_query();
     const bool live = slot < n;
     const double nan = __builtin_nan("");
     D3 p = {nan, nan, nan};                                  // (a slot without a query ranks nothing)
     if (live) {
         const int k = list ? list[slot] : slot;
         if ((unsigned)k < (unsigned)K) p = load3(pts, (size_t)k);
-        else if (wave == 0 && lane < TNN_QUERIES) atomicOr(err, MESH_ERR_INDEX);
+        else if (tnn_owner()) atomicOr(err, MESH_ERR_INDEX);
     }
-    double bd = __builtin_inf();
-    int bi = EV_NONE;
-    for (int base = 0; base < F; base += EV_TILE) {
-        const int m = F - base < EV_TILE ? F - base : EV_TILE;
-        eval_stage(tile, tri, F, base, m);
-        for (int j = slice; j < m; j += TNN_SLICES) {        // ascending index: `<` keeps the lowest among equals
+    double bd;
+    int bi;
+    tnn_search<9, EV_TILE, 1>(
+        F, bd, bi,
+        [&](double (*tile)[EV_TILE], int base, int m) {
+            for (int e = threadIdx.x; e < 9 * m; e += TNN_BLOCK) {
+                const int row = e / m, j = e - row * m;
+                tile[row][j] = tri[(size_t)row * F + base + j];
+            }
+        },
+        [&](const double (*tile)[EV_TILE], int j) {
             const D3 a = {tile[0][j], tile[1][j], tile[2][j]}, b = {tile[3][j], tile[4][j], tile[5][j]},
                      c = {tile[6][j], tile[7][j], tile[8][j]};
             double v, w;
             D3 q;
-            const double d2 = closest_on_face(p, a, b, c, v, w, q);
-            const bool better = d2 < bd;
-            bd = better ? d2 : bd;
-            bi = better ? base + j : bi;
-        }
-    }
-    tnn_combine(bd, bi, part_d, part_i);
-    if (!(wave == 0 && lane < TNN_QUERIES && live)) return;
+            return closest_on_face(p, a, b, c, v, w, q);
+        });
+    if (!(tnn_owner() && live)) return;
     D3 uvw = {nan, nan, nan}, q = {nan, nan, nan};
     double d = __builtin_inf();
-    if (bi == EV_NONE) {
+    if (bi == TNN_NONE) {
         atomicOr(err, MESH_ERR_NAN);
         bi = -1;
     } else {
@@ -293,12 +277,6 @@ __global__ void __launch_bounds__(RED_BLOCK) eval_total_kernel(int n_wg, const d
     }
 }
 
-inline int reduce_grid(long long n)
-{
-    const long long want = (n + RED_BLOCK - 1) / RED_BLOCK;
-    return (int)(want < 1 ? 1 : (want < RED_MAX_WGS ? want : RED_MAX_WGS));
-}
-
 inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
 
 }  // namespace
@@ -377,7 +355,7 @@ int gsr_eval_distance_stats(long long K, const double* dist, int T, const double
         return fail_msg("gsr_eval_distance_stats: arrays must be 8-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     GSR_CHECK(hipMemsetAsync(out, 0, (3 + (size_t)T) * 8, st));
-    const int n_wg = reduce_grid(K);
+    const int n_wg = K > 0 ? reduce_workgroups(K) : 1;      // (K = 0: one workgroup writes the zero partials)
     double* partials = static_cast<double*>(workspace);
     eval_stats_kernel<<<(unsigned)n_wg, RED_BLOCK, 0, st>>>(K, dist, T, thresholds, partials, static_cast<unsigned long long*>(out));
     eval_total_kernel<2><<<1, RED_BLOCK, 0, st>>>(n_wg, partials, static_cast<double*>(out));
@@ -395,7 +373,7 @@ int gsr_eval_image_sse(int C, int H, int W, const float* pred, long long ps0, lo
     if (!aligned8(workspace) || !aligned8(out)) return fail_msg("gsr_eval_image_sse: workspace and out must be 8-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     GSR_CHECK(hipMemsetAsync(out, 0, 16, st));
-    const int n_wg = reduce_grid((long long)C * H * W);
+    const int n_wg = reduce_workgroups((long long)C * H * W);
     double* partials = static_cast<double*>(workspace);
     eval_image_sse_kernel<<<(unsigned)n_wg, RED_BLOCK, 0, st>>>(C, H, W, pred, ps0, ps1, ps2, gt, gs0, gs1, gs2, mask, clamp01, partials,
                                                                  static_cast<unsigned long long*>(out) + 1);

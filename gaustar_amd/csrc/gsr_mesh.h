@@ -25,4 +25,11 @@ __device__ __forceinline__ bool mesh_face(const int* __restrict__ faces, int f, 
     return (unsigned)v[0] < (unsigned)V && (unsigned)v[1] < (unsigned)V && (unsigned)v[2] < (unsigned)V;
 }
 
+// the key of the undirected edge (a, b): min << 32 | max
+__device__ __forceinline__ long long edge_key(int a, int b)
+{
+    const int lo = a < b ? a : b, hi = a < b ? b : a;
+    return ((long long)lo << 32) | (long long)(unsigned)hi;
+}
+
 }  // namespace gsr

@@ -21,6 +21,7 @@
 #include "../../include/gsr.h"
 #include "gsr_entry.h"
 #include "gsr_reduce.h"
+#include "gsr_v3.h"
 #include <cstdio>
 
 namespace gsr {
@@ -30,19 +31,12 @@ namespace {
 constexpr int ML_UNIFORM = 0, ML_COT = 1, ML_COTCURV = 2;
 constexpr double ML_HERON_MIN = 1e-12;   // pytorch3d cot_laplacian: area = sqrt(clamp(s (s-A) (s-B) (s-C), min = 1e-12))
 
+// (contracted, unlike gsr_surface.h's D3: the f64 Laplacian path was written and pinned with the build's default)
 struct D3 { double x, y, z; };
 __device__ __forceinline__ D3 ld3d(const float* __restrict__ v, int i) { return D3{(double)v[3 * i], (double)v[3 * i + 1], (double)v[3 * i + 2]}; }
 __device__ __forceinline__ D3 sub(D3 a, D3 b) { return D3{a.x - b.x, a.y - b.y, a.z - b.z}; }
 __device__ __forceinline__ double norm(D3 a) { return sqrt(a.x * a.x + a.y * a.y + a.z * a.z); }
 __device__ __forceinline__ void axpy(D3& s, double a, D3 v) { s.x += a * v.x; s.y += a * v.y; s.z += a * v.z; }
-
-struct V3 { float x, y, z; };
-__device__ __forceinline__ V3 ld3(const float* __restrict__ v, int i) { return V3{v[3 * i], v[3 * i + 1], v[3 * i + 2]}; }
-__device__ __forceinline__ V3 sub(V3 a, V3 b) { return V3{a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ V3 add(V3 a, V3 b) { return V3{a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ V3 mul(float s, V3 a) { return V3{s * a.x, s * a.y, s * a.z}; }
-__device__ __forceinline__ float dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ V3 cross(V3 a, V3 b) { return V3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
 
 }  // namespace
 
@@ -81,12 +75,6 @@ WsLayout ws_layout(int V, int F)
     w.fc = o; o += align_up((size_t)(F > 0 ? F : 0) * 4 * sizeof(double));
     w.total = o + 256;
     return w;
-}
-
-int capped_workgroups(int n)
-{
-    const long long wg = ((long long)n + RED_BLOCK - 1) / RED_BLOCK;
-    return (int)(wg < RED_MAX_WGS ? wg : RED_MAX_WGS);
 }
 
 __device__ __forceinline__ float cross_area(const MeshLapArgs& m, int f, V3* u, V3* w, V3* c, float* len)
@@ -335,7 +323,7 @@ int gsr_mesh_lap_forward(int V, int F, const float* verts, const int* faces, con
         const MeshLapArgs m = make_args(V, F, verts, faces, nbr_offsets, nbr, vf_offsets, vf_entries, method, laplacian_factor,
                                         area_reg_factor, workspace);
         const int want_cot = m.use_lap && method != ML_UNIFORM && F > 0;
-        const int n_wg_f = capped_workgroups(F), n_wg_v = capped_workgroups(V);
+        const int n_wg_f = reduce_workgroups(F), n_wg_v = reduce_workgroups(V);
         if (want_cot || m.use_areg) mesh_lap_face_kernel<<<n_wg_f, RED_BLOCK, 0, st>>>(m, want_cot);
         if (m.use_areg) mesh_lap_areg_kernel<<<n_wg_f, RED_BLOCK, 0, st>>>(m, n_wg_f);
         if (m.use_lap) mesh_lap_vertex_kernel<<<n_wg_v, RED_BLOCK, 0, st>>>(m);

@@ -23,6 +23,7 @@
 #include "../../include/gsr.h"
 #include "gsr_entry.h"
 #include "gsr_reduce.h"
+#include "gsr_v3.h"
 #include <cstdio>
 
 namespace gsr {
@@ -32,15 +33,6 @@ namespace {
 constexpr int MR_BLOCK = 256;       // backward (the forward pair runs RED_BLOCK lanes)
 constexpr int MR_VPB = 32;          // backward: vertices per workgroup (config C: ~24 incidences each -> 3 chunks of 256)
 constexpr float MR_EPS = 1e-8f;     // torch.nn.functional.cosine_similarity's default eps, as pytorch3d calls it
-
-struct V3 { float x, y, z; };
-__device__ __forceinline__ V3 ld3(const float* __restrict__ v, int i) { return V3{v[3 * i], v[3 * i + 1], v[3 * i + 2]}; }
-__device__ __forceinline__ V3 sub(V3 a, V3 b) { return V3{a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ V3 add(V3 a, V3 b) { return V3{a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ V3 mul(float s, V3 a) { return V3{s * a.x, s * a.y, s * a.z}; }
-__device__ __forceinline__ V3 neg(V3 a) { return V3{-a.x, -a.y, -a.z}; }
-__device__ __forceinline__ float dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ V3 cross(V3 a, V3 b) { return V3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
 
 }  // namespace
 
@@ -207,13 +199,6 @@ MeshRegArgs make_args(int F, int E, int Q, const float* verts, const int* faces,
     return m;
 }
 
-int fwd_workgroups(int F, int E, int Q)
-{
-    const long long n = (long long)Q + E + F;
-    const long long wg = (n + RED_BLOCK - 1) / RED_BLOCK;
-    return (int)(wg < RED_MAX_WGS ? wg : RED_MAX_WGS);
-}
-
 int mesh_reg_check(const char* fn, int V, int F, int E, int Q, const float* verts, const int* faces, const int* edges,
                    const int* pairs)
 {
@@ -259,7 +244,7 @@ int gsr_mesh_reg_forward(int V, int F, int E, int Q, const float* verts, const i
         Scope sc(ST_LOSS, st);
         const MeshRegArgs m = make_args(F, E, Q, verts, faces, edges, pairs, ref_edge_len, ref_area, nc_factor, edge_factor, area_factor);
         double* partials = static_cast<double*>(workspace);
-        const int n_wg = fwd_workgroups(F, E, Q);
+        const int n_wg = reduce_workgroups((long long)Q + E + F);
         if (n_wg > 0) mesh_reg_fwd_kernel<<<n_wg, RED_BLOCK, 0, st>>>(m, partials);
         mesh_reg_finalize_kernel<<<1, RED_BLOCK, 0, st>>>(n_wg, partials, Q, E, F, nc_factor, edge_factor, area_factor, m.use_nc,
                                                          m.use_edge, m.use_area, loss_out);

@@ -251,12 +251,7 @@ ParamRegArgs make_args(int N, int M, const float* delta_t, const float* delta_r,
     return a;
 }
 
-int n_workgroups(int N)
-{
-    const long long groups = ((long long)N + PR_G - 1) / PR_G;
-    const long long wg = (groups + PR_BLOCK - 1) / PR_BLOCK;
-    return (int)(wg < RED_MAX_WGS ? wg : RED_MAX_WGS);
-}
+int n_workgroups(int N) { return reduce_workgroups(((long long)N + PR_G - 1) / PR_G); }   // (PR_BLOCK lanes each take a group)
 
 // gsr_param_reg_backward's launch: a skipped term touches no gradient buffer
 void launch_param_reg_grad(ParamRegArgs a, float factor_t, float factor_r, float sh_factor, const float* scale, float* d_delta_t,

@@ -71,6 +71,13 @@ __device__ __forceinline__ void tree_total(int n_wg, const double* __restrict__ 
     }
 }
 
+// the grid of an element pass over n elements: a workgroup per RED_BLOCK of them, grid-stride beyond RED_MAX_WGS (0 for n = 0)
+inline int reduce_workgroups(long long n)
+{
+    const long long wg = (n + RED_BLOCK - 1) / RED_BLOCK;
+    return (int)(wg < RED_MAX_WGS ? wg : RED_MAX_WGS);
+}
+
 inline size_t reduce_workspace_bytes() { return align_up(RED_STRIDE * sizeof(double) * RED_MAX_WGS) + 256; }
 
 }  // namespace

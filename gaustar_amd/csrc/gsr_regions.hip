@@ -39,12 +39,6 @@ constexpr int RG_WALK = 8;                                 // neighbours looked 
 
 struct RegionBox { double lo[3], hi[3]; };
 
-__device__ __forceinline__ long long edge_key(int a, int b)
-{
-    const int lo = a < b ? a : b, hi = a < b ? b : a;
-    return ((long long)lo << 32) | (long long)(unsigned)hi;
-}
-
 // ---------------------------------------------------------------------------------------------------- edge multiplicity
 // Face-edge e of face (a, b, c) is (a, b), (b, c), (c, a) for e = 0, 1, 2 (trimesh's faces_to_edges).
 __global__ void __launch_bounds__(RG_BLOCK) regions_edge_key_kernel(int F, const int* __restrict__ faces, const unsigned char* __restrict__ mask,

@@ -19,7 +19,7 @@
 // same inputs give the same bits, the bits tests/remesh_ref.py gives.
 #include "../../include/gsr.h"
 #include "gsr_entry.h"
-#include "gsr_mesh.h"
+#include "gsr_surface.h"
 
 #pragma clang fp contract(off)
 
@@ -30,12 +30,6 @@ namespace {
 constexpr int RM_BLOCK = MESH_BLOCK;
 constexpr long long RM_SENTINEL = 0x7fffffffffffffffll;   // above every key
 constexpr double RM_DET_REL = 1e-10;                       // Cramer's rule iff |det| > RM_DET_REL s^3, s = the largest |entry| of the 3x3
-
-__device__ __forceinline__ long long edge_key(int a, int b)
-{
-    const int lo = a < b ? a : b, hi = a < b ? b : a;
-    return ((long long)lo << 32) | (long long)(unsigned)hi;
-}
 
 // the vertex -> face lists of one round: vertex v's live incidences are corners[off[v] .. off[v + 1]) in ascending 3 face + corner
 struct VertexFaces {
@@ -51,14 +45,6 @@ struct VertexFaces {
         return c >= 0 && c < n3 ? (int)(c / 3) : -1;
     }
 };
-
-struct Vec3 { double x, y, z; };
-
-__device__ __forceinline__ Vec3 load3(const double* __restrict__ p, int v) { return {p[3 * (size_t)v], p[3 * (size_t)v + 1], p[3 * (size_t)v + 2]}; }
-__device__ __forceinline__ Vec3 sub(Vec3 a, Vec3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-// each component two rounded products and one subtraction
-__device__ __forceinline__ Vec3 cross(Vec3 a, Vec3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-__device__ __forceinline__ double dot(Vec3 a, Vec3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
 
 // ---------------------------------------------------------------------------------------------------- setup
 __global__ void __launch_bounds__(RM_BLOCK) remesh_widen_kernel(long long n, const float* __restrict__ in, double* __restrict__ out)
@@ -88,9 +74,9 @@ __global__ void __launch_bounds__(RM_BLOCK) remesh_face_quadric_kernel(int F, in
     if (!ok) {
         atomicOr(err, MESH_ERR_INDEX);
     } else {
-        const Vec3 x0 = load3(pos, v[0]);
-        const Vec3 n = cross(sub(load3(pos, v[1]), x0), sub(load3(pos, v[2]), x0));
-        const double len = sqrt(dot(n, n));
+        const D3 x0 = load3(pos, (size_t)v[0]);
+        const D3 n = cross3(sub3(load3(pos, (size_t)v[1]), x0), sub3(load3(pos, (size_t)v[2]), x0));
+        const double len = sqrt(dot3(n, n));
         if (len > 0.0) {
             p[0] = n.x / len; p[1] = n.y / len; p[2] = n.z / len;
             p[3] = -((p[0] * x0.x + p[1] * x0.y) + p[2] * x0.z);
@@ -172,7 +158,7 @@ __global__ void __launch_bounds__(RM_BLOCK) remesh_edge_kernel(int n, int V, con
 struct Quadric { double q[10]; };   // aa ab ac ad bb bc bd cc cd dd
 
 // max(x^T Q x, 0) with x = (p, 1): the four rows first, each ((a x + b y) + c z) + d, then ((x r0 + y r1) + z r2) + r3
-__device__ __forceinline__ double quadric_cost(const Quadric& Q, Vec3 p)
+__device__ __forceinline__ double quadric_cost(const Quadric& Q, D3 p)
 {
     const double* q = Q.q;
     const double r0 = ((q[0] * p.x + q[1] * p.y) + q[2] * p.z) + q[3];
@@ -186,7 +172,7 @@ __device__ __forceinline__ double quadric_cost(const Quadric& Q, Vec3 p)
 __device__ __forceinline__ double abs_max(double a, double b) { const double x = fabs(b); return x > a ? x : a; }
 
 // the position of the merged vertex and its cost
-__device__ __forceinline__ double place(const Quadric& Q, Vec3 pu, Vec3 pv, Vec3& best)
+__device__ __forceinline__ double place(const Quadric& Q, D3 pu, D3 pv, D3& best)
 {
     const double* q = Q.q;
     const double c00 = q[4] * q[7] - q[5] * q[5], c01 = q[1] * q[7] - q[5] * q[2], c02 = q[1] * q[5] - q[4] * q[2];
@@ -202,7 +188,7 @@ __device__ __forceinline__ double place(const Quadric& Q, Vec3 pu, Vec3 pv, Vec3
         best = {dx / det, dy / det, dz / det};
         return quadric_cost(Q, best);
     }
-    const Vec3 mid = {0.5 * (pu.x + pv.x), 0.5 * (pu.y + pv.y), 0.5 * (pu.z + pv.z)};
+    const D3 mid = {0.5 * (pu.x + pv.x), 0.5 * (pu.y + pv.y), 0.5 * (pu.z + pv.z)};
     double cost = quadric_cost(Q, pu);
     best = pu;
     const double cv = quadric_cost(Q, pv), cm = quadric_cost(Q, mid);
@@ -214,15 +200,15 @@ __device__ __forceinline__ double place(const Quadric& Q, Vec3 pu, Vec3 pv, Vec3
 __device__ __forceinline__ bool has(const int (&c)[3], int w) { return c[0] == w || c[1] == w || c[2] == w; }
 
 // false where moving u and v to x turns face c over (n_before . n_after < 0) or flattens it (== 0 with n_before != 0)
-__device__ __forceinline__ bool keeps_side(const double* __restrict__ pos, const int (&c)[3], int u, int v, Vec3 x)
+__device__ __forceinline__ bool keeps_side(const double* __restrict__ pos, const int (&c)[3], int u, int v, D3 x)
 {
-    Vec3 p[3], y[3];
+    D3 p[3], y[3];
     for (int k = 0; k < 3; ++k) {
-        p[k] = load3(pos, c[k]);
+        p[k] = load3(pos, (size_t)c[k]);
         y[k] = (c[k] == u || c[k] == v) ? x : p[k];
     }
-    const Vec3 nb = cross(sub(p[1], p[0]), sub(p[2], p[0])), na = cross(sub(y[1], y[0]), sub(y[2], y[0]));
-    const double d = dot(nb, na);
+    const D3 nb = cross3(sub3(p[1], p[0]), sub3(p[2], p[0])), na = cross3(sub3(y[1], y[0]), sub3(y[2], y[0]));
+    const double d = dot3(nb, na);
     if (d < 0.0) return false;
     if (d == 0.0 && (nb.x != 0.0 || nb.y != 0.0 || nb.z != 0.0)) return false;
     return true;
@@ -275,8 +261,8 @@ __device__ long long candidate_key(int e, int u, int v, int V, const VertexFaces
     // placement and cost
     Quadric Q;
     for (int t = 0; t < 10; ++t) Q.q[t] = Qv[10 * (size_t)u + t] + Qv[10 * (size_t)v + t];
-    Vec3 x;
-    const double cost = place(Q, load3(pos, u), load3(pos, v), x);
+    D3 x;
+    const double cost = place(Q, load3(pos, (size_t)u), load3(pos, (size_t)v), x);
     const unsigned bits = __float_as_uint((float)cost);
     if ((bits & 0x7f800000u) == 0x7f800000u) return RM_SENTINEL;
     // flip test over the other faces of u, then of v
@@ -428,19 +414,19 @@ __global__ void __launch_bounds__(RM_BLOCK) remesh_smooth_kernel(int V, const in
 {
     const int v = blockIdx.x * RM_BLOCK + threadIdx.x;
     if (v >= V) return;
-    const Vec3 p = load3(in, v);
-    Vec3 r = p;
+    const D3 p = load3(in, (size_t)v);
+    D3 r = p;
     const int b = off[v], e = off[v + 1];
     if (e > b && !(locked && locked[v])) {
         double sx = 0.0, sy = 0.0, sz = 0.0, sw = 0.0;
         for (int i = b; i < e; ++i) {
             const int n = nbr[i];
             if ((unsigned)n >= (unsigned)V) continue;
-            const Vec3 q = load3(in, n);
+            const D3 q = load3(in, (size_t)n);
             double w = 1.0;
             if (!uniform) {
-                const Vec3 d = sub(p, q);
-                w = 1.0 / (sqrt(dot(d, d)) + 1e-12);
+                const D3 d = sub3(p, q);
+                w = 1.0 / (sqrt(dot3(d, d)) + 1e-12);
             }
             sx += w * q.x; sy += w * q.y; sz += w * q.z;
             sw += w;

@@ -283,8 +283,7 @@ int gsr_splice_mean(long long n, const double* x, void* workspace, double* mean,
     if ((reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(mean)) & 7)
         return fail_msg("gsr_splice_mean: arrays must be 8-byte aligned");
     hipStream_t st = (hipStream_t)stream;
-    const long long want = (n + RED_BLOCK - 1) / RED_BLOCK;
-    const int n_wg = (int)(want < RED_MAX_WGS ? want : RED_MAX_WGS);
+    const int n_wg = reduce_workgroups(n);
     double* partials = static_cast<double*>(workspace);
     splice_sum_kernel<<<(unsigned)n_wg, RED_BLOCK, 0, st>>>(n, x, partials);
     splice_mean_kernel<<<1, RED_BLOCK, 0, st>>>(n_wg, partials, n, mean);

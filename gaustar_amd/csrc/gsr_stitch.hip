@@ -6,8 +6,8 @@
 // The reference does this on the host with pytorch3d's knn_points, trimesh's group_rows / nondegenerate_faces /
 // remove_unreferenced_vertices and scipy's connected_components.  Here, over device tensors:
 //   nearest vertex      stitch_nn_kernel           the one O(Bq Bc) step: per query the (d2, index) minimum over the candidates,
-//                                                  d2 in float64 without contraction; 16 queries per workgroup, the candidates
-//                                                  staged through LDS in tiles of 1024 and split 16 ways among the lanes
+//                                                  d2 in float64 without contraction; gsr_surface.h's tnn_search: 16 queries per
+//                                                  workgroup, the candidates staged through LDS in tiles of 1024, split 16 ways
 //   index lists         stitch_check_list_kernel   range and uniqueness of a boundary list, through the err word
 //   snap groups         stitch_group_min / _remap_kernel   after the two snaps every listed vertex sits at an original pc1
 //                                                  position, named by the LOWEST pc1 index that holds it (the nearest search
@@ -25,8 +25,8 @@
 #include "../../include/gsr.h"
 #include "gsr_entry.h"
 #include "gsr_internal.h"
-#include "gsr_mesh.h"
 #include "gsr_unionfind.h"
+#include "gsr_surface.h"
 
 #pragma clang fp contract(off)
 
@@ -35,81 +35,47 @@ namespace gsr {
 namespace {
 
 constexpr int ST_BLOCK = MESH_BLOCK;
-constexpr int NN_BLOCK = 256;       // four waves
-constexpr int NN_QUERIES = 16;      // queries of a workgroup: lane & 15 of every wave
-constexpr int NN_SLICES = 16;       // shares of a tile's candidates: 4 waves x (lane >> 4); slice s takes j = s, s + 16, ...
 constexpr int NN_TILE = 1024;       // candidates staged in LDS at once: 3 x 1024 doubles = 24 KiB
-
-// the lexicographic (d2, index) minimum: the same whatever the order the parts are combined in
-__device__ __forceinline__ void nn_take(double& bd, int& bi, double od, int oi)
-{
-    if (od < bd || (od == bd && oi < bi)) { bd = od; bi = oi; }
-}
-
-__device__ __forceinline__ bool finite3(float x, float y, float z) { return (x - x) == 0.f && (y - y) == 0.f && (z - z) == 0.f; }
 
 // idx [Bq], d2 [Bq]; max_bits [1] (zero before): the largest d2's bits.  grid = ceil(Bq / 16).  A coordinate that is not finite
 // sets err bit 1 (the differences would be NaN and rank nothing); idx stays inside [0, Bc) even then.
-__global__ void __launch_bounds__(NN_BLOCK) stitch_nn_kernel(int Bq, int Bc, const float* __restrict__ q, const float* __restrict__ c,
+__global__ void __launch_bounds__(TNN_BLOCK) stitch_nn_kernel(int Bq, int Bc, const float* __restrict__ q, const float* __restrict__ c,
                                                              int* __restrict__ idx, double* __restrict__ d2,
                                                              unsigned long long* __restrict__ max_bits, int* __restrict__ err)
 {
-    __shared__ double tile[3][NN_TILE];
-    __shared__ double part_d[NN_BLOCK / 64][NN_QUERIES];
-    __shared__ int part_i[NN_BLOCK / 64][NN_QUERIES];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int ql = lane & (NN_QUERIES - 1), slice = wave * 4 + (lane >> 4);
-    const int qi = blockIdx.x * NN_QUERIES + ql;
+    const int qi = blockIdx.x * TNN_QUERIES + tnn_query();
     const bool live = qi < Bq;
     double qx = 0., qy = 0., qz = 0.;
     if (live) {
-        const float x = q[3 * (size_t)qi], y = q[3 * (size_t)qi + 1], z = q[3 * (size_t)qi + 2];
-        if (slice == 0 && !finite3(x, y, z)) atomicOr(err, MESH_ERR_NAN);
-        qx = (double)x; qy = (double)y; qz = (double)z;
+        qx = (double)q[3 * (size_t)qi]; qy = (double)q[3 * (size_t)qi + 1]; qz = (double)q[3 * (size_t)qi + 2];
+        if (tnn_owner() && !finite3(D3{qx, qy, qz})) atomicOr(err, MESH_ERR_NAN);
     }
-    double bd = __builtin_inf();
-    int bi = 0x7fffffff;
-    for (int base = 0; base < Bc; base += NN_TILE) {
-        const int n = Bc - base < NN_TILE ? Bc - base : NN_TILE;
-        __syncthreads();                                     // (the tile before is read to its end)
-        const float* src = c + 3 * (size_t)base;
-        for (int e = t; e < 3 * n; e += NN_BLOCK) {
-            const float v = src[e];
-            if (blockIdx.x == 0 && (v - v) != 0.f) atomicOr(err, MESH_ERR_NAN);
-            tile[e % 3][e / 3] = (double)v;
-        }
-        __syncthreads();
-#pragma unroll 4
-        for (int j = slice; j < n; j += NN_SLICES) {        // ascending index: `<` keeps the lowest among equals
-            const double dx = qx - tile[0][j], dy = qy - tile[1][j], dz = qz - tile[2][j];
-            const double d = (dx * dx + dy * dy) + dz * dz;
-            if (d < bd) { bd = d; bi = base + j; }
-        }
-    }
-#pragma unroll
-    for (int m = 16; m < 64; m <<= 1) {                      // the four slices of this wave
-        const double od = __shfl_xor(bd, m);
-        const int oi = __shfl_xor(bi, m);
-        nn_take(bd, bi, od, oi);
-    }
-    if (lane < NN_QUERIES) { part_d[wave][lane] = bd; part_i[wave][lane] = bi; }
-    __syncthreads();
-    if (wave != 0) return;
+    double bd;
+    int bi;
+    tnn_search<3, NN_TILE, 4>(
+        Bc, bd, bi,
+        [&](double (*tile)[NN_TILE], int base, int n) {
+            const float* src = c + 3 * (size_t)base;
+            for (int e = threadIdx.x; e < 3 * n; e += TNN_BLOCK) {
+                const float v = src[e];
+                if (blockIdx.x == 0 && (v - v) != 0.f) atomicOr(err, MESH_ERR_NAN);
+                tile[e % 3][e / 3] = (double)v;
+            }
+        },
+        [&](const double (*tile)[NN_TILE], int j) { return tnn_d2(tile, j, qx, qy, qz); });
+    if (threadIdx.x >= 64) return;                           // (wave 0 holds the results; its 16 query lanes take the maximum)
     unsigned long long mb = 0ull;
-    if (lane < NN_QUERIES) {
-        for (int w = 1; w < NN_BLOCK / 64; ++w) nn_take(bd, bi, part_d[w][lane], part_i[w][lane]);
-        if (live) {
-            idx[qi] = bi == 0x7fffffff ? 0 : bi;
-            d2[qi] = bd;
-            if (bd == bd) mb = (unsigned long long)__double_as_longlong(bd);   // (bd >= 0: the bits' order is the values')
-        }
+    if (tnn_owner() && live) {
+        idx[qi] = bi == TNN_NONE ? 0 : bi;
+        d2[qi] = bd;
+        if (bd == bd) mb = (unsigned long long)__double_as_longlong(bd);   // (bd >= 0: the bits' order is the values')
     }
 #pragma unroll
-    for (int m = 1; m < NN_QUERIES; m <<= 1) {
+    for (int m = 1; m < TNN_QUERIES; m <<= 1) {
         const unsigned long long o = __shfl_xor(mb, m);
         mb = o > mb ? o : mb;
     }
-    if (lane == 0 && mb) atomicMax(max_bits, mb);
+    if (threadIdx.x == 0 && mb) atomicMax(max_bits, mb);
 }
 
 // mark [V] int32 (zero before): err bit 0 for an index outside [0, V), bit 2 for an index listed twice
@@ -299,7 +265,7 @@ using namespace gsr;
 extern "C" {
 
 int gsr_stitch_nn_tile(void) { return NN_TILE; }
-int gsr_stitch_nn_queries(void) { return NN_QUERIES; }
+int gsr_stitch_nn_queries(void) { return TNN_QUERIES; }
 
 int gsr_stitch_nearest(int Bq, int Bc, const float* queries, const float* candidates, int* idx, double* d2,
                        unsigned long long* max_bits, int* err, gsr_stream_t stream)
@@ -312,7 +278,7 @@ int gsr_stitch_nearest(int Bq, int Bc, const float* queries, const float* candid
     if (Bq == 0) return 0;
     if (Bc == 0) return fail_msg("gsr_stitch_nearest: no candidates");
     if (!queries || !candidates || !idx || !d2 || !err) return fail_msg("gsr_stitch_nearest: required pointer is null");
-    stitch_nn_kernel<<<(unsigned)((Bq + NN_QUERIES - 1) / NN_QUERIES), NN_BLOCK, 0, st>>>(Bq, Bc, queries, candidates, idx, d2, max_bits, err);
+    stitch_nn_kernel<<<(unsigned)((Bq + TNN_QUERIES - 1) / TNN_QUERIES), TNN_BLOCK, 0, st>>>(Bq, Bc, queries, candidates, idx, d2, max_bits, err);
     GSR_CHECK_LAUNCH("stitch_nn_kernel");
     return 0;
 }

@@ -1,6 +1,7 @@
-// gsr_surface.h -- what the kernels that work with points ON a mesh's surface (gsr_track.hip, gsr_eval.hip) share: a point of
-// three doubles, the dot product and bary_to_point as include/gsr.h states them, a face's three f64 vertices with the err word's
-// checks, and the (key, index) minimum of the searches that give 16 queries to a workgroup of 256 and split a tile 16 ways.
+// gsr_surface.h -- what the kernels that work in float64 on a mesh (gsr_track.hip, gsr_eval.hip, gsr_remesh.hip, and
+// gsr_stitch.hip's search) share: a point of three doubles, the dot and cross products and bary_to_point as include/gsr.h states
+// them, a face's three f64 vertices with the err word's checks, and tnn_search, the tiled (key, index)-minimum search of
+// stitch_nn_kernel, track_nn_kernel and eval_closest_kernel: 16 queries to a workgroup of 256, a tile split 16 ways.
 // All of it float64 without contraction: the pragma below stands in front of these functions (an including file's own pragma
 // comes after its includes and would leave them contracted) and holds for the rest of the translation unit.
 #pragma once
@@ -15,12 +16,15 @@ namespace {
 constexpr int TNN_BLOCK = 256;      // four waves
 constexpr int TNN_QUERIES = 16;     // queries of a workgroup: lane & 15 of every wave
 constexpr int TNN_SLICES = 16;      // shares of a tile: 4 waves x (lane >> 4); slice s takes j = s, s + 16, ...
+constexpr int TNN_NONE = 0x7fffffff;   // the index of a search in which no candidate ranked (every key NaN)
 
 struct D3 { double x, y, z; };
 
 __device__ __forceinline__ D3 load3(const double* __restrict__ p, size_t i) { return {p[3 * i], p[3 * i + 1], p[3 * i + 2]}; }
 __device__ __forceinline__ void store3(double* __restrict__ p, size_t i, D3 v) { p[3 * i] = v.x; p[3 * i + 1] = v.y; p[3 * i + 2] = v.z; }
 __device__ __forceinline__ D3 sub3(D3 a, D3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
+// each component two rounded products and one subtraction
+__device__ __forceinline__ D3 cross3(D3 a, D3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
 __device__ __forceinline__ double dot3(D3 a, D3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
 __device__ __forceinline__ bool finite1(double x) { return (x - x) == 0.; }
 __device__ __forceinline__ bool finite3(D3 a) { return finite1(a.x) && finite1(a.y) && finite1(a.z); }
@@ -62,6 +66,49 @@ __device__ __forceinline__ void tnn_combine(double& bd, int& bi, double (*part_d
     __syncthreads();
     if (lane < TNN_QUERIES)
         for (int w = 0; w < TNN_BLOCK / 64; ++w) tnn_take(bd, bi, part_d[w][lane], part_i[w][lane]);
+}
+
+// A thread's place in a search workgroup: thread t = 64 wave + lane holds query (lane & 15) and slice 4 wave + (lane >> 4) of
+// every tile.  Threads 0 .. 15 (slice 0 of each query) do what is done once per query: its checks, and after tnn_search its tail.
+__device__ __forceinline__ int tnn_query() { return threadIdx.x & (TNN_QUERIES - 1); }
+__device__ __forceinline__ bool tnn_owner() { return threadIdx.x < TNN_QUERIES; }
+
+// (bd, bi) = the smallest key(tile, j) over candidates j in [0, M) and the LOWEST j that has it, (+inf, TNN_NONE) if no key is
+// below +inf; valid in lanes < 16 of EVERY wave (tnn_combine).  The candidates pass through an LDS tile of ROWS x TILE doubles:
+// stage(tile, base, n) writes candidates [base, base + n) to columns [0, n), all TNN_BLOCK threads taking part, between the two
+// barriers here; key(tile, j) is this thread's query against column j.  The whole workgroup calls this, or none of it.
+// UNROLL is the slice loop's unroll count (1: none).
+template <int ROWS, int TILE, int UNROLL, class Stage, class Key>
+__device__ __forceinline__ void tnn_search(int M, double& bd, int& bi, Stage stage, Key key)
+{
+    __shared__ double tile[ROWS][TILE];
+    __shared__ double part_d[TNN_BLOCK / 64][TNN_QUERIES];
+    __shared__ int part_i[TNN_BLOCK / 64][TNN_QUERIES];
+    const int slice = (threadIdx.x >> 6) * 4 + ((threadIdx.x & 63) >> 4);
+    double d_min = __builtin_inf();                          // (locals: with the loop on the references track_nn_kernel carried
+    int j_min = TNN_NONE;                                    //  a second copy of the minimum, two VGPRs and two selects a pair)
+    for (int base = 0; base < M; base += TILE) {
+        const int n = M - base < TILE ? M - base : TILE;
+        __syncthreads();                                     // (the tile before is read to its end)
+        stage(tile, base, n);
+        __syncthreads();
+#pragma unroll UNROLL
+        for (int j = slice; j < n; j += TNN_SLICES) {        // ascending index: `<` keeps the lowest among equals
+            const double d = key(tile, j);
+            if (d < d_min) { d_min = d; j_min = base + j; }
+        }
+    }
+    tnn_combine(d_min, j_min, part_d, part_i);
+    bd = d_min;
+    bi = j_min;
+}
+
+// the squared distance from (qx, qy, qz) to column j of a tile of three rows x, y, z
+template <int TILE>
+__device__ __forceinline__ double tnn_d2(const double (*tile)[TILE], int j, double qx, double qy, double qz)
+{
+    const double dx = qx - tile[0][j], dy = qy - tile[1][j], dz = qz - tile[2][j];
+    return (dx * dx + dy * dy) + dz * dz;
 }
 
 }  // namespace

@@ -6,14 +6,14 @@
 //   rebind, survivors   track_survivors_kernel     a point whose face survived is re-expressed on that face (:94-107); the
 //                                                  others are flagged for the to-do list; three integer counts
 //   to-do list          track_todo_kernel          flag -> (torch.cumsum) -> scatter, its length in a device word
-//   nearest centre      track_nn_kernel            the one O(K F1) step (:110-112): stitch_nn_kernel's shape -- 256 threads, 16
+//   nearest centre      track_nn_kernel            the one O(K F1) step (:110-112): gsr_surface.h's tnn_search -- 256 threads, 16
 //                                                  queries per workgroup, the centres staged through LDS in tiles of 1024
-//                                                  (3 x 1024 doubles = 24 KiB) and split 16 ways among the lanes -- for f64
+//                                                  (3 x 1024 doubles = 24 KiB) and split 16 ways among the lanes -- with f64
 //                                                  queries, f64 centres and the rounded square root as the key
 //   rebind, displaced   track_displaced_kernel     the nearest face's barycentrics, clamped and renormalised (:115-121)
 // All arithmetic is float64 without contraction, every operation in the order include/gsr.h states.  No float atomics, no
 // scratch: the counts are integer atomics, the search combines by the lexicographic (key, index) minimum.  The point type, the dot
-// product, bary_to_point, a face's vertices and that minimum are gsr_surface.h's, shared with gsr_eval.hip.
+// product, bary_to_point, a face's vertices and that search are gsr_surface.h's, shared with gsr_eval.hip and gsr_stitch.hip.
 //
 // The square root.  numpy's argmin compares sqrt(d2), and two different d2 can share a rounded square root, so the minimum of
 // (d2, index) is not the answer: the search takes the square root of every pair and keeps the (s, index) minimum.  The other
@@ -132,14 +132,6 @@ __global__ void __launch_bounds__(TR_BLOCK) track_todo_kernel(int K, const int* 
     if (k == K - 1) *n_todo = s < 0 ? 0 : (s > K ? K : s);
 }
 
-__device__ __forceinline__ void tnn_stage(double (*tile)[TNN_TILE], const double* __restrict__ c, int base, int n)
-{
-    __syncthreads();                                         // (the tile before is read to its end)
-    const double* src = c + 3 * (size_t)base;
-    for (int e = threadIdx.x; e < 3 * n; e += TNN_BLOCK) tile[e % 3][e / 3] = src[e];
-    __syncthreads();
-}
-
 // idx [slot] int32 = the lowest j among those with the smallest sqrt((dx dx + dy dy) + dz dz), d = query - centre_j; slot s <
 // n = (n_live ? *n_live : K) is query (list ? list[s] : s).  grid = ceil(K / 16): the surplus workgroups exit on n.  A query or
 // centre that is NaN ranks nothing; idx stays inside [0, F1) even then.
@@ -147,15 +139,10 @@ __global__ void __launch_bounds__(TNN_BLOCK) track_nn_kernel(int K, const int* _
                                                              const double* __restrict__ q, const double* __restrict__ c,
                                                              int* __restrict__ idx)
 {
-    __shared__ double tile[3][TNN_TILE];
-    __shared__ double part_d[TNN_BLOCK / 64][TNN_QUERIES];
-    __shared__ int part_i[TNN_BLOCK / 64][TNN_QUERIES];
     int n = n_live ? *n_live : K;
     n = n < K ? n : K;
-    if (blockIdx.x * TNN_QUERIES >= n) return;               // (the whole workgroup)
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int ql = lane & (TNN_QUERIES - 1), slice = wave * 4 + (lane >> 4);
-    const int slot = blockIdx.x * TNN_QUERIES + ql;
+    if (blockIdx.x * TNN_QUERIES >= n) return;               // (the whole workgroup, ahead of tnn_search's barriers)
+    const int slot = blockIdx.x * TNN_QUERIES + tnn_query();
     const bool live = slot < n;
     double qx = 0., qy = 0., qz = 0.;
     if (live) {
@@ -163,20 +150,16 @@ __global__ void __launch_bounds__(TNN_BLOCK) track_nn_kernel(int K, const int* _
         k = (unsigned)k < (unsigned)K ? k : 0;
         qx = q[3 * (size_t)k]; qy = q[3 * (size_t)k + 1]; qz = q[3 * (size_t)k + 2];
     }
-    double bd = __builtin_inf();
-    int bi = 0x7fffffff;
-    for (int base = 0; base < F1; base += TNN_TILE) {
-        const int m = F1 - base < TNN_TILE ? F1 - base : TNN_TILE;
-        tnn_stage(tile, c, base, m);
-#pragma unroll 4
-        for (int j = slice; j < m; j += TNN_SLICES) {        // ascending index: `<` keeps the lowest among equals
-            const double dx = qx - tile[0][j], dy = qy - tile[1][j], dz = qz - tile[2][j];
-            const double d = sqrt((dx * dx + dy * dy) + dz * dz);
-            if (d < bd) { bd = d; bi = base + j; }
-        }
-    }
-    tnn_combine(bd, bi, part_d, part_i);
-    if (wave == 0 && lane < TNN_QUERIES && live) idx[slot] = bi == 0x7fffffff ? 0 : bi;
+    double bd;
+    int bi;
+    tnn_search<3, TNN_TILE, 4>(
+        F1, bd, bi,
+        [&](double (*tile)[TNN_TILE], int base, int m) {
+            const double* src = c + 3 * (size_t)base;
+            for (int e = threadIdx.x; e < 3 * m; e += TNN_BLOCK) tile[e % 3][e / 3] = src[e];
+        },
+        [&](const double (*tile)[TNN_TILE], int j) { return sqrt(tnn_d2(tile, j, qx, qy, qz)); });
+    if (tnn_owner() && live) idx[slot] = bi == TNN_NONE ? 0 : bi;
 }
 
 // slot s < n (as in track_nn_kernel) is point k and takes face j = idx[s]: ids_out[k] = j, bary_out[k] = point_to_bary(face j,

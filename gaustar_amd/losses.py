@@ -286,6 +286,29 @@ def _mesh_reg_refs(ref, n, dev, what):
     return r
 
 
+def _mesh_verts(verts, topo):
+    """verts [V,3] on the topology's device, checked -> the detached contiguous float32 tensor the mesh-loss kernels read"""
+    if not verts.is_cuda:
+        raise RuntimeError("gaustar_amd.losses: verts must live on a HIP (cuda) device -- there is no CPU path")
+    if verts.dim() != 2 or verts.size(1) != 3 or int(verts.size(0)) != topo.V:
+        raise RuntimeError(f"verts must have dimensions ({topo.V}, 3), got {tuple(verts.shape)}")
+    if topo.device != verts.device:
+        raise RuntimeError("the mesh topology lives on another device than the vertices")
+    v = verts.detach()
+    if v.dtype != torch.float32 or not v.is_contiguous():
+        v = v.float().contiguous()
+    return v
+
+
+def _check_vertex_grad(dL_dverts, v, topo):
+    """The buffer a mesh loss's grad_into writes must match the saved vertices v -> their device"""
+    dev = v.device
+    if dL_dverts.dtype != torch.float32 or not dL_dverts.is_contiguous() or tuple(dL_dverts.shape) != tuple(v.shape) \
+            or dL_dverts.device != dev:
+        raise RuntimeError(f"dL_dverts must be a contiguous float32 ({topo.V}, 3) tensor on {dev}")
+    return dev
+
+
 class _SurfaceMeshLoss(torch.autograd.Function):
     """The three surface-mesh regularisers of refine.py:676-706 as ONE autograd node over the vertices.  Forward:
     gsr_mesh_reg_forward (an element pass + a fixed-order reduction) -> {nc, edge, area, total} on the device.  Backward:
@@ -294,16 +317,7 @@ class _SurfaceMeshLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, verts, topo, nc_factor, ref_edge_len, edge_factor, ref_area, area_factor):
         lib = _lib.load()
-        if not verts.is_cuda:
-            raise RuntimeError("gaustar_amd.losses: verts must live on a HIP (cuda) device -- there is no CPU path")
-        if verts.dim() != 2 or verts.size(1) != 3 or int(verts.size(0)) != topo.V:
-            raise RuntimeError(f"verts must have dimensions ({topo.V}, 3), got {tuple(verts.shape)}")
-        dev = verts.device
-        if topo.device != dev:
-            raise RuntimeError("the mesh topology lives on another device than the vertices")
-        v = verts.detach()
-        if v.dtype != torch.float32 or not v.is_contiguous():
-            v = v.float().contiguous()
+        v, dev = _mesh_verts(verts, topo), verts.device
         re = _mesh_reg_refs(ref_edge_len, topo.E, dev, "ref_edge_len")
         ra = _mesh_reg_refs(ref_area, topo.F, dev, "ref_area")
         cfg = (float(nc_factor), float(edge_factor), float(area_factor))
@@ -311,7 +325,7 @@ class _SurfaceMeshLoss(torch.autograd.Function):
             ws = torch.empty(lib.gsr_mesh_reg_workspace_bytes(topo.V, topo.F, topo.E, topo.Q), dtype=torch.uint8, device=dev)
             out = torch.empty(4, dtype=torch.float32, device=dev)
             _lib.check(lib.gsr_mesh_reg_forward(
-                topo.V, topo.F, topo.E, topo.Q, _vp(v), _vp(topo.faces), _vp(topo.edges), _vp(topo.pairs), _op(re), _op(ra), *cfg,
+                topo.V, topo.F, topo.E, topo.Q, _vp(v), _vp(topo.faces), _vp(topo.edges), _vp(topo.pairs), _lib.ptr(re), _lib.ptr(ra), *cfg,
                 _vp(ws), _vp(out), _stream()), "gsr_mesh_reg_forward")
         ctx.topo, ctx.cfg, ctx.in_dtype = topo, cfg, verts.dtype
         if ctx.needs_input_grad[0]:
@@ -326,15 +340,12 @@ class _SurfaceMeshLoss(torch.autograd.Function):
         lib = _lib.load()
         v, re, ra = ctx.saved_tensors
         topo = ctx.topo
-        dev = v.device
-        if dL_dverts.dtype != torch.float32 or not dL_dverts.is_contiguous() or tuple(dL_dverts.shape) != tuple(v.shape) \
-                or dL_dverts.device != dev:
-            raise RuntimeError(f"dL_dverts must be a contiguous float32 ({topo.V}, 3) tensor on {dev}")
+        dev = _check_vertex_grad(dL_dverts, v, topo)
         with _host.on_device(dev):
             keep, sp = _scale_ptr(g_loss, dev)
             _lib.check(lib.gsr_mesh_reg_backward(
                 topo.V, topo.F, topo.E, topo.Q, _vp(v), _vp(topo.faces), _vp(topo.edges), _vp(topo.pairs), _vp(topo.csr_offsets),
-                _vp(topo.csr_entries), _op(re), _op(ra), *ctx.cfg, sp, _vp(dL_dverts), int(accumulate), _stream()),
+                _vp(topo.csr_entries), _lib.ptr(re), _lib.ptr(ra), *ctx.cfg, sp, _vp(dL_dverts), int(accumulate), _stream()),
                 "gsr_mesh_reg_backward")
         return dL_dverts
 
@@ -349,10 +360,6 @@ class _SurfaceMeshLoss(torch.autograd.Function):
 
 def _vp(t):
     return ctypes.c_void_p(t.data_ptr())
-
-
-def _op(t):
-    return None if t is None else _vp(t)
 
 
 def surface_mesh_loss(verts: torch.Tensor, topology, nc_factor: float, ref_edge_len: Optional[torch.Tensor] = None,
@@ -379,17 +386,8 @@ class _MeshSmoothnessLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, verts, topo, laplacian_factor, method, area_reg_factor):
-        if not verts.is_cuda:
-            raise RuntimeError("gaustar_amd.losses: verts must live on a HIP (cuda) device -- there is no CPU path")
+        v, dev = _mesh_verts(verts, topo), verts.device
         lib = _lib.load()
-        if verts.dim() != 2 or verts.size(1) != 3 or int(verts.size(0)) != topo.V:
-            raise RuntimeError(f"verts must have dimensions ({topo.V}, 3), got {tuple(verts.shape)}")
-        dev = verts.device
-        if topo.device != dev:
-            raise RuntimeError("the mesh topology lives on another device than the vertices")
-        v = verts.detach()
-        if v.dtype != torch.float32 or not v.is_contiguous():
-            v = v.float().contiguous()
         cfg = (_LAP_METHODS[method], float(laplacian_factor), float(area_reg_factor))
         lists = (*topo.vertex_neighbours, *topo.vertex_face_csr)
         with _host.on_device(dev):
@@ -411,10 +409,7 @@ class _MeshSmoothnessLoss(torch.autograd.Function):
         lib = _lib.load()
         v, ws = ctx.saved_tensors
         topo = ctx.topo
-        dev = v.device
-        if dL_dverts.dtype != torch.float32 or not dL_dverts.is_contiguous() or tuple(dL_dverts.shape) != tuple(v.shape) \
-                or dL_dverts.device != dev:
-            raise RuntimeError(f"dL_dverts must be a contiguous float32 ({topo.V}, 3) tensor on {dev}")
+        dev = _check_vertex_grad(dL_dverts, v, topo)
         lists = (*topo.vertex_neighbours, *topo.vertex_face_csr)
         with _host.on_device(dev):
             keep, sp = _scale_ptr(g_loss, dev)
@@ -506,7 +501,7 @@ class _GaussianParamLoss(torch.autograd.Function):
             ws = torch.empty(lib.gsr_param_reg_workspace_bytes(N), dtype=torch.uint8, device=dev)
             out = torch.empty(5, dtype=torch.float32, device=dev)
             _lib.check(lib.gsr_param_reg_forward(
-                N, M, _op(dt), _op(dr), _op(w), w_rs, w_cs, cfg[4], cfg[5], _op(dens), cfg[6], _op(dc), _op(pre), cfg[7],
+                N, M, _lib.ptr(dt), _lib.ptr(dr), _lib.ptr(w), w_rs, w_cs, cfg[4], cfg[5], _lib.ptr(dens), cfg[6], _lib.ptr(dc), _lib.ptr(pre), cfg[7],
                 _vp(ws), _vp(out), _stream()), "gsr_param_reg_forward")
         ctx.cfg = cfg
         ctx.have = tuple(x is not None for x in (dt, dr, w, dens, dc, pre))
@@ -533,8 +528,8 @@ class _GaussianParamLoss(torch.autograd.Function):
         with _host.on_device(dev):
             keep, sp = _scale_ptr(g_loss, dev)
             _lib.check(lib.gsr_param_reg_backward(
-                N, M, _op(dt), _op(dr), _op(w), w_rs, w_cs, factor_t, factor_r, _op(dens), min_opacity, _op(dc), _op(pre),
-                sh_factor, sp, *[_op(b) for b in buffers], int(accumulate), _stream()), "gsr_param_reg_backward")
+                N, M, _lib.ptr(dt), _lib.ptr(dr), _lib.ptr(w), w_rs, w_cs, factor_t, factor_r, _lib.ptr(dens), min_opacity, _lib.ptr(dc), _lib.ptr(pre),
+                sh_factor, sp, *[_lib.ptr(b) for b in buffers], int(accumulate), _stream()), "gsr_param_reg_backward")
         return buffers
 
     @staticmethod
