@@ -64,6 +64,7 @@ SIGNATURES = {
     "gsr_debug_export": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gsr_debug_export_masks": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "gsr_debug_export_units": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gsr_sh_to_rgb": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gsr_sh_to_rgb_backward": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p]),

@@ -45,6 +45,7 @@ template <class Counter> uint32_t next_nonzero(Counter& c)
 // one process):   GSR_OWN_COUNTERS   the library's self-cleaning counter block (off: the image buffer's counters, a fill per view)
 //                 GSR_SORT_IN_BLEND  short lists are sorted inside the forward blend (off: a separate sort kernel)
 //                 GSR_REPLAN         a planned view builds the next view's plan (off: a plan lives until a view outgrows it)
+//                 GSR_BWD_LIVE       the backward blend's waves leave on the forward's per-(unit, block) flags (off: flags ignored)
 // Once per process: GSR_SYNC_SPIN      stage 1 polls the pinned pad for its totals (off: hipStreamSynchronize)
 //                   GSR_EARLY_SCATTER  the fused forward queues scatter behind the scan before the host has the totals
 bool env_on(const char* name)
@@ -835,7 +836,7 @@ int gsr_backward_mt(int P, int D, int M, int R, int num_segments, int num_channe
     if (R > 0) {
         {
             Scope sc(ST_BLEND_BWD, st);
-            launch_blend_bwd(C, W, H, num_segments, background, features_of(colors_precomp, g), g, im, b, dL_dpix, grad_acc, st);
+            launch_blend_bwd(C, W, H, num_segments, background, features_of(colors_precomp, g), g, im, b, dL_dpix, grad_acc, env_on("GSR_BWD_LIVE"), st);
         }
         GSR_CHECK_LAUNCH("blend_bwd_kernel");
     }
@@ -1044,6 +1045,30 @@ int gsr_debug_export(int P, int R, int num_segments, int W, int H, const void* g
         BinState b = carve_bin(const_cast<void*>(binning_buffer), R, nonneg(num_segments));
         GSR_CHECK(hipMemcpyAsync(point_list, b.point_list, 4 * (size_t)R, hipMemcpyDeviceToDevice, st));
     }
+    return 0;
+}
+
+__global__ void export_units_kernel(int U, const uint4* __restrict__ table, uint32_t* __restrict__ unit_info, uint8_t* __restrict__ unit_live)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= U) return;
+    const uint4 v = table[i];
+    if (unit_info) {
+        unit_info[4 * i] = v.x & UNIT_TILE_MASK; unit_info[4 * i + 1] = v.y; unit_info[4 * i + 2] = v.z; unit_info[4 * i + 3] = v.w;
+    }
+    if (unit_live)
+        for (int blk = 0; blk < 4; blk++) unit_live[4 * i + blk] = (uint8_t)((v.x >> (UNIT_LIVE_SHIFT + blk)) & 1u);
+}
+
+int gsr_debug_export_units(int R, int num_segments, const void* binning_buffer, uint32_t* unit_info, uint8_t* unit_live,
+                           gsr_stream_t stream)
+{
+    g_err.clear();
+    if (R <= 0 || num_segments <= 0) return 0;
+    if (!binning_buffer) return fail_msg("gsr_debug_export_units: required pointer is null");
+    BinState b = carve_bin(const_cast<void*>(binning_buffer), R, num_segments);
+    export_units_kernel<<<(num_segments + 255) / 256, 256, 0, (hipStream_t)stream>>>(num_segments, b.unit_info, unit_info, unit_live);
+    GSR_CHECK_LAUNCH("export_units_kernel");
     return 0;
 }
 

@@ -119,7 +119,7 @@ blend_bwd_kernel(int W, int H, int gx, const uint4* __restrict__ unit_info, cons
                       const float4* __restrict__ rec_b, const RecTail<C>* __restrict__ rec_c, const float* __restrict__ bg,
                       const float* __restrict__ final_T, const uint32_t* __restrict__ n_contrib,
                       const float* __restrict__ dL_dpix, float* __restrict__ grad_acc, uint64_t* __restrict__ trace,
-                      const uint32_t* __restrict__ order)
+                      const uint32_t* __restrict__ order, uint32_t live_off)
 {
     using L = QuadLds<C>;
     const uint64_t t_start = trace ? wall_clock64() : 0;
@@ -137,24 +137,21 @@ blend_bwd_kernel(int W, int H, int gx, const uint4* __restrict__ unit_info, cons
     uint32_t wave_sel = slot_id & 3u;
     const uint32_t full = (n_units >> 6) << 6;
     if (blockIdx.x >= full * 4u) { unit = blockIdx.x >> 2; wave_sel = blockIdx.x & 3u; }
-#ifdef GSR_EXP_LIVE
-    // (experiment build, tools/dead_exit_exp.py: the debug pointer is not a launch order but a table of live bits per unit -- word
-    // [n_units] = 0: every wave that finds work records its bit; 1: a wave whose bit is clear leaves right here, before any vector load --
-    // what a per-(unit, block) flag written by the forward would buy, without touching the forward)
-    uint32_t* const live_tab = const_cast<uint32_t*>(order);
-    const bool live_use = live_tab != nullptr && live_tab[n_units] == 1u;
-    if (live_use && ((live_tab[unit] >> wave_sel) & 1u) == 0u) return;
-#else
     // (a launch ORDER of the units, when there is one: position in the dispatch sequence -> unit; gsr_debug_set_bwd_order)
     if (order != nullptr) unit = order[unit];
-#endif
+    // The forward's verdict on this (unit, block), one bit above the tile in the table entry's first word: clear = no pixel of the
+    // block blended an instance of the unit, so every pair of this wave fails `position < last contributor && power <= 0 && alpha
+    // >= 1/255` (the forward's own tests, bit for bit) and its moments are all zero.  The wave leaves HERE, on the scalar load it
+    // starts with anyway: a wave cannot retire under outstanding loads, and the head below has about 7 KB of them in flight before
+    // it could find out for itself (kany == 0, 3.3 us later).  live_off = 0xf: the flags are ignored (GSR_BWD_LIVE=0).
     const uint4 info = unit_info[unit];
-    const int tile = (int)info.x;
+    const uint32_t live4 = (info.x >> UNIT_LIVE_SHIFT) | live_off;
+    const int tile = (int)(info.x & UNIT_TILE_MASK);
     const uint32_t list0 = info.y;
     const int n = (int)info.z;
     const uint32_t unit0 = info.w;
     const int s0 = (int)(unit - unit0) * 64;
-    if (s0 >= n) return;
+    if ((s0 >= n) | (((live4 >> wave_sel) & 1u) == 0u)) return;
     const int wave = (int)wave_sel, lane = threadIdx.x;
     const int tx = tile % gx, ty = tile / gx;
     const int sx = tx * TILE + (wave & 1) * SUB, sy = ty * TILE + (wave >> 1) * SUB;
@@ -265,10 +262,7 @@ blend_bwd_kernel(int W, int H, int gx, const uint4* __restrict__ unit_info, cons
         ks[3] = ((unsigned long long)rfl(a23[3]) << 32) | rfl(a23[2]);
     }
     const unsigned long long kany = ks[0] | ks[1] | ks[2] | ks[3];
-    if (kany == 0ull) return;
-#ifdef GSR_EXP_LIVE
-    if (live_tab != nullptr && !live_use && lane == 0) atomicOr(&live_tab[unit], 1u << wave);
-#endif
+    if (kany == 0ull) return;   // (only waves the forward could not rule out get here: flags ignored, long or split lists)
     // ---- the pixels' start state, parked per pixel lane; the trips read it in their own lane order
     {
         float4* st = reinterpret_cast<float4*>(lds + STG + STG_B * lane);
@@ -485,10 +479,11 @@ bool launch_blend_bwd_variant(int C, int W, int H, int U, const float* bg, Image
 const uint32_t* g_bwd_order = nullptr;   // (experiments: gsr_debug_set_bwd_order)
 
 void launch_blend_bwd(int C, int W, int H, int U, const float* bg, const float* feats, GeomState g, ImageState im,
-                      BinState b, const float* dL_dpix, float* grad_acc, hipStream_t st)
+                      BinState b, const float* dL_dpix, float* grad_acc, bool use_live, hipStream_t st)
 {
     (void)feats; (void)g;
     if (U <= 0) return;
+    const uint32_t live_off = use_live ? 0u : 0xfu;   // (the forward's live bits of a unit: taken for set when they are not to be used)
 #ifdef GSR_BWD_VARIANT
     if (launch_blend_bwd_variant(C, W, H, U, bg, im, b, dL_dpix, grad_acc, st)) return;
 #endif
@@ -497,13 +492,13 @@ void launch_blend_bwd(int C, int W, int H, int U, const float* bg, const float* 
     uint64_t* tr = g_trace ? g_trace + 2 * (size_t)t.T : nullptr;
     if (C == 3)
         blend_bwd_kernel<3><<<4 * U, 64, pad, st>>>(W, H, t.gx, b.unit_info, b.snap, b.masks, b.point_list, b.rec_a, b.rec_b,
-                                                    static_cast<const RecTail<3>*>(b.rec_c), bg, im.final_T, im.n_contrib, dL_dpix, grad_acc, tr, g_bwd_order);
+                                                    static_cast<const RecTail<3>*>(b.rec_c), bg, im.final_T, im.n_contrib, dL_dpix, grad_acc, tr, g_bwd_order, live_off);
     else if (C == 4)
         blend_bwd_kernel<4><<<4 * U, 64, pad, st>>>(W, H, t.gx, b.unit_info, b.snap, b.masks, b.point_list, b.rec_a, b.rec_b,
-                                                    static_cast<const RecTail<4>*>(b.rec_c), bg, im.final_T, im.n_contrib, dL_dpix, grad_acc, tr, g_bwd_order);
+                                                    static_cast<const RecTail<4>*>(b.rec_c), bg, im.final_T, im.n_contrib, dL_dpix, grad_acc, tr, g_bwd_order, live_off);
     else
         blend_bwd_kernel<6><<<4 * U, 64, pad, st>>>(W, H, t.gx, b.unit_info, b.snap, b.masks, b.point_list, b.rec_a, b.rec_b,
-                                                    static_cast<const RecTail<6>*>(b.rec_c), bg, im.final_T, im.n_contrib, dL_dpix, grad_acc, tr, g_bwd_order);
+                                                    static_cast<const RecTail<6>*>(b.rec_c), bg, im.final_T, im.n_contrib, dL_dpix, grad_acc, tr, g_bwd_order, live_off);
 }
 
 }  // namespace gsr

@@ -25,7 +25,11 @@
 //    tests -> blend;
 //  * whenever a pixel moves on to a word of a new 64-entry segment its running (T, C) is stored as that segment's
 //    snapshot: the state the backward's units resume from (gsr_blend_bwd.hip); the tile's first snapshot slot keeps
-//    the final (T, C).
+//    the final (T, C);
+//  * a pixel also keeps one bit per 64-entry unit in which it BLENDED an instance; at the tile's end every wave ORs the word over
+//    its 64 pixels and the tile leaves four bits per unit -- one per block -- in the unit table (gsr_internal.h UNIT_LIVE_SHIFT): the
+//    backward's wave for a (unit, block) nobody blended in has nothing to replay and leaves before it loads anything.  A list of
+//    up to 2 048 entries has at most 32 units -- one word; longer lists and tiles blended in parts are flagged live throughout.
 //
 // Template over the number of colour channels C: 3 is the reference's NUM_CHANNELS (cuda_rasterizer/config.h:15);
 // 6 renders TWO targets that share geometry (GauSTAR's RGB + depth-as-colour passes, refine.py:552 and :607) in one
@@ -75,7 +79,7 @@ blend_fwd_kernel(int W, int H, int gx, const uint2* __restrict__ ranges, const u
                  const float4* __restrict__ g1,
                  const float* __restrict__ feats, const float* __restrict__ bg, float* __restrict__ out_color,
                  float* __restrict__ final_T, uint32_t* __restrict__ n_contrib, const uint32_t* __restrict__ seg_off,
-                 uint2* __restrict__ masks, float4* __restrict__ snap, float4* __restrict__ rec_a, float4* __restrict__ rec_b,
+                 uint2* __restrict__ masks, uint4* __restrict__ unit_info, float4* __restrict__ snap, float4* __restrict__ rec_a, float4* __restrict__ rec_b,
                  RecTail<C>* __restrict__ rec_c, const uint2* __restrict__ part_list, const uint32_t* __restrict__ totals,
                  float4* __restrict__ part_fin, uint32_t* __restrict__ part_last, uint32_t* __restrict__ part_ticket,
                  uint32_t part_grid, bool parts_sort, uint32_t split_n, bool keep,
@@ -254,9 +258,19 @@ blend_fwd_kernel(int W, int H, int gx, const uint2* __restrict__ ranges, const u
     if constexpr (PLANNED) {
         if (threadIdx.x == 0) { plan.im_ranges[tile] = make_uint2(list0, list0 + n); plan.im_seg_off[tile] = unit0; }
         if (keep)
-            for (uint32_t u = threadIdx.x; u < (rg.y >> 6); u += 256u) plan.unit_info[unit0 + u] = make_uint4((uint32_t)tile, list0, n, unit0);
+            for (uint32_t u = threadIdx.x; u < (rg.y >> 6); u += 256u) unit_info[unit0 + u] = make_uint4((uint32_t)tile, list0, n, unit0);
     }
     const bool long_list = n > split_n;   // (wave-uniform) blended in parts: split_n = PART_FROM in views that split at all
+    // The units' live bits (see the head of the file): the units the backward launches for this tile are those of its list --
+    // planned: of its whole bucket, a unit past the list's end is flagged dead --; exact flags where a pixel's word holds every
+    // unit and the walk below is the one that blends them, "live" everywhere else.  (The table's entries exist: scatter wrote
+    // them before this launch, a planned tile its own a few lines up -- thread u the entry it writes again here and at the end.)
+    // (wave-uniform and needed again at the tile's end: kept in scalar registers through the walk)
+    const uint32_t live_units = __builtin_amdgcn_readfirstlane(PLANNED ? rg.y >> 6 : (n + 63u) >> 6);
+    const uint32_t live_tile = __builtin_amdgcn_readfirstlane((uint32_t)tile);
+    const bool live_exact = !long_list && n <= 32u * 64u;
+    if (snaps && !is_part && !live_exact)
+        for (uint32_t u = threadIdx.x; u < live_units; u += 256u) unit_info[unit0 + u].x = live_tile | (0xfu << UNIT_LIVE_SHIFT);
     if (MODE == 2 && !is_part && long_list) return;   // its parts do everything, the last of them the combine
     // Depth sort of this tile's list, right here (lists up to 2 048 entries; longer ones were sorted by tile_sort_big_kernel
     // before this launch).  As a kernel of its own the sort is latency-bound (key loads, cross-lane exchanges, barriers:
@@ -337,6 +351,7 @@ blend_fwd_kernel(int W, int H, int gx, const uint2* __restrict__ ranges, const u
 #pragma unroll
     for (int ch = 0; ch < C; ch++) Cc[ch] = 0.f;
     uint32_t last = 0;
+    uint32_t live = 0;   // bit u: the pixel blended an instance of the tile's unit u (lists of at most 32 units; the head of the file)
     bool done = !inside;
     // segment (SNAP_SEG list positions) of the word this pixel consumed last.  A part that is not the tile's first starts
     // "nowhere": the first word of ANY of its units, the first one included, opens a segment and leaves a snapshot
@@ -510,6 +525,7 @@ blend_fwd_kernel(int W, int H, int gx, const uint2* __restrict__ ranges, const u
             for (int ch = 0; ch < C; ch++) Cc[ch] += col[ch] * w;
             T = upd ? test_T : T;
             last = upd ? c0 + slot + 1u : last;
+            live |= (upd ? 1u : 0u) << (((c0 + slot) >> 6) & 31u);   // (off the T chain: nothing reads it before the tile's end)
             // (the trip's results are operands of the wait: the compiler otherwise sinks most of the arithmetic BEHIND it)
             if constexpr (C == 3)
                 asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(wnext), "+v"(nxt.a), "+v"(nxt.b), "+v"(nxt.k), "+v"(T), "+v"(last), "+v"(Cc[0]), "+v"(Cc[1]), "+v"(Cc[2]) : : "memory");
@@ -594,6 +610,7 @@ blend_fwd_kernel(int W, int H, int gx, const uint2* __restrict__ ranges, const u
             for (int ch = 0; ch < C; ch++) Cc[ch] += col[ch] * w;
             T = upd ? test_T : T;
             last = upd ? c0 + slot + 1u : last;
+            live |= (upd ? 1u : 0u) << (((c0 + slot) >> 6) & 31u);   // (off the T chain: nothing reads it before the tile's end)
             asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(wnext) : : "memory");   // (long landed: the gathers above were issued after it)
             nw = need ? (nz != 0u ? wnext : 0u) : nw;
             nh = need ? t : nh;
@@ -836,6 +853,23 @@ blend_fwd_kernel(int W, int H, int gx, const uint2* __restrict__ ranges, const u
         }
     
     }
+    if (snaps && !is_part && live_exact && live_units > 0u) {   // (workgroup-uniform)
+        // OR over the block's 64 pixels (a pixel outside the image blended nothing), the four blocks' words side by side in the
+        // LDS the last walk has left, and thread u puts unit u's four bits above the tile in the unit's table entry
+        uint32_t any = live;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) any |= (uint32_t)__shfl_xor((int)any, o, 64);
+        uint32_t* const any_of = reinterpret_cast<uint32_t*>(smem);
+        __syncthreads();   // every wave is through with the chunk in LDS
+        if (lane == 0) any_of[wave] = any;
+        __syncthreads();
+        for (uint32_t u = threadIdx.x; u < live_units; u += 256u) {
+            uint32_t bits = 0;
+#pragma unroll
+            for (int blk = 0; blk < 4; blk++) bits |= (u < 32u ? (any_of[blk] >> u) & 1u : 0u) << blk;
+            unit_info[unit0 + u].x = live_tile | (bits << UNIT_LIVE_SHIFT);
+        }
+    }
     if (inside) {
         const size_t pix = (size_t)W * py + px;
         const size_t HW = (size_t)H * W;
@@ -875,7 +909,7 @@ static void launch_fwd_c(int W, int H, int R, int U, uint32_t max_count, const f
         constexpr int M = decltype(mode)::value;
         blend_fwd_kernel<C, FWD_CHUNK, M><<<grid, 256, M == 1 ? 0 : pad, st>>>(
             W, H, t.gx, im.ranges, im.order, b.point_list, sort_small ? b.keys : nullptr, g.g0, g.g1, feats, bg, out_color,
-            im.final_T, im.n_contrib, im.seg_off, b.masks, b.snap, b.rec_a, b.rec_b, static_cast<RecTail<C>*>(b.rec_c), b.part_list,
+            im.final_T, im.n_contrib, im.seg_off, b.masks, b.unit_info, b.snap, b.rec_a, b.rec_b, static_cast<RecTail<C>*>(b.rec_c), b.part_list,
             im.totals, b.part_fin, b.part_last, b.part_ticket, part_grid, max_count <= SORT_SMALL_CAP, split_n, keep_masks,
             M != 1 ? static_cast<float4*>(zero_ptr) : nullptr, M != 1 ? (uint32_t)(zero_bytes / 16) : 0u, M != 1 ? counters : nullptr,
             (uint32_t)shard_stride(t.T), M != 1 ? g_trace : nullptr, PlanRun{}, M == 0 && job ? *job : PlanJob{});
@@ -904,7 +938,7 @@ static void launch_fwd_planned_c(int W, int H, const float* bg, const float* fea
     const unsigned grid = (rides ? 1u : 0u) + ((unsigned)t.T - n_light) + (n_light + FWD_LIGHT_TILES - 1u) / FWD_LIGHT_TILES;
     blend_fwd_kernel<C, FWD_CHUNK, 0, true><<<grid, 256, pad, st>>>(
         W, H, t.gx, plan.ranges, plan.order, b.point_list, b.keys, g.g0, g.g1, feats, bg, out_color, im.final_T, im.n_contrib,
-        plan.seg_off, b.masks, b.snap, b.rec_a, b.rec_b, static_cast<RecTail<C>*>(b.rec_c), b.part_list, im.totals, b.part_fin,
+        plan.seg_off, b.masks, b.unit_info, b.snap, b.rec_a, b.rec_b, static_cast<RecTail<C>*>(b.rec_c), b.part_list, im.totals, b.part_fin,
         b.part_last, b.part_ticket, 0u, false, 0xffffffffu, keep_masks, static_cast<float4*>(zero_ptr), (uint32_t)(zero_bytes / 16),
         nullptr, 0u, g_trace, plan, rides ? *job : PlanJob{});
 }

@@ -143,13 +143,20 @@ constexpr int GRAD_RS = 12;  // floats per record of the backward accumulation t
 
 __host__ __device__ constexpr size_t rec_tail_bytes(int C) { return C == 6 ? 16 : C == 4 ? 8 : 4; }   // == sizeof(RecTail<C>)
 
+// The unit table's first word holds the tile in its low 28 bits (an image has far fewer tiles) and the forward's four live bits
+// of the unit above them: the backward's wave has both with the one scalar load it starts with.
+constexpr int UNIT_LIVE_SHIFT = 28;
+constexpr uint32_t UNIT_TILE_MASK = (1u << UNIT_LIVE_SHIFT) - 1u;
 struct BinState {            // per instance / per segment
     uint64_t* keys;          // [R] (depth_bits << 32) | gaussian, bucketed by tile, unsorted within the bucket
     uint32_t* point_list;    // [R] gaussian ids, tile-major, depth-ascending, ties by ascending id
     float4* rec_a;           // [R] the forward's staged instance records in list order (make_rec: {x, y, a', b'},
     float4* rec_b;           // [R] {c', opacity, colour 0, colour 1}, conic in the exp2 domain), written by blend_fwd
     void* rec_c;             // [R] RecTail<C>: colours 2 .. C-1       for the backward's units (contiguous reads)
-    uint4* unit_info;        // [U] {tile, first list entry of the tile, entries of the tile, first unit of the tile}
+    uint4* unit_info;        // [U] {tile | live << 28, first list entry of the tile, entries of the tile, first unit of the tile}
+                             // live (UNIT_LIVE_SHIFT; written by blend_fwd at the tile's end): bit b set <=> some pixel of 8x8 block b
+                             // blended an instance of the unit, or the forward could not tell; clear <=> the backward's wave for
+                             // that (unit, block) has nothing to replay and leaves at once
     uint2* masks;            // [U][4 blocks][64 lanes] per-pixel 64-bit words over the unit's 64 list positions
                              // {positions 0-31, positions 32-63}; block = 2*by + bx, lane = 8*(y % 8) + (x % 8)
     uint2* part_list;        // [part_capacity] {tile, first list position} of every part of a list blended in parts
@@ -353,7 +360,7 @@ void launch_blend_fwd(int C, int W, int H, int R, int U, uint32_t max_count, con
                       BinState b, float* out_color, bool keep_masks, void* zero_ptr, size_t zero_bytes, uint32_t* counters,
                       bool sort_small, hipStream_t st, const PlanJob* job = nullptr, bool* job_rides = nullptr, int num_parts = -1);
 void launch_blend_bwd(int C, int W, int H, int U, const float* bg, const float* feats, GeomState g, ImageState im, BinState b,
-                      const float* dL_dpix, float* grad_acc, hipStream_t st);
+                      const float* dL_dpix, float* grad_acc, bool use_live, hipStream_t st);
 // (v.opacities and v.colors_precomp are not read; v.scales / v.rotations are null under v.cov3D_precomp)
 void launch_geom_bwd(const ViewArgs& v, GeomState g, int C, const float* grad_acc, float* dL_dmean2D, float* dL_dopacity,
                      float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,

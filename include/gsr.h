@@ -263,6 +263,14 @@ int gsr_debug_export(int P, int R, int num_segments, int W, int H, const void* g
  * list are zero).  Words of segments the forward never reached (every pixel of the tile saturated before) are undefined.
  * No reference counterpart. */
 int gsr_debug_export_masks(int R, int num_segments, const void* binning_buffer, uint64_t* masks, gsr_stream_t stream);
+/* Same for the backward's unit table and the forward's live flags, which the table carries above the tile number (either may be
+ * null): unit_info [num_segments][4] uint32 {tile, first list entry of the tile, entries of the tile, first unit of the tile};
+ * unit_live [num_segments][4] uint8, one byte per (unit, 8x8 block): 0 <=> no pixel of the block blended an instance of the unit
+ * -- the backward's wave for that pair leaves at once (GSR_BWD_LIVE=0: the flags are ignored) --, 1 <=> some pixel did, or the
+ * forward does not tell (lists above 2 048 entries, tiles blended in parts).  Defined after a forward that keeps backward state,
+ * for the units of the view's tiles (planned views: of their whole buckets).  No reference counterpart. */
+int gsr_debug_export_units(int R, int num_segments, const void* binning_buffer, uint32_t* unit_info, uint8_t* unit_live,
+                           gsr_stream_t stream);
 
 /* ---- Producers of rasterizer inputs.
  * gsr_sh_to_rgb replaces SuGaR.get_points_rgb (gaustar_scene/sugar_model.py:674-718):

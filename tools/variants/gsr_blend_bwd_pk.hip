@@ -74,7 +74,7 @@ blend_bwd_pk_kernel(int W, int H, int gx, const uint4* __restrict__ unit_info, c
     const uint32_t full = (n_units >> 6) << 6;
     if (blockIdx.x >= full * 4u) { unit = blockIdx.x >> 2; wave_sel = blockIdx.x & 3u; }
     const uint4 info = unit_info[unit];
-    const int tile = (int)info.x;
+    const int tile = (int)(info.x & UNIT_TILE_MASK);   // (the forward's live bits ride above the tile)
     const uint32_t list0 = info.y;
     const int n = (int)info.z;
     const uint32_t unit0 = info.w;

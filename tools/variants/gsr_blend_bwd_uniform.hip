@@ -113,7 +113,7 @@ blend_bwd_unit(int W, int H, int gx, const uint4* __restrict__ unit_info, const 
     // (rec_a/b/c).  As a chain (unit -> tile -> ranges -> n_contrib -> words -> snapshot; words -> list -> id -> geometry)
     // the head of a unit was six dependent trips to memory, a third of a unit's life, with nothing to issue meanwhile.
     const uint4 info = unit_info[unit];
-    const int tile = (int)info.x;
+    const int tile = (int)(info.x & UNIT_TILE_MASK);   // (the forward's live bits ride above the tile)
     const uint32_t list0 = info.y;
     const int n = (int)info.z;
     const uint32_t unit0 = info.w;
