@@ -12,6 +12,7 @@ stand-ins for pytorch3d's `Meshes` / `mesh_normal_consistency`), `sweep` (forwar
 `tracking` (points followed on the surface through topology updates: SurfaceTracker, track_faces),
 `remesh` (quadric mesh decimation and Laplacian / Taubin smoothing: how an init_mesh_100k.obj is made),
 `knn` (exact K-nearest neighbours with spatial culling: pytorch3d's knn_points, simple-knn's distCUDA2),
+`density` (the Gaussians' density field: SuGaR's compute_density and get_covariance, behind the model's postprocess_mesh),
 `evaluate` (how good a result is: point-to-mesh distance, Chamfer distance and F-score of two meshes, PSNR and SSIM of renders) and
 `formats` (cameras.json, 3DGS PLY, SuGaR .pt, OBJ, grey PNG) -- import them as submodules.
 """

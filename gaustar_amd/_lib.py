@@ -260,6 +260,12 @@ SIGNATURES = {
     "gsr_knn_mean_d2": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "gsr_knn_segment_mean": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gsr_knn_weighted_mean": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_void_p]),
+    # the Gaussians' density field (sugar_model.py:1017-1040, :619-625): gaustar_amd.density; the err word's bit 0 = an index
+    # outside [-1, P)
+    "gsr_density_queries_per_wave": (c_int, []),
+    "gsr_density_queries_per_workgroup": (c_int, []),
+    "gsr_density_pack": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gsr_density_eval": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gsr_adam_step": (c_int, [c_longlong, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_double, c_double, c_int,
                               c_void_p]),
     "gsr_adam_step_multi": (c_int, [c_int, POINTER(c_longlong), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),

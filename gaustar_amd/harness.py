@@ -238,6 +238,16 @@ class _RenderMeshBound(torch.autograd.Function):
                 new(d_rest, o_rest), new(d_dt, o_mesh[3]), new(d_dr, o_mesh[4]), None)
 
 
+@dataclass
+class PostprocessResult:
+    """SurfaceGaussians.postprocess_mesh: the new model, face_mask [F] bool over the old model's faces (True: kept),
+    kept_per_iteration: the faces left after every peel, restored: the peeled faces the density brought back."""
+    model: "SurfaceGaussians"
+    face_mask: torch.Tensor
+    kept_per_iteration: list
+    restored: int
+
+
 class SurfaceGaussians(nn.Module):
     """Gaussians bound to a triangle mesh: SuGaR with binded_to_surface_mesh = True (sugar_model.py:160-403), parameters
     under the reference's names so that a reference state dict loads with load_state_dict."""
@@ -508,6 +518,106 @@ class SurfaceGaussians(nn.Module):
         if num_samples >= 0:
             return self.knn_idx[torch.randperm(self.n_points, device=self.device)[:num_samples]]
         return self.knn_idx
+
+    # -------------------------------------------------------------------------------- the density field and the border clean-up
+    def get_covariance(self, return_full_matrix=False, return_sqrt=False, inverse_scales=False):
+        """sugar_model.py:619-639: density.get_covariance(self.scaling, self.quaternions, ...)."""
+        from . import density
+        return density.get_covariance(self.scaling, self.quaternions, return_full_matrix, return_sqrt, inverse_scales)
+
+    def get_gaussians_closest_to_samples(self, x, n_closest_gaussian=None):
+        """sugar_model.py:1007-1015: [Q,K] int64, the K nearest Gaussian centres of every row of x [Q,3] f32 (knn.knn_points, so
+        a slot beyond the Gaussians there are holds 0, as pytorch3d pads).  K = n_closest_gaussian, else `knn_to_track`,
+        which is set to 16 if the model has none (:1009-1011)."""
+        from . import knn
+        if n_closest_gaussian is None:
+            if not hasattr(self, "knn_to_track"):
+                self.knn_to_track = 16
+            n_closest_gaussian = self.knn_to_track
+        with torch.no_grad():
+            return knn.knn_points(x[None], self.points.detach()[None], K=int(n_closest_gaussian)).idx[0]
+
+    def compute_density(self, x, closest_gaussians_idx=None, density_factor=1., return_closest_gaussian_opacities=False):
+        """sugar_model.py:1017-1040 on the model's own points / scaling / quaternions / strengths: density.compute_density,
+        with the `knn_to_track` nearest Gaussians (16 if the model has none) when no indices are given."""
+        from . import density
+        if closest_gaussians_idx is None and not hasattr(self, "knn_to_track"):
+            self.knn_to_track = 16
+        with torch.no_grad():
+            return density.compute_density(x, self.points, self.scaling, self.quaternions, self.strengths,
+                                           closest_gaussians_idx=closest_gaussians_idx, K=getattr(self, "knn_to_track", 16),
+                                           density_factor=density_factor,
+                                           return_closest_gaussian_opacities=return_closest_gaussian_opacities)
+
+    @torch.no_grad()
+    def postprocess_mesh(self, iterations: int = 5, density_threshold: float = 0.1, K: Optional[int] = None) -> "PostprocessResult":
+        """--postprocess_mesh (refined_mesh.py:1155-1217): `iterations` times the faces with an edge that fewer than two of the
+        remaining faces share are peeled off (:1173-1177, by regions' masked edge counts), then a peeled face returns iff the
+        density of ALL the model's Gaussians at its centre ((v0 + v1) + v2) / 3 is > density_threshold (:1180-1182; the K
+        nearest, K = `knn_to_track` or 16), and a new model is built on the faces that are left: the same vertices,
+        unreferenced ones included, the parameters gathered by face, not loose-bound (:1185-1216).  Every face starts inside:
+        the reference's initial mask (:1169) has one entry per Gaussian and fits its per-face use only with one Gaussian per
+        triangle.  -> PostprocessResult.  ValueError if no face is left.  One host read, at the end."""
+        from . import density, regions
+        G = self.n_gaussians_per_surface_triangle
+        self._fence()
+        faces = regions._faces_i32(self._surface_mesh_faces)
+        F, dev = int(faces.shape[0]), faces.device
+        verts = self._points.detach()
+        err = torch.zeros(2, dtype=torch.int32, device=dev)       # [0]: the edge kernels' word, [1]: the density's
+        mask = torch.ones(F, dtype=torch.bool, device=dev)
+        kept = []
+        for _ in range(int(iterations)):
+            if F == 0:
+                break
+            counts = regions._edge_counts(faces, err[0:1], mask.view(torch.uint8))
+            mask = mask & (counts >= 2).all(dim=1)
+            kept.append(mask.sum())
+        removed = ~mask
+        fv = verts[self._surface_mesh_faces]
+        centres = ((fv[:, 0] + fv[:, 1]) + fv[:, 2]) / 3
+        if K is None:
+            K = getattr(self, "knn_to_track", 16)
+        pts = self.points.detach()
+        records = density.pack_records(pts, self.scaling.detach(), self.quaternions.detach(), self.strengths.detach())
+        # which faces were removed stays on the device: a face that stayed asks with a NaN centre, which the search answers
+        # with an empty row without looking at a candidate, and whose density, 0, is not read
+        centres = torch.where(removed[:, None], centres, torch.full_like(centres, float("nan"))).contiguous()
+        idx = density.closest_gaussians(centres, pts.contiguous(), int(K))
+        dens, _ = density.eval_records(centres, idx, records, 1.0, False, err[1:2])
+        back = removed & (dens > float(density_threshold))
+        mask = mask | back
+        host = torch.stack([err[0].long(), err[1].long(), back.sum(), mask.sum(), *kept]).cpu().tolist()
+        regions._raise_if(host[0])
+        density._raise_if(host[1])
+        if host[3] == 0:
+            raise ValueError("postprocess_mesh: no face is left")
+        sel = torch.argsort((~mask).to(torch.uint8), stable=True)[:host[3]]      # the kept faces in order, their number known: no read
+        new = SurfaceGaussians(verts, self._surface_mesh_faces[sel], n_gaussians_per_surface_triangle=G, sh_levels=self.sh_levels,
+                               surface_mesh_thickness=self._thickness(), min_gaussian_scale=self.min_gaussian_scale,
+                               max_gaussian_scale=self.max_gaussian_scale, loose_bind=False)
+        rows = (sel[:, None] * G + torch.arange(G, device=dev)).reshape(-1)
+        for name in ("_scales", "_quaternions", "all_densities", "_sh_coordinates_dc", "_sh_coordinates_rest"):
+            getattr(new, name).copy_(getattr(self, name).detach()[rows])
+        new.return_one_densities = self.return_one_densities
+        return PostprocessResult(model=new, face_mask=mask, kept_per_iteration=[int(k) for k in host[4:]], restored=int(host[2]))
+
+    def to_gaussian_cloud(self):
+        """convert_refined_sugar_into_gaussians (sugar_model.py:1416-1437) -> formats.GaussianCloud on the host: xyz = points,
+        opacity = all_densities (logits), features_dc / features_rest = the SH parameters, scaling = log(scaling)
+        (scale_inverse_activation), rotation = quaternions."""
+        from . import formats
+        with torch.no_grad():
+            self._fence()
+            n = lambda t: t.detach().float().cpu().numpy()
+            return formats.GaussianCloud(xyz=n(self.points), features_dc=n(self._sh_coordinates_dc),
+                                         features_rest=n(self._sh_coordinates_rest), opacity=n(self.all_densities.view(-1, 1)),
+                                         scaling=n(torch.log(self.scaling)), rotation=n(self.quaternions))
+
+    def export_ply(self, path: str) -> None:
+        """--export_ply (train_seq.py's default): the 3DGS viewer's PLY of to_gaussian_cloud(), by formats.save_ply."""
+        from . import formats
+        formats.save_ply(path, self.to_gaussian_cloud())
 
     def warp_mesh(self, cameras, frames, **kw):
         """The surface mesh moved to the next frame along the optical flow of `cameras` (warp_mesh.py:216-401):

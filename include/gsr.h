@@ -1094,6 +1094,39 @@ int gsr_knn_segment_mean(int n, int S, int C, const long long* segment_ids, cons
 int gsr_knn_weighted_mean(int N, int K, int C, int M, const int* idx, const float* d2, const double* values, double inv_scale,
                           double* out, gsr_stream_t stream);
 
+/* ---- The Gaussians' density field: SuGaR's compute_density (gaustar_scene/sugar_model.py:1017-1040) with the inverse scaled
+ * rotation of get_covariance(return_full_matrix=True, return_sqrt=True, inverse_scales=True) (:619-625) folded in, over the
+ * neighbours get_gaussians_closest_to_samples (:1007-1015) finds: gaustar_amd.density, and through it postprocess_mesh
+ * (gaustar_trainers/refined_mesh.py:1180-1182).  The inputs are f32; every term is formed in float64 without contraction, in
+ * the order below (tests/density_ref.py restates it), and rounded to f32 once at the end.  All device pointers; every call is
+ * asynchronous on `stream`, none synchronises the host, none uses float atomics, LDS or scratch, and a result is the same bits
+ * in every call.
+ * gsr_density_queries_per_wave / _per_workgroup: 16 lanes serve a query, so 4 queries share a wave64 and 16 a workgroup.
+ * gsr_density_pack: replaces the three gathers of :1024-1028 by one record.  points [P,3], scaling [P,3] (activated, as
+ *   SuGaR.scaling), quaternions [P,4] (real part first, any norm), strengths [P] -> records: P x 48 bytes, three float4
+ *   {cx, cy, cz, strength}, {qr, qi, qj, qk}, {s0, s1, s2, 0}, the inputs' bits verbatim.  Every array 16-byte aligned (the
+ *   kernel moves 16 bytes at a time).  P == 0 is a no-op.
+ * gsr_density_eval: replaces :1031-1035.  x [Q,3] f32, idx [Q,K] int32 with 1 <= K <= 32 and -1 in an empty slot (gsr_knn_search's
+ *   rows).  Per slot with Gaussian (c, q, s, strength):
+ *     d = (double) x - (double) c;  two_s = 2 / (((qr qr + qi qi) + qj qj) + qk qk);  R = pytorch3d's quaternion_to_matrix:
+ *     R00 = 1 - two_s (qj qj + qk qk), R01 = two_s (qi qj - qk qr), R02 = two_s (qi qk + qj qr), R10 = two_s (qi qj + qk qr),
+ *     R11 = 1 - two_s (qi qi + qk qk), R12 = two_s (qj qk - qi qr), R20 = two_s (qi qk - qj qr), R21 = two_s (qj qk + qi qr),
+ *     R22 = 1 - two_s (qi qi + qj qj);  inv_a = 1 / (s_a < 1e-8 ? 1e-8 : s_a);
+ *     w_a = inv_a ((R[0][a] d0 + R[1][a] d1) + R[2][a] d2), a = 0, 1, 2  (:1032's (R diag(inv))^T d);
+ *     m = (w0 w0 + w1 w1) + w2 w2, then m < 0 ? 0 : (m > 1e8 ? 1e8 : m)  (:1033's clamp; a NaN stays);
+ *     t = ((double) density_factor (double) strength) exp(-0.5 m)  (:1034).
+ *   An empty slot, and a slot from K up to 31, has t = +0.0.  u_j = t_j + t_{j+16} for j = 0..15; then four rounds r = 1, 2, 4, 8
+ *   of u_j <- u_j + u_{j xor r} over all j at once: a balanced tree, the same in every j.  density [Q] f32 = (float) u_0;
+ *   neighbor_opacities: NULL, or [Q,K] f32 = (float) t (the second value of return_closest_gaussian_opacities, :1038).
+ *   err: one int32, zero before; bit 0 is set when an index lies outside [-1, P), and that slot counts as empty.  Refused
+ *   before any device work: K outside 1..32, P < 1 or a null pointer with Q > 0.  Q == 0 is a no-op. */
+int gsr_density_queries_per_wave(void);
+int gsr_density_queries_per_workgroup(void);
+int gsr_density_pack(int P, const float* points, const float* scaling, const float* quaternions, const float* strengths, void* records,
+                     gsr_stream_t stream);
+int gsr_density_eval(int Q, int P, int K, const float* x, const int* idx, const void* records, float density_factor, float* density,
+                     float* neighbor_opacities, int* err, gsr_stream_t stream);
+
 /* Tuning aid: when device_buffer is non-NULL (4*T uint64), the two blend kernels record the start/end wall
  * clock (100 MHz) of every workgroup: forward at [2*b], backward at [2*(T+b)], b = launch index.  NULL = off. */
 int gsr_debug_set_trace(void* device_buffer);
