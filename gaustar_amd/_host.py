@@ -14,6 +14,11 @@ def raw_stream(dev_index: int) -> int:
     return torch._C._cuda_getCurrentRawStream(dev_index)
 
 
+def stream_of(t: torch.Tensor) -> int:
+    """raw_stream of the device tensor `t` is on: for a worker that is handed tensors and no device."""
+    return torch._C._cuda_getCurrentRawStream(t.device.index)
+
+
 class on_device:
     """`with torch.cuda.device(dev)` only when `dev` is not the current device already."""
     __slots__ = ("ctx",)

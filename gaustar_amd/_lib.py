@@ -153,7 +153,7 @@ SIGNATURES = {
     "gsr_fusion_emit": (c_int, [POINTER(c_int), c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                 c_void_p, c_void_p, c_void_p]),
     # The four mesh-surgery groups below share one err word (csrc/gsr_mesh.h: index = 1, NaN / not finite = 2, duplicate = 4),
-    # which gaustar_amd.regions._raise_if decodes, for gaustar_amd.handover too.
+    # which gaustar_amd._meshargs.raise_if decodes for them and for the later mesh features (tracking, evaluate, remesh).
     # re-mesh regions at topology errors: edge multiplicity, face components, boxes, cuts (refined_mesh.py:463-693, front
     # half): gaustar_amd.regions; gsr_regions_cut_emit is the tail of every compaction, after either mark call
     "gsr_regions_edge_keys": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -324,12 +324,6 @@ def check(rc: int, what: str) -> None:
     if rc != 0:
         msg = load().gsr_last_error()
         raise GsrError(f"{what} failed: {msg.decode() if msg else rc}")
-
-
-def stream_ptr():
-    """The current torch stream as the ABI's gsr_stream_t."""
-    import torch   # (here: the loader itself stays importable without torch)
-    return c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def ptr(t):

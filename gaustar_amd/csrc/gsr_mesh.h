@@ -1,7 +1,7 @@
 // gsr_mesh.h -- what the mesh-surgery kernels (gsr_regions.hip, gsr_stitch.hip, gsr_splice.hip, gsr_handover.hip, gsr_track.hip,
 // gsr_eval.hip, gsr_remesh.hip) share.
 // Every call of those files that takes `int* err` ORs into one word, which gaustar_amd.regions may pass through calls of
-// several files before its one decoder (regions._raise_if) reads it: the bits are defined here and nowhere else.
+// several files before its one decoder (gaustar_amd/_meshargs.py: raise_if) reads it: the bits are defined here and there.
 #pragma once
 
 namespace gsr {

@@ -18,10 +18,11 @@ from typing import Optional
 
 import torch
 
-from . import _lib, knn, producers
-from ._lib import ptr as _p, stream_ptr as _stream
+from . import _host, _lib, _meshargs as _ma, knn, producers
+from ._lib import ptr as _p
 
 RECORD_FLOATS = 12      # 48 bytes: {cx, cy, cz, strength}, {qr, qi, qj, qk}, {s0, s1, s2, 0}
+ERR_TEXTS = dict(index="compute_density: closest_gaussians_idx holds an index outside [-1, number of Gaussians)", dup=None, nan=None)
 
 
 def _f32(t, name: str, shape_tail) -> torch.Tensor:
@@ -51,8 +52,8 @@ def pack_records(points, scaling, quaternions, strengths) -> torch.Tensor:
     if not (s.device == q.device == w.device == pts.device):
         raise ValueError("compute_density: the Gaussians' tensors are on different devices")
     rec = torch.empty(P, RECORD_FLOATS, dtype=torch.float32, device=pts.device)
-    with torch.cuda.device(pts.device):
-        _lib.check(_lib.load().gsr_density_pack(P, _p(pts), _p(s), _p(q), _p(w), _p(rec), _stream()), "gsr_density_pack")
+    with _host.on_device(pts.device):
+        _lib.check(_lib.load().gsr_density_pack(P, _p(pts), _p(s), _p(q), _p(w), _p(rec), _host.stream_of(pts)), "gsr_density_pack")
     return rec
 
 
@@ -63,15 +64,10 @@ def eval_records(x: torch.Tensor, idx: torch.Tensor, records: torch.Tensor, dens
     Q, K, P = int(x.shape[0]), int(idx.shape[1]), int(records.shape[0])
     dens = torch.empty(Q, dtype=torch.float32, device=x.device)
     opac = torch.empty(Q, K, dtype=torch.float32, device=x.device) if opacities else None
-    with torch.cuda.device(x.device):
+    with _host.on_device(x.device):
         _lib.check(_lib.load().gsr_density_eval(Q, P, K, _p(x), _p(idx), _p(records), float(density_factor), _p(dens), _p(opac),
-                                                _p(err), _stream()), "gsr_density_eval")
+                                                _p(err), _host.stream_of(x)), "gsr_density_eval")
     return dens, opac
-
-
-def _raise_if(err: int) -> None:
-    if err & 1:
-        raise ValueError("compute_density: closest_gaussians_idx holds an index outside [-1, number of Gaussians)")
 
 
 @torch.no_grad()
@@ -92,7 +88,7 @@ def compute_density(x, points, scaling, quaternions, strengths, closest_gaussian
     P = int(records.shape[0])
     if records.device != xq.device:
         raise ValueError("compute_density: x and the Gaussians are on different devices")
-    err = torch.zeros(1, dtype=torch.int32, device=xq.device)
+    err = _ma.new_err(xq.device)
     given = closest_gaussians_idx is not None
     if given:
         idx = closest_gaussians_idx
@@ -112,7 +108,7 @@ def compute_density(x, points, scaling, quaternions, strengths, closest_gaussian
         raise ValueError("compute_density: there are no Gaussians")
     dens, opac = eval_records(xq, idx, records, density_factor, return_closest_gaussian_opacities, err)
     if given and xq.shape[0] > 0:
-        _raise_if(int(err.cpu()))
+        _ma.raise_if(int(err.cpu()), **ERR_TEXTS)
     return (dens, opac) if return_closest_gaussian_opacities else dens
 
 

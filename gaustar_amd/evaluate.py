@@ -35,12 +35,14 @@ from typing import Callable, NamedTuple, Optional, Sequence, Tuple, Union
 import numpy as np
 import torch
 
-from . import _lib
-from ._lib import ptr as _p, stream_ptr as _stream
-from .tracking import _mesh_f64, _points_f64
+from . import _host, _lib, _meshargs as _ma
+from ._lib import ptr as _p
 
 _NAN = "a vertex or a query point is NaN or infinite, or too large for its distance to be formed: no face is closest"
 _NO_AREA = "no face of the mesh has a positive, finite area (of at least 2^-991): it cannot be sampled"
+# (no list can name a vertex twice here, and "no area" wins over the NaN it usually comes with)
+_ERR = dict(index="a vertex index, or another index into the mesh or the points, lies outside its array", dup=None, nan=_NAN,
+            degenerate=_NO_AREA, degenerate_first=True)
 
 
 class SurfaceHit(NamedTuple):
@@ -93,17 +95,8 @@ class ViewMetrics(NamedTuple):
     mean_ssim: float
 
 
-def _raise_eval(err: int) -> None:
-    if err & 1:
-        raise ValueError("a vertex index, or another index into the mesh or the points, lies outside its array")
-    if err & 8:
-        raise ValueError(_NO_AREA)
-    if err & 2:
-        raise ValueError(_NAN)
-
-
 def _mesh(verts, faces):
-    verts, faces = _mesh_f64(verts, faces)
+    verts, faces = _ma.mesh_f64(verts, faces)
     if int(faces.shape[0]) == 0:
         raise ValueError("the mesh has no faces")
     return verts, faces
@@ -114,7 +107,8 @@ def _face_records(verts: torch.Tensor, faces: torch.Tensor, err: torch.Tensor) -
     """tri [9,F] f64 on the current stream: what every search over this mesh stages."""
     F = int(faces.shape[0])
     tri = torch.empty(9, F, dtype=torch.float64, device=faces.device)
-    _lib.check(_lib.load().gsr_eval_gather(F, int(verts.shape[0]), _p(faces), _p(verts), _p(tri), _p(err), _stream()), "gsr_eval_gather")
+    _lib.check(_lib.load().gsr_eval_gather(F, int(verts.shape[0]), _p(faces), _p(verts), _p(tri), _p(err), _host.stream_of(faces)),
+               "gsr_eval_gather")
     return tri
 
 
@@ -127,7 +121,7 @@ def _closest(pts: torch.Tensor, tri: torch.Tensor, err: torch.Tensor, subset=Non
     closest = torch.full((S, 3), float("nan"), dtype=torch.float64, device=dev)
     dist = torch.full((S,), float("inf"), dtype=torch.float64, device=dev)
     _lib.check(_lib.load().gsr_eval_closest(S, _p(subset), _p(n_live), K, int(tri.shape[1]), _p(pts), _p(tri), _p(face), _p(bary),
-                                            _p(closest), _p(dist), _p(err), _stream()), "gsr_eval_closest")
+                                            _p(closest), _p(dist), _p(err), _host.stream_of(pts)), "gsr_eval_closest")
     return SurfaceHit(dist, face, bary, closest)
 
 
@@ -146,21 +140,22 @@ def surface_distance(points: torch.Tensor, verts: torch.Tensor, faces: torch.Ten
     One host read: the err word.  ValueError: no faces, an index outside its array, a coordinate that is not finite."""
     verts, faces = _mesh(verts, faces)
     dev = faces.device
-    pts = _points_f64(points, dev, "points")
+    pts = _ma.points_f64(points, dev, "points")
     if subset is not None:
         subset = _i32_on(subset, dev, 1, "subset")
     if n_live is not None:
         n_live = _i32_on(n_live.reshape(-1), dev, 1, "n_live")
-    err = torch.zeros(1, dtype=torch.int32, device=dev)
-    hit = _closest(pts, _face_records(verts, faces, err), err, subset, n_live)
-    _raise_eval(int(err.cpu()))
+    err = _ma.new_err(dev)
+    with _host.on_device(dev):
+        hit = _closest(pts, _face_records(verts, faces, err), err, subset, n_live)
+    _ma.raise_if(int(err.cpu()), **_ERR)
     return hit
 
 
 # ------------------------------------------------------------------------------------------------ samples
 def _sample(verts: torch.Tensor, faces: torch.Tensor, n: int, seed: int, err: torch.Tensor) -> SurfaceSamples:
     """Nothing read back: what makes the weights unusable lands in err bit 3."""
-    lib, st, dev = _lib.load(), _stream(), faces.device
+    lib, st, dev = _lib.load(), _host.stream_of(faces), faces.device
     F, V = int(faces.shape[0]), int(verts.shape[0])
     area = torch.empty(F, dtype=torch.float64, device=dev)
     _lib.check(lib.gsr_eval_areas(F, V, _p(faces), _p(verts), _p(area), _p(err), st), "gsr_eval_areas")
@@ -195,15 +190,16 @@ def sample_surface(verts: torch.Tensor, faces: torch.Tensor, n: int, seed: int =
     face without area none; `seed` moves the points inside their faces, not the faces.  One host read: the err word."""
     verts, faces = _mesh(verts, faces)
     n = _n_samples(n)
-    err = torch.zeros(1, dtype=torch.int32, device=faces.device)
-    smp = _sample(verts, faces, n, seed, err)
-    _raise_eval(int(err.cpu()))
+    err = _ma.new_err(faces.device)
+    with _host.on_device(faces.device):
+        smp = _sample(verts, faces, n, seed, err)
+    _ma.raise_if(int(err.cpu()), **_ERR)
     return smp
 
 
 # ------------------------------------------------------------------------------------------------ mesh against mesh
 def _stats_into(dist: torch.Tensor, thr: torch.Tensor, ws: torch.Tensor, out: torch.Tensor) -> None:
-    _lib.check(_lib.load().gsr_eval_distance_stats(int(dist.shape[0]), _p(dist), int(thr.shape[0]), _p(thr), _p(ws), _p(out), _stream()),
+    _lib.check(_lib.load().gsr_eval_distance_stats(int(dist.shape[0]), _p(dist), int(thr.shape[0]), _p(thr), _p(ws), _p(out), _host.stream_of(dist)),
                "gsr_eval_distance_stats")
 
 
@@ -232,17 +228,18 @@ def mesh_distance(a, b, n_samples: int = 100_000, thresholds: Sequence[float] = 
         raise ValueError(f"at most {_lib.load().gsr_eval_max_thresholds()} thresholds")
     thr = torch.tensor(taus, dtype=torch.float64, device=dev) if T else torch.zeros(0, dtype=torch.float64, device=dev)
     status = torch.zeros(2 * (3 + T) + 1, dtype=torch.int64, device=dev)
-    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    err = _ma.new_err(dev)
     ws = _workspace(dev)
     hits = []
-    for d, (src, dst, s) in enumerate((((va, fa), (vb, fb), seed), ((vb, fb), (va, fa), seed + 1))):
-        smp = _sample(*src, n, s, err)
-        hit = _closest(smp.points, _face_records(*dst, err), err)
-        _stats_into(hit.dist, thr, ws, status[d * (3 + T):])
-        hits.append(hit)
+    with _host.on_device(dev):
+        for d, (src, dst, s) in enumerate((((va, fa), (vb, fb), seed), ((vb, fb), (va, fa), seed + 1))):
+            smp = _sample(*src, n, s, err)
+            hit = _closest(smp.points, _face_records(*dst, err), err)
+            _stats_into(hit.dist, thr, ws, status[d * (3 + T):])
+            hits.append(hit)
     status[-1:] = err
     host = status.cpu().numpy()                                       # the one read
-    _raise_eval(int(host[-1]))
+    _ma.raise_if(int(host[-1]), **_ERR)
     dirs = []
     for d in range(2):
         blk = host[d * (3 + T):(d + 1) * (3 + T)]
@@ -280,7 +277,7 @@ def _sse_into(pred: torch.Tensor, gt: torch.Tensor, mask: Optional[torch.Tensor]
     """out [2] 64-bit words: f64 SSE, int64 count.  Views are used as they are."""
     C, H, W = (int(v) for v in pred.shape)
     _lib.check(_lib.load().gsr_eval_image_sse(C, H, W, _p(pred), pred.stride(0), pred.stride(1), pred.stride(2), _p(gt), gt.stride(0),
-                                              gt.stride(1), gt.stride(2), _p(mask), int(bool(clamp)), _p(ws), _p(out), _stream()),
+                                              gt.stride(1), gt.stride(2), _p(mask), int(bool(clamp)), _p(ws), _p(out), _host.stream_of(pred)),
                "gsr_eval_image_sse")
 
 
@@ -305,7 +302,8 @@ def image_metrics(pred: torch.Tensor, gt: torch.Tensor, mask: Optional[torch.Ten
             raise ValueError("mask must be [H,W] bool or uint8 on the images' GPU")
         mask = mask.to(torch.uint8).contiguous()
     out = torch.zeros(3, dtype=torch.float64, device=dev)
-    _sse_into(pred, gt, mask, clamp, _workspace(dev), out)
+    with _host.on_device(dev):
+        _sse_into(pred, gt, mask, clamp, _workspace(dev), out)
     if mask is None:
         from . import losses
         out[2] = losses.ssim(pred.clamp(0.0, 1.0) if clamp else pred, gt).double()

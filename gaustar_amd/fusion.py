@@ -37,8 +37,8 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import _lib
-from ._lib import ptr as _p, stream_ptr as _stream
+from . import _host, _lib
+from ._lib import ptr as _p
 
 UNIT = 16          # voxels along a unit's edge (ScalableTSDFVolume volume_unit_resolution)
 BG_RGB = (0.0, 1.0, 0.0)   # refined_mesh.py:354
@@ -325,12 +325,13 @@ def integrate_views(volume: TSDFVolume, depth: torch.Tensor, rgb8: torch.Tensor,
         raise RuntimeError("the images and the volume must be on the same GPU")
     depth, rgb8 = depth.contiguous(), rgb8.contiguous()
     cam = cam28(intrinsic, extrinsic)
-    st = _stream()
-    _lib.check(lib.gsr_fusion_touch(H, W, _p(depth), cam, volume.voxel_size, volume.sdf_trunc, volume.grid, _p(volume.touched), st),
-               "gsr_fusion_touch")
-    _lib.check(lib.gsr_fusion_integrate(H, W, _p(depth), _p(rgb8), cam, volume.voxel_size, volume.sdf_trunc, volume.grid,
-                                        _p(volume.touched), _p(volume.tsdf), _p(volume.weight), _p(volume.color), st),
-               "gsr_fusion_integrate")
+    st = _host.stream_of(depth)
+    with _host.on_device(depth.device):
+        _lib.check(lib.gsr_fusion_touch(H, W, _p(depth), cam, volume.voxel_size, volume.sdf_trunc, volume.grid, _p(volume.touched), st),
+                   "gsr_fusion_touch")
+        _lib.check(lib.gsr_fusion_integrate(H, W, _p(depth), _p(rgb8), cam, volume.voxel_size, volume.sdf_trunc, volume.grid,
+                                            _p(volume.touched), _p(volume.tsdf), _p(volume.weight), _p(volume.color), st),
+                   "gsr_fusion_integrate")
     volume.n_views += 1
 
 
@@ -355,19 +356,20 @@ def extract_triangle_mesh(volume: TSDFVolume) -> Tuple[torch.Tensor, torch.Tenso
     mask = torch.empty(n, dtype=torch.uint8, device=dev)
     vcnt = torch.empty(n, dtype=torch.int32, device=dev)
     tcnt = torch.empty(n, dtype=torch.int32, device=dev)
-    st = _stream()
-    _lib.check(lib.gsr_fusion_count(volume.grid, _p(volume.tsdf), _p(volume.weight), _p(table), _p(mask), _p(vcnt), _p(tcnt), st),
-               "gsr_fusion_count")
-    vscan = torch.cumsum(vcnt, 0, dtype=torch.int32)
-    tscan = torch.cumsum(tcnt, 0, dtype=torch.int32)
-    del vcnt, tcnt
-    nv, nf = (int(v) for v in torch.stack([vscan[-1], tscan[-1]]).cpu())
-    verts = torch.empty(nv, 3, dtype=torch.float32, device=dev)
-    colors = torch.empty(nv, 3, dtype=torch.float32, device=dev)
-    faces = torch.empty(nf, 3, dtype=torch.int32, device=dev)
-    _lib.check(lib.gsr_fusion_emit(volume.grid, volume.voxel_size, _p(volume.tsdf), _p(volume.color), _p(mask), _p(vscan), _p(tscan),
-                                   _p(table), _p(verts) if nv else None, _p(faces) if nf else None, _p(colors) if nv else None, st),
-               "gsr_fusion_emit")
+    st = _host.stream_of(mask)
+    with _host.on_device(mask.device):
+        _lib.check(lib.gsr_fusion_count(volume.grid, _p(volume.tsdf), _p(volume.weight), _p(table), _p(mask), _p(vcnt), _p(tcnt), st),
+                   "gsr_fusion_count")
+        vscan = torch.cumsum(vcnt, 0, dtype=torch.int32)
+        tscan = torch.cumsum(tcnt, 0, dtype=torch.int32)
+        del vcnt, tcnt
+        nv, nf = (int(v) for v in torch.stack([vscan[-1], tscan[-1]]).cpu())
+        verts = torch.empty(nv, 3, dtype=torch.float32, device=dev)
+        colors = torch.empty(nv, 3, dtype=torch.float32, device=dev)
+        faces = torch.empty(nf, 3, dtype=torch.int32, device=dev)
+        _lib.check(lib.gsr_fusion_emit(volume.grid, volume.voxel_size, _p(volume.tsdf), _p(volume.color), _p(mask), _p(vscan), _p(tscan),
+                                       _p(table), _p(verts) if nv else None, _p(faces) if nf else None, _p(colors) if nv else None, st),
+                   "gsr_fusion_emit")
     return verts, faces, colors
 
 
@@ -421,8 +423,9 @@ def prepare_images(rgb: torch.Tensor, depth_alpha: torch.Tensor, depth_trunc: fl
     depth, rgb8 = out if out is not None else (torch.empty(H, W, dtype=torch.float32, device=dev),
                                                torch.empty(H, W, 3, dtype=torch.uint8, device=dev))
     ws = torch.empty(int(lib.gsr_fusion_prep_workspace_bytes(H, W)), dtype=torch.uint8, device=dev)
-    _lib.check(lib.gsr_fusion_prep(H, W, _p(depth_alpha), _p(rgb), int(bool(mask_background)), int(bool(remove_depth_edge)),
-                                   float(depth_trunc), _p(ws), _p(depth), _p(rgb8), _stream()), "gsr_fusion_prep")
+    with _host.on_device(dev):
+        _lib.check(lib.gsr_fusion_prep(H, W, _p(depth_alpha), _p(rgb), int(bool(mask_background)), int(bool(remove_depth_edge)),
+                                       float(depth_trunc), _p(ws), _p(depth), _p(rgb8), _host.stream_of(rgb)), "gsr_fusion_prep")
     return depth, rgb8
 
 

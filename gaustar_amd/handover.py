@@ -20,9 +20,8 @@ from __future__ import annotations
 
 import torch
 
-from . import _lib
-from ._lib import ptr as _p, stream_ptr as _stream
-from .regions import _faces_i32 as _faces, _raise_if
+from . import _host, _lib, _meshargs as _ma
+from ._lib import ptr as _p
 
 FILLED = -2 ** 31            # a face_origin entry: the face was made by fill_small_holes
 SH_C0 = 0.28209479177387814
@@ -52,7 +51,8 @@ def sh_face_colors(sh_dc: torch.Tensor, G: int) -> torch.Tensor:
     x = sh_dc.detach().contiguous()
     F = x.numel() // (3 * G)
     out = torch.empty(F, 4, dtype=torch.uint8, device=x.device)
-    _lib.check(_lib.load().gsr_handover_face_colors(F, G, _p(x), _p(out), _stream()), "gsr_handover_face_colors")
+    with _host.on_device(x.device):
+        _lib.check(_lib.load().gsr_handover_face_colors(F, G, _p(x), _p(out), _host.raw_stream(x.device.index)), "gsr_handover_face_colors")
     return out
 
 
@@ -60,14 +60,15 @@ def sh_face_colors(sh_dc: torch.Tensor, G: int) -> torch.Tensor:
 def vertex_to_face_colors(faces: torch.Tensor, vertex_colors: torch.Tensor) -> torch.Tensor:
     """[F,4] uint8: per vertex clip(rint(255 c), 0, 255), per face and channel the floor of the integer mean of its three
     vertices, alpha 255.  An index outside the vertices raises ValueError.  One host read: the err word."""
-    faces = _faces(faces)
-    c = _vertex_colors(vertex_colors, faces.device)
-    F = int(faces.shape[0])
-    out = torch.empty(F, 4, dtype=torch.uint8, device=faces.device)
-    err = torch.zeros(1, dtype=torch.int32, device=faces.device)
-    _lib.check(_lib.load().gsr_handover_vertex_to_face(F, int(c.shape[0]), _p(faces), _p(c), int(c.shape[1]), _p(out), _p(err), _stream()),
-               "gsr_handover_vertex_to_face")
-    _raise_if(int(err.cpu()))
+    faces = _ma.faces_i32(faces)
+    dev, F = faces.device, int(faces.shape[0])
+    c = _vertex_colors(vertex_colors, dev)
+    out = torch.empty(F, 4, dtype=torch.uint8, device=dev)
+    err = _ma.new_err(dev)
+    with _host.on_device(dev):
+        _lib.check(_lib.load().gsr_handover_vertex_to_face(F, int(c.shape[0]), _p(faces), _p(c), int(c.shape[1]), _p(out), _p(err),
+                                                           _host.raw_stream(dev.index)), "gsr_handover_vertex_to_face")
+    _ma.raise_if(int(err.cpu()))
     return out
 
 
@@ -75,19 +76,20 @@ def vertex_to_face_colors(faces: torch.Tensor, vertex_colors: torch.Tensor) -> t
 def face_to_vertex_colors(faces: torch.Tensor, face_rgba: torch.Tensor, n_verts: int) -> torch.Tensor:
     """[n_verts,4] uint8: per vertex and channel the floor of the integer mean over its incident faces whose alpha is not 0,
     alpha 255; a vertex without such a face gets (0, 0, 0, 0).  Integer sums: the same bytes every call.  One host read."""
-    faces = _faces(faces)
+    faces = _ma.faces_i32(faces)
     dev, F, V = faces.device, int(faces.shape[0]), int(n_verts)
     rgba = _rgba(face_rgba, dev, "face_rgba")
     if rgba.shape[0] != F or V < 0:
         raise ValueError("face_rgba must have one row per face, and n_verts must not be negative")
     sums = torch.empty(max(V, 1), 4, dtype=torch.int32, device=dev)
     out = torch.empty(V, 4, dtype=torch.uint8, device=dev)
-    err = torch.zeros(1, dtype=torch.int32, device=dev)
-    _lib.check(_lib.load().gsr_handover_face_to_vertex(F, V, _p(faces), _p(rgba), _p(sums), _p(out), _p(err), _stream()),
-               "gsr_handover_face_to_vertex")
+    err = _ma.new_err(dev)
+    with _host.on_device(dev):
+        _lib.check(_lib.load().gsr_handover_face_to_vertex(F, V, _p(faces), _p(rgba), _p(sums), _p(out), _p(err), _host.raw_stream(dev.index)),
+                   "gsr_handover_face_to_vertex")
     if V == 0 and F:
-        _raise_if(1)                                               # (faces without vertices)
-    _raise_if(int(err.cpu()))
+        _ma.raise_if(1)                                               # (faces without vertices)
+    _ma.raise_if(int(err.cpu()))
     return out
 
 
@@ -96,7 +98,7 @@ def sh_dc_from_vertex_colors(faces: torch.Tensor, vertex_colors: torch.Tensor, b
     """[F G,3] f32: RGB2SH of the barycentric blend of each face's vertex colours (sugar_model.py:237-240, :386): per Gaussian g
     and channel c = (b_g0 v0 + b_g1 v1) + b_g2 v2, dc = (c - 0.5) / C0 in f32, nothing contracted.  bary: [G,3] f32.  One host
     read: the err word."""
-    faces = _faces(faces)
+    faces = _ma.faces_i32(faces)
     dev, F = faces.device, int(faces.shape[0])
     c = _vertex_colors(vertex_colors, dev)
     if bary.dim() != 2 or bary.shape[1] != 3 or bary.dtype != torch.float32 or bary.device != dev:
@@ -104,10 +106,11 @@ def sh_dc_from_vertex_colors(faces: torch.Tensor, vertex_colors: torch.Tensor, b
     bary = bary.detach().contiguous()
     G = int(bary.shape[0])
     out = torch.empty(F * G, 3, dtype=torch.float32, device=dev)
-    err = torch.zeros(1, dtype=torch.int32, device=dev)
-    _lib.check(_lib.load().gsr_handover_sh_dc(F, G, int(c.shape[0]), _p(faces), _p(c), int(c.shape[1]), _p(bary), _p(out), _p(err),
-                                              _stream()), "gsr_handover_sh_dc")
-    _raise_if(int(err.cpu()))
+    err = _ma.new_err(dev)
+    with _host.on_device(dev):
+        _lib.check(_lib.load().gsr_handover_sh_dc(F, G, int(c.shape[0]), _p(faces), _p(c), int(c.shape[1]), _p(bary), _p(out), _p(err),
+                                                  _host.raw_stream(dev.index)), "gsr_handover_sh_dc")
+    _ma.raise_if(int(err.cpu()))
     return out
 
 
@@ -121,15 +124,16 @@ def gather_face_colors(origin: torch.Tensor, base_rgba: torch.Tensor, fusion_fac
     dev, n = origin.device, int(origin.shape[0])
     origin = origin.contiguous()
     base = _rgba(base_rgba, dev, "base_rgba")
-    ff = _faces(fusion_faces)
+    ff = _ma.faces_i32(fusion_faces)
     if ff.device != dev:
         raise RuntimeError("the fusion mesh must be on the same GPU")
     c = _vertex_colors(fusion_vertex_colors, dev)
     out = torch.empty(n, 4, dtype=torch.uint8, device=dev)
-    err = torch.zeros(1, dtype=torch.int32, device=dev)
-    _lib.check(_lib.load().gsr_handover_gather(n, _p(origin), int(base.shape[0]), _p(base), int(ff.shape[0]), int(c.shape[0]), _p(ff),
-                                               _p(c), int(c.shape[1]), _p(out), _p(err), _stream()), "gsr_handover_gather")
-    _raise_if(int(err.cpu()))
+    err = _ma.new_err(dev)
+    with _host.on_device(dev):
+        _lib.check(_lib.load().gsr_handover_gather(n, _p(origin), int(base.shape[0]), _p(base), int(ff.shape[0]), int(c.shape[0]), _p(ff),
+                                                   _p(c), int(c.shape[1]), _p(out), _p(err), _host.raw_stream(dev.index)), "gsr_handover_gather")
+    _ma.raise_if(int(err.cpu()))
     return out
 
 

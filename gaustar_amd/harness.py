@@ -558,21 +558,22 @@ class SurfaceGaussians(nn.Module):
         unreferenced ones included, the parameters gathered by face, not loose-bound (:1185-1216).  Every face starts inside:
         the reference's initial mask (:1169) has one entry per Gaussian and fits its per-face use only with one Gaussian per
         triangle.  -> PostprocessResult.  ValueError if no face is left.  One host read, at the end."""
-        from . import density, regions
+        from . import _host, _meshargs, density, regions
         G = self.n_gaussians_per_surface_triangle
         self._fence()
-        faces = regions._faces_i32(self._surface_mesh_faces)
+        faces = _meshargs.faces_i32(self._surface_mesh_faces)
         F, dev = int(faces.shape[0]), faces.device
         verts = self._points.detach()
         err = torch.zeros(2, dtype=torch.int32, device=dev)       # [0]: the edge kernels' word, [1]: the density's
         mask = torch.ones(F, dtype=torch.bool, device=dev)
         kept = []
-        for _ in range(int(iterations)):
-            if F == 0:
-                break
-            counts = regions._edge_counts(faces, err[0:1], mask.view(torch.uint8))
-            mask = mask & (counts >= 2).all(dim=1)
-            kept.append(mask.sum())
+        with _host.on_device(dev):
+            for _ in range(int(iterations)):
+                if F == 0:
+                    break
+                counts = regions._edge_counts(faces, err[0:1], mask.view(torch.uint8))
+                mask = mask & (counts >= 2).all(dim=1)
+                kept.append(mask.sum())
         removed = ~mask
         fv = verts[self._surface_mesh_faces]
         centres = ((fv[:, 0] + fv[:, 1]) + fv[:, 2]) / 3
@@ -588,8 +589,8 @@ class SurfaceGaussians(nn.Module):
         back = removed & (dens > float(density_threshold))
         mask = mask | back
         host = torch.stack([err[0].long(), err[1].long(), back.sum(), mask.sum(), *kept]).cpu().tolist()
-        regions._raise_if(host[0])
-        density._raise_if(host[1])
+        _meshargs.raise_if(host[0])
+        _meshargs.raise_if(host[1], **density.ERR_TEXTS)
         if host[3] == 0:
             raise ValueError("postprocess_mesh: no face is left")
         sel = torch.argsort((~mask).to(torch.uint8), stable=True)[:host[3]]      # the kept faces in order, their number known: no read

@@ -21,8 +21,8 @@ from typing import Optional
 
 import torch
 
-from . import _lib
-from ._lib import ptr as _p, stream_ptr as _stream
+from . import _host, _lib
+from ._lib import ptr as _p
 
 KNN = namedtuple("KNN", "dists idx knn")      # pytorch3d.ops.knn._KNN
 MORTON_BITS = 10
@@ -86,13 +86,13 @@ def _search(queries: torch.Tensor, candidates: Optional[torch.Tensor], K: int, e
     if exclude_self and N != M:
         raise ValueError("nearest_neighbors: exclude_self needs the queries to be the candidates")
     dev = q.device
-    with torch.cuda.device(dev):
+    with _host.on_device(dev):
         idx = torch.empty(N, K, dtype=torch.int32, device=dev)
         d2 = torch.empty(N, K, dtype=torch.float32, device=dev)
         st = torch.zeros(2, dtype=torch.int64, device=dev) if stats else None
         if N == 0:
             return idx, d2, st
-        stream = _stream()
+        stream = _host.stream_of(q)
         if M > 0:
             lo, scale = _box(c)
             ccode, corder = torch.sort(_morton(c, lo, scale), stable=True)
@@ -181,8 +181,8 @@ def dist_cuda2(points: torch.Tensor) -> torch.Tensor:
     idx, d2, _ = _search(points, None, 3, True, True, False)
     P = int(d2.shape[0])
     out = torch.empty(P, dtype=torch.float32, device=d2.device)
-    with torch.cuda.device(d2.device):
-        _lib.check(lib.gsr_knn_mean_d2(P, 3, _p(d2), _p(out), _stream()), "gsr_knn_mean_d2")
+    with _host.on_device(d2.device):
+        _lib.check(lib.gsr_knn_mean_d2(P, 3, _p(d2), _p(out), _host.stream_of(d2)), "gsr_knn_mean_d2")
     return out
 
 
@@ -195,9 +195,9 @@ def segment_mean(sorted_ids: torch.Tensor, order: torch.Tensor, values: torch.Te
     dev = values.device
     out = torch.zeros(S, C, dtype=torch.float64, device=dev)
     count = torch.zeros(S, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
+    with _host.on_device(dev):
         _lib.check(lib.gsr_knn_segment_mean(n, int(S), C, _p(sorted_ids.contiguous()), _p(order.contiguous()),
-                                            _p(values.contiguous()), _p(out), _p(count), _stream()), "gsr_knn_segment_mean")
+                                            _p(values.contiguous()), _p(out), _p(count), _host.stream_of(out)), "gsr_knn_segment_mean")
     return out, count
 
 
@@ -209,9 +209,9 @@ def weighted_mean(idx: torch.Tensor, d2: torch.Tensor, values: torch.Tensor, inv
     N, K = int(idx.shape[0]), int(idx.shape[1])
     M, C = int(values.shape[0]), int(values.shape[1])
     out = torch.empty(N, C, dtype=torch.float64, device=values.device)
-    with torch.cuda.device(values.device):
+    with _host.on_device(values.device):
         _lib.check(lib.gsr_knn_weighted_mean(N, K, C, M, _p(idx.contiguous()), _p(d2.contiguous()), _p(values.contiguous()),
-                                             float(inv_scale), _p(out), _stream()), "gsr_knn_weighted_mean")
+                                             float(inv_scale), _p(out), _host.stream_of(out)), "gsr_knn_weighted_mean")
     return out
 
 

@@ -40,8 +40,8 @@ from typing import Callable, List, Optional
 import numpy as np
 import torch
 
-from . import _lib, formats, sweep
-from ._lib import ptr as _p, stream_ptr as _stream
+from . import _host, _lib, formats, sweep
+from ._lib import ptr as _p
 
 ZNEAR = 0.01
 BACKGROUND = 100.0
@@ -109,7 +109,7 @@ def _view(lib, v, f, block, H: int, W: int, znear: float, background: float, ret
     ws = torch.empty(int(lib.gsr_mesh_depth_workspace_bytes(H, W, F)), dtype=torch.uint8, device=dev)
     face = out.face if return_faces else None
     _lib.check(lib.gsr_mesh_depth_view(H, W, V, F, _p(v), _p(f), block, float(znear), float(background), int(small_max), _p(ws),
-                                       _p(out.depth), _p(out.mask), _p(face), _p(out.n_clipped), _stream()), "gsr_mesh_depth_view")
+                                       _p(out.depth), _p(out.mask), _p(face), _p(out.n_clipped), _host.stream_of(v)), "gsr_mesh_depth_view")
     return MeshDepthView(out.depth, out.mask, face, out.n_clipped)
 
 
@@ -134,7 +134,8 @@ def mesh_depth_view(verts, faces, extr, intr, H: int, W: int, *, principal_point
     dev = _device_of(verts, device)
     v, f = _upload(verts, faces, dev)
     block = cam16(extr, intr, *_principal(principal_point, H, W))
-    return _view(_lib.load(), v, f, block, H, W, znear, background, return_faces, small_max, out)
+    with _host.on_device(v.device):
+        return _view(_lib.load(), v, f, block, H, W, znear, background, return_faces, small_max, out)
 
 
 @torch.no_grad()
@@ -162,7 +163,8 @@ def render_mesh_depth(verts, faces, rig: dict, sink: Callable[[int, MeshDepthVie
         pp = (intr[i][0, 2], intr[i][1, 2]) if use_principal_point else None
         sink(i, _view(lib, v, f, cam16(extr[i], intr[i], *_principal(pp, H, W)), H, W, znear, background, return_faces, small_max, None))
 
-    sweep.run_shard(work, len(mine), views_in_flight, dev)
+    with _host.on_device(v.device):      # (for the plain loop; the pipelines' workers set their device themselves)
+        sweep.run_shard(work, len(mine), views_in_flight, dev)
     return mine
 
 

@@ -63,8 +63,8 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import _lib, regions
-from ._lib import ptr as _p, stream_ptr as _stream
+from . import _host, _lib, _meshargs as _ma, regions
+from ._lib import ptr as _p
 from .meshes import MeshTopology
 
 WEIGHTS = ("inverse_distance", "uniform")
@@ -103,7 +103,7 @@ def _f32_attrs(attrs: Sequence[torch.Tensor], V: int, dev) -> Tuple[torch.Tensor
 
 
 class _Round:
-    """The buffers of the rounds and one round's launches."""
+    """The buffers of the rounds and one round's launches (simplify_mesh has made the mesh's device the current one)."""
 
     def __init__(self, verts: torch.Tensor, faces: torch.Tensor, locked: Optional[torch.Tensor], attrs):
         self.lib = _lib.load()
@@ -113,7 +113,7 @@ class _Round:
         self.faces = faces.clone()
         self.attrs = tuple(a.detach().clone().contiguous() for a in attrs)
         self.locked = locked
-        self.err = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.err = _ma.new_err(dev)
         self.pos = torch.empty(V, 3, dtype=torch.float64, device=dev)
         self.live = torch.empty(F, dtype=torch.int32, device=dev)
         self.quadric = torch.empty(V, 10, dtype=torch.float64, device=dev)
@@ -124,7 +124,7 @@ class _Round:
         self.fixed = torch.empty(V, dtype=torch.uint8, device=dev)
         self.m1 = torch.empty(V, dtype=torch.int64, device=dev)
         self.m2 = torch.empty(V, dtype=torch.int64, device=dev)
-        st = _stream()
+        st = _host.stream_of(faces)
         face_quadric = torch.empty(F, 10, dtype=torch.float64, device=dev)
         _lib.check(self.lib.gsr_remesh_setup(F, V, _p(verts), _p(self.faces), _p(self.pos), _p(self.live), _p(face_quadric), _p(self.err),
                                              st), "gsr_remesh_setup")
@@ -143,7 +143,7 @@ class _Round:
     def select(self, n_live: int):
         """One round up to the independent set -> (state for apply, sorted selected keys, their number: one host read)."""
         lib, V, F = self.lib, self.V, self.F
-        st = _stream()
+        st = _host.stream_of(self.faces)
         if self.stale:
             self.corners = self._vertex_faces(st)
             self.stale = False
@@ -172,12 +172,12 @@ class _Round:
                    "gsr_remesh_select")
         ranked = torch.sort(selected)[0]
         word = torch.cat([(ranked != _SENTINEL).sum(dtype=torch.int64).view(1), self.err.to(torch.int64)]).cpu()
-        regions._raise_if(int(word[1]))
+        _ma.raise_if(int(word[1]))
         return (n, n_edges, euv, placement, corners, selected), ranked, int(word[0])
 
     def apply(self, state, ranked: torch.Tensor, n_apply: int) -> None:
         n, n_edges, euv, placement, corners, selected = state
-        st = _stream()
+        st = _host.stream_of(self.faces)
         threshold = ranked[n_apply - 1:n_apply]
         for a in self.attrs:
             C = int(a.numel() // self.V)
@@ -205,10 +205,8 @@ def simplify_mesh(verts: torch.Tensor, faces: torch.Tensor, target_faces: int, l
     takes the mean of its two.  target_faces >= F returns the input unchanged with the identity face_origin and 0 rounds.
     The inputs are not modified.  Host reads: one per round (the number of selected edges and the err word), then the
     compaction's totals.  A face with a vertex index outside [0, V) raises ValueError."""
-    faces = regions._faces_i32(faces)
-    dev, F = faces.device, int(faces.shape[0])
-    verts = regions._verts_f32(verts, dev)
-    V = int(verts.shape[0])
+    verts, faces = _ma.mesh_f32(verts, faces)
+    dev, F, V = faces.device, int(faces.shape[0]), int(verts.shape[0])
     target = int(target_faces)
     if target < 0:
         raise ValueError("target_faces must not be negative")
@@ -217,22 +215,23 @@ def simplify_mesh(verts: torch.Tensor, faces: torch.Tensor, target_faces: int, l
     if target >= F:
         return _identity(verts, faces, attrs)
     if V == 0:
-        regions._raise_if(1)                 # (faces without vertices: every index is outside the mesh)
-    rd = _Round(verts, faces, locked, attrs)
+        _ma.raise_if(1)                         # (faces without vertices: every index is outside the mesh)
     n_live, n_rounds, stalled = F, 0, False
     n_apply = ctypes.c_int(0)
-    while n_live > target:
-        state, ranked, n_selected = rd.select(n_live)
-        _lib.check(rd.lib.gsr_remesh_cap(n_live, target, n_selected, ctypes.byref(n_apply)), "gsr_remesh_cap")
-        if n_apply.value == 0:
-            stalled = True
-            break
-        rd.apply(state, ranked, n_apply.value)
-        n_live -= 2 * n_apply.value
-        n_rounds += 1
-    out = torch.empty(V, 3, dtype=torch.float32, device=dev)
-    _lib.check(rd.lib.gsr_remesh_narrow(3 * V, _p(rd.pos), _p(out), _stream()), "gsr_remesh_narrow")
-    cut, _scan = regions._compact(out, rd.faces, None, (rd.live != 0).to(torch.uint8), rd.attrs, rd.err)
+    with _host.on_device(dev):
+        rd = _Round(verts, faces, locked, attrs)
+        while n_live > target:
+            state, ranked, n_selected = rd.select(n_live)
+            _lib.check(rd.lib.gsr_remesh_cap(n_live, target, n_selected, ctypes.byref(n_apply)), "gsr_remesh_cap")
+            if n_apply.value == 0:
+                stalled = True
+                break
+            rd.apply(state, ranked, n_apply.value)
+            n_live -= 2 * n_apply.value
+            n_rounds += 1
+        out = torch.empty(V, 3, dtype=torch.float32, device=dev)
+        _lib.check(rd.lib.gsr_remesh_narrow(3 * V, _p(rd.pos), _p(out), _host.stream_of(out)), "gsr_remesh_narrow")
+        cut, _scan = regions._compact(out, rd.faces, None, (rd.live != 0).to(torch.uint8), rd.attrs, rd.err)
     origin = torch.nonzero(cut.face_mask).view(-1).to(torch.int32)
     return SimplifiedMesh(verts=cut.verts, faces=cut.faces, face_origin=origin, attrs=cut.attrs, n_rounds=n_rounds, stalled=stalled)
 
@@ -243,22 +242,21 @@ def _smooth(verts: torch.Tensor, faces: torch.Tensor, steps: int, lam_even: floa
         raise ValueError(f"weights must be one of {WEIGHTS}")
     if steps < 0:
         raise ValueError("iterations must not be negative")
-    faces = regions._faces_i32(faces)
-    dev = faces.device
-    verts = regions._verts_f32(verts, dev)
-    V = int(verts.shape[0])
+    verts, faces = _ma.mesh_f32(verts, faces)
+    dev, V = faces.device, int(verts.shape[0])
     locked = _locked_u8(locked, V, dev)
     if V == 0 or steps == 0:
         return verts.clone()
     try:
         off, nbr = MeshTopology.of(faces, V).vertex_neighbours
     except IndexError:
-        regions._raise_if(1)
+        _ma.raise_if(1)
     work = torch.empty(2, V, 3, dtype=torch.float64, device=dev)
     out = torch.empty(V, 3, dtype=torch.float32, device=dev)
-    _lib.check(_lib.load().gsr_remesh_smooth(V, _p(off), _p(nbr), _p(locked), int(steps), float(lam_even), float(lam_odd),
-                                             int(weights == "uniform"), _p(verts), _p(work[0]), _p(work[1]), _p(out), _stream()),
-               "gsr_remesh_smooth")
+    with _host.on_device(dev):
+        _lib.check(_lib.load().gsr_remesh_smooth(V, _p(off), _p(nbr), _p(locked), int(steps), float(lam_even), float(lam_odd),
+                                                 int(weights == "uniform"), _p(verts), _p(work[0]), _p(work[1]), _p(out), _host.stream_of(out)),
+                   "gsr_remesh_smooth")
     return out
 
 

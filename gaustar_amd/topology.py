@@ -27,8 +27,8 @@ from typing import Callable, Optional, Sequence, Union
 import numpy as np
 import torch
 
-from . import _lib, sweep
-from ._lib import ptr as _p, stream_ptr as _stream
+from . import _host, _lib, sweep
+from ._lib import ptr as _p
 
 MAX_DEPTH = 10.0   # refined_mesh.py:24
 
@@ -159,45 +159,46 @@ def detect_topology_errors(model, cameras: Sequence, gt_depth: Union[torch.Tenso
             raise ValueError(f"camera {i}: GT depth {tuple(g.shape)} / render {tuple(render.shape)} vs rig shape {(H, W)}")
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         _lib.check(lib.gsr_topo_view(H, W, V, _p(verts), _p(g), _p(render), _p(surface), float(max_depth),
-                                     sweep.cam14(rig["extrinsics"][i], rig["intrinsics"][i]), _p(ws), _p(local[j]), _stream()),
+                                     sweep.cam14(rig["extrinsics"][i], rig["intrinsics"][i]), _p(ws), _p(local[j]), _host.stream_of(verts)),
                    "gsr_topo_view")
 
-    sweep.run_shard(work, len(mine), views_in_flight, dev)
-    table = sweep.gather_rows(local, C, rank, world)
+    with _host.on_device(verts.device):
+        sweep.run_shard(work, len(mine), views_in_flight, dev)
+        table = sweep.gather_rows(local, C, rank, world)
 
-    # ---- over the rig (every rank, same table, same bits)
-    stream = _stream()
-    value = torch.empty(V, dtype=torch.float64, device=dev)
-    count = torch.empty(V, dtype=torch.int32, device=dev)
-    valid = torch.empty(V, dtype=torch.uint8, device=dev)
-    ymin = verts[:, 1].min().reshape(1) if V else None
-    _lib.check(lib.gsr_topo_aggregate(C, V, _p(table.contiguous()), _p(verts), _p(ymin), float(depth_scalar), int(min_observe),
-                                      int(bool(detect_floor)), _p(value), _p(count), _p(valid), stream), "gsr_topo_aggregate")
-    off, nbr = topo.vertex_neighbours
-    sweeps = int(mesh_prop) if mesh_prop else 0
-    prop = torch.empty_like(value)
-    tmp = torch.empty_like(value)
-    va, vb = torch.empty_like(valid), torch.empty_like(valid)
-    _lib.check(lib.gsr_topo_propagate(V, _p(off), _p(nbr), sweeps, _p(value), _p(valid), _p(prop), _p(tmp), _p(va), _p(vb), stream),
-               "gsr_topo_propagate")
+        # ---- over the rig (every rank, same table, same bits)
+        stream = _host.stream_of(verts)
+        value = torch.empty(V, dtype=torch.float64, device=dev)
+        count = torch.empty(V, dtype=torch.int32, device=dev)
+        valid = torch.empty(V, dtype=torch.uint8, device=dev)
+        ymin = verts[:, 1].min().reshape(1) if V else None
+        _lib.check(lib.gsr_topo_aggregate(C, V, _p(table.contiguous()), _p(verts), _p(ymin), float(depth_scalar), int(min_observe),
+                                          int(bool(detect_floor)), _p(value), _p(count), _p(valid), stream), "gsr_topo_aggregate")
+        off, nbr = topo.vertex_neighbours
+        sweeps = int(mesh_prop) if mesh_prop else 0
+        prop = torch.empty_like(value)
+        tmp = torch.empty_like(value)
+        va, vb = torch.empty_like(valid), torch.empty_like(valid)
+        _lib.check(lib.gsr_topo_propagate(V, _p(off), _p(nbr), sweeps, _p(value), _p(valid), _p(prop), _p(tmp), _p(va), _p(vb), stream),
+                   "gsr_topo_propagate")
 
-    vmin = verts.amin(0).contiguous()
-    keys = torch.empty(V, dtype=torch.int64, device=dev)
-    flags = torch.zeros(1, dtype=torch.int32, device=dev)
-    _lib.check(lib.gsr_topo_voxel_keys(V, _p(verts), _p(vmin), float(voxel_size), _p(keys), _p(flags), stream), "gsr_topo_voxel_keys")
-    skeys, order = torch.sort(keys, stable=True)
-    change = torch.ones(V, dtype=torch.int64, device=dev)
-    change[1:] = (skeys[1:] != skeys[:-1]).long()
-    vid = torch.cumsum(change, 0)
-    vid -= 1
-    vox_ws = torch.empty(int(lib.gsr_topo_voxel_workspace_bytes(V)) // 4 + 4, dtype=torch.float32, device=dev)
-    vox_value = torch.empty(V, dtype=torch.float64, device=dev)
-    interp = torch.empty(V, dtype=torch.float64, device=dev)
-    _lib.check(lib.gsr_topo_voxel_interp(V, _p(verts), _p(vmin), float(voxel_size), _p(skeys), _p(order.contiguous()), _p(vid),
-                                         _p(prop), _p(vox_ws), _p(vox_value), _p(interp), stream), "gsr_topo_voxel_interp")
-    face_colour = torch.empty(F, dtype=torch.uint8, device=dev)
-    face_loss = torch.empty(F, dtype=torch.float32, device=dev)
-    _lib.check(lib.gsr_topo_faces(F, _p(topo.faces), _p(interp), _p(face_colour), _p(face_loss), stream), "gsr_topo_faces")
+        vmin = verts.amin(0).contiguous()
+        keys = torch.empty(V, dtype=torch.int64, device=dev)
+        flags = torch.zeros(1, dtype=torch.int32, device=dev)
+        _lib.check(lib.gsr_topo_voxel_keys(V, _p(verts), _p(vmin), float(voxel_size), _p(keys), _p(flags), stream), "gsr_topo_voxel_keys")
+        skeys, order = torch.sort(keys, stable=True)
+        change = torch.ones(V, dtype=torch.int64, device=dev)
+        change[1:] = (skeys[1:] != skeys[:-1]).long()
+        vid = torch.cumsum(change, 0)
+        vid -= 1
+        vox_ws = torch.empty(int(lib.gsr_topo_voxel_workspace_bytes(V)) // 4 + 4, dtype=torch.float32, device=dev)
+        vox_value = torch.empty(V, dtype=torch.float64, device=dev)
+        interp = torch.empty(V, dtype=torch.float64, device=dev)
+        _lib.check(lib.gsr_topo_voxel_interp(V, _p(verts), _p(vmin), float(voxel_size), _p(skeys), _p(order.contiguous()), _p(vid),
+                                             _p(prop), _p(vox_ws), _p(vox_value), _p(interp), stream), "gsr_topo_voxel_interp")
+        face_colour = torch.empty(F, dtype=torch.uint8, device=dev)
+        face_loss = torch.empty(F, dtype=torch.float32, device=dev)
+        _lib.check(lib.gsr_topo_faces(F, _p(topo.faces), _p(interp), _p(face_colour), _p(face_loss), stream), "gsr_topo_faces")
 
     unbind, n_changed = unbind_weights(face_loss, face_colour, G)
     head = torch.stack([n_changed, flags[0].long(), vid[-1] + 1 if V else torch.zeros((), dtype=torch.long, device=dev)]).cpu()

@@ -26,11 +26,11 @@ from typing import NamedTuple, Optional, Tuple
 import numpy as np
 import torch
 
-from . import _lib
-from ._lib import ptr as _p, stream_ptr as _stream
-from .regions import _faces_i32, _raise_if
+from . import _host, _lib, _meshargs as _ma
+from ._lib import ptr as _p
 
 _NAN = "a vertex or a tracked position is NaN or infinite"
+_ERR = dict(nan=_NAN, degenerate="a re-bound barycentric is not >= 0: the nearest face of a point is degenerate")   # (bit 3 ranks last)
 _STATUS_WORDS = 8          # err, kept, moved, lost, the to-do list's length
 
 
@@ -42,32 +42,9 @@ class RebindStats(NamedTuple):
     n_lost: int
 
 
-def _raise_track(err: int) -> None:
-    _raise_if(err, _NAN)
-    if err & 8:
-        raise ValueError("a re-bound barycentric is not >= 0: the nearest face of a point is degenerate")
-
-
-def _mesh_f64(verts: torch.Tensor, faces: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
-    if not torch.is_tensor(faces) or not torch.is_tensor(verts) or faces.device.type != "cuda":
-        raise ValueError("verts and faces must be tensors on a GPU")
-    faces = _faces_i32(faces)
-    if verts.dim() != 2 or verts.shape[1] != 3 or verts.dtype not in (torch.float32, torch.float64):
-        raise ValueError("verts must be [V,3] float64 (or float32, which is widened)")
-    if verts.device != faces.device:
-        raise ValueError("verts and faces must be on the same GPU")
-    return verts.detach().to(torch.float64).contiguous(), faces
-
-
-def _points_f64(x: torch.Tensor, dev, what: str) -> torch.Tensor:
-    if x.dim() != 2 or x.shape[1] != 3 or x.dtype != torch.float64 or x.device != dev:
-        raise ValueError(f"{what} must be [K,3] float64 on the tracker's GPU")
-    return x.detach().contiguous()
-
-
 def _nearest_and_bind(K: int, todo, n_todo, pos, verts, faces, ids, bary, clamp: bool, err):
     """centres -> nearest centre of every listed point -> its barycentrics on that face, all on the current stream."""
-    lib, st, dev = _lib.load(), _stream(), pos.device
+    lib, st, dev = _lib.load(), _host.stream_of(pos), pos.device
     F1, V1 = int(faces.shape[0]), int(verts.shape[0])
     centres = torch.empty(F1, 3, dtype=torch.float64, device=dev)
     idx = torch.empty(max(K, 1), dtype=torch.int32, device=dev)
@@ -103,7 +80,7 @@ class SurfaceTracker:
                 raise ValueError("face_bary must be [K,3] float64")
             self.face_bary = b.to(dev).contiguous().clone()
         self.face_ids_ori = self.face_ids.clone()
-        self._err = torch.zeros(1, dtype=torch.int32, device=dev)      # what positions() found since the last rebind()
+        self._err = _ma.new_err(dev)                                      # what positions() found since the last rebind()
         self._n_faces = None                                           # the faces of the mesh positions() last saw
 
     @classmethod
@@ -128,14 +105,15 @@ class SurfaceTracker:
     def positions(self, verts: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
         """[K,3] f64 = bary_to_point(verts[faces[face_ids]], face_bary) (:70).  Nothing is read back: a point whose id, face or
         vertices are not valid gets a NaN row, and the next rebind() raises for it."""
-        verts, faces = _mesh_f64(verts, faces)
+        verts, faces = _ma.mesh_f64(verts, faces)
         if faces.device != self.device:
             raise ValueError("the mesh must be on the tracker's GPU")
         K = len(self)
         self._n_faces = int(faces.shape[0])
         pos = torch.empty(K, 3, dtype=torch.float64, device=self.device)
-        _lib.check(_lib.load().gsr_track_positions(K, int(faces.shape[0]), int(verts.shape[0]), _p(faces), _p(verts), _p(self.face_ids),
-                                                   _p(self.face_bary), _p(pos), _p(self._err), _stream()), "gsr_track_positions")
+        with _host.on_device(self.device):
+            _lib.check(_lib.load().gsr_track_positions(K, int(faces.shape[0]), int(verts.shape[0]), _p(faces), _p(verts), _p(self.face_ids),
+                                                       _p(self.face_bary), _p(pos), _p(self._err), _host.stream_of(pos)), "gsr_track_positions")
         return pos
 
     @torch.no_grad()
@@ -147,10 +125,10 @@ class SurfaceTracker:
         counts together.  A ValueError (a mask of another length than the old mesh's faces, an empty new mesh, a bad index, a
         coordinate that is not finite, a degenerate nearest face) leaves the tracker as it was."""
         dev, K = self.device, len(self)
-        new_verts, new_faces = _mesh_f64(new_verts, new_faces)
+        new_verts, new_faces = _ma.mesh_f64(new_verts, new_faces)
         if new_faces.device != dev:
             raise ValueError("the new mesh must be on the tracker's GPU")
-        pos = _points_f64(pos, dev, "pos")
+        pos = _ma.points_f64(pos, dev, "pos")
         mask = track_face_mask
         if not torch.is_tensor(mask) or mask.dim() != 1 or mask.dtype not in (torch.bool, torch.uint8) or mask.device != dev:
             raise ValueError("track_face_mask must be [F0] bool on the tracker's GPU")
@@ -161,7 +139,7 @@ class SurfaceTracker:
             raise ValueError(f"track_face_mask has {F0} entries, the mesh the positions were taken on has {self._n_faces} faces")
         if F1 == 0:
             raise ValueError("the new mesh has no faces")
-        lib, st = _lib.load(), _stream()
+        lib, st = _lib.load(), _host.stream_of(pos)
         mask = mask.to(torch.uint8).contiguous()
         ones = (mask != 0).to(torch.int32)
         rank = torch.cumsum(ones, 0, dtype=torch.int32) - ones                    # np.sum(mask[:i]) (:94)
@@ -171,16 +149,17 @@ class SurfaceTracker:
         err, stats, n_todo = status[0:], status[1:], status[4:]
         flag = torch.empty(K, dtype=torch.int32, device=dev)
         todo = torch.empty(max(K, 1), dtype=torch.int32, device=dev)
-        _lib.check(lib.gsr_track_rebind_survivors(K, F0, F1, V1, _p(mask), _p(rank), _p(new_faces), _p(new_verts), _p(pos), _p(ids),
-                                                  _p(bary), _p(flag), _p(stats), _p(err), st), "gsr_track_rebind_survivors")
-        scan = torch.cumsum(flag, 0, dtype=torch.int32)
-        _lib.check(lib.gsr_track_todo(K, _p(flag), _p(scan), _p(todo), _p(n_todo), st), "gsr_track_todo")
-        _nearest_and_bind(K, todo, n_todo, pos, new_verts, new_faces, ids, bary, True, err)
+        with _host.on_device(dev):
+            _lib.check(lib.gsr_track_rebind_survivors(K, F0, F1, V1, _p(mask), _p(rank), _p(new_faces), _p(new_verts), _p(pos), _p(ids),
+                                                      _p(bary), _p(flag), _p(stats), _p(err), st), "gsr_track_rebind_survivors")
+            scan = torch.cumsum(flag, 0, dtype=torch.int32)
+            _lib.check(lib.gsr_track_todo(K, _p(flag), _p(scan), _p(todo), _p(n_todo), st), "gsr_track_todo")
+            _nearest_and_bind(K, todo, n_todo, pos, new_verts, new_faces, ids, bary, True, err)
         host = status.cpu().tolist()                                              # the one read
         self._err.zero_()
         if host[0] & 1 and F0 and K and int(self.face_ids.max()) >= F0:
             raise ValueError(f"a tracked face id is not below {F0}, the length of track_face_mask")
-        _raise_track(host[0])
+        _ma.raise_if(host[0], **_ERR)
         self.face_ids, self.face_bary, self._n_faces = ids, bary, None
         return RebindStats(host[1], host[2], host[3])
 
@@ -202,9 +181,9 @@ def bind_points(verts: torch.Tensor, faces: torch.Tensor, points: torch.Tensor, 
         from . import evaluate
         hit = evaluate.surface_distance(points, verts, faces)
         return hit.face, hit.bary
-    verts, faces = _mesh_f64(verts, faces)
+    verts, faces = _ma.mesh_f64(verts, faces)
     dev = faces.device
-    pts = _points_f64(points, dev, "points")
+    pts = _ma.points_f64(points, dev, "points")
     K = int(pts.shape[0])
     if int(faces.shape[0]) == 0:
         raise ValueError("the mesh has no faces")
@@ -212,9 +191,10 @@ def bind_points(verts: torch.Tensor, faces: torch.Tensor, points: torch.Tensor, 
         raise ValueError(_NAN)
     ids = torch.zeros(K, dtype=torch.int32, device=dev)
     bary = torch.empty(K, 3, dtype=torch.float64, device=dev)
-    err = torch.zeros(1, dtype=torch.int32, device=dev)
-    _nearest_and_bind(K, None, None, pts, verts, faces, ids, bary, False, err)
-    _raise_track(int(err.cpu()))
+    err = _ma.new_err(dev)
+    with _host.on_device(dev):
+        _nearest_and_bind(K, None, None, pts, verts, faces, ids, bary, False, err)
+    _ma.raise_if(int(err.cpu()), **_ERR)
     return ids, bary
 
 

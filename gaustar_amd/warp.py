@@ -41,8 +41,8 @@ from typing import Callable, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib, formats, sweep
-from ._lib import ptr as _p, stream_ptr as _stream
+from . import _host, _lib, formats, sweep
+from ._lib import ptr as _p
 
 PROP_SWEEPS = 20     # mesh_vert_propagate(max_ite=20) (warp_mesh.py:384, :133)
 SMOOTH_SWEEPS = 5    # mesh_color_smoothing(ite_num=5) (:394)
@@ -139,14 +139,8 @@ def warp_mesh(verts, faces, rig: dict, frames: Callable[[int], tuple], cfg: Warp
     topo = meshes.MeshTopology.of(ft, V)        # (cached on a faces tensor that is passed again)
     f, F = topo.faces, topo.F
     C = int(np.asarray(rig["shape"]).shape[0])
-    stream = _stream()
-
-    # ---- once per warp: world-space vertex normals
-    vf_off, vf_ent = topo.vertex_face_csr
     fbuf = torch.empty(max(F, 1), 6, dtype=torch.float64, device=dev)
     normals = torch.empty(V, 3, dtype=torch.float64, device=dev)
-    _lib.check(lib.gsr_vertex_normals(V, F, _p(v), _p(f), _p(vf_off), _p(vf_ent), _p(fbuf), _p(normals), stream),
-               "gsr_vertex_normals")
 
     # ---- per camera: one row [V,3] of the table
     mine = sweep.camera_shard(C, rank, world)
@@ -171,43 +165,48 @@ def warp_mesh(verts, faces, rig: dict, frames: Callable[[int], tuple], cfg: Warp
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         _lib.check(lib.gsr_warp_view(H, W, V, _p(v), _p(normals), _p(ff), _p(fb), _pad6(ff, pad), _p(dc), _p(dn),
                                      sweep.cam14(rig["extrinsics"][i], rig["intrinsics"][i]), params, _p(ws), _p(local[j]),
-                                     _stream()), "gsr_warp_view")
+                                     _host.stream_of(v)), "gsr_warp_view")
 
-    sweep.run_shard(work, len(mine), views_in_flight, dev)
-    table = sweep.gather_rows(local, C, rank, world)
+    with _host.on_device(v.device):
+        # ---- once per warp: world-space vertex normals
+        vf_off, vf_ent = topo.vertex_face_csr
+        _lib.check(lib.gsr_vertex_normals(V, F, _p(v), _p(f), _p(vf_off), _p(vf_ent), _p(fbuf), _p(normals), _host.stream_of(v)),
+                   "gsr_vertex_normals")
+        sweep.run_shard(work, len(mine), views_in_flight, dev)
+        table = sweep.gather_rows(local, C, rank, world)
 
-    # ---- over the rig (every rank, same table, same bits)
-    stream = _stream()
-    move = torch.empty(V, 3, dtype=torch.float64, device=dev)
-    observed = torch.empty(V, dtype=torch.int32, device=dev)
-    count = torch.empty(V, dtype=torch.int32, device=dev)
-    valid = torch.empty(V, dtype=torch.uint8, device=dev)
-    _lib.check(lib.gsr_warp_aggregate(C, V, _p(table.contiguous()), int(cfg.min_observe), _p(move), _p(observed), _p(count),
-                                      _p(valid), stream), "gsr_warp_aggregate")
-    off, nbr = topo.vertex_neighbours
-    prop = vox = None
-    if cfg.post_processing == "voxel":
-        vox = _voxel_interpolate(lib, v, move, valid, cfg, stream)
-    else:
-        # propagation: the valid set evolves independently of the values, so one scalar call per component is the vector result
-        comp = move.t().contiguous()
-        prop_c = torch.empty_like(comp)
-        tmp = torch.empty(V, dtype=torch.float64, device=dev)
-        va, vb = torch.empty_like(valid), torch.empty_like(valid)
-        for k in range(3):
-            _lib.check(lib.gsr_topo_propagate(V, _p(off), _p(nbr), PROP_SWEEPS, _p(comp[k]), _p(valid), _p(prop_c[k]), _p(tmp),
-                                              _p(va), _p(vb), stream), "gsr_topo_propagate")
-        prop = prop_c.t().contiguous()
-    pre = vox if prop is None else prop
-    smooth = torch.empty_like(pre)
-    stmp = torch.empty_like(pre)
-    _lib.check(lib.gsr_warp_smooth(V, _p(off), _p(nbr), SMOOTH_SWEEPS, _p(pre), _p(smooth), _p(stmp), stream), "gsr_warp_smooth")
-    res = MeshWarp(move_raw=move, move_propagated=prop, move_smoothed=smooth, verts_raw=v + move,
-                   verts_propagated=None if prop is None else v + prop, verts_smoothed=v + smooth, observed=observed, count=count,
-                   move_voxel=vox, verts_voxel=None if vox is None else v + vox)
-    if return_stages:
-        res.table, res.normals = table.view(C, V, 3), normals
-    torch.cuda.current_stream().synchronize()
+        # ---- over the rig (every rank, same table, same bits)
+        stream = _host.stream_of(v)
+        move = torch.empty(V, 3, dtype=torch.float64, device=dev)
+        observed = torch.empty(V, dtype=torch.int32, device=dev)
+        count = torch.empty(V, dtype=torch.int32, device=dev)
+        valid = torch.empty(V, dtype=torch.uint8, device=dev)
+        _lib.check(lib.gsr_warp_aggregate(C, V, _p(table.contiguous()), int(cfg.min_observe), _p(move), _p(observed), _p(count),
+                                          _p(valid), stream), "gsr_warp_aggregate")
+        off, nbr = topo.vertex_neighbours
+        prop = vox = None
+        if cfg.post_processing == "voxel":
+            vox = _voxel_interpolate(lib, v, move, valid, cfg, stream)
+        else:
+            # propagation: the valid set evolves independently of the values, so one scalar call per component is the vector result
+            comp = move.t().contiguous()
+            prop_c = torch.empty_like(comp)
+            tmp = torch.empty(V, dtype=torch.float64, device=dev)
+            va, vb = torch.empty_like(valid), torch.empty_like(valid)
+            for k in range(3):
+                _lib.check(lib.gsr_topo_propagate(V, _p(off), _p(nbr), PROP_SWEEPS, _p(comp[k]), _p(valid), _p(prop_c[k]), _p(tmp),
+                                                  _p(va), _p(vb), stream), "gsr_topo_propagate")
+            prop = prop_c.t().contiguous()
+        pre = vox if prop is None else prop
+        smooth = torch.empty_like(pre)
+        stmp = torch.empty_like(pre)
+        _lib.check(lib.gsr_warp_smooth(V, _p(off), _p(nbr), SMOOTH_SWEEPS, _p(pre), _p(smooth), _p(stmp), stream), "gsr_warp_smooth")
+        res = MeshWarp(move_raw=move, move_propagated=prop, move_smoothed=smooth, verts_raw=v + move,
+                       verts_propagated=None if prop is None else v + prop, verts_smoothed=v + smooth, observed=observed, count=count,
+                       move_voxel=vox, verts_voxel=None if vox is None else v + vox)
+        if return_stages:
+            res.table, res.normals = table.view(C, V, 3), normals
+        torch.cuda.current_stream().synchronize()
     return res
 
 

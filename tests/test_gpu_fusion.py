@@ -112,7 +112,7 @@ def _count(hip_lib, vol):
     vcnt, tcnt = (torch.full((n,), -7, dtype=torch.int32, device=DEV) for _ in range(2))
     table = torch.from_numpy(fusion.mc_table()).to(DEV)
     _lib.check(hip_lib.gsr_fusion_count(vol.grid, _lib.ptr(vol.tsdf), _lib.ptr(vol.weight), _lib.ptr(table), _lib.ptr(mask),
-                                        _lib.ptr(vcnt), _lib.ptr(tcnt), _lib.stream_ptr()), "gsr_fusion_count")
+                                        _lib.ptr(vcnt), _lib.ptr(tcnt), torch._C._cuda_getCurrentRawStream(mask.device.index)), "gsr_fusion_count")
     return mask.cpu().numpy(), vcnt.cpu().numpy(), tcnt.cpu().numpy()
 
 

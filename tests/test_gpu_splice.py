@@ -124,7 +124,7 @@ def test_bad_index_empty_and_closed():
         regions.face_areas(_t(np.zeros((4, 3), np.float32)), _t(bad))
     # the err word itself, and that the face is left out: the other three faces' hole is still found
     lib = _lib.load()
-    p, st = _lib.ptr, _lib.stream_ptr()
+    p, st = _lib.ptr, torch._C._cuda_getCurrentRawStream(DEV.index)
     tf = _t(bad)
     err = torch.zeros(1, dtype=torch.int32, device=DEV)
     counts = _t(rr.face_edge_counts(bad))

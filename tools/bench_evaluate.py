@@ -37,7 +37,8 @@ def step(reps: int, host_queries: int, views: int) -> dict:
     import eval_ref as ref
     from bench_splice import inputs, timed
     from gaustar_amd import _lib, evaluate, harness, regions, scene
-    from gaustar_amd._lib import ptr as p, stream_ptr
+    from gaustar_amd._host import stream_of
+    from gaustar_amd._lib import ptr as p
     assert torch.cuda.is_available(), "bench_evaluate needs a GPU"
     dev = torch.device("cuda:0")
     bv, bf, fv, ff, raw = inputs()
@@ -63,8 +64,8 @@ def step(reps: int, host_queries: int, views: int) -> dict:
 
     lib, centres = _lib.load(), torch.empty(F, 3, dtype=torch.float64, device=dev)
     idx = torch.empty(N_SAMPLES, dtype=torch.int32, device=dev)
-    _lib.check(lib.gsr_track_centres(F, int(result[0].shape[0]), p(result[1]), p(result[0]), p(centres), p(err), stream_ptr()), "centres")
-    nn = lambda: _lib.check(lib.gsr_track_nearest(N_SAMPLES, None, None, F, p(smp.points), p(centres), p(idx), stream_ptr()), "nearest")
+    _lib.check(lib.gsr_track_centres(F, int(result[0].shape[0]), p(result[1]), p(result[0]), p(centres), p(err), stream_of(centres)), "centres")
+    nn = lambda: _lib.check(lib.gsr_track_nearest(N_SAMPLES, None, None, F, p(smp.points), p(centres), p(idx), stream_of(idx)), "nearest")
     _, *out["track_nn"] = timed(nn, reps)
 
     md, *out["mesh_distance"] = timed(lambda: evaluate.mesh_distance(result, base, n_samples=N_SAMPLES), reps)

@@ -47,10 +47,10 @@ def step(reps: int, inner: int) -> dict:
     import torch
     import handover_ref as ref
     from bench_splice import inputs
-    from gaustar_amd import _lib, handover, harness, regions
+    from gaustar_amd import _host, _lib, handover, harness, regions
     assert torch.cuda.is_available(), "bench_handover needs a GPU"
     dev = torch.device("cuda:0")
-    lib, p, st = _lib.load(), _lib.ptr, _lib.stream_ptr()
+    lib, p, st = _lib.load(), _lib.ptr, _host.raw_stream(dev.index)
     bv, bf, fv, ff, raw = inputs()
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
     rng = np.random.default_rng(0)

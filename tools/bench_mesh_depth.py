@@ -49,10 +49,10 @@ def step(reps: int, inner: int) -> dict:
     import numpy as np
     import torch
     import meshdepth_ref as ref
-    from gaustar_amd import _lib, harness, mesh_depth, scene, topology
+    from gaustar_amd import _host, _lib, harness, mesh_depth, scene, topology
     assert torch.cuda.is_available(), "bench_mesh_depth needs a GPU"
     dev = torch.device("cuda:0")
-    lib, p, st = _lib.load(), _lib.ptr, _lib.stream_ptr()
+    lib, p, st = _lib.load(), _lib.ptr, _host.raw_stream(dev.index)
     v, f = scene.icosphere(6, scene.SUBJECT_RADIUS, scene.SUBJECT_CENTER)
     rig = topology.rig_from_cameras([harness.nerf_camera_from_scene(c) for c in scene.ring_cameras(W=W, H=H)])
     C, V, F = len(rig["shape"]), len(v), len(f)
