@@ -9,12 +9,13 @@ gradient all-reduce.  Either side of the rasterizer: `pro
 means / scales / quaternions), `losses` (l1 + dssim, masked depth L1, surface-mesh regularisers), `meshes` (single-mesh
 stand-ins for pytorch3d's `Meshes` / `mesh_normal_consistency`), `sweep` (forward-only camera sweeps),
 `mesh_depth` (a mesh's depth maps, masks and visible faces over the rig: the inputs of a tracked sequence),
+`dataprep` (what a sequence needs before frame 0: rectified images, the coloured base mesh, the COLMAP files),
 `tracking` (points followed on the surface through topology updates: SurfaceTracker, track_faces),
 `remesh` (quadric mesh decimation and Laplacian / Taubin smoothing: how an init_mesh_100k.obj is made),
 `knn` (exact K-nearest neighbours with spatial culling: pytorch3d's knn_points, simple-knn's distCUDA2),
 `density` (the Gaussians' density field: SuGaR's compute_density and get_covariance, behind the model's postprocess_mesh),
 `evaluate` (how good a result is: point-to-mesh distance, Chamfer distance and F-score of two meshes, PSNR and SSIM of renders) and
-`formats` (cameras.json, 3DGS PLY, SuGaR .pt, OBJ, grey PNG) -- import them as submodules.
+`formats` (cameras.json, 3DGS PLY, SuGaR .pt, OBJ, grey and RGB PNG) -- import them as submodules.
 """
 from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, rasterize_gaussians  # noqa: F401
 from .tracking import RebindStats, SurfaceTracker, bind_points, track_faces  # noqa: F401

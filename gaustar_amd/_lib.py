@@ -142,6 +142,15 @@ SIGNATURES = {
     "gsr_mesh_depth_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "gsr_mesh_depth_view": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, POINTER(c_double), c_double, c_float, c_int,
                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # a sequence's inputs before frame 0: rectified images, the first mesh's vertex colours (ahq2gaustar.py:50-81, :124-160):
+    # gaustar_amd.dataprep
+    "gsr_image_rectify": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, POINTER(c_double), POINTER(c_double),
+                                  POINTER(ctypes.c_ubyte), c_void_p]),
+    "gsr_mesh_color_view": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, POINTER(c_double), c_double, c_void_p,
+                                    c_void_p]),
+    "gsr_mesh_color_workspace_bytes": (c_size_t, [c_int]),
+    "gsr_mesh_color_finish": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, POINTER(ctypes.c_ubyte), c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_void_p]),
     # TSDF fusion of the rig's renders and mesh extraction (refined_mesh.py:311-459): gaustar_amd.fusion
     "gsr_fusion_prep_workspace_bytes": (c_size_t, [c_int, c_int]),
     "gsr_fusion_volume_bytes": (c_size_t, [POINTER(c_int)]),

@@ -10,7 +10,8 @@ SuGaR / GauSTAR `{iter}.pt` checkpoints -- enough to render a real checkpoint wi
 * OBJ: the meshes gaustar_tools/warp_mesh.py:230 loads with trimesh (process=False, maintain_order=True) and :364-397
   exports: `v x y z [r g b]` and triangular `f` lines, vertex order kept (load_obj / save_obj).
 * PNG: the 8-bit grey masks `img_{c:04d}_alpha.png` that data_process/render_depth_from_mesh.py:93 writes with cv2.imwrite and
-  gaustar_scene/cameras.py:97-106 reads (save_png_gray8 / load_png_gray8; zlib and struct only, neither cv2 nor PIL).
+  gaustar_scene/cameras.py:97-106 reads (save_png_gray8 / load_png_gray8; zlib and struct only, neither cv2 nor PIL), and the
+  8-bit RGB images gaustar_amd.dataprep writes (save_png_rgb8 / load_png_rgb8, colour type 2, the same chunk code).
 * .pt: sugar_model.py:1313-1318 (`save_model`): {'state_dict': ..., extra keys}; state-dict entries `_points`,
   `_surface_mesh_faces`, `_scales`, `_quaternions`, `all_densities`, `_sh_coordinates_dc`, `_sh_coordinates_rest`,
   `surface_mesh_thickness`, `_delta_t`, `_delta_r`.
@@ -284,31 +285,29 @@ def save_obj(path: str, verts, faces, colours=None) -> None:
         fh.write("\n".join(lines) + "\n")
 
 
-# ---------------------------------------------------------------------------------------------- PNG (8-bit grey)
+# ---------------------------------------------------------------------------------------------- PNG (8-bit grey, 8-bit RGB)
 _PNG_MAGIC = b"\x89PNG\r\n\x1a\n"
+_PNG_KINDS = {0: (1, "greyscale"), 2: (3, "RGB")}     # colour type -> (bytes per pixel, its name in messages)
 
 
 def _png_chunk(tag: bytes, data: bytes) -> bytes:
     return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
 
 
-def save_png_gray8(path: str, array) -> None:
-    """array [H,W] uint8 -> an 8-bit greyscale PNG (colour type 0, no interlace, filter 0 on every row)."""
-    a = np.asarray(array)
-    if a.ndim != 2 or a.dtype != np.uint8 or a.shape[0] < 1 or a.shape[1] < 1:
-        raise ValueError(f"save_png_gray8 takes a non-empty [H,W] uint8 array, got {a.dtype} {a.shape}")
-    H, W = a.shape
-    rows = np.zeros((H, W + 1), np.uint8)      # (one filter byte in front of every row)
-    rows[:, 1:] = a
-    data = _PNG_MAGIC + _png_chunk(b"IHDR", struct.pack(">IIBBBBB", W, H, 8, 0, 0, 0, 0)) + \
+def _save_png8(path: str, a: np.ndarray, colour: int) -> None:
+    """a [H,W,bpp] uint8 -> an 8-bit PNG of colour type `colour` (no interlace, filter 0 on every row)."""
+    H, W, bpp = a.shape
+    rows = np.zeros((H, W * bpp + 1), np.uint8)      # (one filter byte in front of every row)
+    rows[:, 1:] = a.reshape(H, W * bpp)
+    data = _PNG_MAGIC + _png_chunk(b"IHDR", struct.pack(">IIBBBBB", W, H, 8, colour, 0, 0, 0)) + \
         _png_chunk(b"IDAT", zlib.compress(rows.tobytes(), 6)) + _png_chunk(b"IEND", b"")
     with open(path, "wb") as fh:
         fh.write(data)
 
 
-def load_png_gray8(path: str) -> np.ndarray:
-    """An 8-bit greyscale, non-interlaced PNG -> [H,W] uint8 (all five row filters; chunk CRCs are checked).  Any other PNG
-    raises ValueError."""
+def _load_png8(path: str, want: int) -> np.ndarray:
+    """An 8-bit, non-interlaced PNG of colour type `want` -> [H,W,bpp] uint8 (all five row filters; chunk CRCs are checked)."""
+    bpp, name = _PNG_KINDS[want]
     with open(path, "rb") as fh:
         blob = fh.read()
     if blob[:8] != _PNG_MAGIC:
@@ -330,24 +329,26 @@ def load_png_gray8(path: str) -> np.ndarray:
     if head is None or not ended:
         raise ValueError(f"{path}: truncated PNG")
     W, H, depth, colour, comp, filt, interlace = head
-    if (depth, colour, comp, filt, interlace) != (8, 0, 0, 0, 0) or W < 1 or H < 1:
-        raise ValueError(f"{path}: not an 8-bit greyscale, non-interlaced PNG (depth {depth}, colour type {colour}, interlace {interlace})")
+    if (depth, colour, comp, filt, interlace) != (8, want, 0, 0, 0) or W < 1 or H < 1:
+        raise ValueError(f"{path}: not an 8-bit {name}, non-interlaced PNG (depth {depth}, colour type {colour}, interlace {interlace})")
     raw = zlib.decompress(b"".join(idat))
-    if len(raw) != H * (W + 1):
+    N = W * bpp
+    if len(raw) != H * (N + 1):
         raise ValueError(f"{path}: {len(raw)} bytes of image data for a {W} x {H} image")
-    rows = np.frombuffer(raw, np.uint8).reshape(H, W + 1)
-    out = np.zeros((H, W), np.uint8)
-    prev = np.zeros(W, np.int64)
+    rows = np.frombuffer(raw, np.uint8).reshape(H, N + 1)
+    out = np.zeros((H, N), np.uint8)
+    prev = np.zeros(N, np.int64)
     for r in range(H):
         kind, x = int(rows[r, 0]), rows[r, 1:].astype(np.int64)
         if kind == 0:
             cur = x
         elif kind == 2:                                  # up
             cur = (x + prev) & 255
-        elif kind in (1, 3, 4):                          # sub, average, Paeth: each byte needs its left neighbour
-            cur = np.zeros(W, np.int64)
-            left = upleft = 0
-            for c in range(W):
+        elif kind in (1, 3, 4):                          # sub, average, Paeth: each byte needs the one a pixel to its left
+            cur = np.zeros(N, np.int64)
+            for c in range(N):
+                left = int(cur[c - bpp]) if c >= bpp else 0
+                upleft = int(prev[c - bpp]) if c >= bpp else 0
                 up = int(prev[c])
                 if kind == 1:
                     pred = left
@@ -357,11 +358,37 @@ def load_png_gray8(path: str) -> np.ndarray:
                     p = left + up - upleft
                     pa, pb, pc = abs(p - left), abs(p - up), abs(p - upleft)
                     pred = left if pa <= pb and pa <= pc else (up if pb <= pc else upleft)
-                left = (int(x[c]) + pred) & 255
-                upleft = up
-                cur[c] = left
+                cur[c] = (int(x[c]) + pred) & 255
         else:
             raise ValueError(f"{path}: row {r} has filter type {kind}")
         out[r] = cur
         prev = cur
-    return out
+    return out.reshape(H, W, bpp)
+
+
+def save_png_gray8(path: str, array) -> None:
+    """array [H,W] uint8 -> an 8-bit greyscale PNG (colour type 0, no interlace, filter 0 on every row)."""
+    a = np.asarray(array)
+    if a.ndim != 2 or a.dtype != np.uint8 or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError(f"save_png_gray8 takes a non-empty [H,W] uint8 array, got {a.dtype} {a.shape}")
+    _save_png8(path, a[:, :, None], 0)
+
+
+def load_png_gray8(path: str) -> np.ndarray:
+    """An 8-bit greyscale, non-interlaced PNG -> [H,W] uint8 (all five row filters; chunk CRCs are checked).  Any other PNG
+    raises ValueError."""
+    return _load_png8(path, 0)[:, :, 0]
+
+
+def save_png_rgb8(path: str, array) -> None:
+    """array [H,W,3] uint8 (r, g, b) -> an 8-bit RGB PNG (colour type 2, no interlace, filter 0 on every row): the rectified
+    images gaustar_amd.dataprep writes where the reference writes JPEG."""
+    a = np.asarray(array)
+    if a.ndim != 3 or a.shape[2] != 3 or a.dtype != np.uint8 or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError(f"save_png_rgb8 takes a non-empty [H,W,3] uint8 array, got {a.dtype} {a.shape}")
+    _save_png8(path, a, 2)
+
+
+def load_png_rgb8(path: str) -> np.ndarray:
+    """An 8-bit RGB, non-interlaced PNG -> [H,W,3] uint8.  Any other PNG (palette, alpha, 16-bit) raises ValueError."""
+    return _load_png8(path, 2)

@@ -607,6 +607,52 @@ int gsr_mesh_depth_view(int H, int W, int V, int F, const double* verts, const i
                         float background, int small_max, void* workspace, float* depth, unsigned char* mask, int* face_or_null,
                         int* n_clipped, gsr_stream_t stream);
 
+/* ---- A sequence's inputs before frame 0 (data_process/ahq2gaustar.py): the rectified images and the coloured base mesh.
+ * All device pointers unless marked [host]; every call is asynchronous on `stream`, none synchronises the host, none uses
+ * float atomics; everything is f64 in the stated order, nothing contracted (tests/prep_ref.py restates the rules in numpy).
+ * gsr_image_rectify: ahq2gaustar.py:50-81 (`img_translate`, `rgb_convert`) and gaustar_tools/cmr_convert.py:71-109, :214-223
+ *   (`img_convert`: cv2.undistort followed by the translation) in ONE resampling.  src, dst [H,W,C] uint8, contiguous, C in
+ *   {1, 3, 4}, dst != src, H W < 2^31, any alignment.  cam4: [host] fx, fy, cx, cy; dist5_or_null: [host] k1, k2, p1, p2, k3
+ *   (OpenCV's order); border: [host] C bytes.  For output pixel (row r, column c), everything in double:
+ *   Plain path, taken iff dist5 is null or all five coefficients are exactly 0:
+ *     su = c + (cx - 0.5 W), sv = r + (cy - 0.5 H).
+ *     This is img_translate's dst(c) = src(c + dx).
+ *   Distorted path:
+ *     x = (c - 0.5 W) / fx, y = (r - 0.5 H) / fy, r2 = x x + y y.
+ *     rad = 1 + r2 (k1 + r2 (k2 + r2 k3)).
+ *     xd = x rad + (2 p1 x y + p2 (r2 + 2 x x)).
+ *     yd = y rad + (p1 (r2 + 2 y y) + 2 p2 x y).
+ *     su = fx xd + cx, sv = fy yd + cy.
+ *   Bilinear sampling:
+ *     x0 = floor(su), ax = su - x0, likewise y0, ay.
+ *     The four taps are src where inside the image and border[ch] where outside (cv2's BORDER_CONSTANT).
+ *     If su or sv is not finite or outside the int range, the pixel is border.
+ *     Value = (t00 (1 - ax) + t01 ax) (1 - ay) + (t10 (1 - ax) + t11 ax) ay.
+ *     Stored as (uint8) rint(value), half to even.
+ *   Products are formed left to right; "outside the int range" is outside [-2^31, 2^31 - 1).  Departures: cv2 interpolates
+ *   with 5-bit fixed-point weights and the reference resamples twice; cv2 was not available, parity with it is not pinned.
+ * gsr_mesh_color_view: one camera of ahq2gaustar.py:124-160 `compute_mesh_color` (:141-151).  verts [V,3] double, image
+ *   [H,W,3] uint8 RGB, depth [H,W] f32, cam14 [host] as gsr_warp_view's.  Per vertex: gsr_warp_view's projection (no principal
+ *   point), row and column by its lookup int(pix + 0.5), visible = valid && fabs(lz - (double)depth[row, col]) < threshold
+ *   (NaN compares false; no test on the sign of lz).  A visible vertex adds its pixel's r, g, b and 1 to sums [V,4] int32 by
+ *   integer atomic adds: the sums of several cameras do not depend on their order or on the streams they ran on.
+ * gsr_mesh_color_finish: :157-158 and the colours of vertices no camera saw.  sums [V,4] int32 (16-byte aligned) ->
+ *   mean [V,3] double = sum / (double)n (NaN where n = 0); rgb [V,3] uint8 = (2 sum + n) / (2 n) in 64-bit integers, the mean
+ *   rounded half up; filled_at [V] uint8 = 0 where n > 0.  Then fill_sweeps (0..254) Jacobi sweeps over gsr_topo_propagate's
+ *   neighbour list: in sweep s = 1, 2, ... a vertex without a colour after sweep s - 1 that has k > 0 neighbours with one takes,
+ *   per channel, (2 S + k) / (2 k) of those neighbours' rgb and filled_at = s; a sweep reads only the previous sweep's
+ *   state.  A vertex still without a colour gets default_color ([host] 3 bytes) and filled_at = 255.  counters [2] int32:
+ *   vertices with n = 0, vertices that got default_color.  The reference leaves NaN on unseen vertices; fill_sweeps = 0 keeps
+ *   its seen set.  workspace: gsr_mesh_color_workspace_bytes(V) bytes, 4-byte aligned.  V == 0 is a no-op. */
+int gsr_image_rectify(int H, int W, int C, const unsigned char* src, unsigned char* dst, const double* cam4,
+                      const double* dist5_or_null, const unsigned char* border, gsr_stream_t stream);
+int gsr_mesh_color_view(int H, int W, int V, const double* verts, const unsigned char* image, const float* depth,
+                        const double* cam14, double threshold, int* sums, gsr_stream_t stream);
+size_t gsr_mesh_color_workspace_bytes(int V);
+int gsr_mesh_color_finish(int V, const int* sums, const int* nbr_offsets, const int* nbr, int fill_sweeps,
+                          const unsigned char* default_color, void* workspace, double* mean, unsigned char* rgb,
+                          unsigned char* filled_at, int* counters, gsr_stream_t stream);
+
 /* ---- TSDF fusion of the rig's renders and mesh extraction (gaustar_trainers/refined_mesh.py:311-459 `extract_mesh_fusion`).
  * The volume follows Open3D's legacy ScalableTSDFVolume(voxel_length, sdf_trunc, RGB8) -- units of 16^3 voxels,
  * depth_sampling_stride 4 -- by the rules restated in tests/fusion_ref.py (Open3D itself was not available: parity with it
