@@ -11,6 +11,7 @@ stand-ins for pytorch3d's `Meshes` / `mesh_normal_consistency`), `sweep` (forwar
 `mesh_depth` (a mesh's depth maps, masks and visible faces over the rig: the inputs of a tracked sequence),
 `dataprep` (what a sequence needs before frame 0: rectified images, the coloured base mesh, the COLMAP files),
 `tracking` (points followed on the surface through topology updates: SurfaceTracker, track_faces),
+`edit` (what a tracked sequence is for: cutting a model, attaching one that rides on tracked anchors, painting a decal),
 `remesh` (quadric mesh decimation and Laplacian / Taubin smoothing: how an init_mesh_100k.obj is made),
 `knn` (exact K-nearest neighbours with spatial culling: pytorch3d's knn_points, simple-knn's distCUDA2),
 `density` (the Gaussians' density field: SuGaR's compute_density and get_covariance, behind the model's postprocess_mesh),

@@ -275,6 +275,19 @@ SIGNATURES = {
     "gsr_density_queries_per_workgroup": (c_int, []),
     "gsr_density_pack": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gsr_density_eval": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # editing a tracked sequence: rigid fit's sums, moving a model with its SH, selecting, cutting, painting
+    # (gaustar_tools/internal_use_tools/gstar_edit.py): gaustar_amd.edit; the err word is the mesh kernels'
+    "gsr_edit_fit_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "gsr_edit_fit_sums": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gsr_edit_transform_points": (c_int, [c_longlong, c_int, c_int, c_void_p, POINTER(c_double), POINTER(c_double), c_void_p, c_void_p]),
+    "gsr_edit_rotate_sh": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gsr_edit_faces_in_halfspaces": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int, POINTER(c_int), POINTER(c_double), c_void_p,
+                                             c_void_p, c_void_p]),
+    "gsr_edit_gather_rows": (c_int, [c_int, c_int, c_void_p, c_int, c_int, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_int),
+                                     c_void_p, c_void_p]),
+    "gsr_edit_paint": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int,
+                               c_void_p, c_int, c_double, c_double, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                               c_void_p]),
     "gsr_adam_step": (c_int, [c_longlong, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_double, c_double, c_int,
                               c_void_p]),
     "gsr_adam_step_multi": (c_int, [c_int, POINTER(c_longlong), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),

@@ -1,7 +1,8 @@
-// gsr_surface.h -- what the kernels that work in float64 on a mesh (gsr_track.hip, gsr_eval.hip, gsr_remesh.hip, and
-// gsr_stitch.hip's search) share: a point of three doubles, the dot and cross products and bary_to_point as include/gsr.h states
-// them, a face's three f64 vertices with the err word's checks, and tnn_search, the tiled (key, index)-minimum search of
-// stitch_nn_kernel, track_nn_kernel and eval_closest_kernel: 16 queries to a workgroup of 256, a tile split 16 ways.
+// gsr_surface.h -- what the kernels that work in float64 on a mesh (gsr_track.hip, gsr_eval.hip, gsr_remesh.hip, gsr_edit.hip and
+// gsr_stitch.hip's search) share: a point of three doubles, the dot and cross products, bary_to_point and point_to_bary as
+// include/gsr.h states them, a face's three f64 vertices with the err word's checks, and tnn_search, the tiled (key, index)-
+// minimum search of stitch_nn_kernel, track_nn_kernel and eval_closest_kernel: 16 queries to a workgroup of 256, a tile split
+// 16 ways.
 // All of it float64 without contraction: the pragma below stands in front of these functions (an including file's own pragma
 // comes after its includes and would leave them contracted) and holds for the rest of the translation unit.
 #pragma once
@@ -33,6 +34,17 @@ __device__ __forceinline__ bool finite3(D3 a) { return finite1(a.x) && finite1(a
 __device__ __forceinline__ D3 bary_to_point(D3 t0, D3 t1, D3 t2, D3 b)
 {
     return {(b.x * t0.x + b.y * t1.x) + b.z * t2.x, (b.x * t0.y + b.y * t1.y) + b.z * t2.y, (b.x * t0.z + b.y * t1.z) + b.z * t2.z};
+}
+
+// trimesh's points_to_barycentric, method "cramer", as include/gsr.h states it
+__device__ __forceinline__ D3 point_to_bary(D3 t0, D3 t1, D3 t2, D3 p)
+{
+    const D3 e0 = sub3(t1, t0), e1 = sub3(t2, t0), w = sub3(p, t0);
+    const double d00 = dot3(e0, e0), d01 = dot3(e0, e1), d02 = dot3(e0, w), d11 = dot3(e1, e1), d12 = dot3(e1, w);
+    const double inv = 1.0 / (d00 * d11 - d01 * d01);
+    const double b2 = (d00 * d12 - d01 * d02) * inv;
+    const double b1 = (d11 * d02 - d01 * d12) * inv;
+    return {(1.0 - b1) - b2, b1, b2};
 }
 
 // the three vertices of face f of a mesh of V vertices; false (and err) when an index is outside or a coordinate not finite

@@ -13,7 +13,8 @@
 //   rebind, displaced   track_displaced_kernel     the nearest face's barycentrics, clamped and renormalised (:115-121)
 // All arithmetic is float64 without contraction, every operation in the order include/gsr.h states.  No float atomics, no
 // scratch: the counts are integer atomics, the search combines by the lexicographic (key, index) minimum.  The point type, the dot
-// product, bary_to_point, a face's vertices and that search are gsr_surface.h's, shared with gsr_eval.hip and gsr_stitch.hip.
+// product, bary_to_point, point_to_bary (gsr_edit.hip's too), a face's vertices and that search are gsr_surface.h's, shared
+// with gsr_eval.hip and gsr_stitch.hip.
 //
 // The square root.  numpy's argmin compares sqrt(d2), and two different d2 can share a rounded square root, so the minimum of
 // (d2, index) is not the answer: the search takes the square root of every pair and keeps the (s, index) minimum.  The other
@@ -37,17 +38,6 @@ namespace {
 
 constexpr int TR_BLOCK = MESH_BLOCK;
 constexpr int TNN_TILE = 1024;      // centres staged in LDS at once: 3 x 1024 doubles = 24 KiB
-
-// trimesh's points_to_barycentric, method "cramer", as include/gsr.h states it
-__device__ __forceinline__ D3 point_to_bary(D3 t0, D3 t1, D3 t2, D3 p)
-{
-    const D3 e0 = sub3(t1, t0), e1 = sub3(t2, t0), w = sub3(p, t0);
-    const double d00 = dot3(e0, e0), d01 = dot3(e0, e1), d02 = dot3(e0, w), d11 = dot3(e1, e1), d12 = dot3(e1, w);
-    const double inv = 1.0 / (d00 * d11 - d01 * d01);
-    const double b2 = (d00 * d12 - d01 * d02) * inv;
-    const double b1 = (d11 * d02 - d01 * d12) * inv;
-    return {(1.0 - b1) - b2, b1, b2};
-}
 
 __device__ __forceinline__ void wave_count(bool mine, int* __restrict__ word)
 {

@@ -11,7 +11,8 @@ SuGaR / GauSTAR `{iter}.pt` checkpoints -- enough to render a real checkpoint wi
   exports: `v x y z [r g b]` and triangular `f` lines, vertex order kept (load_obj / save_obj).
 * PNG: the 8-bit grey masks `img_{c:04d}_alpha.png` that data_process/render_depth_from_mesh.py:93 writes with cv2.imwrite and
   gaustar_scene/cameras.py:97-106 reads (save_png_gray8 / load_png_gray8; zlib and struct only, neither cv2 nor PIL), and the
-  8-bit RGB images gaustar_amd.dataprep writes (save_png_rgb8 / load_png_rgb8, colour type 2, the same chunk code).
+  8-bit RGB images gaustar_amd.dataprep writes (save_png_rgb8 / load_png_rgb8, colour type 2, the same chunk code);
+  load_png_rgba8 reads a decal with alpha (colour type 6) for gaustar_amd.edit.
 * .pt: sugar_model.py:1313-1318 (`save_model`): {'state_dict': ..., extra keys}; state-dict entries `_points`,
   `_surface_mesh_faces`, `_scales`, `_quaternions`, `all_densities`, `_sh_coordinates_dc`, `_sh_coordinates_rest`,
   `surface_mesh_thickness`, `_delta_t`, `_delta_r`.
@@ -285,9 +286,9 @@ def save_obj(path: str, verts, faces, colours=None) -> None:
         fh.write("\n".join(lines) + "\n")
 
 
-# ---------------------------------------------------------------------------------------------- PNG (8-bit grey, 8-bit RGB)
+# ---------------------------------------------------------------------------------------------- PNG (8-bit grey, RGB, RGBA)
 _PNG_MAGIC = b"\x89PNG\r\n\x1a\n"
-_PNG_KINDS = {0: (1, "greyscale"), 2: (3, "RGB")}     # colour type -> (bytes per pixel, its name in messages)
+_PNG_KINDS = {0: (1, "greyscale"), 2: (3, "RGB"), 6: (4, "RGBA")}     # colour type -> (bytes per pixel, its name in messages)
 
 
 def _png_chunk(tag: bytes, data: bytes) -> bytes:
@@ -392,3 +393,8 @@ def save_png_rgb8(path: str, array) -> None:
 def load_png_rgb8(path: str) -> np.ndarray:
     """An 8-bit RGB, non-interlaced PNG -> [H,W,3] uint8.  Any other PNG (palette, alpha, 16-bit) raises ValueError."""
     return _load_png8(path, 2)
+
+
+def load_png_rgba8(path: str) -> np.ndarray:
+    """An 8-bit RGBA, non-interlaced PNG -> [H,W,4] uint8 (r, g, b, a): a decal for gaustar_amd.edit.paint_decal's "replace"."""
+    return _load_png8(path, 6)

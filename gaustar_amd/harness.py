@@ -646,6 +646,27 @@ class SurfaceGaussians(nn.Module):
         faces) -> [K,3] f64, the f32 vertices widened."""
         return tracker.positions(self._points.detach(), self._surface_mesh_faces)
 
+    # -------------------------------------------------------------------------------- editing (gstar_edit.py): gaustar_amd.edit
+    def cut(self, keep_faces):
+        """edit.cut_model(self, keep_faces): a new model of the faces with keep_faces [F] bool set and their Gaussians."""
+        from . import edit
+        return edit.cut_model(self, keep_faces)
+
+    def merged_with(self, other):
+        """edit.merge_models(self, other): one model of both, other's faces behind this model's."""
+        from . import edit
+        return edit.merge_models(self, other)
+
+    def transform(self, R, t, rotate_sh: bool = True):
+        """edit.transform_model(self, R, t, rotate_sh): x -> R x + t in place, the SH coefficients turned with it."""
+        from . import edit
+        return edit.transform_model(self, R, t, rotate_sh)
+
+    def paint_decal(self, anchors, uv, triangles, texture, **kw):
+        """edit.paint_decal(self, anchors, uv, triangles, texture, **kw): a texture glued to tracked points, in place."""
+        from . import edit
+        return edit.paint_decal(self, anchors, uv, triangles, texture, **kw)
+
     def surface_distance(self, points):
         """The closest point of the model's own mesh for every point of points [K,3] f64: evaluate.surface_distance(points,
         vertices, faces) -> evaluate.SurfaceHit, the f32 vertices widened."""

@@ -1173,6 +1173,65 @@ int gsr_density_pack(int P, const float* points, const float* scaling, const flo
 int gsr_density_eval(int Q, int P, int K, const float* x, const int* idx, const void* records, float density_factor, float* density,
                      float* neighbor_opacities, int* err, gsr_stream_t stream);
 
+/* ---- Editing a tracked sequence: the per-Gaussian passes of gaustar_tools/internal_use_tools/gstar_edit.py (cut_gstar :74-119,
+ * merge_gstar :122-184, edit_gs_color :295-388, best_fit_transform :28-71), which the reference runs on the host in numpy,
+ * trimesh and cv2: gaustar_amd.edit.  tests/edit_ref.py restates every rule below in numpy.  All device pointers unless marked
+ * [host]; every call is asynchronous on `stream`, none synchronises the host, none uses float atomics or scratch.  err: the
+ * mesh kernels' word (csrc/gsr_mesh.h), ORed into: bit 0 = a vertex or face index outside its array; the calls that index
+ * nothing (fit_sums, transform_points, rotate_sh) take it and leave it alone (it may be NULL there).
+ * gsr_edit_fit_sums: replaces :48-54 for T frames at once.  src [K,3], dst [T,K,3] f64 (a [K,3] dst is T = 1).  Anchor k counts
+ *   in frame t iff its six coordinates src[k], dst[t,k] are finite (a lost point is a NaN row of face_trajectory).  out [T,16]
+ *   f64 = {n, abar (3), bbar (3), H row-major (9)}: n the anchors that count, abar = (sum a) / n, bbar = (sum b) / n, H[i][j] =
+ *   sum (a_i - abar_i)(b_j - bbar_j), every term one rounded product of two rounded differences.  Two element passes
+ *   (centroids, then H about them) and a finish, each one launch over all frames; the sums are taken per workgroup and then
+ *   over the workgroups in a fixed order (csrc/gsr_reduce.h), so two calls give the same bits; against the exactly rounded sum
+ *   of the same terms a sum of m terms is within m 2^-53 sum |term|.  n == 0 gives NaN centroids and H = 0.  :55-64 (the SVD
+ *   of H, the reflection fix, t = bbar - R abar) are the host's: gaustar_amd.edit.fit_rigid.  workspace: T <= 65535 frames,
+ *   gsr_edit_fit_workspace_bytes(T, K) bytes.  T == 0 is a no-op; K == 0 is refused.
+ * gsr_edit_transform_points: replaces :146 (`np.matmul(R, v) + t`).  x: n rows of `stride` floats; columns [offset, offset + 3)
+ *   of every row become, in place and per coordinate i, (float) (((R[i][0] x + R[i][1] y) + R[i][2] z) + t[i]) in float64 from
+ *   the f32 inputs: three rounded products, three rounded sums, one rounding to f32.  R [host] 9 doubles row-major; t [host] 3
+ *   doubles, or NULL: the last sum is left out (a direction: `_delta_t`, the vector part of `_delta_r`).
+ * gsr_edit_rotate_sh: no counterpart (the reference turns an attached object, :146, and leaves its world-frame SH coefficients
+ *   as they were).  rest_in, rest_out [N, M - 1, 3] f32, 16-byte aligned, M = 4, 9 or 16; D [M,M] f64 row-major, block diagonal
+ *   with blocks of 1, 3, 5, 7 (gaustar_amd.edit.sh_rotation_matrices).  Per Gaussian, channel c and coefficient i of band l
+ *   (o = l l <= i < o + 2 l + 1): s = D[i][o] x[o], then s = s + D[i][k] x[k] for k = o + 1 .. o + 2 l ascending, x[k] =
+ *   (double) rest_in[n][k - 1][c]; rest_out[n][i - 1][c] = (float) s.  rest_out may be rest_in.
+ * gsr_edit_faces_in_halfspaces: replaces :81-102, the planes as data.  verts [V,3] f32, faces [F,3] int32; n_groups <= 16
+ *   groups of group_sizes[g] >= 1 planes [host], 64 planes (a, b, c, d) in all, planes [host] [sum,4] f64 in group order.  A
+ *   face's centre is per coordinate ((v0 + v1) + v2) / 3.0 in float64 (:82); mask [F] uint8 = 1 iff for some group every plane
+ *   of it has ((a cx + b cy) + c cz) + d > 0, strictly.  A face with an index outside [0, V) gets 0 and sets err.
+ * gsr_edit_gather_rows: replaces :114-116 (`state_dict[key][gs_mask]`) for all keys in one launch.  kept [n_faces] int32 = the
+ *   old face of every new face, each in [0, F).  n_tables <= 8 arrays of 32-bit words: src[e] [F G, row_words[e]], dst[e]
+ *   [n_faces G, row_words[e]] (src, dst, row_words: [host] arrays of n_tables entries); rows [G j, G j + G) of dst[e] are rows
+ *   [G kept[j], ...) of src[e].  An entry of kept outside [0, F) gives zeros and sets err.
+ * gsr_edit_paint: replaces :316-385.  The model: N = F G Gaussians, verts [V,3] f32, faces [F,3] int32, bary [G,3] f32; Gaussian
+ *   n = G f + g sits at p = (b_g0 v0 + b_g1 v1) + b_g2 v2 per coordinate, float64 from the f32 inputs (:320-322, there f32).
+ *   tri [n_tri,15] f64, n_tri <= 64: per triangle its corners t0, t1, t2 and their (u, v).  The triangles are walked in order
+ *   (a Gaussian inside two of them is treated twice, :354); per triangle: bary = point_to_bary(t0, t1, t2, p) (gsr_track's
+ *   rule, :358); nrm = -cross(t1 - t0, t2 - t1) / sqrt((x x + y y) + z z), dist = dot(t0 - p, nrm) (:284-292); inside iff every
+ *   bary >= -bary_slack and -max_dist < dist < max_dist (:359-362).  An inside Gaussian: with shrink != 0 both of its scales
+ *   become shrink_scale (:364); (u, v) = bary_to_point of the corners' (u, v); row = trunc(u h), col = trunc(v w), toward zero
+ *   (:369); a texel outside the texture [h,w,C] uint8 (r, g, b order) counts in n_outside and leaves the colour alone.  mode 0,
+ *   multiply (:379): rgb = rgb (float) (tex[row][col][0] / 255.0); mode 1, replace (:373-376), C = 3 or 4: where C == 3 or
+ *   tex[row][col][3] > alpha_min, rgb = (float) (tex[row][col][0..2] / 255.0).  rgb = dc C0 + 0.5f is formed by the first
+ *   triangle that paints and carried through the later ones; at the end dc = (rgb - 0.5f) / C0 (:334, :384), in f32 without
+ *   contraction.  scales [N,2], sh_dc [N,3] in place; a Gaussian that was not painted keeps its dc bits, one that was in no
+ *   triangle its scales.  stats [2 + n_tri] int32, cleared by the call: the Gaussians painted, the (Gaussian, triangle) pairs
+ *   whose texel fell outside, the Gaussians inside each triangle.  A face index outside sets err and leaves the Gaussian out. */
+size_t gsr_edit_fit_workspace_bytes(int T, int K);
+int gsr_edit_fit_sums(int T, int K, const double* src, const double* dst, void* workspace, double* out, int* err, gsr_stream_t stream);
+int gsr_edit_transform_points(long long n, int stride, int offset, float* x, const double* R, const double* t, int* err,
+                              gsr_stream_t stream);
+int gsr_edit_rotate_sh(int N, int M, const double* D, const float* rest_in, float* rest_out, int* err, gsr_stream_t stream);
+int gsr_edit_faces_in_halfspaces(int F, int V, const int* faces, const float* verts, int n_groups, const int* group_sizes,
+                                 const double* planes, unsigned char* mask, int* err, gsr_stream_t stream);
+int gsr_edit_gather_rows(int n_faces, int F, const int* kept, int G, int n_tables, const void* const* src, void* const* dst,
+                         const int* row_words, int* err, gsr_stream_t stream);
+int gsr_edit_paint(int N, int G, int F, int V, const int* faces, const float* verts, const float* bary, int n_tri, const double* tri,
+                   int h, int w, int C, const unsigned char* texture, int mode, double bary_slack, double max_dist, int shrink,
+                   float shrink_scale, int alpha_min, float* scales, float* sh_dc, int* stats, int* err, gsr_stream_t stream);
+
 /* Tuning aid: when device_buffer is non-NULL (4*T uint64), the two blend kernels record the start/end wall
  * clock (100 MHz) of every workgroup: forward at [2*b], backward at [2*(T+b)], b = launch index.  NULL = off. */
 int gsr_debug_set_trace(void* device_buffer);
