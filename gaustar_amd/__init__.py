@@ -10,6 +10,7 @@ means / scales / quaternions), `losses` (l1 + dssim, masked depth L1, surface-me
 stand-ins for pytorch3d's `Meshes` / `mesh_normal_consistency`), `sweep` (forward-only camera sweeps),
 `mesh_depth` (a mesh's depth maps, masks and visible faces over the rig: the inputs of a tracked sequence),
 `dataprep` (what a sequence needs before frame 0: rectified images, the coloured base mesh, the COLMAP files),
+`hull` (shape from silhouettes: the per-frame meshes those inputs are rendered from, carved out of the rig's alpha masks),
 `tracking` (points followed on the surface through topology updates: SurfaceTracker, track_faces),
 `edit` (what a tracked sequence is for: cutting a model, attaching one that rides on tracked anchors, painting a decal),
 `remesh` (quadric mesh decimation and Laplacian / Taubin smoothing: how an init_mesh_100k.obj is made),

@@ -288,6 +288,12 @@ SIGNATURES = {
     "gsr_edit_paint": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int,
                                c_void_p, c_int, c_double, c_double, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                c_void_p]),
+    # shape from silhouettes: a mask's signed distance, the carve of a fusion volume by the rig, its TSDF: gaustar_amd.hull
+    "gsr_hull_mask_distance_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "gsr_hull_mask_distance": (c_int, [c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "gsr_hull_camera_bytes": (c_int, []),
+    "gsr_hull_carve": (c_int, [c_int, c_void_p, c_void_p, c_double, POINTER(c_int), c_void_p, c_void_p, c_void_p]),
+    "gsr_hull_finish": (c_int, [POINTER(c_int), c_void_p, c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gsr_adam_step": (c_int, [c_longlong, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_double, c_double, c_int,
                               c_void_p]),
     "gsr_adam_step_multi": (c_int, [c_int, POINTER(c_longlong), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),

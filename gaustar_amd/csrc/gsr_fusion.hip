@@ -25,6 +25,7 @@
 #include "../../include/gsr.h"
 #include "gsr_entry.h"
 #include "gsr_rig.h"
+#include "gsr_volume.h"
 #include <string>
 
 #pragma clang fp contract(off)
@@ -33,19 +34,12 @@ namespace gsr {
 
 namespace {
 
-constexpr int FU = 16;             // voxels along a unit's edge (ScalableTSDFVolume's volume_unit_resolution)
 constexpr int FU_STRIDE = 4;       // depth_sampling_stride
-constexpr int FU_QUADS = FU * FU * FU / 4;   // float4 per unit and plane
 
 struct FusionCamera {
     double E[12];    // world-to-camera (COLMAP axes), rows of [R | t]
     double Ei[12];   // its inverse (inverted on the host in double), rows of [R' | t']
     double fx, fy, cx, cy;
-};
-
-struct FusionGrid {
-    int u0[3];   // unit index (floor(p / L)) of the first unit along x, y, z
-    int nu[3];   // units along x, y, z
 };
 
 inline FusionCamera fusion_camera(const double* cam28)
@@ -54,13 +48,6 @@ inline FusionCamera fusion_camera(const double* cam28)
     for (int i = 0; i < 12; ++i) { c.E[i] = cam28[i]; c.Ei[i] = cam28[12 + i]; }
     c.fx = cam28[24]; c.fy = cam28[25]; c.cx = cam28[26]; c.cy = cam28[27];
     return c;
-}
-
-inline FusionGrid fusion_grid(const int* grid6)
-{
-    FusionGrid g;
-    for (int a = 0; a < 3; ++a) { g.u0[a] = grid6[a]; g.nu[a] = grid6[3 + a]; }
-    return g;
 }
 
 // ---------------------------------------------------------------------------------------------------- image preparation
@@ -349,19 +336,6 @@ hipError_t launch_fusion_touch(int H, int W, const float* depth, const double* c
     const int ns = ((W + FU_STRIDE - 1) / FU_STRIDE) * ((H + FU_STRIDE - 1) / FU_STRIDE);
     fusion_touch_kernel<<<blocks(ns), RIG_BLOCK, 0, st>>>(H, W, depth, fusion_camera(cam28), voxel, trunc, g, touched);
     return hipSuccess;
-}
-
-// the [host] grid block of the fusion calls: a directory of at least one unit per axis whose voxels can be counted in an int
-const char* fusion_grid_error(const int* grid)
-{
-    if (!grid) return "grid is null";
-    long long units = 1;
-    for (int a = 0; a < 3; ++a) {
-        if (grid[3 + a] <= 0 || grid[3 + a] > (1 << 16)) return "units per axis must be in [1, 65536]";
-        if (grid[a] < -(1 << 24) || grid[a] > (1 << 24)) return "first unit index out of range";
-        units *= grid[3 + a];
-    }
-    return units * 4096 >= (1ll << 31) ? "the volume has 2^31 voxels or more" : nullptr;
 }
 
 bool fusion_camera_ok(const double* cam)

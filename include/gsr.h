@@ -1232,6 +1232,41 @@ int gsr_edit_paint(int N, int G, int F, int V, const int* faces, const float* ve
                    int h, int w, int C, const unsigned char* texture, int mode, double bary_slack, double max_dist, int shrink,
                    float shrink_scale, int alpha_min, float* scales, float* sh_dc, int* stats, int* err, gsr_stream_t stream);
 
+/* ---- Shape from silhouettes: the visual hull of the rig's alpha masks as a volume of the TSDF fusion above, so that
+ * gsr_fusion_count / gsr_fusion_emit extract its mesh: gaustar_amd.hull.  The reference takes the per-frame meshes its depth
+ * maps and masks are rendered from out of HumanRF (README.md:38-39); this replaces that source, not a function of the reference.
+ * All device pointers unless marked [host]; every call is asynchronous on `stream`, none synchronises the host, none uses
+ * atomics: every output is a pure function of the inputs, and the carve state does not depend on the cameras' order or on how
+ * they are split into calls.  tests/hull_ref.py restates the rules.
+ * gsr_hull_mask_distance: mask [H,W] uint8, H, W >= 2, H <= 65535; a pixel is inside iff mask >= threshold (0..256); 1 <= radius
+ *   <= 127.  d2 [H,W] int16: for an inside pixel +min(radius^2, the squared distance to the nearest outside pixel of the image),
+ *   for an outside pixel -min(radius^2, the squared distance to the nearest inside pixel); what lies beyond the border is
+ *   neither, so an image of one kind holds +-radius^2 throughout, and no entry is 0.  Exact (integers).  workspace:
+ *   gsr_hull_mask_distance_workspace_bytes(H, W) bytes.
+ * gsr_hull_carve: field [voxels] f32 (+inf before the first camera) and count [voxels] int32 (0 before), 16-byte aligned, over
+ *   the fusion's `grid` with the fusion's voxel centres.  cameras: n_cameras records of gsr_hull_camera_bytes() = 144 bytes: 9
+ *   doubles R (row-major) and 3 doubles t of the COLMAP world-to-camera transform, fx, fy, cx, cy (doubles; pixel centres at
+ *   integer coordinates), the device pointer of the camera's d2 map, int H, int W.  cameras_host: [host] the same bytes, which
+ *   are checked (finite, fx, fy > 0, H, W >= 2, d2 not null) before the launch reads its device copy.  Per voxel centre p and
+ *   camera, in double without contraction:
+ *     q = ((R_r0 p.x + R_r1 p.y) + R_r2 p.z) + t_r per row r; nothing happens unless q.z > 0.01;
+ *     u = fx (q.x / q.z) + cx, v = fy (q.y / q.z) + cy; nothing happens unless 0 <= u <= W - 1 and 0 <= v <= H - 1;
+ *     x0 = min(floor(u), W - 2), y0 = min(floor(v), H - 2), a = u - x0, b = v - y0;
+ *     phi(e) = sign(e) (sqrt(|e|) - 0.5) of the entries at (y0, x0), (y0, x0 + 1), (y0 + 1, x0), (y0 + 1, x0 + 1);
+ *     top = phi00 + a (phi01 - phi00), bot = phi10 + a (phi11 - phi10), phi = top + b (bot - top);
+ *     d = (phi q.z) (2 / (fx + fy)); field = min(field, (float) d); count += 1.
+ * gsr_hull_finish: min_views >= 1.  weight = 1 where count >= min_views, else 0; tsdf = (float) clamp(-(double) field /
+ *   sdf_trunc, -1, 1) under weight 1, else 0 (negative inside, as gsr_fusion_count reads it); touched [units] uint8 = 1 iff the
+ *   unit holds a voxel with weight 1 and |tsdf| < 1.  The fusion's color planes are not written. */
+size_t gsr_hull_mask_distance_workspace_bytes(int H, int W);
+int gsr_hull_mask_distance(int H, int W, const unsigned char* mask, int threshold, int radius, void* workspace, short* d2,
+                           gsr_stream_t stream);
+int gsr_hull_camera_bytes(void);
+int gsr_hull_carve(int n_cameras, const void* cameras_host, const void* cameras, double voxel_size, const int* grid, float* field,
+                   int* count, gsr_stream_t stream);
+int gsr_hull_finish(const int* grid, const float* field, const int* count, int min_views, double sdf_trunc, float* tsdf, float* weight,
+                    unsigned char* touched, gsr_stream_t stream);
+
 /* Tuning aid: when device_buffer is non-NULL (4*T uint64), the two blend kernels record the start/end wall
  * clock (100 MHz) of every workgroup: forward at [2*b], backward at [2*(T+b)], b = launch index.  NULL = off. */
 int gsr_debug_set_trace(void* device_buffer);
