@@ -19,6 +19,17 @@ def stream_of(t: torch.Tensor) -> int:
     return torch._C._cuda_getCurrentRawStream(t.device.index)
 
 
+def resolve_device(device=None, like=None, *, what: str, exc=RuntimeError) -> torch.device:
+    """Which GPU a mirror works on: an explicit `device`, else `like`'s where that is a tensor on a GPU, else the current one.
+    Anything but a GPU raises exc(f"{what} needs a GPU") before any call into the runtime; the index is always filled in."""
+    if device is None and isinstance(like, torch.Tensor) and like.is_cuda:
+        return like.device
+    dev = torch.device("cuda" if device is None else device)
+    if dev.type != "cuda":
+        raise exc(f"{what} needs a GPU")
+    return dev if dev.index is not None else torch.device("cuda", torch.cuda.current_device())
+
+
 class on_device:
     """`with torch.cuda.device(dev)` only when `dev` is not the current device already."""
     __slots__ = ("ctx",)

@@ -1,9 +1,11 @@
 """What the Python mirrors of the mesh kernels share around their launches: the checks of a mesh argument and the err word
-(csrc/gsr_mesh.h; a call chain may pass one word through kernels of several files before it is read).  No feature imports."""
+(csrc/gsr_mesh.h; a call chain may pass one word through kernels of several files before it is read), and the way a mesh given
+as numpy or torch gets onto the device.  No feature imports."""
 from __future__ import annotations
 
 from typing import Optional, Tuple
 
+import numpy as np
 import torch
 
 MESH_ERR_INDEX, MESH_ERR_NAN, MESH_ERR_DUP, MESH_ERR_DEGENERATE = 1, 2, 4, 8      # csrc/gsr_mesh.h
@@ -13,6 +15,33 @@ INDEX = "a vertex index, or another index into the mesh, lies outside its array"
 DUP = "a boundary list names a vertex twice"
 NAN_BOX = "a vertex or Gaussian centre of a kept region is NaN: its box is not defined"
 NAN_BOUNDARY = "a boundary position is NaN or infinite: its nearest vertex is not defined"
+
+
+def tensor_of(x) -> torch.Tensor:
+    """numpy (or what numpy reads) or torch -> a tensor where the data is; numpy memory is shared when it is contiguous."""
+    return x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
+
+
+def upload(x, dev, dtype: torch.dtype) -> torch.Tensor:
+    """numpy or torch -> `dtype` on `dev`; a tensor that is both already is passed through."""
+    return tensor_of(x).to(dev, dtype)
+
+
+def verts_on(verts, dev) -> torch.Tensor:
+    """numpy or torch -> [V,3] f64 contiguous on `dev`: what the f64 rig passes (mesh_depth, warp, dataprep) read."""
+    v = upload(verts, dev, torch.float64).detach().contiguous()
+    if v.dim() != 2 or v.shape[1] != 3:
+        raise ValueError(f"verts must be [V,3], got {tuple(v.shape)}")
+    return v
+
+
+def mesh_on(verts, faces, dev) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(verts_on, faces [F,3] int32 contiguous on `dev`) from numpy or torch, the vertices first."""
+    v = verts_on(verts, dev)
+    f = upload(faces, dev, torch.int32).contiguous()
+    if f.dim() != 2 or f.shape[1] != 3:
+        raise ValueError(f"faces must be [F,3], got {tuple(f.shape)}")
+    return v, f
 
 
 def new_err(dev) -> torch.Tensor:

@@ -30,8 +30,10 @@
 // shortcut skips a camera or a voxel.  No atomics of any kind, no scratch.  tests/hull_ref.py restates it all in numpy.
 #include "../../include/gsr.h"
 #include "gsr_entry.h"
+#include "gsr_rig.h"
 #include "gsr_volume.h"
 
+#include <cstddef>
 #include <cstdint>
 #include <string>
 
@@ -203,12 +205,11 @@ __global__ void __launch_bounds__(HC_BLOCK) hull_col_kernel(int H, int W, const 
 
 // ---------------------------------------------------------------------------------------------------- the carve
 struct HullCamera {          // 144 bytes; gaustar_amd.hull.CAMERA_DTYPE
-    double R[9];             // world-to-camera rotation, row-major (COLMAP axes)
-    double t[3];
-    double fx, fy, cx, cy;
+    RigPinhole cam;          // world-to-camera (COLMAP axes), focal lengths and principal point
     const short* d2;         // [H,W] int16 on the device: gsr_hull_mask_distance's
     int H, W;
 };
+static_assert(sizeof(HullCamera) == 144 && offsetof(HullCamera, d2) == 128, "HullCamera is CAMERA_DTYPE's layout");
 
 __host__ __device__ __forceinline__ double hull_phi(int v)
 {
@@ -220,11 +221,12 @@ __host__ __device__ __forceinline__ double hull_phi(int v)
 __host__ __device__ __forceinline__ void carve_voxel(const HullCamera& c, double scale, double px, double py, double pz, float& field,
                                                      int& count)
 {
-    const double qx = ((c.R[0] * px + c.R[1] * py) + c.R[2] * pz) + c.t[0];
-    const double qy = ((c.R[3] * px + c.R[4] * py) + c.R[5] * pz) + c.t[1];
-    const double qz = ((c.R[6] * px + c.R[7] * py) + c.R[8] * pz) + c.t[2];
+    double qx, qy, qz;
+    rig_local(c.cam.rc, px, py, pz, qx, qy, qz);
     if (!(qz > HULL_ZNEAR)) return;
-    const double u = c.fx * (qx / qz) + c.cx, v = c.fy * (qy / qz) + c.cy;
+    double u, v;
+    rig_pixel(c.cam.rc.fx, qx, qz, c.cam.cx, u);
+    rig_pixel(c.cam.rc.fy, qy, qz, c.cam.cy, v);
     if (!(u >= 0.0 && u <= (double)(c.W - 1) && v >= 0.0 && v <= (double)(c.H - 1))) return;
     const int x0 = min((int)u, c.W - 2), y0 = min((int)v, c.H - 2);   // (u, v >= 0: the conversion is the floor)
     const double a = u - (double)x0, b = v - (double)y0;
@@ -254,12 +256,12 @@ __global__ void __launch_bounds__(HV_BLOCK) hull_carve_kernel(int n, const HullC
         const double c0 = ox + ((double)(x0 + 0) + 0.5) * voxel, c1 = ox + ((double)(x0 + 1) + 0.5) * voxel;
         const double c2 = ox + ((double)(x0 + 2) + 0.5) * voxel, c3 = ox + ((double)(x0 + 3) + 0.5) * voxel;
         for (int k = 0; k < n; ++k) {
-            const HullCamera cam = cams[k];
-            const double scale = 2.0 / (cam.fx + cam.fy);
-            carve_voxel(cam, scale, c0, cy, cz, F.x, C.x);
-            carve_voxel(cam, scale, c1, cy, cz, F.y, C.y);
-            carve_voxel(cam, scale, c2, cy, cz, F.z, C.z);
-            carve_voxel(cam, scale, c3, cy, cz, F.w, C.w);
+            const HullCamera hc = cams[k];
+            const double scale = 2.0 / (hc.cam.rc.fx + hc.cam.rc.fy);
+            carve_voxel(hc, scale, c0, cy, cz, F.x, C.x);
+            carve_voxel(hc, scale, c1, cy, cz, F.y, C.y);
+            carve_voxel(hc, scale, c2, cy, cz, F.z, C.z);
+            carve_voxel(hc, scale, c3, cy, cz, F.w, C.w);
         }
         *reinterpret_cast<float4*>(field + at) = F;
         *reinterpret_cast<int4*>(count + at) = C;
@@ -309,10 +311,11 @@ const char* hull_cameras_error(int n, const HullCamera* cams)
 {
     for (int k = 0; k < n; ++k) {
         const HullCamera& c = cams[k];
+        const RigCamera& rc = c.cam.rc;
         for (int i = 0; i < 9; ++i)
-            if (!is_finite(c.R[i])) return "a camera is not finite";
-        if (!is_finite(c.t[0]) || !is_finite(c.t[1]) || !is_finite(c.t[2]) || !is_finite(c.cx) || !is_finite(c.cy)) return "a camera is not finite";
-        if (!(c.fx > 0.0) || !(c.fy > 0.0) || !is_finite(c.fx) || !is_finite(c.fy)) return "focal lengths must be positive and finite";
+            if (!is_finite(rc.R[i])) return "a camera is not finite";
+        if (!is_finite(rc.t[0]) || !is_finite(rc.t[1]) || !is_finite(rc.t[2]) || !is_finite(c.cam.cx) || !is_finite(c.cam.cy)) return "a camera is not finite";
+        if (!(rc.fx > 0.0) || !(rc.fy > 0.0) || !is_finite(rc.fx) || !is_finite(rc.fy)) return "focal lengths must be positive and finite";
         if (c.H < 2 || c.W < 2) return "a distance map must be at least 2 x 2";
         if ((long long)c.H * c.W >= (1ll << 31)) return "a distance map is too large";
         if (!c.d2 || (reinterpret_cast<uintptr_t>(c.d2) & 1)) return "a distance map is null or not 2-byte aligned";

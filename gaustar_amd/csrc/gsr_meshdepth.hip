@@ -61,11 +61,6 @@ constexpr int MD_SMALL_MAX = 256;
 constexpr int MD_FACE_LANES = 8;       // lanes of md_face_kernel per face
 constexpr unsigned long long MD_EMPTY = ~0ull;
 
-struct MdCamera {
-    RigCamera rc;
-    double cx, cy;
-};
-
 struct MdCounters {   // zeroed by the wrapper before md_face_kernel
     unsigned n_mid, n_huge;
     int n_clipped;
@@ -79,7 +74,7 @@ struct MdFace {
 
 enum { MD_SKIP = 0, MD_CLIPPED = 1, MD_DRAW = 2 };
 
-__device__ __forceinline__ int md_setup(const MdCamera& cam, int H, int W, int V, const double* __restrict__ verts,
+__device__ __forceinline__ int md_setup(const RigPinhole& cam, int H, int W, int V, const double* __restrict__ verts,
                                         const int* __restrict__ faces, int f, double znear, MdFace& t)
 {
     bool clipped = false;
@@ -87,13 +82,11 @@ __device__ __forceinline__ int md_setup(const MdCamera& cam, int H, int W, int V
         const int v = faces[3 * (size_t)f + k];
         if ((unsigned)v >= (unsigned)V) return MD_SKIP;
         const double* p = verts + 3 * (size_t)v;
-        const RigCamera& c = cam.rc;
-        const double lx = c.R[0] * p[0] + c.R[1] * p[1] + c.R[2] * p[2] + c.t[0];
-        const double ly = c.R[3] * p[0] + c.R[4] * p[1] + c.R[5] * p[2] + c.t[1];
-        const double lz = c.R[6] * p[0] + c.R[7] * p[1] + c.R[8] * p[2] + c.t[2];
+        double lx, ly, lz;
+        rig_local(cam.rc, p[0], p[1], p[2], lx, ly, lz);
         clipped = clipped || lz <= znear;
-        t.x[k] = c.fx * (lx / lz) + cam.cx;
-        t.y[k] = c.fy * (ly / lz) + cam.cy;
+        rig_pixel(cam.rc.fx, lx, lz, cam.cx, t.x[k]);
+        rig_pixel(cam.rc.fy, ly, lz, cam.cy, t.y[k]);
         t.z[k] = lz;
     }
     if (clipped) return MD_CLIPPED;
@@ -138,7 +131,7 @@ __device__ __forceinline__ void md_put(unsigned long long* __restrict__ keys, si
 // MD_FACE_LANES neighbouring lanes per face: each derives the face (the loads coalesce) and walks every MD_FACE_LANES-th pixel
 // of its range in row-major order
 __global__ void __launch_bounds__(MD_BLOCK) md_face_kernel(int H, int W, int V, int F, const double* __restrict__ verts,
-                                                           const int* __restrict__ faces, MdCamera cam, double znear, int small_max,
+                                                           const int* __restrict__ faces, RigPinhole cam, double znear, int small_max,
                                                            unsigned long long* __restrict__ keys, MdCounters* __restrict__ cnt,
                                                            int* __restrict__ big)
 {
@@ -169,7 +162,7 @@ __global__ void __launch_bounds__(MD_BLOCK) md_face_kernel(int H, int W, int V, 
 }
 
 __global__ void __launch_bounds__(MD_BLOCK) md_big_kernel(int H, int W, int V, int F, const double* __restrict__ verts,
-                                                          const int* __restrict__ faces, MdCamera cam, double znear,
+                                                          const int* __restrict__ faces, RigPinhole cam, double znear,
                                                           unsigned long long* __restrict__ keys, const MdCounters* __restrict__ cnt,
                                                           const int* __restrict__ big)
 {
@@ -276,7 +269,7 @@ int gsr_mesh_depth_view(int H, int W, int V, int F, const double* verts, const i
     unsigned long long* keys = static_cast<unsigned long long*>(workspace);
     MdCounters* cnt = reinterpret_cast<MdCounters*>(static_cast<char*>(workspace) + md_keys_bytes(H, W));
     int* big = reinterpret_cast<int*>(cnt + 1);
-    MdCamera cam;
+    RigPinhole cam;
     cam.rc = rig_camera(cam16);
     cam.cx = cam16[14];
     cam.cy = cam16[15];

@@ -1,6 +1,7 @@
-// gsr_rig.h -- what the per-camera passes of a rig share (gsr_topo.hip: detect_topo_err, gsr_warp.hip: warp_mesh_using_flow):
-// the camera and its f64 projection, query_at_image's index, the depth-edge statistic get_depth_edge(depth, 2 R + 1) and the
-// two image passes that reduce a depth map to the maxima it is normalised by, and the ping-pong loop of the Jacobi sweeps.
+// gsr_rig.h -- what the per-camera passes of a rig share (gsr_topo.hip: detect_topo_err, gsr_warp.hip: warp_mesh_using_flow;
+// the camera alone also gsr_prep.hip, gsr_meshdepth.hip, gsr_hull.hip): the camera and its f64 projection, query_at_image's
+// index, the depth-edge statistic get_depth_edge(depth, 2 R + 1) and the two image passes that reduce a depth map to the
+// maxima it is normalised by, and the ping-pong loop of the Jacobi sweeps.
 //
 // Floating point follows the numpy restatements (tests/topo_ref.py, tests/warp_ref.py) operation by operation, so contraction
 // into FMAs is off.  The pragma stands HERE because clang fixes the contraction mode where a function or template is defined,
@@ -33,16 +34,32 @@ inline RigCamera rig_camera(const double* cam14)
     return cam;
 }
 
+// with the principal point in pixels: gsr_mesh_depth_view's [host] block and a HullCamera's head (_rig.camera_block's 16 doubles)
+struct RigPinhole {
+    RigCamera rc;
+    double cx, cy;
+};
+
+// local = R p + t, each row as ((R0 x + R1 y) + R2 z) + t
+__host__ __device__ __forceinline__ void rig_local(const RigCamera& cam, double px, double py, double pz, double& lx, double& ly, double& lz)
+{
+    lx = ((cam.R[0] * px + cam.R[1] * py) + cam.R[2] * pz) + cam.t[0];
+    ly = ((cam.R[3] * px + cam.R[4] * py) + cam.R[5] * pz) + cam.t[1];
+    lz = ((cam.R[6] * px + cam.R[7] * py) + cam.R[8] * pz) + cam.t[2];
+}
+
+// one pixel coordinate of a local point: the quotient, then the product, then the sum.  (Not returned by value: clang then
+// takes the pixel for well defined and hull_carve_kernel's bounds test comes out with two operands exchanged.)
+__host__ __device__ __forceinline__ void rig_pixel(double f, double l, double lz, double c, double& pix) { pix = f * (l / lz) + c; }
+
 // warp_mesh.py:47-74 in double: local = R p + t, row = fy y / z + H / 2, col = fx x / z + W / 2 (no principal point).  The
 // pixel is the un-rounded one: query_at_image adds its 0.5 itself (rig_query)
 __device__ __forceinline__ void rig_project(const RigCamera& cam, int H, int W, double px, double py, double pz, double& lx,
                                             double& ly, double& lz, double& pr, double& pc)
 {
-    lx = cam.R[0] * px + cam.R[1] * py + cam.R[2] * pz + cam.t[0];
-    ly = cam.R[3] * px + cam.R[4] * py + cam.R[5] * pz + cam.t[1];
-    lz = cam.R[6] * px + cam.R[7] * py + cam.R[8] * pz + cam.t[2];
-    pr = cam.fy * (ly / lz) + H * 0.5;
-    pc = cam.fx * (lx / lz) + W * 0.5;
+    rig_local(cam, px, py, pz, lx, ly, lz);
+    rig_pixel(cam.fy, ly, lz, H * 0.5, pr);
+    rig_pixel(cam.fx, lx, lz, W * 0.5, pc);
 }
 
 // query_at_image's index (warp_mesh.py:106-117): np.int32(pix + 0.5) truncates toward zero, NaN and values out of the int32

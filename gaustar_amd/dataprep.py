@@ -42,7 +42,7 @@ from typing import Callable, Optional, Sequence, Union
 import numpy as np
 import torch
 
-from . import _host, _lib, _meshargs as _ma, formats, mesh_depth, sweep
+from . import _host, _lib, _meshargs as _ma, _rig, formats, mesh_depth, sweep
 from ._lib import ptr as _p
 
 THRESHOLD = 0.005                  # ahq2gaustar.py:149
@@ -64,10 +64,6 @@ class MeshColors:
     n_unfilled: int
 
 
-def _tensor(x) -> torch.Tensor:
-    return x if isinstance(x, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(x))
-
-
 # ---------------------------------------------------------------------------------------------- images
 @torch.no_grad()
 def rectify_image(image, intr, dist=None, border=0, out: Optional[torch.Tensor] = None, device=None) -> torch.Tensor:
@@ -77,7 +73,7 @@ def rectify_image(image, intr, dist=None, border=0, out: Optional[torch.Tensor] 
     scalar or C values, what pixels outside the source show (cv2's BORDER_CONSTANT).  out: a contiguous uint8 tensor of the
     image's shape on the device, written in place (any alignment; it must not be `image` itself).  Runs on the current stream
     without a host read."""
-    img = _tensor(image)
+    img = _ma.tensor_of(image)
     if img.dtype != torch.uint8 or img.dim() not in (2, 3):
         raise ValueError(f"image must be [H,W] or [H,W,C] uint8, got {img.dtype} {tuple(img.shape)}")
     H, W = int(img.shape[0]), int(img.shape[1])
@@ -100,13 +96,9 @@ def rectify_image(image, intr, dist=None, border=0, out: Optional[torch.Tensor] 
     if b.size not in (1, C) or (b < 0).any() or (b > 255).any() or (b != np.floor(b)).any():
         raise ValueError(f"border must be one byte value or {C} of them")
     bytes_c = (ctypes.c_ubyte * C)(*[int(x) for x in np.broadcast_to(b, (C,))])
-    if device is None:
-        device = img.device if img.is_cuda else (out.device if out is not None else torch.device("cuda", torch.cuda.current_device()))
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError("rectify_image needs a GPU")
-    if dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
+    if device is None and out is not None and not img.is_cuda:
+        device = out.device
+    dev = _host.resolve_device(device, img, what="rectify_image")
     if out is not None and (out.dtype != torch.uint8 or tuple(out.shape) != tuple(img.shape) or out.device != dev or not out.is_contiguous()):
         raise ValueError(f"out must be a contiguous uint8 tensor of shape {tuple(img.shape)} on {dev}")
     with _host.on_device(dev):
@@ -120,39 +112,9 @@ def rectify_image(image, intr, dist=None, border=0, out: Optional[torch.Tensor] 
 
 
 # ---------------------------------------------------------------------------------------------- colours
-def _rig_arrays(rig: dict):
-    shape = np.asarray(rig["shape"])
-    intr, extr = np.asarray(rig["intrinsics"], np.float64), np.asarray(rig["extrinsics"], np.float64)
-    C = int(shape.shape[0])
-    if shape.ndim != 2 or shape.shape[1] != 2 or intr.shape != (C, 3, 3) or extr.shape[0] != C or extr.shape[1] < 3 or extr.shape[2:] != (4,):
-        raise ValueError("rig must hold intrinsics [C,3,3], extrinsics [C,4,4] (or [C,3,4]) and shape [C,2]")
-    if C > MAX_CAMERAS:
-        raise ValueError(f"{C} cameras: more than {MAX_CAMERAS}, a channel's sum would not fit an int32")
-    if C and (shape < 1).any():
-        raise ValueError("rig['shape'] must be positive")
-    return shape, intr, extr, C
-
-
-def _check_stack(x, C: int, shape, tail: tuple, dtype, what: str) -> None:
-    """x [C,H,W,*tail] of `dtype` whose (H, W) is every camera's rig['shape'] -- or a callable, checked per view."""
-    if callable(x):
-        return
-    if not isinstance(x, (np.ndarray, torch.Tensor)):
-        raise ValueError(f"{what} must be an array [C,H,W{',3' if tail else ''}] or a callable")
-    want_np, want_t = dtype
-    if x.dtype not in (want_np, want_t) or x.ndim != 3 + len(tail) or int(x.shape[0]) != C or tuple(x.shape[3:]) != tail:
-        raise ValueError(f"{what} must be [C,H,W{',3' if tail else ''}] {want_t} with C = {C}, got {x.dtype} {tuple(x.shape)}")
-    hw = (int(x.shape[1]), int(x.shape[2]))
-    for i in range(C):
-        if (int(shape[i][0]), int(shape[i][1])) != hw:
-            raise ValueError(f"{what} are {hw} but rig['shape'][{i}] is {tuple(int(s) for s in shape[i])}")
-
-
-def _one(x, i: int, H: int, W: int, tail: tuple, dtype: torch.dtype, dev, what: str) -> torch.Tensor:
-    t = _tensor(x(i) if callable(x) else x[i])
-    if t.dtype != dtype or tuple(t.shape) != (H, W, *tail):
-        raise ValueError(f"{what} {i} must be {(H, W, *tail)} {dtype}, got {t.dtype} {tuple(t.shape)}")
-    return t.to(dev).contiguous()
+_RIG_CHECKS = dict(min_side=1, max_cameras=MAX_CAMERAS)      # what _rig.Rig.of checks beyond the layout
+_IMAGE = ((3,), (torch.uint8,))          # (tail, dtypes) of _rig.check_images / fetch_image
+_DEPTH = ((), (torch.float32,))
 
 
 @torch.no_grad()
@@ -160,51 +122,40 @@ def view_color_sums(verts, rig: dict, images, depths=None, faces=None, threshold
                     rank: Optional[int] = None, world: Optional[int] = None, device=None) -> torch.Tensor:
     """sums [V,4] int32 on the device: per vertex the sum of the pixels (r, g, b) it projects to and the number of cameras, over
     the cameras of this rank's shard (sweep.camera_shard) that see it (ahq2gaustar.py:140-151): valid lookup and
-    |lz - depth| < threshold.  rig: the `cmr` dict (intrinsics [C,3,3], extrinsics [C,4,4], shape [C,2] = (H, W)); the images
-    are rectified ones, the principal point is not read.  images: [C,H,W,3] uint8 RGB (numpy or torch) or a callable
-    i -> [H,W,3]; depths: [C,H,W] f32 or a callable i -> [H,W]; None renders them from (verts, faces) with
-    mesh_depth at the centre principal point, which is what the reference's pipeline does in two steps through files.
-    Integer sums: the same bits for every views_in_flight, and the shards of all ranks add up to the whole rig's."""
+    |lz - depth| < threshold.  rig: the `cmr` dict (_rig.py); the images are rectified ones, the principal point is not read.
+    images: [C,H,W,3] uint8 RGB (numpy or torch) or a callable i -> [H,W,3]; depths: [C,H,W] f32 or a callable i -> [H,W];
+    None renders them from (verts, faces) with mesh_depth at the centre principal point, which is what the reference's pipeline
+    does in two steps through files.  Integer sums: the same bits for every views_in_flight, and all ranks' shards add up."""
     lib = _lib.load()
-    shape, intr, extr, C = _rig_arrays(rig)
-    _check_stack(images, C, shape, (3,), (np.uint8, torch.uint8), "images")
+    rig = _rig.Rig.of(rig, **_RIG_CHECKS)
+    _rig.check_images(images, rig, *_IMAGE, "image", stack_only=True)
     if depths is not None:
-        _check_stack(depths, C, shape, (), (np.float32, torch.float32), "depths")
+        _rig.check_images(depths, rig, *_DEPTH, "depth", stack_only=True)
     elif faces is None:
         raise ValueError("without depths the mesh's faces are needed to render them")
-    dev = mesh_depth._device_of(verts, device)
-    if dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
-    if depths is None:
-        v, f = mesh_depth._upload(verts, faces, dev)
-    else:
-        v = _tensor(verts).detach().to(dev, torch.float64).contiguous()
-        if v.dim() != 2 or v.shape[1] != 3:
-            raise ValueError(f"verts must be [V,3], got {tuple(v.shape)}")
+    dev = _host.resolve_device(device, verts, what="mesh_depth")
+    v, f = _ma.mesh_on(verts, faces, dev) if depths is None else (_ma.verts_on(verts, dev), None)
     V = int(v.shape[0])
-    mine = sweep.camera_shard(C, rank, world)
+    mine = sweep.camera_shard(rig.C, rank, world)
     with _host.on_device(dev):
         sums = torch.zeros(V, 4, dtype=torch.int32, device=dev)
 
-    def work(_t, j):
-        i = mine[j]
-        H, W = int(shape[i][0]), int(shape[i][1])
-        img = _one(images, i, H, W, (3,), torch.uint8, dev, "image")
+    def per_camera(_j, i):
+        H, W = rig.hw(i)
+        img = _rig.fetch_image(images, i, (H, W), *_IMAGE, dev, "image")
         if depths is None:
-            depth = mesh_depth._view(lib, v, f, mesh_depth.cam16(extr[i], intr[i], W / 2, H / 2), H, W, mesh_depth.ZNEAR,
-                                     mesh_depth.BACKGROUND, False, 0, None).depth
+            depth = mesh_depth._view(lib, v, f, rig.cam16(i), H, W, mesh_depth.ZNEAR, mesh_depth.BACKGROUND, False, 0, None).depth
         else:
-            depth = _one(depths, i, H, W, (), torch.float32, dev, "depth")
-        _lib.check(lib.gsr_mesh_color_view(H, W, V, _p(v), _p(img), _p(depth), sweep.cam14(extr[i], intr[i]), float(threshold), _p(sums),
+            depth = _rig.fetch_image(depths, i, (H, W), *_DEPTH, dev, "depth")
+        _lib.check(lib.gsr_mesh_color_view(H, W, V, _p(v), _p(img), _p(depth), rig.cam14(i), float(threshold), _p(sums),
                                            _host.stream_of(v)), "gsr_mesh_color_view")
 
-    with _host.on_device(dev):      # (for the plain loop; the pipelines' workers set their device themselves)
-        sweep.run_shard(work, len(mine), views_in_flight, dev)
+    sweep.run_cameras(mine, per_camera, views_in_flight, dev)
     return sums
 
 
 def _device_faces(faces, dev) -> torch.Tensor:
-    f = _tensor(faces)
+    f = _ma.tensor_of(faces)
     if f.dtype not in (torch.int32, torch.int64):
         raise ValueError("faces must be int32 or int64")
     return _ma.faces_i32(f.to(dev))
@@ -311,7 +262,8 @@ def write_colmap(folder, rig: dict, verts, rgb) -> None:
     are rectified).  images.txt: `i qw qx qy qz tx ty tz i img_{i:04d}.jpg` and an empty line per camera (rotmat2qvec of
     extrinsics[i][:3, :3]).  points3D.ply: binary little endian, one vertex element of x y z nx ny nz (float, normals zero) and
     red green blue (uchar), written with struct / numpy as plyfile would."""
-    shape, intr, extr, C = _rig_arrays(rig)
+    rig = _rig.Rig.of(rig, **_RIG_CHECKS)
+    intr, extr, C = rig.intr, rig.extr, rig.C
     v = _host_array(verts, np.float64)
     if v.ndim != 2 or v.shape[1] != 3:
         raise ValueError(f"verts must be [V,3], got {v.shape}")
@@ -322,7 +274,7 @@ def write_colmap(folder, rig: dict, verts, rgb) -> None:
         fh.write("# Camera list with one line of data per camera:\n#   CAMERA_ID, MODEL, WIDTH, HEIGHT, PARAMS[fx,fy,cx,cy]\n"
                  f"# Number of cameras: {C}\n")
         for i in range(C):
-            H, W = int(shape[i][0]), int(shape[i][1])
+            H, W = rig.hw(i)
             fh.write(" ".join([str(i), "PINHOLE", str(W), str(H), _s(intr[i][0, 0]), _s(intr[i][1, 1]), _s(W * 0.5), _s(H * 0.5)]) + "\n")
     with open(os.path.join(folder, "images.txt"), "w") as fh:
         fh.write("# Image list with two lines of data per image:\n#   IMAGE_ID, QW, QX, QY, QZ, TX, TY, TZ, CAMERA_ID, NAME\n"
@@ -387,10 +339,8 @@ def prepare_first_frame(source_dir, mesh_dir, gstar_dir, frame_0: int = 0, frame
     Returns the MeshColors of step 3."""
     root = os.fspath(gstar_dir)
     cam_path = os.path.join(root, "rgb_cameras.npz")
-    info = dict(np.load(cam_path))
-    rig = {"intrinsics": np.asarray(info["intrinsics"], np.float64), "extrinsics": np.asarray(info["extrinsics"], np.float64),
-           "shape": np.asarray(info["shape"], np.int32)}
-    shape, intr, _extr, C = _rig_arrays(rig)
+    rig, info = _rig.Rig.load(cam_path, **_RIG_CHECKS)
+    intr, C = rig.intr, rig.C
     dist = np.asarray(info["dist_coeffs"], np.float64) if "dist_coeffs" in info else None
     if dist is not None and dist.shape != (C, 5):
         raise ValueError(f"{cam_path}: dist_coeffs must be [{C},5], got {dist.shape}")
@@ -402,8 +352,8 @@ def prepare_first_frame(source_dir, mesh_dir, gstar_dir, frame_0: int = 0, frame
         os.makedirs(os.path.join(root, f"{f:04d}/images"), exist_ok=True)
         for c in range(C):
             src = load_image_rgb8(image_path(c, f))
-            if src.shape[:2] != (int(shape[c][0]), int(shape[c][1])):
-                raise ValueError(f"{image_path(c, f)}: {src.shape[:2]} but the camera's shape is {tuple(int(s) for s in shape[c])}")
+            if src.shape[:2] != rig.hw(c):
+                raise ValueError(f"{image_path(c, f)}: {src.shape[:2]} but the camera's shape is {rig.hw(c)}")
             img = rectify_image(src, intr[c], None if dist is None else dist[c], border)
             formats.save_png_rgb8(os.path.join(root, f"{f:04d}/images/img_{c:04d}.png"), img.cpu().numpy())
     mesh_depth.render_mesh_depth_files(cam_path, mesh_dir, root, wo_cxcy=True, from_humanrf=True, mesh_res=res, frame_0=frames[0],

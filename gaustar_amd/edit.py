@@ -63,13 +63,6 @@ class PaintResult(NamedTuple):
 
 
 # ------------------------------------------------------------------------------------------------ argument checks
-def _device(device=None) -> torch.device:
-    dev = torch.device("cuda" if device is None else device)
-    if dev.type != "cuda":
-        raise ValueError("the edit kernels run on a GPU")
-    return torch.device("cuda", torch.cuda.current_device()) if dev.index is None else dev
-
-
 def _host_f64(x, shape, what: str) -> np.ndarray:
     """x (numpy, list or tensor) as a C-contiguous float64 array whose shape matches `shape` (None: any length)."""
     if torch.is_tensor(x):
@@ -177,9 +170,7 @@ def fit_sums(src, dst, device=None) -> torch.Tensor:
         raise ValueError("fit_rigid needs anchors")
     if T > 65535:
         raise ValueError("at most 65535 frames in one call")
-    if device is None:
-        device = a.device if a.is_cuda else (b.device if b.is_cuda else None)
-    dev = _device(device)
+    dev = _host.resolve_device(device, a if a.is_cuda else b, what="gaustar_amd.edit", exc=ValueError)
     a, b = a.to(dev).contiguous(), b.to(dev).contiguous()
     out = torch.empty(T, 16, dtype=torch.float64, device=dev)
     lib = _lib.load()
@@ -569,7 +560,7 @@ def edit_sequence(work_dir: str, out_dir: str, frames: Sequence[int], iteration:
     else exported from the edited model (:106, :172).  -> the checkpoints' paths."""
     from . import formats
     from .harness import SurfaceGaussians
-    dev = _device(device)
+    dev = _host.resolve_device(device, what="gaustar_amd.edit", exc=ValueError)
     frames = [int(f) for f in frames]
     anchors = _frame_anchors(trajectory, frames)
     for op in ops:

@@ -632,14 +632,12 @@ class SurfaceGaussians(nn.Module):
         (render_depth_from_mesh.py:13-101 on the model's mesh): mesh_depth.mesh_depth_view(vertices, faces, ...) with the
         camera's row of topology.rig_from_cameras -> mesh_depth.MeshDepthView.  camera_or_index: a NerfCamera, or an index into
         `cameras`.  use_principal_point=True (in kw) reads the camera's principal point instead of (W / 2, H / 2)."""
-        from . import mesh_depth, topology
+        from . import _rig, mesh_depth, topology
         cam = cameras[int(camera_or_index)] if isinstance(camera_or_index, (int, np.integer)) else camera_or_index
-        rig = topology.rig_from_cameras([cam])
-        H, W = (int(x) for x in rig["shape"][0])
+        rig = _rig.Rig.of(topology.rig_from_cameras([cam]))
         if kw.pop("use_principal_point", False):
-            kw["principal_point"] = (rig["intrinsics"][0][0, 2], rig["intrinsics"][0][1, 2])
-        return mesh_depth.mesh_depth_view(self._points.detach(), self._surface_mesh_faces, rig["extrinsics"][0], rig["intrinsics"][0],
-                                          H, W, **kw)
+            kw["principal_point"] = rig.principal(0, True)
+        return mesh_depth.mesh_depth_view(self._points.detach(), self._surface_mesh_faces, rig.extr[0], rig.intr[0], *rig.hw(0), **kw)
 
     def track(self, tracker):
         """Where a tracking.SurfaceTracker's points sit on the model's own mesh (tracking_util.py:70): tracker.positions(vertices,
@@ -791,15 +789,11 @@ class SurfaceGaussians(nn.Module):
         `all_densities` inverse_sigmoid(initial_opacity) -- the reference's value when opacities are learnt (:315).
         kw: `device` (default: the tensors' GPU, else the current one) and __init__'s other arguments.  Missing colours
         raise ValueError."""
-        from . import handover
+        from . import _host, _meshargs as _ma, handover
         if vertex_colors is None:
             raise ValueError("from_mesh needs vertex colours: the mesh file has none")
-        dev = kw.pop("device", None)
-        if dev is None:
-            dev = verts.device if isinstance(verts, torch.Tensor) and verts.device.type == "cuda" else torch.device("cuda", torch.cuda.current_device())
-        v = torch.as_tensor(np.asarray(verts) if not isinstance(verts, torch.Tensor) else verts).to(dev, torch.float32)
-        f = torch.as_tensor(np.asarray(faces) if not isinstance(faces, torch.Tensor) else faces).to(dev, torch.long)
-        c = torch.as_tensor(np.asarray(vertex_colors) if not isinstance(vertex_colors, torch.Tensor) else vertex_colors).to(dev, torch.float32)
+        dev = _host.resolve_device(kw.pop("device", None), verts, what="from_mesh")
+        v, f, c = _ma.upload(verts, dev, torch.float32), _ma.upload(faces, dev, torch.long), _ma.upload(vertex_colors, dev, torch.float32)
         if c.dim() != 2 or c.shape[0] != v.shape[0] or c.shape[1] < 3:
             raise ValueError(f"vertex_colors must be [V,>=3] with V = {int(v.shape[0])}, got {tuple(c.shape)}")
         if not 0.0 < float(initial_opacity) < 1.0:

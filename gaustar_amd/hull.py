@@ -14,9 +14,8 @@ with that many views the visual hull is a tight, robust and deterministic surfac
     write_hull_meshes(gstar_dir, mask_path, mesh_dir, 0, 10, 1)   # mesh_{f:06d}_smooth_{res}.obj, the names that
         # mesh_depth.render_mesh_depth_files(from_humanrf=True) and dataprep.prepare_first_frame read
 
-`rig` is the `cmr` dict used everywhere else (intrinsics [C,3,3], extrinsics [C,4,4] COLMAP world-to-camera, shape [C,2] =
-(H, W)); masks are rectified ones and the principal point is (W / 2, H / 2), mesh_depth's default, unless
-use_principal_point reads it from the intrinsics.  The rules are stated in include/gsr.h and restated in tests/hull_ref.py.
+`rig` is the `cmr` dict (_rig.py); masks are rectified ones, the principal point the image's centre unless use_principal_point
+reads it from the intrinsics.  The rules are stated in include/gsr.h and restated in tests/hull_ref.py.
 
 What to know about the result:
   * a pixel beyond the image's border is unknown, neither inside nor outside: a silhouette that touches the border is not
@@ -41,20 +40,15 @@ import numpy as np
 import torch
 import torch.distributed as tdist
 
-from . import _host, _lib, formats, fusion, sweep
+from . import _host, _lib, _rig, formats, fusion, sweep
 from ._lib import ptr as _p
 
 ZNEAR = 0.01
 MAX_RADIUS = 127
 CAMERA_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("fx", "<f8"), ("fy", "<f8"), ("cx", "<f8"), ("cy", "<f8"),
-                         ("d2", "<u8"), ("H", "<i4"), ("W", "<i4")])      # gsr_hull.hip's HullCamera
-
-
-def _device(device=None) -> torch.device:
-    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError("gaustar_amd.hull needs a GPU")
-    return dev if dev.index is not None else torch.device("cuda", torch.cuda.current_device())
+                         ("d2", "<u8"), ("H", "<i4"), ("W", "<i4")])      # gsr_hull.hip's HullCamera: Rig.cam16's 16 doubles, then its own
+_RIG_CHECKS = dict(min_side=2, finite=True, positive_focal=True)      # what _rig.Rig.of checks beyond the layout
+_IMAGE = ((), (torch.uint8, torch.int16))     # (tail, dtypes) of _rig.check_images / fetch_image: a mask, or its distance map
 
 
 def _check_radius(radius) -> int:
@@ -98,7 +92,7 @@ def mask_distance(mask, threshold: int = 128, radius: int = 8, device=None) -> t
             raise ValueError(f"mask must be uint8, got {a.dtype}")
         m = torch.from_numpy(np.ascontiguousarray(a))
         _check_image(m, torch.uint8, "mask")
-        m = m.to(_device(device))
+        m = m.to(_host.resolve_device(device, what="gaustar_amd.hull"))
     H, W = int(m.shape[0]), int(m.shape[1])
     if H > 65535:
         raise ValueError(f"mask has {H} rows: more than 65535")
@@ -110,20 +104,11 @@ def mask_distance(mask, threshold: int = 128, radius: int = 8, device=None) -> t
     return d2
 
 
-def _rig_arrays(rig: dict):
-    shape = np.asarray(rig["shape"])
-    intr, extr = np.asarray(rig["intrinsics"], np.float64), np.asarray(rig["extrinsics"], np.float64)
-    C = int(shape.shape[0])
-    if shape.ndim != 2 or shape.shape[1] != 2 or intr.shape != (C, 3, 3) or extr.ndim != 3 or extr.shape[0] != C or extr.shape[1] < 3 \
-            or extr.shape[2] != 4:
-        raise ValueError("rig must hold intrinsics [C,3,3], extrinsics [C,4,4] (or [C,3,4]) and shape [C,2]")
-    if C and (shape < 2).any():
-        raise ValueError("rig['shape'] must be at least 2 x 2")
-    if not (np.isfinite(intr).all() and np.isfinite(extr).all()):
-        raise ValueError("the rig's cameras must be finite")
-    if C and not ((intr[:, 0, 0] > 0).all() and (intr[:, 1, 1] > 0).all()):
-        raise ValueError("the rig's focal lengths must be positive")
-    return shape, intr, extr, C
+def _rig_of(rig, need_camera: bool = False) -> _rig.Rig:
+    rig = _rig.Rig.of(rig, **_RIG_CHECKS)
+    if need_camera and not rig.C:
+        raise ValueError("the rig has no camera")
+    return rig
 
 
 _warned_radius = False
@@ -131,9 +116,8 @@ _warned_radius = False
 
 def _radius_needed(rig: dict, lo, hi, sdf_trunc: float) -> Tuple[float, float]:
     """(z_min, the cap radius_for's rule asks for before it is limited to 127; inf when the box reaches behind znear)."""
-    _shape, intr, extr, C = _rig_arrays(rig)
-    if not C:
-        raise ValueError("the rig has no camera")
+    rig = _rig_of(rig, need_camera=True)
+    intr, extr = rig.intr, rig.extr
     if not sdf_trunc > 0:
         raise ValueError("sdf_trunc must be positive")
     lo, hi = np.asarray(lo, np.float64).reshape(3), np.asarray(hi, np.float64).reshape(3)
@@ -168,35 +152,12 @@ class HullVolume(fusion.TSDFVolume):
     fusion.extract_triangle_mesh reads those.  color stays zero."""
 
     def __init__(self, lo, hi, voxel_size: float = 0.008, sdf_trunc: float = 0.02, device=None):
-        super().__init__(lo, hi, voxel_size, sdf_trunc, _device(device))
+        super().__init__(lo, hi, voxel_size, sdf_trunc, _host.resolve_device(device, what="gaustar_amd.hull"))
 
     def _allocate(self, u0, nu, voxel_size, sdf_trunc, device):
         super()._allocate(u0, nu, voxel_size, sdf_trunc, device)
         self.field = torch.full_like(self.tsdf, float("inf"))
         self.count = torch.zeros(self.tsdf.shape, dtype=torch.int32, device=self.device)
-
-
-def _one_image(src, i: int, H: int, W: int, dev) -> torch.Tensor:
-    x = src(i) if callable(src) else src[i]
-    t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(x)))
-    if t.dtype not in (torch.uint8, torch.int16) or tuple(t.shape) != (H, W):
-        raise ValueError(f"image {i} must be a [{H},{W}] uint8 mask or int16 distance map, got {t.dtype} {tuple(t.shape)}")
-    return t.to(dev).contiguous()
-
-
-def _check_images(src, C: int, shape) -> None:
-    if callable(src):
-        return
-    if not hasattr(src, "__len__") or len(src) != C:
-        raise ValueError(f"need one mask or distance map per camera of the rig ({C})")
-    for i in range(C):
-        x = src[i]
-        dt = x.dtype
-        if dt not in (np.uint8, np.int16, torch.uint8, torch.int16) or tuple(x.shape) != (int(shape[i][0]), int(shape[i][1])):
-            raise ValueError(f"image {i} must be a {tuple(int(v) for v in shape[i])} uint8 mask or int16 distance map, "
-                             f"got {dt} {tuple(x.shape)}")
-        if isinstance(x, torch.Tensor) and x.device.type != "cuda":
-            raise ValueError(f"image {i}: a torch tensor must be on a GPU (pass numpy for host data)")
 
 
 @torch.no_grad()
@@ -206,7 +167,7 @@ def carve_views(volume: HullVolume, rig: dict, masks_or_distances, views_in_flig
     """The cameras of this rank's shard (sweep.camera_shard) into volume.field / volume.count.  masks_or_distances: one image
     per camera of the rig, [C,H,W] or a list (shapes may differ) or a callable i -> image; uint8 = a mask, whose distance map
     is made here (threshold; radius, default radius_for the volume's box), int16 = a distance map of mask_distance, taken as it
-    is.  The distance maps of up to `chunk` cameras are made `views_in_flight` at a time on as many streams (sweep.run_shard),
+    is.  The distance maps of up to `chunk` cameras are made `views_in_flight` at a time on as many streams (sweep.run_cameras),
     then one launch carves them; a rig of 160 cameras never holds 160 maps.  When the job has more than one rank
     (torch.distributed initialised and world > 1), field is all-reduced with MIN and count with SUM once, so every rank ends
     with the whole rig's state; with an explicit rank / world and no process group, the caller's shards simply accumulate in
@@ -214,8 +175,9 @@ def carve_views(volume: HullVolume, rig: dict, masks_or_distances, views_in_flig
     camera indices of the shard."""
     if not isinstance(volume, HullVolume):
         raise ValueError("volume must be a HullVolume")
-    shape, intr, extr, C = _rig_arrays(rig)
-    _check_images(masks_or_distances, C, shape)
+    rig = _rig_of(rig)
+    C = rig.C
+    _rig.check_images(masks_or_distances, rig, *_IMAGE, "mask or distance map", on_gpu=True)
     t = _check_threshold(threshold)
     if int(chunk) < 1:
         raise ValueError("chunk must be at least 1")
@@ -230,19 +192,16 @@ def carve_views(volume: HullVolume, rig: dict, masks_or_distances, views_in_flig
         part = mine[start:start + int(chunk)]
         maps = [None] * len(part)
 
-        def work(_t, j, part=part, maps=maps):
-            i = part[j]
-            H, W = int(shape[i][0]), int(shape[i][1])
-            img = _one_image(masks_or_distances, i, H, W, dev)
+        def per_camera(j, i, maps=maps):
+            img = _rig.fetch_image(masks_or_distances, i, rig.hw(i), *_IMAGE, dev, "mask or distance map")
             maps[j] = img if img.dtype == torch.int16 else mask_distance(img, t, R)
 
-        with _host.on_device(dev):      # (for the plain loop; the pipelines' workers set their device themselves)
-            sweep.run_shard(work, len(part), views_in_flight, dev)
+        sweep.run_cameras(part, per_camera, views_in_flight, dev)
+        with _host.on_device(dev):
             table = np.zeros(len(part), CAMERA_DTYPE)
-            for j, i in enumerate(part):
-                H, W = int(shape[i][0]), int(shape[i][1])
-                cx, cy = (intr[i][0, 2], intr[i][1, 2]) if use_principal_point else (W / 2, H / 2)
-                table[j] = (extr[i][:3, :3].reshape(-1), extr[i][:3, 3], intr[i][0, 0], intr[i][1, 1], cx, cy, maps[j].data_ptr(), H, W)
+            table.view(np.float64).reshape(len(part), -1)[:, :16] = [rig.cam16(i, use_principal_point) for i in part]   # 128 bytes a row
+            table["d2"] = [m.data_ptr() for m in maps]
+            table["H"], table["W"] = np.array([rig.hw(i) for i in part]).T
             cams = torch.from_numpy(table.view(np.uint8).reshape(-1)).to(dev)
             _lib.check(lib.gsr_hull_carve(len(part), table.ctypes.data, _p(cams), volume.voxel_size, volume.grid, _p(volume.field),
                                           _p(volume.count), _host.stream_of(volume.field)), "gsr_hull_carve")
@@ -290,9 +249,7 @@ def rig_box(rig: dict, shrink: float = 0.35) -> Tuple[np.ndarray, np.ndarray]:
     """Where a capture's subject stands: a cube around the point nearest to all optical axes (least squares), its half-size
     `shrink` times the distance from there to the nearest camera.  The cameras of a capture stand around the subject and look
     at it; a box that reached them would need an unbounded distance cap (radius_for)."""
-    _shape, _intr, extr, C = _rig_arrays(rig)
-    if not C:
-        raise ValueError("the rig has no camera")
+    extr = _rig_of(rig, need_camera=True).extr
     if not 0 < shrink < 1:
         raise ValueError("shrink must be in (0, 1)")
     centres = -np.einsum("cji,cj->ci", extr[:, :3, :3], extr[:, :3, 3])
@@ -322,7 +279,7 @@ def hull_bounds(rig: dict, masks, lo=None, hi=None, coarse_voxel: float = 0.032,
     R = int(min(MAX_RADIUS, max(1.0, _radius_needed(rig, vol.origin, top, vol.sdf_trunc)[1])))
     # (no warning where this is capped: a capped distance can only make a far voxel look near, and the box wider)
     carve_views(vol, rig, masks, views_in_flight, 0, 1, threshold=threshold, radius=R, use_principal_point=use_principal_point)
-    finish(vol, default_min_views(len(np.asarray(rig["shape"]))) if min_views is None else min_views)
+    finish(vol, default_min_views(_rig_of(rig).C) if min_views is None else min_views)
     with _host.on_device(vol.device):
         near = (vol.weight == 1) & (vol.tsdf < 1)
         ext = []
@@ -353,9 +310,7 @@ def hull_mesh(rig: dict, masks, lo=None, hi=None, voxel_size: float = 0.008, sdf
     one rank; for a sharded carve call carve_views yourself."""
     if int(taubin_iterations) < 0 or int(target_faces) < 0:
         raise ValueError("taubin_iterations and target_faces must not be negative")
-    _shape, _intr, _extr, C = _rig_arrays(rig)
-    if not C:
-        raise ValueError("the rig has no camera")
+    C = _rig_of(rig, need_camera=True).C
     kw = dict(threshold=threshold, use_principal_point=use_principal_point)
     if lo is None or hi is None:
         lo, hi = hull_bounds(rig, masks, lo, hi, coarse_voxel, min_views=min_views, views_in_flight=views_in_flight, device=device, **kw)
@@ -389,10 +344,7 @@ def write_hull_meshes(gstar_dir, mask_path: Union[str, os.PathLike, Callable[[in
     `rgb_cameras.npz` (intrinsics, extrinsics, shape); mask_path: a callable (camera index, frame) -> the 8-bit grey PNG of
     that camera's rectified alpha mask (formats.load_png_gray8), or the capture's directory (actorshq_mask_path).  The principal
     point is (W / 2, H / 2), as prepare_first_frame renders (wo_cxcy=True).  Returns the paths written."""
-    info = dict(np.load(os.path.join(os.fspath(gstar_dir), "rgb_cameras.npz")))
-    rig = {"intrinsics": np.asarray(info["intrinsics"], np.float64), "extrinsics": np.asarray(info["extrinsics"], np.float64),
-           "shape": np.asarray(info["shape"], np.int32)}
-    _shape, _intr, _extr, C = _rig_arrays(rig)
+    rig = _rig.Rig.load(os.path.join(os.fspath(gstar_dir), "rgb_cameras.npz"), **_RIG_CHECKS)[0]
     path_of = mask_path if callable(mask_path) else actorshq_mask_path(mask_path)
     frames = list(range(int(frame_0), int(frame_end), int(interval)))
     if not frames:
@@ -400,7 +352,7 @@ def write_hull_meshes(gstar_dir, mask_path: Union[str, os.PathLike, Callable[[in
     os.makedirs(os.fspath(mesh_dir), exist_ok=True)
     out = []
     for f in frames:
-        masks = [formats.load_png_gray8(path_of(c, f)) for c in range(C)]
+        masks = [formats.load_png_gray8(path_of(c, f)) for c in range(rig.C)]
         verts, faces = hull_mesh(rig, masks, lo, hi, voxel_size, sdf_trunc, min_views, taubin_iterations, target_faces,
                                  threshold=threshold, views_in_flight=views_in_flight, device=device)
         if not int(faces.shape[0]):

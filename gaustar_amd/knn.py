@@ -187,6 +187,24 @@ def dist_cuda2(points: torch.Tensor) -> torch.Tensor:
 
 
 @torch.no_grad()
+def voxel_groups(lib, pts: torch.Tensor, voxel_size: float, stream):
+    """pts [n,3] f32 contiguous, n >= 1, binned into voxels from their minimum corner (gsr_topo_voxel_keys: Open3D's VoxelGrid
+    rule) and grouped by a stable sort -> (vmin [3] f32, skeys [n] int64 ascending, order [n] int64, vid [n] int64: each sorted
+    point's dense voxel id, head [n] bool: a voxel's first point, flags [1] int32: set when an axis spans too many voxels for a
+    key).  Nothing is read back: vid[-1] + 1 voxels, and flags, are the caller's to read."""
+    n, dev = int(pts.shape[0]), pts.device
+    vmin = pts.amin(0).contiguous()
+    keys = torch.empty(n, dtype=torch.int64, device=dev)
+    flags = torch.zeros(1, dtype=torch.int32, device=dev)
+    _lib.check(lib.gsr_topo_voxel_keys(n, _p(pts), _p(vmin), float(voxel_size), _p(keys), _p(flags), stream), "gsr_topo_voxel_keys")
+    skeys, order = torch.sort(keys, stable=True)
+    head = torch.ones(n, dtype=torch.bool, device=dev)
+    head[1:] = skeys[1:] != skeys[:-1]
+    vid = torch.cumsum(head.long(), 0) - 1
+    return vmin, skeys, order, vid, head, flags
+
+
+@torch.no_grad()
 def segment_mean(sorted_ids: torch.Tensor, order: torch.Tensor, values: torch.Tensor, S: int):
     """gsr_knn_segment_mean: sorted_ids [n] int64 ascending and dense in [0, S), order [n] int64, values [n,C] f64 by element
     -> (mean [S,C] f64 summed in sorted order, count [S] int32)."""

@@ -22,14 +22,13 @@ from the reference's renderer:
   * pixels nothing covers hold `background` (default 100.0; every consumer only needs it above max_depth = 10; aitviewer's own
     far value is not pinned);
   * the `_depth.jpg` colour-map preview (:97-101) is not written;
-  * without a principal point (the reference's wo_cxcy=True) cx = W / 2, cy = H / 2, which is what rig_project assumes.
+  * without a principal point (the reference's wo_cxcy=True) cx = W / 2, cy = H / 2 (_rig.py), which rig_project assumes.
 Coverage has inclusive edges and no back-face culling; depth is perspective-correct in f64 and rounded to f32; the nearest
 depth wins a pixel, ties go to the lower face index.  The result is an integer minimum per pixel: bitwise reproducible and
 independent of small_max, of views_in_flight and of the sharding over ranks.
 """
 from __future__ import annotations
 
-import ctypes
 import os
 import threading
 import warnings
@@ -40,7 +39,7 @@ from typing import Callable, List, Optional
 import numpy as np
 import torch
 
-from . import _host, _lib, formats, sweep
+from . import _host, _lib, _meshargs as _ma, _rig, formats, sweep
 from ._lib import ptr as _p
 
 ZNEAR = 0.01
@@ -61,28 +60,8 @@ class MeshDepthView:
 
 
 def cam16(extr, intr, cx: float, cy: float):
-    """The [host] camera block of gsr_mesh_depth_view: sweep.cam14's 14 doubles and the principal point."""
-    return (ctypes.c_double * 16)(*sweep.cam14(np.asarray(extr), np.asarray(intr)), float(cx), float(cy))
-
-
-def _device_of(verts, device):
-    if device is None:
-        device = verts.device if isinstance(verts, torch.Tensor) and verts.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError("mesh_depth needs a GPU")
-    return dev
-
-
-def _upload(verts, faces, dev):
-    """(verts [V,3] f64, faces [F,3] int32) contiguous on `dev`."""
-    v = torch.as_tensor(np.asarray(verts) if not isinstance(verts, torch.Tensor) else verts).detach().to(dev, torch.float64).contiguous()
-    f = torch.as_tensor(np.asarray(faces) if not isinstance(faces, torch.Tensor) else faces).to(dev, torch.int32).contiguous()
-    if v.dim() != 2 or v.shape[1] != 3:
-        raise ValueError(f"verts must be [V,3], got {tuple(v.shape)}")
-    if f.dim() != 2 or f.shape[1] != 3:
-        raise ValueError(f"faces must be [F,3], got {tuple(f.shape)}")
-    return v, f
+    """The [host] camera block of gsr_mesh_depth_view: sweep.cam14's 14 doubles and the principal point (of a Rig: Rig.cam16)."""
+    return _rig.camera_block(extr, intr, (cx, cy))
 
 
 def _check_out(out: MeshDepthView, H: int, W: int, dev, return_faces: bool) -> None:
@@ -113,13 +92,6 @@ def _view(lib, v, f, block, H: int, W: int, znear: float, background: float, ret
     return MeshDepthView(out.depth, out.mask, face, out.n_clipped)
 
 
-def _principal(principal_point, H: int, W: int):
-    if principal_point is None:
-        return W / 2, H / 2
-    cx, cy = principal_point
-    return float(cx), float(cy)
-
-
 @torch.no_grad()
 def mesh_depth_view(verts, faces, extr, intr, H: int, W: int, *, principal_point=None, znear: float = ZNEAR,
                     background: float = BACKGROUND, return_faces: bool = False, small_max: int = 0,
@@ -131,9 +103,8 @@ def mesh_depth_view(verts, faces, extr, intr, H: int, W: int, *, principal_point
     H, W = int(H), int(W)
     if H <= 0 or W <= 0:
         raise ValueError(f"image size must be positive, got {(H, W)}")
-    dev = _device_of(verts, device)
-    v, f = _upload(verts, faces, dev)
-    block = cam16(extr, intr, *_principal(principal_point, H, W))
+    v, f = _ma.mesh_on(verts, faces, _host.resolve_device(device, verts, what="mesh_depth"))
+    block = cam16(extr, intr, *_rig.principal_point(H, W, principal_point))
     with _host.on_device(v.device):
         return _view(_lib.load(), v, f, block, H, W, znear, background, return_faces, small_max, out)
 
@@ -142,29 +113,23 @@ def mesh_depth_view(verts, faces, extr, intr, H: int, W: int, *, principal_point
 def render_mesh_depth(verts, faces, rig: dict, sink: Callable[[int, MeshDepthView], None], *, use_principal_point: bool = False,
                       views_in_flight: int = 2, rank: Optional[int] = None, world: Optional[int] = None, znear: float = ZNEAR,
                       background: float = BACKGROUND, return_faces: bool = False, small_max: int = 0, device=None) -> List[int]:
-    """The mesh over the cameras of `rig` (the `cmr` dict of warp.py / topology.rig_from_cameras: intrinsics [C,3,3],
-    extrinsics [C,4,4], shape [C,2] = (H, W)).  The mesh is uploaded once; per camera i of this rank's shard
+    """The mesh over the cameras of `rig` (the `cmr` dict, _rig.py).  The mesh is uploaded once; per camera i of this rank's shard
     (sweep.camera_shard) the view is rendered and handed to sink(i, view), so a rig of 160 cameras never holds 160 images.
-    With views_in_flight > 1 the cameras run on that many streams (sweep.run_shard) and sink is called from the worker's thread
+    With views_in_flight > 1 the cameras run on that many streams (sweep.run_cameras) and sink is called from the worker's thread
     under the worker's stream: what it enqueues there is ordered after the render, and it must be safe to call from several
     threads.  (With an empty sink a second view in flight gains nothing: a view is some 45 us of device work at 1080p, DESIGN
     section 8 f13; more than one is for a sink that copies or writes.)  use_principal_point: read (cx, cy) from
     intrinsics[i][:2, 2] (the reference's wo_cxcy=False) instead of (W / 2, H / 2).  Returns the camera indices of the shard."""
     lib = _lib.load()
-    dev = _device_of(verts, device)
-    v, f = _upload(verts, faces, dev)
-    shape = np.asarray(rig["shape"])
-    intr, extr = np.asarray(rig["intrinsics"], np.float64), np.asarray(rig["extrinsics"], np.float64)
-    mine = sweep.camera_shard(int(shape.shape[0]), rank, world)
+    rig = _rig.Rig.of(rig)
+    dev = _host.resolve_device(device, verts, what="mesh_depth")
+    v, f = _ma.mesh_on(verts, faces, dev)
+    mine = sweep.camera_shard(rig.C, rank, world)
 
-    def work(_t, j):
-        i = mine[j]
-        H, W = int(shape[i][0]), int(shape[i][1])
-        pp = (intr[i][0, 2], intr[i][1, 2]) if use_principal_point else None
-        sink(i, _view(lib, v, f, cam16(extr[i], intr[i], *_principal(pp, H, W)), H, W, znear, background, return_faces, small_max, None))
+    def per_camera(_j, i):
+        sink(i, _view(lib, v, f, rig.cam16(i, use_principal_point), *rig.hw(i), znear, background, return_faces, small_max, None))
 
-    with _host.on_device(v.device):      # (for the plain loop; the pipelines' workers set their device themselves)
-        sweep.run_shard(work, len(mine), views_in_flight, dev)
+    sweep.run_cameras(mine, per_camera, views_in_flight, dev)
     return mine
 
 
@@ -193,13 +158,10 @@ def render_mesh_depth_files(camera_path, mesh_folder, gstar_folder, test=False, 
     covered), label = '_humanrf' or ''.  The `_depth.jpg` preview is not written.  The compressed npz is host-bound: the files
     are written by a pool of at most 8 threads, at most twice that many images waiting, while the GPU renders on.  Warns once
     per frame whose mesh has faces at or behind `znear`."""
-    info = dict(np.load(os.fspath(camera_path)))
-    shape = np.array(info["shape"], dtype=np.int32)
-    ids, intr, extr = np.asarray(info["ids"]), np.array(info["intrinsics"], np.float64), np.array(info["extrinsics"], np.float64)
-    if test:
-        ids, intr, extr = ids[TEST_CAMERAS], intr[TEST_CAMERAS], extr[TEST_CAMERAS]
-    C = len(ids)
-    rig = {"intrinsics": intr, "extrinsics": extr, "shape": shape[:C]}
+    rig, info = _rig.Rig.load(camera_path)
+    sel = TEST_CAMERAS if test else slice(None)
+    C = len(np.asarray(info["ids"])[sel])
+    rig = _rig.Rig.of({"intrinsics": rig.intr[sel], "extrinsics": rig.extr[sel], "shape": rig.shape[:C]})
     label = "_humanrf" if from_humanrf else ""
     scale = 1.0 if from_humanrf else 0.001
     frames = _mesh_paths(mesh_folder, from_humanrf, mesh_res, int(frame_0), int(frame_end), int(interval))

@@ -8,14 +8,13 @@ GPU; `nccl` = RCCL on ROCm, `gloo` for the CPU tests): rank r renders cameras r,
 per-view rows are brought together with one all_gather.  There is no other communication."""
 from __future__ import annotations
 
-import ctypes
 from typing import Callable, List, Optional, Sequence
 
 import numpy as np
 import torch
 import torch.distributed as tdist
 
-from . import dist as gdist
+from . import _host, _rig, dist as gdist
 
 
 def camera_shard(n_cameras: int, rank: Optional[int] = None, world: Optional[int] = None) -> List[int]:
@@ -50,10 +49,8 @@ def gather_rows(local_rows: torch.Tensor, n_total: int, rank: Optional[int] = No
 
 def cam14(extr: np.ndarray, intr: np.ndarray):
     """The [host] camera block of gsr_topo_view / gsr_warp_view from one camera of the reference's `cmr`: the COLMAP
-    world-to-camera rotation (row-major) and translation, fx, fy."""
-    vals = list(np.asarray(extr[:3, :3], np.float64).reshape(-1)) + list(np.asarray(extr[:3, 3], np.float64)) + \
-        [float(intr[0, 0]), float(intr[1, 1])]
-    return (ctypes.c_double * 14)(*vals)
+    world-to-camera rotation (row-major) and translation, fx, fy (_rig.camera_block; of a Rig: Rig.cam14(i))."""
+    return _rig.camera_block(extr, intr)
 
 
 def run_shard(work: Callable, n: int, views_in_flight: int, dev) -> None:
@@ -66,6 +63,13 @@ def run_shard(work: Callable, n: int, views_in_flight: int, dev) -> None:
     else:
         for j in range(n):
             work(0, j)
+
+
+def run_cameras(indices: Sequence[int], per_camera: Callable[[int, int], None], views_in_flight: int, dev) -> None:
+    """per_camera(j, i) for j, i in enumerate(indices), the cameras of one rank's shard (camera_shard) or a part of it, through
+    run_shard with `dev` current.  (The guard is for the plain loop: the pipelines' workers set their device themselves.)"""
+    with _host.on_device(dev):
+        run_shard(lambda _t, j: per_camera(j, indices[j]), len(indices), views_in_flight, dev)
 
 
 class ForwardSweep:

@@ -27,16 +27,15 @@ from typing import Callable, Optional, Sequence, Union
 import numpy as np
 import torch
 
-from . import _host, _lib, sweep
+from . import _host, _lib, _rig, knn, sweep
 from ._lib import ptr as _p
 
 MAX_DEPTH = 10.0   # refined_mesh.py:24
 
 
 def rig_from_cameras(cameras: Sequence) -> dict:
-    """The reference's `cmr` layout (rgb_cameras.npz) for NerfCameras: intrinsics [C,3,3] (fx, fy and the principal point in
-    pixels, which the reference's projection ignores),
-    extrinsics [C,4,4] COLMAP world-to-camera, shape [C,2] = (H, W), all float64 numpy.  The extrinsic is the inverse of
+    """The reference's `cmr` dict (rgb_cameras.npz; the layout: _rig.py) for NerfCameras, float64 numpy and int64 shape; the
+    reference's projection ignores the principal point in the intrinsics.  The extrinsic is the inverse of
     NerfCamera.rasterizer_camera()'s axis flip: the world-to-camera matrix its view matrix holds, in double."""
     C = len(cameras)
     intr = np.zeros((C, 3, 3))
@@ -130,7 +129,7 @@ def detect_topology_errors(model, cameras: Sequence, gt_depth: Union[torch.Tenso
     dev = model.device
     if dev.type != "cuda":
         raise RuntimeError("detect_topology_errors needs the model on a GPU")
-    rig = rig_from_cameras(cameras) if rig is None else rig
+    rig = _rig.Rig.of(rig_from_cameras(cameras) if rig is None else rig)
     C = len(cameras)
     verts = model._points.detach().float().contiguous()
     V = int(verts.shape[0])
@@ -150,20 +149,19 @@ def detect_topology_errors(model, cameras: Sequence, gt_depth: Union[torch.Tenso
         g = g[..., 0] if g.dim() == 3 else g
         return g.to(device=dev, dtype=torch.float32).contiguous()
 
-    def work(_t, j):
-        i = mine[j]
+    def per_camera(j, i):
         render, surface = renders(cameras[i])
         g = gt_of(i)
-        H, W = int(rig["shape"][i][0]), int(rig["shape"][i][1])
+        H, W = rig.hw(i)
         if tuple(g.shape) != (H, W) or tuple(render.shape) != (H, W):
             raise ValueError(f"camera {i}: GT depth {tuple(g.shape)} / render {tuple(render.shape)} vs rig shape {(H, W)}")
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         _lib.check(lib.gsr_topo_view(H, W, V, _p(verts), _p(g), _p(render), _p(surface), float(max_depth),
-                                     sweep.cam14(rig["extrinsics"][i], rig["intrinsics"][i]), _p(ws), _p(local[j]), _host.stream_of(verts)),
+                                     rig.cam14(i), _p(ws), _p(local[j]), _host.stream_of(verts)),
                    "gsr_topo_view")
 
     with _host.on_device(verts.device):
-        sweep.run_shard(work, len(mine), views_in_flight, dev)
+        sweep.run_cameras(mine, per_camera, views_in_flight, dev)
         table = sweep.gather_rows(local, C, rank, world)
 
         # ---- over the rig (every rank, same table, same bits)
@@ -182,15 +180,7 @@ def detect_topology_errors(model, cameras: Sequence, gt_depth: Union[torch.Tenso
         _lib.check(lib.gsr_topo_propagate(V, _p(off), _p(nbr), sweeps, _p(value), _p(valid), _p(prop), _p(tmp), _p(va), _p(vb), stream),
                    "gsr_topo_propagate")
 
-        vmin = verts.amin(0).contiguous()
-        keys = torch.empty(V, dtype=torch.int64, device=dev)
-        flags = torch.zeros(1, dtype=torch.int32, device=dev)
-        _lib.check(lib.gsr_topo_voxel_keys(V, _p(verts), _p(vmin), float(voxel_size), _p(keys), _p(flags), stream), "gsr_topo_voxel_keys")
-        skeys, order = torch.sort(keys, stable=True)
-        change = torch.ones(V, dtype=torch.int64, device=dev)
-        change[1:] = (skeys[1:] != skeys[:-1]).long()
-        vid = torch.cumsum(change, 0)
-        vid -= 1
+        vmin, skeys, order, vid, _head, flags = knn.voxel_groups(lib, verts, voxel_size, stream)
         vox_ws = torch.empty(int(lib.gsr_topo_voxel_workspace_bytes(V)) // 4 + 4, dtype=torch.float32, device=dev)
         vox_value = torch.empty(V, dtype=torch.float64, device=dev)
         interp = torch.empty(V, dtype=torch.float64, device=dev)

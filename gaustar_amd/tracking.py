@@ -59,11 +59,7 @@ class SurfaceTracker:
     with (tracking_util.py:48).  face_bary=None puts every point at its face's centre, np.ones(3) / 3 (:50)."""
 
     def __init__(self, face_ids, face_bary=None, device="cuda"):
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise ValueError("a SurfaceTracker lives on a GPU")
-        if dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
+        dev = _host.resolve_device(device, what="a SurfaceTracker", exc=ValueError)
         ids = torch.as_tensor(np.array(face_ids) if isinstance(face_ids, np.ndarray) else face_ids)      # (a copy: it may be read-only)
         if ids.dim() != 1 or ids.dtype not in (torch.int32, torch.int64):
             raise ValueError("face_ids must be [K] int32 or int64")

@@ -41,7 +41,7 @@ from typing import Callable, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _host, _lib, formats, sweep
+from . import _host, _lib, _meshargs as _ma, _rig, formats, sweep
 from ._lib import ptr as _p
 
 PROP_SWEEPS = 20     # mesh_vert_propagate(max_ite=20) (warp_mesh.py:384, :133)
@@ -117,28 +117,21 @@ def warp_mesh(verts, faces, rig: dict, frames: Callable[[int], tuple], cfg: Warp
               views_in_flight: int = 2, rank: Optional[int] = None, world: Optional[int] = None,
               return_stages: bool = False, device=None) -> MeshWarp:
     """warp_mesh_using_flow's computation (warp_mesh.py:259-397) for the mesh (verts [V,3], faces [F,3]; numpy or torch) seen
-    by the cameras of `rig` (the `cmr` dict: intrinsics [C,3,3], extrinsics [C,4,4] COLMAP world-to-camera, shape [C,2] =
-    (H, W)).  frames(i) -> (flow_f, flow_b, depth_cur, depth_next) for camera i, on any device: the raw RAFT flows [h,w,2]
-    in (x, y) order and the depth maps [H,W] of frames f and f + interval; called once per camera of this rank's shard.
-    pad: (top, bottom, left, right) of the flows (pad.txt), or None."""
+    by the cameras of `rig` (the `cmr` dict, _rig.py).  frames(i) -> (flow_f, flow_b, depth_cur, depth_next) for camera i, on
+    any device: the raw RAFT flows [h,w,2] in (x, y) order and the depth maps [H,W] of frames f and f + interval; called once
+    per camera of this rank's shard.  pad: (top, bottom, left, right) of the flows (pad.txt), or None."""
     if cfg.post_processing not in ("mesh", "voxel"):
         raise ValueError(f"warp_mesh: post_processing={cfg.post_processing!r} is not implemented (only 'mesh' and 'voxel')")
     lib = _lib.load()
-    if device is None:
-        device = verts.device if isinstance(verts, torch.Tensor) and verts.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError("warp_mesh needs a GPU")
+    rig = _rig.Rig.of(rig)
+    dev = _host.resolve_device(device, verts, what="warp_mesh")
     from . import meshes
-    v = torch.as_tensor(np.asarray(verts) if not isinstance(verts, torch.Tensor) else verts).to(dev, torch.float64).contiguous()
-    if v.dim() != 2 or v.shape[1] != 3:
-        raise ValueError(f"verts must be [V,3], got {tuple(v.shape)}")
+    v = _ma.verts_on(verts, dev)
     V = int(v.shape[0])
-    ft = faces if isinstance(faces, torch.Tensor) and faces.device == dev and faces.dtype == torch.long else \
-        torch.as_tensor(np.asarray(faces) if not isinstance(faces, torch.Tensor) else faces).to(dev, torch.long)
-    topo = meshes.MeshTopology.of(ft, V)        # (cached on a faces tensor that is passed again)
+    # (upload passes a long tensor on `dev` through: MeshTopology.of caches on a faces tensor that is passed again)
+    topo = meshes.MeshTopology.of(_ma.upload(faces, dev, torch.long), V)
     f, F = topo.faces, topo.F
-    C = int(np.asarray(rig["shape"]).shape[0])
+    C = rig.C
     fbuf = torch.empty(max(F, 1), 6, dtype=torch.float64, device=dev)
     normals = torch.empty(V, 3, dtype=torch.float64, device=dev)
 
@@ -154,17 +147,16 @@ def warp_mesh(verts, faces, rig: dict, frames: Callable[[int], tuple], cfg: Warp
             t = t[..., 0]
         return t.to(device=dev, dtype=torch.float32).contiguous()
 
-    def work(_t, j):
-        i = mine[j]
+    def per_camera(j, i):
         ff, fb, dc, dn = (to_dev(x, n, i) for x, n in zip(frames(i), ("flow_f", "flow_b", "depth_cur", "depth_next")))
-        H, W = int(rig["shape"][i][0]), int(rig["shape"][i][1])
+        H, W = rig.hw(i)
         if tuple(dc.shape) != (H, W) or tuple(dn.shape) != (H, W):
             raise ValueError(f"camera {i}: depth {tuple(dc.shape)} / {tuple(dn.shape)} vs rig shape {(H, W)}")
         if ff.dim() != 3 or ff.shape[2] != 2 or ff.shape != fb.shape:
             raise ValueError(f"camera {i}: flows must be [h,w,2] of one shape, got {tuple(ff.shape)} / {tuple(fb.shape)}")
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         _lib.check(lib.gsr_warp_view(H, W, V, _p(v), _p(normals), _p(ff), _p(fb), _pad6(ff, pad), _p(dc), _p(dn),
-                                     sweep.cam14(rig["extrinsics"][i], rig["intrinsics"][i]), params, _p(ws), _p(local[j]),
+                                     rig.cam14(i), params, _p(ws), _p(local[j]),
                                      _host.stream_of(v)), "gsr_warp_view")
 
     with _host.on_device(v.device):
@@ -172,7 +164,7 @@ def warp_mesh(verts, faces, rig: dict, frames: Callable[[int], tuple], cfg: Warp
         vf_off, vf_ent = topo.vertex_face_csr
         _lib.check(lib.gsr_vertex_normals(V, F, _p(v), _p(f), _p(vf_off), _p(vf_ent), _p(fbuf), _p(normals), _host.stream_of(v)),
                    "gsr_vertex_normals")
-        sweep.run_shard(work, len(mine), views_in_flight, dev)
+        sweep.run_cameras(mine, per_camera, views_in_flight, dev)
         table = sweep.gather_rows(local, C, rank, world)
 
         # ---- over the rig (every rank, same table, same bits)
@@ -217,7 +209,6 @@ def _voxel_interpolate(lib, v, move, valid, cfg: WarpConfig, stream) -> torch.Te
     """warp_mesh.py:368-371: build_voxel_from_pc over the observed vertices and interpolate_in_voxel for every vertex ->
     [V,3] f64.  Reads the device twice (the observed vertices, the number of voxels)."""
     from . import knn
-    dev = v.device
     vs = float(cfg.voxel_size)
     sel = torch.nonzero(valid).reshape(-1)
     n = int(sel.shape[0])
@@ -225,14 +216,7 @@ def _voxel_interpolate(lib, v, move, valid, cfg: WarpConfig, stream) -> torch.Te
         raise ValueError("warp_mesh: post_processing='voxel' found no vertex seen by min_observe cameras: there is no voxel")
     v32 = v.float().contiguous()
     pts = v32[sel].contiguous()
-    vmin = pts.amin(0).contiguous()
-    keys = torch.empty(n, dtype=torch.int64, device=dev)
-    flags = torch.zeros(1, dtype=torch.int32, device=dev)
-    _lib.check(lib.gsr_topo_voxel_keys(n, _p(pts), _p(vmin), vs, _p(keys), _p(flags), stream), "gsr_topo_voxel_keys")
-    skeys, order = torch.sort(keys, stable=True)
-    head = torch.ones(n, dtype=torch.bool, device=dev)
-    head[1:] = skeys[1:] != skeys[:-1]
-    vid = torch.cumsum(head.long(), 0) - 1
+    vmin, skeys, order, vid, head, flags = knn.voxel_groups(lib, pts, vs, stream)
     n_vox, overflow = (int(x) for x in torch.stack([vid[-1] + 1, flags[0].long()]).cpu())
     if overflow:
         raise ValueError(f"the observed vertices span more than 2^{VOXEL_BITS} voxels of {vs} along an axis")
@@ -285,10 +269,8 @@ def warp_mesh_using_flow(mesh_path, data_root, work_root, f_idx, interval=1, cmr
     the function); with cfg.post_processing = 'voxel' warp_voxel.obj is written instead of warp_mesh_prop.obj (:373-376)."""
     if save_inter:
         raise ValueError("warp_mesh_using_flow: save_inter=True is not implemented")
-    if cmr is None:
-        cmr = np.load(data_root + "rgb_cameras.npz")
-    rig = {k: np.asarray(cmr[k]) for k in ("intrinsics", "extrinsics", "shape")}
-    C = int(rig["shape"].shape[0])
+    rig, _info = _rig.Rig.load(data_root + "rgb_cameras.npz" if cmr is None else cmr)
+    C = rig.C
     cfg = WarpConfig() if cfg is None else cfg
     out_dir = work_root + f"{(f_idx + interval):04d}/coarse_mesh/"
     os.makedirs(out_dir, exist_ok=True)
