@@ -14,6 +14,11 @@ def raw_stream(dev_index: int) -> int:
     return torch._C._cuda_getCurrentRawStream(dev_index)
 
 
+def current_stream() -> int:
+    """raw_stream of the current device: for a call made under on_device(the tensors' device)."""
+    return torch._C._cuda_getCurrentRawStream(torch._C._cuda_getDevice())
+
+
 def stream_of(t: torch.Tensor) -> int:
     """raw_stream of the device tensor `t` is on: for a worker that is handed tensors and no device."""
     return torch._C._cuda_getCurrentRawStream(t.device.index)

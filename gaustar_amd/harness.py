@@ -22,8 +22,9 @@ import numpy as np
 import torch
 from torch import nn
 
-from . import producers, rasterizer as _rasterizer, scene
+from . import producers, refine_step as _refine_step, scene
 from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer
+from .refine_step import RenderJob, RenderParams, _PlainCtx, _RenderMeshBound  # noqa: F401 (the last two: their old home)
 
 BARY_COORDS = {  # sugar_model.py:186-226
     1: [[1 / 3, 1 / 3, 1 / 3]],
@@ -121,123 +122,6 @@ def nerf_camera_from_scene(cam: scene.Camera, znear: float = 1e-4, zfar: float =
     return NerfCamera(c2w=c2w[:3, :], fx=fx, fy=fy, width=cam.W, height=cam.H, znear=znear, zfar=zfar)
 
 
-class _PlainCtx:
-    """Stand-in for an autograd context: lets SurfaceGaussians.rgbd_step run the Functions' forward / backward bodies directly."""
-    __slots__ = ("needs_input_grad", "saved_tensors", "__dict__")
-
-    def __init__(self, needs_input_grad):
-        self.needs_input_grad, self.saved_tensors = needs_input_grad, ()
-
-    def save_for_backward(self, *tensors):
-        self.saved_tensors = tensors
-
-    def mark_non_differentiable(self, *tensors):
-        pass
-
-    def set_materialize_grads(self, value):
-        pass
-
-
-class _RenderMeshBound(torch.autograd.Function):
-    """A render of mesh-bound Gaussians as ONE autograd node: the model's parameters in, the image out.  Forward = mesh
-    producer -> colour producer (coefficients read from `_sh_coordinates_dc` / `_sh_coordinates_rest` where they live,
-    sigmoid of the densities from the same kernel) -> rasterizer; backward = the three backward calls in reverse, the
-    colour producer's gradient w.r.t. the positions added in place to the rasterizer's.  The same kernels on the same
-    numbers as the composition of autograd nodes in render_image_gaussian_rasterizer -- what goes away is what autograd puts
-    between them per iteration at config-C size: torch.cat of the coefficients and the two copies that split its gradient
-    (53 MB each way), sigmoid and its backward, the add of the two position gradients, the zero fill of the screen-space
-    gradient carrier, and five graph nodes' worth of host work (tools/window_phases.py)."""
-
-    @staticmethod
-    def forward(ctx, verts, raw_scales, raw_complex, densities, sh_dc, sh_rest, delta_t, delta_r, cfg):
-        dev = verts.device
-        f32 = lambda t: None if t is None else _rasterizer._dev_f32(t.detach(), dev)
-        v, rs, rc, dens, dc, rest, dt, dr = (f32(t) for t in (verts, raw_scales, raw_complex, densities, sh_dc, sh_rest, delta_t, delta_r))
-        st = cfg["settings"]
-        D, M = cfg["sh_levels"] - 1, 1 + int(rest.size(1))
-        view = st.viewmatrix if cfg["depth_channels"] else None
-        # A sharded optimiser may have left the all-gather of some parameters in flight (dist.ShardedAdam(gather_first=...)):
-        # each producer's inputs are fenced right before it is launched, so the mesh producer runs under the SH buckets' gather
-        fence = getattr(cfg.get("sink"), "wait_params", None)
-        p_verts, p_rs, p_rc, p_dens, p_dc, p_rest, p_dt, p_dr = cfg["params"]
-        if fence is not None:
-            fence((p_verts, p_rs, p_rc, p_dt, p_dr))
-        need_bwd = any(ctx.needs_input_grad) and cfg.get("grad", True)
-        # (without a gradient sink the backward's vertex-gradient accumulator is made here and cleared by the forward's launch)
-        ctx.d_verts = torch.empty_like(v) if need_bwd and ctx.needs_input_grad[0] and cfg.get("sink") is None else None
-        points, scaling, quats = producers._mesh_forward_raw(v, cfg["faces"], cfg["bary"], rs, rc, cfg["thickness"], cfg["lo"],
-                                                             cfg["hi"], dt, dr, clear=ctx.d_verts)
-        if fence is not None:
-            fence((p_dc, p_rest, p_dens))
-        colors, opac = producers._sh_forward_raw(points, st.campos, dc, rest, D, M, view, cfg["depth_channels"], dens)
-        box = []
-        out = _rasterizer.rasterize_gaussians_native(
-            st.bg, points, colors, opac, scaling, quats, st.scale_modifier, None, st.viewmatrix, st.projmatrix, st.tanfovx,
-            st.tanfovy, st.image_height, st.image_width, None, 0, st.campos, st.prefiltered, st.debug, need_backward=need_bwd,
-            scratch_box=box)
-        num_rendered, color, radii, geom, binning, img, _max_tile, num_segments = out
-        ctx.save_for_backward(v, rs, rc, dr, dc, rest, points, scaling, quats, colors, opac, radii, geom, binning, img)
-        ctx.cfg, ctx.counts = cfg, (num_rendered, num_segments, D, M, dt is not None, tuple(densities.shape))
-        ctx.zeroed_scratch = box[0] if box else None
-        ctx.mark_non_differentiable(radii)
-        ctx.set_materialize_grads(False)
-        return color, radii
-
-    @staticmethod
-    def backward(ctx, grad_color, _):
-        if grad_color is None:
-            return (None,) * 9
-        v, rs, rc, dr, dc, rest, points, scaling, quats, colors, opac, radii, geom, binning, img = ctx.saved_tensors
-        cfg, (num_rendered, num_segments, D, M, has_dt, dens_shape) = ctx.cfg, ctx.counts
-        st = cfg["settings"]
-        zeroed, ctx.zeroed_scratch = ctx.zeroed_scratch, None
-        _dm2d, d_colors, d_opac, d_points, _dcov, _dsh, d_scaling, d_quats = _rasterizer.rasterize_gaussians_backward_native(
-            st.bg, points, radii, colors, scaling, quats, st.scale_modifier, None, st.viewmatrix, st.projmatrix, st.tanfovx,
-            st.tanfovy, grad_color, None, 0, st.campos, geom, num_rendered, binning, img, st.debug, num_segments=num_segments,
-            zeroed_scratch=zeroed)
-        view = st.viewmatrix if cfg["depth_channels"] else None
-        # A gradient sink (dist.ShardedAdam: views of its flat gradient buffer) takes the parameter gradients where the
-        # reduce-scatter reads them, and hears about the colour producer's -- 70 % of the bytes -- BEFORE the mesh producer's
-        # backward is launched, so their buckets leave while that one still runs.  Only parameters without a gradient yet.
-        sink, params = cfg.get("sink"), cfg["params"]
-        views = sink.grad_views() if sink is not None else {}
-        # (accepts(): first delivery of this step only -- a second render under the same loss goes through autograd's own addition)
-        buf = lambda p: views.get(id(p)) if (p is not None and sink is not None and sink.accepts(p)) else None
-        p_verts, p_rs, p_rc, p_dens, p_dc, p_rest, p_dt, p_dr = params
-        o_dc, o_rest, o_dens = buf(p_dc), buf(p_rest), buf(p_dens)
-        d_dc, d_rest, _, d_dens = producers._sh_backward_raw(points, _rasterizer._dev_f32(st.campos, points.device), dc, rest, D, M,
-                                                             _rasterizer._dev_f32(view, points.device), cfg["depth_channels"], d_colors, opac, d_opac,
-                                                             dpos_inout=d_points, out=(o_dc, o_rest if M > 1 else None, o_dens))
-        # (SurfaceGaussians.rgbd_step(param_reg=...): the parameter regularisers' share lands in the same buffers, before a sink
-        # hears that they are final)
-        hook = cfg.get("sh_grad_hook")
-        if hook is not None:
-            hook(d_dc, d_dens)
-        if sink is not None:
-            sink.written([p for p, o in ((p_dc, o_dc), (p_rest, o_rest if M > 1 else None), (p_dens, o_dens)) if o is not None])
-        o_mesh = (buf(p_verts), buf(p_rs), buf(p_rc), buf(p_dt), buf(p_dr))
-        pre, ctx.d_verts = getattr(ctx, "d_verts", None), None      # (cleared by the forward: good for one backward)
-        cleared = o_mesh[0] is None and pre is not None
-        d_verts, d_rs, d_rc, d_dt, d_dr = producers._mesh_backward_raw(v, cfg["faces"], cfg["bary"], rs, rc, dr, cfg["lo"], cfg["hi"],
-                                                                       has_dt, d_points, d_scaling, d_quats,
-                                                                       out=(pre,) + o_mesh[1:] if cleared else o_mesh, verts_cleared=cleared)
-        # (SurfaceGaussians.rgbd_step(mesh_reg=...): the regulariser's vertex gradient lands in the same buffer, before a sink
-        # hears that the buffer is final)
-        hook = cfg.get("verts_grad_hook")
-        if hook is not None and d_verts is not None:
-            hook(d_verts)
-        hook = cfg.get("delta_grad_hook")
-        if hook is not None and d_dt is not None and d_dr is not None:
-            hook(d_dt, d_dr)
-        if sink is not None:
-            sink.written([p for p, o in zip((p_verts, p_rs, p_rc, p_dt, p_dr), o_mesh) if o is not None and p is not None])
-        # (sink views go back to autograd as FRESH tensor objects: AccumulateGrad adopts an incoming gradient as p.grad only
-        # if nobody else holds that tensor object -- the optimiser's cached views would make it clone all 77 MB instead)
-        new = lambda t, o: t if (t is None or o is None) else t.view(t.shape)
-        return (new(d_verts, o_mesh[0]), new(d_rs, o_mesh[1]), new(d_rc, o_mesh[2]), d_dens.view(dens_shape), new(d_dc, o_dc),
-                new(d_rest, o_rest), new(d_dt, o_mesh[3]), new(d_dr, o_mesh[4]), None)
-
-
 @dataclass
 class PostprocessResult:
     """SurfaceGaussians.postprocess_mesh: the new model, face_mask [F] bool over the old model's faces (True: kept),
@@ -288,7 +172,7 @@ class SurfaceGaussians(nn.Module):
         self.register_buffer("unbind_loss_weight", None, persistent=False)
         self._geom_cache = None
         # optional: an object with grad_views() / written(params) (gaustar_amd.dist.ShardedAdam) that receives the parameter
-        # gradients of render_channels' backward in place -- see _RenderMeshBound.backward
+        # gradients of render_channels' backward in place -- see refine_step.GradHandoff (checked when a render is made)
         self.grad_sink = None
 
     def __getstate__(self):
@@ -895,140 +779,33 @@ class SurfaceGaussians(nn.Module):
         colour channels; bg has one entry per channel) rendered through ONE autograd node (_RenderMeshBound) -- the
         refinement loop's render.  Values and gradients are those of render_image_gaussian_rasterizer / the composition of
         producers.points_rgb_depth, torch.sigmoid and GaussianRasterizer (tests/test_gpu_harness.py)."""
-        cfg = self._channels_cfg(camera, bg, sh_deg, depth_channels, torch.is_grad_enabled())
-        return _RenderMeshBound.apply(self._points, self._scales, self._quaternions, self.all_densities, self._sh_coordinates_dc,
-                                      self._sh_coordinates_rest, self._delta_t if self._loose_bind else None,
-                                      self._delta_r if self._loose_bind else None, cfg)
+        job = RenderJob(self, camera, bg, sh_deg, depth_channels, torch.is_grad_enabled())
+        return _RenderMeshBound.apply(*job.params, job)
 
-    def _channels_cfg(self, camera: NerfCamera, bg: torch.Tensor, sh_deg: Optional[int], depth_channels: int, grad: bool):
-        """What _RenderMeshBound needs besides the parameters (render_channels, rgbd_step)."""
-        if depth_channels not in (0, 1, 3):
-            raise ValueError("depth_channels must be 0, 1 or 3")
-        sh_deg = self.sh_levels - 1 if sh_deg is None else int(sh_deg)
-        settings, _view, _campos = self._settings(camera, bg, 0)
-        producers._check_faces(self._surface_mesh_faces, int(self._points.shape[0]))
-        if self._surface_mesh_faces.dtype != torch.int64 or not self._surface_mesh_faces.is_contiguous():
-            # (the one-node render hands the buffer to the kernels as a raw pointer: a strided or int32 replacement of the
-            # registered buffer would be read with the wrong layout)
-            self._surface_mesh_faces = self._surface_mesh_faces.long().contiguous()
-        dev = self.device
-        cfg = {"settings": settings, "faces": self._surface_mesh_faces, "bary": self._bary_rows(), "depth_channels": int(depth_channels),
-               "thickness": self._thickness(),
-               "lo": float("-inf") if self.min_gaussian_scale is None else float(self.min_gaussian_scale),
-               "hi": float("inf") if self.max_gaussian_scale is None else float(self.max_gaussian_scale), "sh_levels": sh_deg + 1,
-               "sink": getattr(self, "grad_sink", None),
-               "grad": bool(grad),   # (Function.forward cannot tell whether the caller runs under no_grad: see rasterizer._CALL)
-               "params": (self._points, self._scales, self._quaternions, self.all_densities, self._sh_coordinates_dc,
-                          self._sh_coordinates_rest, self._delta_t if self._loose_bind else None,
-                          self._delta_r if self._loose_bind else None)}
-        if settings.campos.device != dev or settings.campos.dtype != torch.float32:
-            raise RuntimeError("camera matrices must be float32 tensors on the model's device")
-        if cfg["sink"] is not None and not (hasattr(cfg["sink"], "grad_views") and hasattr(cfg["sink"], "written") and hasattr(cfg["sink"], "accepts")):
-            raise TypeError("grad_sink must provide grad_views(), accepts(p) and written(params) (gaustar_amd.dist.ShardedAdam)")
-        return cfg
+    def render_params(self) -> RenderParams:
+        """The eight tensors a render reads, by name.  The one place that knows: `_delta_t` / `_delta_r` count only while the
+        model is loosely bound."""
+        loose = self._loose_bind
+        return RenderParams(verts=self._points, raw_scales=self._scales, raw_complex=self._quaternions, densities=self.all_densities,
+                            sh_dc=self._sh_coordinates_dc, sh_rest=self._sh_coordinates_rest,
+                            delta_t=self._delta_t if loose else None, delta_r=self._delta_r if loose else None)
 
     def rgbd_step(self, camera: NerfCamera, bg: torch.Tensor, gt_rgb: torch.Tensor, gt_depth: torch.Tensor, max_depth: float,
                   dssim_factor: float = 0.2, depth_factor: float = 1.0, mask_factor: float = 1.0, grad_scale: Optional[torch.Tensor] = None,
                   sh_deg: Optional[int] = None, mesh_reg: Optional[dict] = None, param_reg: Optional[dict] = None):
-        """One refinement iteration's render + image losses + backward WITHOUT an autograd graph: the 4-channel render of
-        render_channels(depth_channels=1), losses.rgb_depth_loss on it and both backward passes, run back to back through the very
-        functions the autograd path runs (the two Functions' forward / backward bodies, called directly); the parameters' `.grad`
-        are set (added to, if present) exactly as `loss.backward()` would.  -> (loss, image, radii), all detached.
-        For loops whose only loss is this one: what it takes out is host time -- two Function.apply, the engine's thread
-        hand-off and graph walk, eight AccumulateGrad nodes -- about a third of an iteration's Python at config-C size, which
-        is what bounds the loop on a slow host (tools/window_phases.py).  grad_scale: a device scalar d(total)/d(loss), default 1.
-        mesh_reg: the surface-mesh regularisers of refine.py:676-706 as keyword arguments of losses.surface_mesh_loss
-        (nc_factor, ref_edge_len, edge_factor, ref_area, area_factor; `topology` defaults to mesh_topology()): their forward
-        and backward run in the same step, their vertex gradient is added to the mesh producer's in its own buffer, and the
-        returned loss is the image losses + their total -- what `(rgb_depth_loss(...) + surface_mesh_loss(...)).backward()`
-        gives.  None (default): the image losses alone, as before.  The same dict also takes the keyword arguments of
-        losses.mesh_smoothness_loss -- laplacian_factor, laplacian_method ("uniform" by default, "cot" or "cotcurv":
-        refine.py:681-683) and area_reg_factor (refine.py:713-718): when one of the two factors is non-zero their forward runs
-        in the same step, their vertex gradient is added to the same buffer after the other regularisers', and their total is
-        added to the returned loss last -- `(rgb_depth_loss + surface_mesh_loss + mesh_smoothness_loss).backward()`.  Without
-        these keys the step is bit for bit what it was.
-        param_reg: the regularisers on the Gaussians' own parameters (refine.py:739-748, :663-669) as the scalar keyword
-        arguments of losses.gaussian_param_loss (factor_t, factor_r, min_opacity -- None switches the opacity term off --,
-        sh_factor) plus optional `pre_sh_dc` (without it there is no SH term) and `weight` (default: unbind_loss_weight).  The
-        tensors are the model's own parameters; the loose-bind terms are on only while is_loose_bind().  Forward and backward
-        run in the same step, the gradients are added in place to the buffers the render's backward fills (before a sink
-        hears of them) and the total to the returned loss.  None (default): the step as before."""
-        from . import losses as _losses
-        with torch.no_grad():
-            cfg = self._channels_cfg(camera, bg, sh_deg, 1, True)
-            params = (self._points, self._scales, self._quaternions, self.all_densities, self._sh_coordinates_dc, self._sh_coordinates_rest,
-                      self._delta_t if self._loose_bind else None, self._delta_r if self._loose_bind else None)
-            rctx = _PlainCtx(tuple(p is not None and p.requires_grad for p in params) + (False,))
-            image, radii = _RenderMeshBound.forward(rctx, *params, cfg)
-            if mesh_reg is not None:
-                kw = dict(mesh_reg)
-                topo = kw.pop("topology", None) or self.mesh_topology()
-                mctx = _PlainCtx((self._points.requires_grad,) + (False,) * 6)
-                reg_total, _reg_parts = _losses._SurfaceMeshLoss.forward(
-                    mctx, self._points, topo, float(kw.pop("nc_factor")), kw.pop("ref_edge_len", None), float(kw.pop("edge_factor", 0.0)),
-                    kw.pop("ref_area", None), float(kw.pop("area_factor", 0.0)))
-                lap_f, lap_m = float(kw.pop("laplacian_factor", 0.0)), kw.pop("laplacian_method", "uniform")
-                areg_f = float(kw.pop("area_reg_factor", 0.0))
-                sctx = None
-                if lap_f != 0.0 or areg_f != 0.0:
-                    if lap_m not in _losses._LAP_METHODS:
-                        raise ValueError("Method should be one of {uniform, cot, cotcurv}")
-                    sctx = _PlainCtx((self._points.requires_grad,) + (False,) * 4)
-                    smooth_total, _smooth_parts = _losses._MeshSmoothnessLoss.forward(sctx, self._points, topo, lap_f, lap_m, areg_f)
-                if kw:
-                    raise TypeError(f"mesh_reg: unexpected keys {sorted(kw)}")
-            if param_reg is not None:
-                kw = dict(param_reg)
-                loose = self._loose_bind
-                min_op, pre = kw.pop("min_opacity", 0.8), kw.pop("pre_sh_dc", None)
-                weight = kw.pop("weight", None)
-                if weight is None:
-                    weight = getattr(self, "unbind_loss_weight", None)
-                p_dt, p_dr = (self._delta_t, self._delta_r) if loose else (None, None)
-                p_dens = self.all_densities if min_op is not None else None
-                p_dc = self._sh_coordinates_dc if pre is not None else None
-                need = lambda p: p is not None and p.requires_grad
-                pctx = _PlainCtx((need(p_dt), need(p_dr), False, False, False, need(p_dens), False, need(p_dc), False, False))
-                preg_total, _preg_parts = _losses._GaussianParamLoss.forward(
-                    pctx, p_dt, p_dr, weight if loose else None, float(kw.pop("factor_t", 100.0)), float(kw.pop("factor_r", 1.0)), p_dens, 0.0 if min_op is None else float(min_op),
-                    p_dc, pre, float(kw.pop("sh_factor", 1.0)))
-                if kw:
-                    raise TypeError(f"param_reg: unexpected keys {sorted(kw)}")
-            lctx = _PlainCtx((True,) + (False,) * 7)
-            loss, _parts = _losses._RGBDepthLoss.forward(lctx, image, gt_rgb, gt_depth, float(dssim_factor), None, float(max_depth),
-                                                        float(depth_factor), float(mask_factor))
-            if grad_scale is None:
-                one = getattr(self, "_one_cache", None)
-                if one is None or one.device != image.device:
-                    one = self._one_cache = torch.ones((), device=image.device)
-                grad_scale = one
-            if mesh_reg is not None:
-                loss = loss + reg_total
-                if sctx is not None:
-                    loss = loss + smooth_total
-                nodes = [(_losses._SurfaceMeshLoss, mctx)] if mctx.saved_tensors else []
-                if sctx is not None and sctx.saved_tensors:
-                    nodes.append((_losses._MeshSmoothnessLoss, sctx))
-                if nodes:
-                    cfg["verts_grad_hook"] = lambda dv: [fn.grad_into(c, grad_scale, dv, 1) for fn, c in nodes]
-            if param_reg is not None:
-                loss = loss + preg_total
-                if pctx.saved_tensors:
-                    on = lambda p, buf: buf if (p is not None and p.requires_grad) else None
-                    cfg["sh_grad_hook"] = lambda d_dc, d_dens: _losses._GaussianParamLoss.grad_into(
-                        pctx, grad_scale, (None, None, on(p_dens, d_dens), on(p_dc, d_dc)), 1)
-                    cfg["delta_grad_hook"] = lambda d_dt, d_dr: _losses._GaussianParamLoss.grad_into(
-                        pctx, grad_scale, (on(p_dt, d_dt), on(p_dr, d_dr), None, None), 1)
-            d_image = _losses._RGBDepthLoss.backward(lctx, grad_scale, None)[0]
-            grads = _RenderMeshBound.backward(rctx, d_image, None)
-            for p, g in zip(params, grads):
-                if p is None or g is None or not p.requires_grad:
-                    continue
-                if p.grad is None:
-                    p.grad = g
-                else:
-                    p.grad.add_(g)
-        return loss, image, radii
+        """One refinement iteration's render + losses + backward WITHOUT an autograd graph: the 4-channel render of
+        render_channels(depth_channels=1), losses.rgb_depth_loss on it, the regularisers asked for and all backward passes, run
+        through the very functions the autograd path runs; the parameters' `.grad` are set (added to, if present) exactly as
+        `loss.backward()` would.  -> (loss, image, radii), all detached.  What it takes out is host time (tools/window_phases.py).
+        grad_scale: a device scalar d(total)/d(loss), default 1.
+        mesh_reg: dict of the keyword arguments of losses.surface_mesh_loss and, optionally, of losses.mesh_smoothness_loss as
+        laplacian_factor / laplacian_method / area_reg_factor.  param_reg: dict of the scalar keyword arguments of
+        losses.gaussian_param_loss, plus optional `pre_sh_dc` and `weight`.  The terms are those functions' (and their defaults
+        refine_step._mesh_reg_terms / _param_reg_terms state); their gradients are added in place to the buffers the render's
+        backward fills, before a sink hears of them; the returned loss is image + surface + smoothness + parameter terms, summed in
+        that order -- what `(rgb_depth_loss(...) + surface_mesh_loss(...) + ...).backward()` gives.  None (default): without."""
+        return _refine_step.rgbd_step(self, camera, bg, gt_rgb, gt_depth, max_depth, dssim_factor, depth_factor, mask_factor,
+                                      grad_scale, sh_deg, mesh_reg, param_reg)
 
     def _bary_rows(self):
         b = getattr(self, "_bary_rows_cache", None)

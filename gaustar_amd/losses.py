@@ -17,10 +17,44 @@ from typing import Optional, Sequence
 import torch
 
 from . import _host, _lib
+from ._host import current_stream as _stream
+from ._lib import ptr as _vp
 
 
-def _stream():
-    return _host.raw_stream(torch._C._cuda_getDevice())
+def at_inputs(node, values, fill=None):
+    """A tuple with one entry per input of node.forward: `values` at the node's differentiable inputs (node.GRAD_AT, in that
+    order), `fill` at the others.  Both a backward's return value and a plain context's needs_input_grad are made here."""
+    out = [fill] * node.N_INPUTS
+    for i, x in zip(node.GRAD_AT, values):
+        out[i] = x
+    return tuple(out)
+
+
+def needs_input_grad(node, *inputs):
+    """What autograd would put into ctx.needs_input_grad, from the node's differentiable inputs in GRAD_AT order."""
+    return at_inputs(node, [t is not None and t.requires_grad for t in inputs], False)
+
+
+def _scratch(n_bytes, n_out, dev):
+    """-> (the workspace, the float32 vector of parts a forward's kernel fills), both uninitialised."""
+    return torch.empty(n_bytes, dtype=torch.uint8, device=dev), torch.empty(n_out, dtype=torch.float32, device=dev)
+
+
+def _finish(ctx, node, parts, saved):
+    """The common tail of the forwards: `saved` is kept only if a backward will ask for it, and the parts vector carries no
+    gradient -- nor gets a zero-filled one per backward (one fill kernel)."""
+    if any(ctx.needs_input_grad[i] for i in node.GRAD_AT):
+        ctx.save_for_backward(*saved)
+    ctx.mark_non_differentiable(parts)
+    ctx.set_materialize_grads(False)
+
+
+def _backward_into_fresh(node, ctx, g_loss):
+    """The backward of a node over the vertices: its grad_into on a fresh buffer."""
+    if not ctx.saved_tensors or g_loss is None:
+        return at_inputs(node, ())
+    grad = node.grad_into(ctx, g_loss, torch.empty_like(ctx.saved_tensors[0]), 0)
+    return at_inputs(node, (grad.to(ctx.in_dtype),))
 
 
 def _chw_view(t: torch.Tensor, what: str) -> torch.Tensor:
@@ -50,12 +84,13 @@ def _scale_ptr(g_loss: torch.Tensor, dev):
     g = g_loss
     if g.dtype != torch.float32 or g.device != dev or g.dim() != 0 or not g.is_contiguous():
         g = g.detach().to(device=dev, dtype=torch.float32).reshape(()).contiguous()
-    return g, ctypes.c_void_p(g.data_ptr())
+    return g, _vp(g)
 
 
 class _L1DSSIM(torch.autograd.Function):
     """Forward: the value pass (gsr_l1_ssim without a gradient buffer).  Backward: gsr_l1_ssim_backward from the workspace the
     value pass left, scaled by the incoming gradient ON THE DEVICE."""
+    N_INPUTS, GRAD_AT = 4, (0,)
 
     @staticmethod
     def forward(ctx, pred, gt, dssim_factor, margin):
@@ -70,23 +105,19 @@ class _L1DSSIM(torch.autograd.Function):
             raise RuntimeError("the margin leaves an empty image")
         dev = p.device
         with _host.on_device(dev):
-            ws = torch.empty(lib.gsr_l1_ssim_workspace_bytes(C, H, W), dtype=torch.uint8, device=dev)
-            out = torch.empty(3, dtype=torch.float32, device=dev)
+            ws, out = _scratch(lib.gsr_l1_ssim_workspace_bytes(C, H, W), 3, dev)
             _lib.check(lib.gsr_l1_ssim(
-                C, H, W, ctypes.c_void_p(p.data_ptr()), p.stride(0), p.stride(1), p.stride(2),
-                ctypes.c_void_p(g.data_ptr()), g.stride(0), g.stride(1), g.stride(2), float(dssim_factor),
-                ctypes.c_void_p(ws.data_ptr()), ctypes.c_void_p(out.data_ptr()), None, 0, 0, 0, _stream()), "gsr_l1_ssim")
-        if ctx.needs_input_grad[0]:
-            ctx.save_for_backward(p_full, g_full, ws)
+                C, H, W, _vp(p), p.stride(0), p.stride(1), p.stride(2),
+                _vp(g), g.stride(0), g.stride(1), g.stride(2), float(dssim_factor),
+                _vp(ws), _vp(out), None, 0, 0, 0, _stream()), "gsr_l1_ssim")
         ctx.cfg = (float(dssim_factor), margin, pred.shape, pred.dtype)
-        ctx.mark_non_differentiable(out)
-        ctx.set_materialize_grads(False)   # no zero-filled "gradient" of the parts vector per backward (one fill kernel)
+        _finish(ctx, _L1DSSIM, out, (p_full, g_full, ws))
         return out[0], out
 
     @staticmethod
     def backward(ctx, g_loss, _g_parts):
         if not ctx.saved_tensors or g_loss is None:
-            return None, None, None, None
+            return at_inputs(_L1DSSIM, ())
         lib = _lib.load()
         p_full, g_full, ws = ctx.saved_tensors
         f, margin, pred_shape, in_dtype = ctx.cfg
@@ -99,10 +130,10 @@ class _L1DSSIM(torch.autograd.Function):
             gv = _crop(grad_full, margin)
             keep, sp = _scale_ptr(g_loss, dev)
             _lib.check(lib.gsr_l1_ssim_backward(
-                C, H, W, ctypes.c_void_p(p.data_ptr()), p.stride(0), p.stride(1), p.stride(2),
-                ctypes.c_void_p(g.data_ptr()), g.stride(0), g.stride(1), g.stride(2), f, ctypes.c_void_p(ws.data_ptr()), sp,
-                ctypes.c_void_p(gv.data_ptr()), gv.stride(0), gv.stride(1), gv.stride(2), _stream()), "gsr_l1_ssim_backward")
-        return grad_full.reshape(pred_shape).to(in_dtype), None, None, None
+                C, H, W, _vp(p), p.stride(0), p.stride(1), p.stride(2),
+                _vp(g), g.stride(0), g.stride(1), g.stride(2), f, _vp(ws), sp,
+                _vp(gv), gv.stride(0), gv.stride(1), gv.stride(2), _stream()), "gsr_l1_ssim_backward")
+        return at_inputs(_L1DSSIM, (grad_full.reshape(pred_shape).to(in_dtype),))
 
 
 def l1_dssim_loss(pred: torch.Tensor, gt: torch.Tensor, dssim_factor: float = 0.2,
@@ -129,6 +160,8 @@ def ssim(img1: torch.Tensor, img2: torch.Tensor, window_size: int = 11, size_ave
 
 
 class _DepthL1(torch.autograd.Function):
+    N_INPUTS, GRAD_AT = 5, (0,)
+
     @staticmethod
     def forward(ctx, pred, gt, max_depth, depth_factor, mask_factor):
         lib = _lib.load()
@@ -141,23 +174,19 @@ class _DepthL1(torch.autograd.Function):
         H, W = (int(v) for v in p.shape)
         dev = p.device
         with _host.on_device(dev):
-            ws = torch.empty(lib.gsr_depth_l1_workspace_bytes(), dtype=torch.uint8, device=dev)
-            out = torch.empty(4, dtype=torch.float32, device=dev)
+            ws, out = _scratch(lib.gsr_depth_l1_workspace_bytes(), 4, dev)
             _lib.check(lib.gsr_depth_l1(
-                H, W, ctypes.c_void_p(p.data_ptr()), p.stride(0), p.stride(1), ctypes.c_void_p(g.data_ptr()),
+                H, W, _vp(p), p.stride(0), p.stride(1), _vp(g),
                 g.stride(0), g.stride(1), float(max_depth), float(depth_factor), float(mask_factor),
-                ctypes.c_void_p(ws.data_ptr()), ctypes.c_void_p(out.data_ptr()), None, 0, 0, _stream()), "gsr_depth_l1")
-        if ctx.needs_input_grad[0]:
-            ctx.save_for_backward(p, g, out)
+                _vp(ws), _vp(out), None, 0, 0, _stream()), "gsr_depth_l1")
         ctx.cfg = (float(max_depth), float(depth_factor), float(mask_factor), pred.dtype)
-        ctx.mark_non_differentiable(out)
-        ctx.set_materialize_grads(False)   # no zero-filled "gradient" of the parts vector per backward (one fill kernel)
+        _finish(ctx, _DepthL1, out, (p, g, out))
         return out[0] + out[1], out
 
     @staticmethod
     def backward(ctx, g_loss, _g_parts):
         if not ctx.saved_tensors or g_loss is None:
-            return None, None, None, None, None
+            return at_inputs(_DepthL1, ())
         lib = _lib.load()
         p, g, out = ctx.saved_tensors
         max_depth, depth_factor, mask_factor, in_dtype = ctx.cfg
@@ -167,10 +196,10 @@ class _DepthL1(torch.autograd.Function):
             grad = torch.empty(H, W, dtype=torch.float32, device=dev)
             keep, sp = _scale_ptr(g_loss, dev)
             _lib.check(lib.gsr_depth_l1_backward(
-                H, W, ctypes.c_void_p(p.data_ptr()), p.stride(0), p.stride(1), ctypes.c_void_p(g.data_ptr()), g.stride(0),
-                g.stride(1), max_depth, depth_factor, mask_factor, ctypes.c_void_p(out.data_ptr()), sp,
-                ctypes.c_void_p(grad.data_ptr()), W, 1, _stream()), "gsr_depth_l1_backward")
-        return grad.to(in_dtype), None, None, None, None
+                H, W, _vp(p), p.stride(0), p.stride(1), _vp(g), g.stride(0),
+                g.stride(1), max_depth, depth_factor, mask_factor, _vp(out), sp,
+                _vp(grad), W, 1, _stream()), "gsr_depth_l1_backward")
+        return at_inputs(_DepthL1, (grad.to(in_dtype),))
 
 
 def depth_mask_l1_loss(pred_depth: torch.Tensor, gt_depth: torch.Tensor, max_depth: float, depth_factor: float = 1.0,
@@ -185,6 +214,7 @@ class _RGBDepthLoss(torch.autograd.Function):
     """l1 + dssim on channels 0-2 and masked depth L1 on channel 3 of ONE [6,H,W] / [4,H,W] render.  Forward: both value
     passes and ONE reduction kernel (gsr_rgb_depth_loss) -> the total as a device scalar.  Backward: the two gradient passes
     write d(total)/d(render), scaled by the incoming gradient on the device, into ONE tensor (channels 4-5 zero)."""
+    N_INPUTS, GRAD_AT = 8, (0,)
 
     @staticmethod
     def forward(ctx, img6, gt_rgb, gt_depth, dssim_factor, margin, max_depth, depth_factor, mask_factor):
@@ -207,30 +237,25 @@ class _RGBDepthLoss(torch.autograd.Function):
         d = x[3]
         Hd, Wd = (int(v) for v in d.shape)
         dev = x.device
-        vp = lambda t: ctypes.c_void_p(t.data_ptr())
         with _host.on_device(dev):
-            ws = torch.empty(lib.gsr_l1_ssim_workspace_bytes(C, H, W), dtype=torch.uint8, device=dev)
+            ws, out = _scratch(lib.gsr_l1_ssim_workspace_bytes(C, H, W), 8, dev)   # {loss, l1, ssim | depth term, mask term, #fg, #bg | total}
             wd = torch.empty(lib.gsr_depth_l1_workspace_bytes(), dtype=torch.uint8, device=dev)
-            out = torch.empty(8, dtype=torch.float32, device=dev)   # {loss, l1, ssim | depth term, mask term, #fg, #bg | total}
             _lib.check(lib.gsr_rgb_depth_loss(
-                C, H, W, vp(p), p.stride(0), p.stride(1), p.stride(2), vp(g), g.stride(0), g.stride(1), g.stride(2),
-                float(dssim_factor), vp(ws), Hd, Wd, vp(d), d.stride(0), d.stride(1), vp(gd), gd.stride(0), gd.stride(1),
-                float(max_depth), float(depth_factor), float(mask_factor), vp(wd), vp(out), _stream()), "gsr_rgb_depth_loss")
-        if ctx.needs_input_grad[0]:
-            ctx.save_for_backward(x, g_full, gd, ws)
+                C, H, W, _vp(p), p.stride(0), p.stride(1), p.stride(2), _vp(g), g.stride(0), g.stride(1), g.stride(2),
+                float(dssim_factor), _vp(ws), Hd, Wd, _vp(d), d.stride(0), d.stride(1), _vp(gd), gd.stride(0), gd.stride(1),
+                float(max_depth), float(depth_factor), float(mask_factor), _vp(wd), _vp(out), _stream()), "gsr_rgb_depth_loss")
         ctx.cfg = (float(dssim_factor), margin, float(max_depth), float(depth_factor), float(mask_factor), img6.dtype)
         # (what backward reads -- the pixel counts the depth gradient divides by -- is the second copy of the eight numbers the
         # reduction kernel leaves in the workspace's tail (include/gsr.h), not the vector handed to the caller: `out` goes out
         # as it is, without the 32-byte device copy that used to separate the two)
         parts = out[:7]
-        ctx.mark_non_differentiable(parts)
-        ctx.set_materialize_grads(False)   # no zero-filled "gradient" of the parts vector per backward (one fill kernel)
+        _finish(ctx, _RGBDepthLoss, parts, (x, g_full, gd, ws))
         return out[7], parts
 
     @staticmethod
     def backward(ctx, g_loss, _g_parts):
         if not ctx.saved_tensors or g_loss is None:
-            return (None,) * 8
+            return at_inputs(_RGBDepthLoss, ())
         lib = _lib.load()
         x, g_full, gd, ws = ctx.saved_tensors
         f, margin, max_depth, depth_factor, mask_factor, in_dtype = ctx.cfg
@@ -239,7 +264,6 @@ class _RGBDepthLoss(torch.autograd.Function):
         d = x[3]
         Hd, Wd = (int(v) for v in d.shape)
         dev = x.device
-        vp = lambda t: ctypes.c_void_p(t.data_ptr())
         with _host.on_device(dev):
             grad6 = torch.empty_like(x, memory_format=torch.contiguous_format)
             if x.size(0) > 4:
@@ -249,12 +273,12 @@ class _RGBDepthLoss(torch.autograd.Function):
             gv, gdv = _crop(grad6[:3], margin), grad6[3]
             keep, sp = _scale_ptr(g_loss, dev)
             _lib.check(lib.gsr_rgb_depth_loss_backward(
-                C, H, W, vp(p), p.stride(0), p.stride(1), p.stride(2), vp(g), g.stride(0), g.stride(1), g.stride(2), f, vp(ws),
-                Hd, Wd, vp(d), d.stride(0), d.stride(1), vp(gd), gd.stride(0), gd.stride(1), max_depth, depth_factor, mask_factor,
-                ctypes.c_void_p(ws.data_ptr() + ws.numel() - 256), sp, vp(gv), gv.stride(0), gv.stride(1), gv.stride(2), vp(gdv),
+                C, H, W, _vp(p), p.stride(0), p.stride(1), p.stride(2), _vp(g), g.stride(0), g.stride(1), g.stride(2), f, _vp(ws),
+                Hd, Wd, _vp(d), d.stride(0), d.stride(1), _vp(gd), gd.stride(0), gd.stride(1), max_depth, depth_factor, mask_factor,
+                ctypes.c_void_p(ws.data_ptr() + ws.numel() - 256), sp, _vp(gv), gv.stride(0), gv.stride(1), gv.stride(2), _vp(gdv),
                 gdv.stride(0), gdv.stride(1), _stream()),
                 "gsr_rgb_depth_loss_backward")
-        return grad6.to(in_dtype), None, None, None, None, None, None, None
+        return at_inputs(_RGBDepthLoss, (grad6.to(in_dtype),))
 
 
 def rgb_depth_loss(render6: torch.Tensor, gt_rgb: torch.Tensor, gt_depth: torch.Tensor, max_depth: float,
@@ -313,6 +337,7 @@ class _SurfaceMeshLoss(torch.autograd.Function):
     """The three surface-mesh regularisers of refine.py:676-706 as ONE autograd node over the vertices.  Forward:
     gsr_mesh_reg_forward (an element pass + a fixed-order reduction) -> {nc, edge, area, total} on the device.  Backward:
     gsr_mesh_reg_backward, one vertex-major launch scaled by the incoming gradient on the device."""
+    N_INPUTS, GRAD_AT = 7, (0,)
 
     @staticmethod
     def forward(ctx, verts, topo, nc_factor, ref_edge_len, edge_factor, ref_area, area_factor):
@@ -322,16 +347,12 @@ class _SurfaceMeshLoss(torch.autograd.Function):
         ra = _mesh_reg_refs(ref_area, topo.F, dev, "ref_area")
         cfg = (float(nc_factor), float(edge_factor), float(area_factor))
         with _host.on_device(dev):
-            ws = torch.empty(lib.gsr_mesh_reg_workspace_bytes(topo.V, topo.F, topo.E, topo.Q), dtype=torch.uint8, device=dev)
-            out = torch.empty(4, dtype=torch.float32, device=dev)
+            ws, out = _scratch(lib.gsr_mesh_reg_workspace_bytes(topo.V, topo.F, topo.E, topo.Q), 4, dev)
             _lib.check(lib.gsr_mesh_reg_forward(
-                topo.V, topo.F, topo.E, topo.Q, _vp(v), _vp(topo.faces), _vp(topo.edges), _vp(topo.pairs), _lib.ptr(re), _lib.ptr(ra), *cfg,
+                topo.V, topo.F, topo.E, topo.Q, _vp(v), _vp(topo.faces), _vp(topo.edges), _vp(topo.pairs), _vp(re), _vp(ra), *cfg,
                 _vp(ws), _vp(out), _stream()), "gsr_mesh_reg_forward")
         ctx.topo, ctx.cfg, ctx.in_dtype = topo, cfg, verts.dtype
-        if ctx.needs_input_grad[0]:
-            ctx.save_for_backward(v, re, ra)
-        ctx.mark_non_differentiable(out)
-        ctx.set_materialize_grads(False)
+        _finish(ctx, _SurfaceMeshLoss, out, (v, re, ra))
         return out[3], out
 
     @staticmethod
@@ -345,21 +366,13 @@ class _SurfaceMeshLoss(torch.autograd.Function):
             keep, sp = _scale_ptr(g_loss, dev)
             _lib.check(lib.gsr_mesh_reg_backward(
                 topo.V, topo.F, topo.E, topo.Q, _vp(v), _vp(topo.faces), _vp(topo.edges), _vp(topo.pairs), _vp(topo.csr_offsets),
-                _vp(topo.csr_entries), _lib.ptr(re), _lib.ptr(ra), *ctx.cfg, sp, _vp(dL_dverts), int(accumulate), _stream()),
+                _vp(topo.csr_entries), _vp(re), _vp(ra), *ctx.cfg, sp, _vp(dL_dverts), int(accumulate), _stream()),
                 "gsr_mesh_reg_backward")
         return dL_dverts
 
     @staticmethod
     def backward(ctx, g_loss, _g_parts):
-        if not ctx.saved_tensors or g_loss is None:
-            return (None,) * 7
-        v = ctx.saved_tensors[0]
-        grad = _SurfaceMeshLoss.grad_into(ctx, g_loss, torch.empty_like(v), 0)
-        return grad.to(ctx.in_dtype), None, None, None, None, None, None
-
-
-def _vp(t):
-    return ctypes.c_void_p(t.data_ptr())
+        return _backward_into_fresh(_SurfaceMeshLoss, ctx, g_loss)
 
 
 def surface_mesh_loss(verts: torch.Tensor, topology, nc_factor: float, ref_edge_len: Optional[torch.Tensor] = None,
@@ -383,6 +396,7 @@ class _MeshSmoothnessLoss(torch.autograd.Function):
     the vertices.  Forward: gsr_mesh_lap_forward -> {laplacian, area_reg, total} on the device, each already multiplied by
     its factor.  Backward: gsr_mesh_lap_backward, one vertex-major launch over the workspace the forward left, scaled by the
     incoming gradient on the device."""
+    N_INPUTS, GRAD_AT = 5, (0,)
 
     @staticmethod
     def forward(ctx, verts, topo, laplacian_factor, method, area_reg_factor):
@@ -391,16 +405,12 @@ class _MeshSmoothnessLoss(torch.autograd.Function):
         cfg = (_LAP_METHODS[method], float(laplacian_factor), float(area_reg_factor))
         lists = (*topo.vertex_neighbours, *topo.vertex_face_csr)
         with _host.on_device(dev):
-            ws = torch.empty(lib.gsr_mesh_lap_workspace_bytes(topo.V, topo.F), dtype=torch.uint8, device=dev)
-            out = torch.empty(3, dtype=torch.float32, device=dev)
+            ws, out = _scratch(lib.gsr_mesh_lap_workspace_bytes(topo.V, topo.F), 3, dev)
             _lib.check(lib.gsr_mesh_lap_forward(
                 topo.V, topo.F, _vp(v), _vp(topo.faces), *[_vp(t) for t in lists], *cfg, _vp(ws), _vp(out), _stream()),
                 "gsr_mesh_lap_forward")
         ctx.topo, ctx.cfg, ctx.in_dtype = topo, cfg, verts.dtype
-        if ctx.needs_input_grad[0]:
-            ctx.save_for_backward(v, ws)
-        ctx.mark_non_differentiable(out)
-        ctx.set_materialize_grads(False)
+        _finish(ctx, _MeshSmoothnessLoss, out, (v, ws))
         return out[2], out
 
     @staticmethod
@@ -420,11 +430,7 @@ class _MeshSmoothnessLoss(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_loss, _g_parts):
-        if not ctx.saved_tensors or g_loss is None:
-            return (None,) * 5
-        v = ctx.saved_tensors[0]
-        grad = _MeshSmoothnessLoss.grad_into(ctx, g_loss, torch.empty_like(v), 0)
-        return grad.to(ctx.in_dtype), None, None, None, None
+        return _backward_into_fresh(_MeshSmoothnessLoss, ctx, g_loss)
 
 
 def mesh_smoothness_loss(verts: torch.Tensor, topology, laplacian_factor: float = 1.0, method: str = "uniform",
@@ -475,6 +481,7 @@ class _GaussianParamLoss(torch.autograd.Function):
     """The regularisers on the Gaussians' own parameters (refine.py:739-740, :743-748, :663-669) as ONE autograd node.
     Forward: gsr_param_reg_forward -> {loose_t, loose_r, opacity, sh, total} on the device.  Backward: gsr_param_reg_backward,
     one elementwise launch scaled by the incoming gradient on the device."""
+    N_INPUTS, GRAD_AT = 10, (0, 1, 5, 7)       # delta_t, delta_r, densities, sh_dc: the order of grad_into's buffers
 
     @staticmethod
     def forward(ctx, delta_t, delta_r, weight, factor_t, factor_r, densities, min_opacity, sh_dc, pre_sh_dc, sh_factor):
@@ -498,18 +505,14 @@ class _GaussianParamLoss(torch.autograd.Function):
         w, w_rs, w_cs = _weight_strides(weight, N, dev)
         cfg = (N, M, w_rs, w_cs, float(factor_t), float(factor_r), float(min_opacity), float(sh_factor))
         with _host.on_device(dev):
-            ws = torch.empty(lib.gsr_param_reg_workspace_bytes(N), dtype=torch.uint8, device=dev)
-            out = torch.empty(5, dtype=torch.float32, device=dev)
+            ws, out = _scratch(lib.gsr_param_reg_workspace_bytes(N), 5, dev)
             _lib.check(lib.gsr_param_reg_forward(
-                N, M, _lib.ptr(dt), _lib.ptr(dr), _lib.ptr(w), w_rs, w_cs, cfg[4], cfg[5], _lib.ptr(dens), cfg[6], _lib.ptr(dc), _lib.ptr(pre), cfg[7],
+                N, M, _vp(dt), _vp(dr), _vp(w), w_rs, w_cs, cfg[4], cfg[5], _vp(dens), cfg[6], _vp(dc), _vp(pre), cfg[7],
                 _vp(ws), _vp(out), _stream()), "gsr_param_reg_forward")
         ctx.cfg = cfg
         ctx.have = tuple(x is not None for x in (dt, dr, w, dens, dc, pre))
         ctx.in_meta = tuple(None if t is None else (t.shape, t.dtype) for t in (delta_t, delta_r, densities, sh_dc))
-        if any(ctx.needs_input_grad):
-            ctx.save_for_backward(*[x for x in (dt, dr, w, dens, dc, pre) if x is not None])
-        ctx.mark_non_differentiable(out)
-        ctx.set_materialize_grads(False)
+        _finish(ctx, _GaussianParamLoss, out, [x for x in (dt, dr, w, dens, dc, pre) if x is not None])
         return out[4], out
 
     @staticmethod
@@ -528,26 +531,25 @@ class _GaussianParamLoss(torch.autograd.Function):
         with _host.on_device(dev):
             keep, sp = _scale_ptr(g_loss, dev)
             _lib.check(lib.gsr_param_reg_backward(
-                N, M, _lib.ptr(dt), _lib.ptr(dr), _lib.ptr(w), w_rs, w_cs, factor_t, factor_r, _lib.ptr(dens), min_opacity, _lib.ptr(dc), _lib.ptr(pre),
-                sh_factor, sp, *[_lib.ptr(b) for b in buffers], int(accumulate), _stream()), "gsr_param_reg_backward")
+                N, M, _vp(dt), _vp(dr), _vp(w), w_rs, w_cs, factor_t, factor_r, _vp(dens), min_opacity, _vp(dc), _vp(pre),
+                sh_factor, sp, *[_vp(b) for b in buffers], int(accumulate), _stream()), "gsr_param_reg_backward")
         return buffers
 
     @staticmethod
     def backward(ctx, g_loss, _g_parts):
         if not ctx.saved_tensors or g_loss is None:
-            return (None,) * 10
+            return at_inputs(_GaussianParamLoss, ())
         it = iter(ctx.saved_tensors)
         dt, dr, _w, dens, dc, pre = (next(it) if h else None for h in ctx.have)
         _N, M, _rs, _cs, factor_t, factor_r, _mo, sh_factor = ctx.cfg
-        need = ctx.needs_input_grad
+        need_dt, need_dr, need_dens, need_dc = (ctx.needs_input_grad[i] for i in _GaussianParamLoss.GRAD_AT)
         # (a term that is off leaves its buffer untouched: no buffer is made for it, its input's gradient is None)
-        srcs = (dt if need[0] and factor_t != 0.0 else None, dr if need[1] and factor_r != 0.0 else None,
-                dens if need[5] else None, dc if need[7] and pre is not None and M > 0 and sh_factor != 0.0 else None)
+        srcs = (dt if need_dt and factor_t != 0.0 else None, dr if need_dr and factor_r != 0.0 else None,
+                dens if need_dens else None, dc if need_dc and pre is not None and M > 0 and sh_factor != 0.0 else None)
         bufs = tuple(None if s is None else torch.empty_like(s) for s in srcs)
         if any(b is not None for b in bufs):
             _GaussianParamLoss.grad_into(ctx, g_loss, bufs, 0)
-        g = [None if b is None else b.view(m[0]).to(m[1]) for b, m in zip(bufs, ctx.in_meta)]
-        return g[0], g[1], None, None, None, g[2], None, g[3], None, None
+        return at_inputs(_GaussianParamLoss, [None if b is None else b.view(m[0]).to(m[1]) for b, m in zip(bufs, ctx.in_meta)])
 
 
 def gaussian_param_loss(delta_t: Optional[torch.Tensor] = None, delta_r: Optional[torch.Tensor] = None,

@@ -9,11 +9,8 @@ from __future__ import annotations
 import torch
 
 from . import _host, _lib
+from ._host import current_stream as _stream
 from ._lib import ptr as _p
-
-
-def _stream():
-    return _host.raw_stream(torch._C._cuda_getDevice())
 
 
 def _as_f32(t, dev):

@@ -28,7 +28,6 @@ _hs.SurfaceGaussians._settings = timed("  in render4: _settings", _hs.SurfaceGau
 torch.cat = timed("  torch.cat", torch.cat)
 torch.sigmoid = timed("  torch.sigmoid", torch.sigmoid)
 _rz.rasterize_gaussians_backward_native = timed("  in backward: rasterize_gaussians_backward_native", _rz.rasterize_gaussians_backward_native)
-_hs._rasterizer.rasterize_gaussians_backward_native = _rz.rasterize_gaussians_backward_native
 _pr._sh_backward_raw = timed("  in backward: _sh_backward_raw", _pr._sh_backward_raw)
 _pr._mesh_backward_raw = timed("  in backward: _mesh_backward_raw", _pr._mesh_backward_raw)
 _pr._mesh_forward_raw = timed("  in render4: _mesh_forward_raw", _pr._mesh_forward_raw)
