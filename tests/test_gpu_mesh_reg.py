@@ -3,6 +3,7 @@ mesh_normal_consistency, SurfaceGaussians.rgbd_step(mesh_reg=...)) against close
 torch restatement of pytorch3d's algorithm (tests/mesh_reg_ref.py) and the autograd composition refine.py:681-706 builds."""
 import math
 
+import numpy as np
 import pytest
 import torch
 
@@ -96,14 +97,31 @@ def test_gradient_invariances_config_c_mesh(hip_lib):
             assert abs(float((x * g).sum())) <= 1e-5 * tot                                  # scale: NC alone
 
 
-@pytest.mark.parametrize("name", ["icosphere2", "grid", "non_manifold", "degenerate", "noisy_level6"])
+def _twice(mk):
+    """Two disjoint copies of a mesh, the second's vertex indices offset."""
+    v, f = mk()
+    return np.concatenate([v, v]), np.concatenate([f, f + len(v)])
+
+
+@pytest.mark.parametrize("name", ["icosphere2", "grid", "non_manifold", "degenerate", "noisy_level6", "two_noisy_level6"])
 def test_against_f64_restatement(name, hip_lib):
+    """two_noisy_level6: Q + E + F = 655 360 elements, a second trip of 131 072 behind gsr_reduce.h's capped grid."""
+    level6 = lambda: mr.icosphere(6, noise=0.3, seed=3)
     mk = {"icosphere2": lambda: mr.icosphere(2, noise=0.2), "grid": lambda: mr.grid(6, noise=0.05),
           "non_manifold": mr.non_manifold, "degenerate": mr.degenerate,
-          "noisy_level6": lambda: mr.icosphere(6, noise=0.3, seed=3)}[name]
+          "noisy_level6": level6, "two_noisy_level6": lambda: _twice(level6)}[name]
     v, f = _mesh(mk)
     v = v.float().double()                       # the same f32 positions on both sides
-    re, ra = _refs(v, f, seed=4)
+    if name == "two_noisy_level6":               # each copy with the single mesh's references
+        V1, F1 = v.shape[0] // 2, f.shape[0] // 2
+        re, ra = _refs(v[:V1], f[:F1], seed=4)
+        e1, e2 = mr.p3d_edges(f[:F1], V1)[0], mr.p3d_edges(f, 2 * V1)[0]
+        assert torch.equal(e2, torch.cat([e1, e1 + V1]))              # the edges of the copies, in the single mesh's order
+        Q = mr.p3d_pair_index(f, 2 * V1)[2].shape[0]
+        assert Q + e2.shape[0] + f.shape[0] == 655_360
+        re, ra = torch.cat([re, re]), torch.cat([ra, ra])
+    else:
+        re, ra = _refs(v, f, seed=4)
     re, ra = re.float().double(), ra.float().double()
     loss, parts, g = _fused(v.float(), f, re, ra, **FACTORS)
     want, gw = _restated(v, f, re, ra, **FACTORS)
@@ -115,6 +133,12 @@ def test_against_f64_restatement(name, hip_lib):
     assert _grad_err(g, gw) <= 1e-4, _grad_err(g, gw)
     if name in ("non_manifold", "degenerate"):
         assert torch.equal(g[6], torch.zeros(3, device=DEV))     # referenced by no face: exactly 0
+    if name == "two_noisy_level6":
+        # Q, E and F doubled: every term's coefficient is exactly half the single mesh's, so is each copy's gradient, bit for bit
+        _, _, g1 = _fused(v[:V1].float(), f[:F1], re[:len(re) // 2], ra[:F1], **FACTORS)
+        _, _, g1_nc = _fused(v[:V1].float(), f[:F1], nc_factor=1.0)
+        for got, one in ((g, g1), (g_nc, g1_nc)):
+            assert torch.equal(got[:V1], 0.5 * one) and torch.equal(got[V1:], 0.5 * one)
 
 
 def test_backward_is_deterministic_accumulates_and_scales_on_device(hip_lib):

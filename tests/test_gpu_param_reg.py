@@ -79,12 +79,23 @@ def _restated(inp, **over):
     return total.detach(), [p.detach() for p in parts], {k: v.grad for k, v in leaves.items()}
 
 
-@pytest.mark.parametrize("weights", ["binary", "fractional"])
-def test_forward_and_gradients_against_f64_restatement(weights, hip_lib):
+def _sizes():
+    """(N, M) = the module's own first (its ids stay as they were), then tests/beyond_caps.py's: config C's 491 520 Gaussians
+    (480 workgroups: tree_total's lanes add a second partial) and 524 290 groups of four (a second trip of two groups, the last
+    of them ragged)."""
+    import beyond_caps
+    sizes = beyond_caps.param_reg_sizes()
+    assert sizes[0] == (N, M)
+    return [pytest.param(w, n, m, id=w if (n, m) == (N, M) else f"{w}-{n}") for n, m in sizes for w in ("binary", "fractional")]
+
+
+@pytest.mark.parametrize("weights,n,m", _sizes())
+def test_forward_and_gradients_against_f64_restatement(weights, n, m, hip_lib):
     """Each part and the total within 1e-5 relative (a sum of non-negative f32 terms: log2(3N) 2^-24 ~ 1.3e-6 for a tree plus
-    one rounding per element; the kernel sums in double), gradients elementwise at rtol 1e-5 (three to five f32 operations per
-    element) with NO element excluded, the exact zeros with ==; the three weight layouts give identical bits."""
-    inp = _inputs(seed=1, weights=weights)
+    one rounding per element, 1.4e-6 at the largest N; the kernel sums in double), gradients elementwise at rtol 1e-5 (three to
+    five f32 operations per element) with NO element excluded, the exact zeros with ==; the three weight layouts give identical
+    bits."""
+    inp = _inputs(seed=1, n=n, m=m, weights=weights)
     want, want_parts, gw = _restated(inp)
     results = {}
     for name, w in _layouts(inp["weight"]).items():
@@ -104,7 +115,7 @@ def test_forward_and_gradients_against_f64_restatement(weights, hip_lib):
         assert bool((g["delta_t"][inp["delta_t"] == 0] == 0).all()) and bool((g["delta_t"][(wcol == 0).expand(-1, 3)] == 0).all())
         assert bool((g["delta_r"][:, 0] == 0).all()) and bool((g["delta_r"][:, 1:][(wcol == 0).expand(-1, 3)] == 0).all())
         assert bool((g["delta_r"][:, 1:][inp["delta_r"][:, 1:] == 0] == 0).all())
-        assert bool((g["sh_dc"][M:] == 0).all()) and bool((g["sh_dc"][:M] != 0).any())
+        assert bool((g["sh_dc"][m:] == 0).all()) and bool((g["sh_dc"][:m] != 0).any())
         above = torch.sigmoid(inp["densities"].double()) > FACTORS["min_opacity"]
         assert bool((g["densities"][above] == 0).all()) and bool((g["densities"][~above] < 0).all())
     ref_parts_, ref_g = results["[N]"]
