@@ -128,7 +128,9 @@ sh_to_rgb_bwd_kernel(int P, int D, int M, const float* __restrict__ positions, c
 // and the gradient w.r.t. the matrix that reproduces G along every rotation direction is  dL/dR = 1/2 [G]x R
 // (< 1/2 [G]x R, [dw]x R > = G . dw).  From there it is plain chain rule through the frame (no derivative of
 // matrix_to_quaternion is ever needed); a face's three vertex gradients are summed over its G Gaussians in
-// registers and leave as 9 atomics.
+// registers and leave as 9 atomics.  The one exception: a raw complex number at or below F.normalize's eps of 1e-12 is scaled
+// by 1e12 and NOT made a unit vector, R is then no rotation, and rotation_backward differentiates the conversion itself
+// (matrix_to_unit_quaternion_bwd).  Held to float64 autograd by tests/test_gpu_producers_edges.py, for a loss on q itself too.
 struct V3 { float x, y, z; };
 __device__ __forceinline__ V3 v3(float x, float y, float z) { return V3{x, y, z}; }
 __device__ __forceinline__ V3 operator+(V3 a, V3 b) { return V3{a.x + b.x, a.y + b.y, a.z + b.z}; }
@@ -139,7 +141,9 @@ __device__ __forceinline__ V3 cross(V3 a, V3 b) { return V3{a.y * b.z - a.z * b.
 __device__ __forceinline__ float norm(V3 a) { return sqrtf(dot(a, a)); }
 __device__ __forceinline__ V3 ld3(const float* p, size_t i) { return V3{p[3 * i], p[3 * i + 1], p[3 * i + 2]}; }
 __device__ __forceinline__ void st3(float* p, size_t i, V3 v) { p[3 * i] = v.x; p[3 * i + 1] = v.y; p[3 * i + 2] = v.z; }
-// d/dx of x / max(|x|, eps) applied to g (the eps branch, reached only by degenerate input, is treated as a constant scale)
+// d/dx of x / max(|x|, eps) applied to g, for ONE normalisation: at or below eps the result is x / eps, a constant scale, which is
+// what autograd gives for F.normalize.  (eps = 1e-12 is reached only by degenerate input; the face normal's 1e-6 is not, see
+// frame_backward.)
 __device__ __forceinline__ V3 normalize_bwd(V3 unit, float len, float eps, V3 g)
 {
     const float inv = 1.0f / fmaxf(len, eps);
@@ -225,6 +229,38 @@ __device__ __forceinline__ void matrix_to_unit_quaternion(const float (&m)[3][3]
     for (int c = 0; c < 4; c++) q[c] = cand[c] * inv;
 }
 
+// dL/dm of matrix_to_unit_quaternion for ANY matrix m, no rotation assumed: the result is cand / |cand| (the positive factor d
+// drops out, and |cand| >= t_best >= 1 keeps the eps away), and cand is linear in m -- its own entry qa[best]^2 is t_best.
+// A[c] = column c of dL/dm.  Only the backward of a Gaussian whose R is no rotation takes this (rotation_backward).
+__device__ __forceinline__ void matrix_to_unit_quaternion_bwd(const float (&m)[3][3], float4 gq, V3 (&A)[3])
+{
+    const float t[4] = {1.0f + m[0][0] + m[1][1] + m[2][2], 1.0f + m[0][0] - m[1][1] - m[2][2],
+                        1.0f - m[0][0] + m[1][1] - m[2][2], 1.0f - m[0][0] - m[1][1] + m[2][2]};
+    const float qa[4] = {t[0] > 0.f ? sqrtf(t[0]) : 0.f, t[1] > 0.f ? sqrtf(t[1]) : 0.f, t[2] > 0.f ? sqrtf(t[2]) : 0.f,
+                         t[3] > 0.f ? sqrtf(t[3]) : 0.f};
+    int best = 0;
+#pragma unroll
+    for (int c = 1; c < 4; c++) if (qa[c] > qa[best]) best = c;   // the forward's choice, on the forward's numbers
+    float cand[4];
+    if (best == 0) { cand[0] = t[0]; cand[1] = m[2][1] - m[1][2]; cand[2] = m[0][2] - m[2][0]; cand[3] = m[1][0] - m[0][1]; }
+    else if (best == 1) { cand[0] = m[2][1] - m[1][2]; cand[1] = t[1]; cand[2] = m[1][0] + m[0][1]; cand[3] = m[0][2] + m[2][0]; }
+    else if (best == 2) { cand[0] = m[0][2] - m[2][0]; cand[1] = m[1][0] + m[0][1]; cand[2] = t[2]; cand[3] = m[1][2] + m[2][1]; }
+    else { cand[0] = m[1][0] - m[0][1]; cand[1] = m[2][0] + m[0][2]; cand[2] = m[2][1] + m[1][2]; cand[3] = t[3]; }
+    const float inv = 1.0f / sqrtf(cand[0] * cand[0] + cand[1] * cand[1] + cand[2] * cand[2] + cand[3] * cand[3]);
+    const float g[4] = {gq.x, gq.y, gq.z, gq.w};
+    float gd = 0.f;
+#pragma unroll
+    for (int c = 0; c < 4; c++) { cand[c] *= inv; gd += g[c] * cand[c]; }
+    float gc[4];
+#pragma unroll
+    for (int c = 0; c < 4; c++) gc[c] = inv * (g[c] - gd * cand[c]);
+    // (columns of dL/dm; row index = component)
+    if (best == 0) { A[0] = v3(gc[0], gc[3], -gc[2]); A[1] = v3(-gc[3], gc[0], gc[1]); A[2] = v3(gc[2], -gc[1], gc[0]); }
+    else if (best == 1) { A[0] = v3(gc[1], gc[2], gc[3]); A[1] = v3(gc[2], -gc[1], gc[0]); A[2] = v3(gc[3], -gc[0], -gc[1]); }
+    else if (best == 2) { A[0] = v3(-gc[2], gc[1], -gc[0]); A[1] = v3(gc[1], gc[2], gc[3]); A[2] = v3(gc[0], gc[3], -gc[2]); }
+    else { A[0] = v3(-gc[3], gc[0], gc[1]); A[1] = v3(-gc[0], -gc[3], gc[2]); A[2] = v3(gc[1], gc[2], gc[3]); }
+}
+
 __global__ void __launch_bounds__(128)
 mesh_gaussians_fwd_kernel(int F, int G, const float* __restrict__ verts, const long long* __restrict__ faces,
                           const float* __restrict__ bary, const float* __restrict__ raw_scales,
@@ -276,11 +312,20 @@ __device__ __forceinline__ FrameGrad rotation_backward(const FaceFrame& Ff, cons
     float q[4];
     matrix_to_unit_quaternion(Gf.R, q);
     const V3 qv = v3(q[1], q[2], q[3]), gqv = v3(gq.y, gq.z, gq.w);
-    const V3 Gw = 0.5f * (((-gq.x) * qv + q[0] * gqv) + cross(qv, gqv));           // dL/d(rotation vector)
+    V3 Gw = 0.5f * (((-gq.x) * qv + q[0] * gqv) + cross(qv, gqv));                 // dL/d(rotation vector)
     // dL/dR = 1/2 [G]x R, column by column
     V3 A[3];
 #pragma unroll
     for (int c = 0; c < 3; c++) A[c] = 0.5f * cross(Gw, v3(Gf.R[0][c], Gf.R[1][c], Gf.R[2][c]));
+    if (!(Gf.lq > 1e-12f)) {
+        // A raw complex number at or below F.normalize's eps leaves (qc, qs) shorter than a unit vector: R is no rotation, and
+        // the shortcut above does not hold.  There dL/dR comes from the conversion itself, and delta_r (which still turns R
+        // rigidly, dR = [dw]x R) takes dL/dw = sum_c R_c x dL/dR_c.
+        matrix_to_unit_quaternion_bwd(Gf.R, gq, A);
+        Gw = v3(0.f, 0.f, 0.f);
+#pragma unroll
+        for (int c = 0; c < 3; c++) Gw = Gw + cross(v3(Gf.R[0][c], Gf.R[1][c], Gf.R[2][c]), A[c]);
+    }
     V3 gB[3];
     if (Gf.loose) {
         // delta_r: dphi = 2 vec(dd^ (x) conj(d^)), dd^ = (I - d^ d^T) dd / |d|
@@ -315,7 +360,11 @@ __device__ __forceinline__ void frame_backward(const FaceFrame& Ff, V3 gR0, V3 g
     gbR1 = gbR1 + cross(gcr, Ff.R0);
     const V3 ga = normalize_bwd(Ff.bR1, Ff.la, 1e-12f, gbR1);        // bR1 = normalize(v0 - v1)
     gv0 = gv0 + ga; gv1 = gv1 - ga;
-    const V3 gn = normalize_bwd(Ff.R0, Ff.len, 1e-6f, gR0);          // R0 = normalize((e1 x e2) / max(|.|, 1e-6))
+    // R0 = normalize(n / max(|n|, 1e-6)), n = e1 x e2: TWO normalisations.  |n| <= 1e-6 (any face of half a square millimetre
+    // or less in a metre-scale scene) makes the first a constant scale by 1e6 and leaves the second to make R0 a unit vector,
+    // so the derivative is still (1 / |n|) (I - R0 R0^T), not 1e6 I; only |1e6 n| <= 1e-12 is a constant scale all the way.
+    const V3 gn = Ff.len > 1e-6f ? normalize_bwd(Ff.R0, Ff.len, 1e-6f, gR0)
+                                 : 1e6f * normalize_bwd(Ff.R0, Ff.len * 1e6f, 1e-12f, gR0);
     const V3 ge1 = cross(Ff.e2, gn), ge2 = cross(gn, Ff.e1);
     gv1 = gv1 + ge1; gv2 = gv2 + ge2; gv0 = gv0 - (ge1 + ge2);
 }
