@@ -294,6 +294,19 @@ SIGNATURES = {
     "gsr_hull_camera_bytes": (c_int, []),
     "gsr_hull_carve": (c_int, [c_int, c_void_p, c_void_p, c_double, POINTER(c_int), c_void_p, c_void_p, c_void_p]),
     "gsr_hull_finish": (c_int, [POINTER(c_int), c_void_p, c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # RAFT optical flow, the basic model's inference (data_process/RAFT): gaustar_amd.flow; FlowSlice / FlowConvDesc below
+    "gsr_flow_packed_k": (c_int, [c_int]),
+    "gsr_flow_packed_n": (c_int, [c_int]),
+    "gsr_flow_prep_image": (c_int, [c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "gsr_flow_conv": (c_int, [c_void_p, c_void_p]),
+    "gsr_flow_pack_features": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "gsr_flow_corr_volume": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gsr_flow_corr_pool": (c_int, [c_longlong, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "gsr_flow_corr_lookup": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gsr_flow_instance_norm_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "gsr_flow_instance_norm": (c_int, [c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gsr_flow_gru_combine": (c_int, [c_longlong, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gsr_flow_upsample": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "gsr_adam_step": (c_int, [c_longlong, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_double, c_double, c_int,
                               c_void_p]),
     "gsr_adam_step_multi": (c_int, [c_int, POINTER(c_longlong), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),
@@ -315,6 +328,18 @@ class PlanInfo(ctypes.Structure):
     _fields_ = [("state", c_int), ("R_cap", c_int), ("U_cap", c_int), ("max_cap", c_int), ("level", c_int), ("half", c_int),
                 ("pending_half", c_int), ("reserved0", c_int), ("header", c_int * 8), ("arrived", c_int), ("pending", c_int),
                 ("diag", c_int * 4), ("reserved1", c_int * 10)]
+
+
+class FlowSlice(ctypes.Structure):
+    """gsr_flow_slice of include/gsr.h: `channels` channels from `offset` of a buffer of `stride` floats per pixel."""
+    _fields_ = [("base", c_void_p), ("stride", c_longlong), ("offset", c_int), ("channels", c_int)]
+
+
+class FlowConvDesc(ctypes.Structure):
+    """gsr_flow_conv_desc of include/gsr.h, field for field."""
+    _fields_ = [("N", c_int), ("H", c_int), ("W", c_int), ("KH", c_int), ("KW", c_int), ("stride", c_int), ("n_in", c_int),
+                ("Cout", c_int), ("act", c_int), ("residual_relu", c_int), ("inputs", FlowSlice * 3), ("out", FlowSlice),
+                ("residual", FlowSlice), ("weights", c_void_p), ("bias", c_void_p), ("scale", c_void_p), ("shift", c_void_p)]
 
 
 PLAN_INFO_INTS = 32

@@ -1267,6 +1267,68 @@ int gsr_hull_carve(int n_cameras, const void* cameras_host, const void* cameras,
 int gsr_hull_finish(const int* grid, const float* field, const int* count, int min_views, double sdf_trunc, float* tsdf, float* weight,
                     unsigned char* touched, gsr_stream_t stream);
 
+/* ---- RAFT optical flow, the basic model's inference: gaustar_amd.flow.  Replaces data_process/RAFT (demo_GauSTAR.py and the
+ * core/ modules it runs).  All activations are f32, NHWC, on the device; every call is asynchronous on `stream`, none
+ * synchronises the host, none uses atomics, and every output is a pure function of the inputs with a fixed order of
+ * operations.  tests/flow_ref.py restates the model.
+ * gsr_flow_slice [host]: `channels` channels of a buffer of `stride` floats per pixel, starting at channel `offset`; the
+ *   reference's torch.cat's are slices of one buffer.
+ * gsr_flow_prep_image (demo_GauSTAR.py:30-40 load_image, utils/utils.py:7-19 InputPadder 'sintel', raft.py:89-90): image [h,w,3]
+ *   uint8, factor 1, 2 or 4 dividing h and w -> out [Hp,Wp,3]: the factor x factor box mean rounded half to even (cv2's
+ *   INTER_AREA with cvRound), hs = h / factor, Hp = hs rounded up to a multiple of 8, replicate padding with (Hp - hs) / 2
+ *   rows before and the rest after (columns alike), then 2 (x / 255) - 1.
+ * gsr_flow_conv (torch.nn.Conv2d as extractor.py and update.py use it): desc [host].  Input: the concatenation of n_in slices
+ *   over N images of H x W; kernel 1x1, 3x3, 7x7, 1x5 or 5x1 with zero padding KH / 2, KW / 2; stride 1 or 2; 2 <= Cin <= 384,
+ *   2 <= Cout <= 576.  weights: [gsr_flow_packed_k(KH KW Cin)][gsr_flow_packed_n(Cout)] (K rounded up to 16; Cout rounded up to
+ *   64, or 4 columns for Cout <= 4) with row (ky KW + kx) Cin + ci, zeros
+ *   in the padding, 16-byte aligned.  Per output: the k-ordered f32 fma chain from 0 (v_mfma_f32_32x32x2_f32; for Cout <= 4 the
+ *   chains of k = 4 l .. 4 l + 3 (mod 256) for l = 0 .. 63, joined by a fixed tree: one wave per output pixel), + bias, then
+ *   x scale + shift where scale is given (eval-mode batch norm, extractor.py:22-26), then act (0 none, 1 relu, 2 sigmoid, 3
+ *   tanh), then + residual where residual.base is given, then relu if residual_relu (extractor.py:56); stored to the slice
+ *   `out`.  residual may be `out` itself (the flow's update, raft.py:131).
+ * gsr_flow_pack_features / gsr_flow_corr_volume (corr.py:52-60 CorrBlock.corr): fmap [P][C] -> packed [C][P rounded up to 64];
+ *   volume [P1][P2] = (fmap1 . fmap2) / sqrt(C) with the convolution's chain over c; C a power of four (the scale is exact).
+ * gsr_flow_corr_pool (corr.py:25-27): in [rows][h][w] -> out [rows][h/2][w/2], (((a + b) + c) + d) / 4.
+ * gsr_flow_corr_lookup (corr.py:29-50, utils/utils.py:57-71 bilinear_sampler): for feature pixel (x, y) of the h8 x w8 grid
+ *   with flow (fx, fy), level l of dims (h2, w2) >> l and 0 <= i, j < 9: out[pixel][81 l + 9 i + j] = the bilinear sample of the
+ *   pixel's level-l map at ((x + fx) / 2^l + i - 4, (y + fy) / 2^l + j - 4), taps outside the map counting 0.
+ * gsr_flow_instance_norm (torch.nn.InstanceNorm2d, extractor.py:28-32, :50-56): x [N][HW][C] -> (x - mean) / sqrt(var + 1e-5)
+ *   per (image, channel), biased variance, sums in f64 in a fixed order; then relu if `relu`; then relu(residual + .) where
+ *   residual is given.  out may be x.
+ * gsr_flow_gru_combine (update.py:50-51, :57-58): mode 0: out = gate h; mode 1: out = (1 - gate) h + gate q; slices of
+ *   4-aligned channels; out may be h.
+ * gsr_flow_upsample (raft.py:72-83 upsample_flow, utils/utils.py:21-24 unpad, demo_GauSTAR.py:99): mask [h8 w8][576] the mask
+ *   head's output; out [h,w,2] in (x, y) order: pixel (Y, X) lies at (Y + pad_top, X + pad_left) of the padded image, in cell
+ *   (y, x) at (i, j); weights = softmax_k(0.25 mask[64 k + 8 i + j]), out = sum_k w_k 8 flow(y + k / 3 - 1, x + k % 3 - 1),
+ *   cells outside the grid counting 0. */
+typedef struct gsr_flow_slice {
+    const float* base;
+    long long stride;
+    int offset, channels;
+} gsr_flow_slice;
+typedef struct gsr_flow_conv_desc {
+    int N, H, W, KH, KW, stride, n_in, Cout, act, residual_relu;
+    gsr_flow_slice in[3];
+    gsr_flow_slice out, residual;
+    const float *weights, *bias, *scale, *shift;
+} gsr_flow_conv_desc;
+int gsr_flow_packed_k(int K);
+int gsr_flow_packed_n(int Cout);
+int gsr_flow_prep_image(int h, int w, const unsigned char* image, int factor, float* out, gsr_stream_t stream);
+int gsr_flow_conv(const gsr_flow_conv_desc* desc, gsr_stream_t stream);
+int gsr_flow_pack_features(int P, int C, const float* fmap, float* packed, gsr_stream_t stream);
+int gsr_flow_corr_volume(int P1, int P2, int C, const float* fmap1, const float* packed2, float* volume, gsr_stream_t stream);
+int gsr_flow_corr_pool(long long rows, int h, int w, const float* in, float* out, gsr_stream_t stream);
+int gsr_flow_corr_lookup(int h8, int w8, int h2, int w2, const gsr_flow_slice* flow, const float* level0, const float* level1,
+                         const float* level2, const float* level3, float* out, gsr_stream_t stream);
+size_t gsr_flow_instance_norm_workspace_bytes(int N, int HW, int C);
+int gsr_flow_instance_norm(int N, int HW, int C, const float* x, int relu, const float* residual, float* out, void* workspace,
+                           gsr_stream_t stream);
+int gsr_flow_gru_combine(long long P, int mode, const gsr_flow_slice* gate, const gsr_flow_slice* h, const gsr_flow_slice* q,
+                         const gsr_flow_slice* out, gsr_stream_t stream);
+int gsr_flow_upsample(int h8, int w8, const gsr_flow_slice* flow, const float* mask, int pad_top, int pad_left, int h, int w, float* out,
+                      gsr_stream_t stream);
+
 /* Tuning aid: when device_buffer is non-NULL (4*T uint64), the two blend kernels record the start/end wall
  * clock (100 MHz) of every workgroup: forward at [2*b], backward at [2*(T+b)], b = launch index.  NULL = off. */
 int gsr_debug_set_trace(void* device_buffer);
