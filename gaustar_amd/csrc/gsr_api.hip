@@ -819,6 +819,8 @@ int gsr_backward_mt(int P, int D, int M, int R, int num_segments, int num_channe
     if (R > 0 && num_segments <= 0)
         return fail_msg("gsr_backward: num_segments of the forward is required (a forward-only render cannot be differentiated)");
     if (!channels_ok(num_channels)) return fail_msg("gsr_backward: num_channels must be 3, 4 or 6");
+    if (gsr_grad_scratch_bytes(P) > (size_t)0xffffffffu)   // (the backward blend addresses the table by 32-bit byte offsets)
+        return fail_msg("gsr_backward: more than 89 million Gaussians (the accumulation table must stay below 4 GiB)");
     if (num_channels != 3 && !colors_precomp)
         return fail_msg("gsr_backward: multi-target renders need precomputed colours [P, num_channels]");
     const int C = num_channels;

@@ -37,9 +37,13 @@
 //    records (ds_add_f32 costs the CU's LDS pipe ~190 cycles per wave instruction on this chip).  Everything is f32: no r|w table,
 //    no bf16 splits, no matrix instructions -- the four-channel render's blue and depth gradients are exact again (rounds 4-5
 //    packed them into two bf16 columns);
-//  * the table is flushed ROW-MAJOR: one atomic instruction covers the consecutive floats of ~7 packed 48-byte records
-//    grad_acc[gaussian][12] = {sum r, sum r dx, sum r dy, sum r dx^2, sum r dx dy, sum r dy^2, c_0 .. c_{C-1}}, so the memory
-//    pipeline merges lanes per cache line (1.5 M atomic requests per 1080p view instead of 8 M).
+//  * the table is flushed ROW-MAJOR: one atomic instruction covers the consecutive floats of five whole packed 48-byte records
+//    (six channels: four) grad_acc[gaussian][12] = {sum r, sum r dx, sum r dy, sum r dx^2, sum r dx dy, sum r dy^2, c_0 .. c_{C-1}},
+//    so the memory pipeline merges lanes per cache line (1.5 M atomic requests per 1080p view instead of 8 M);
+//  * outside the trips the wave's bookkeeping is scalar: the kept lanes, the chunk's and the sub-blocks' are 64-bit masks in
+//    scalar registers (bit-reversed kept words) that serve as execute masks and as the operands of the rank counts; the LDS is
+//    cleared once per wave and the flush hands the moment table back clean; the first chunk -- nearly always the only one -- is
+//    straight-line code (NOTEBOOK "Backward blend: head, lists, clearing and flush": - 4.1 M vector instructions per view).
 // Rounding: T and A come out of re-associated products (tree order within a trip); the alpha decisions (power <= 0, alpha >=
 // 1/255, position < last contributor) are the forward's bit for bit.
 // Measured against the uniform loop (profiles/r06_bwd_quad_counters.txt, config C): 51.7 M vector instructions per view instead of
@@ -84,7 +88,7 @@ template <int C> struct QuadLds {
     static constexpr int REC = 0;                    // Q + 1 records (the last: a null record for the lanes past a list's end)
     static constexpr int MOM = REC + (Q + 1) * REC_B;
     static constexpr int STG = MOM + (Q + 1) * MOM_B;
-    static constexpr int LST = STG + 64 * STG_B;     // 4 sub-blocks x 4 instances-of-a-trip x Q / 4 trips: record offset / 16 of the (4 t + j)-th kept instance
+    static constexpr int LST = STG + 64 * STG_B;     // 4 sub-blocks x Q bytes: byte 4 t + j = record offset / 16 of the sub-block's (4 t + j)-th kept instance (trip t, bank j)
     static constexpr int ORW = LST + 4 * Q + 16;     // 4 x u64: the sub-blocks' kept words (16 bytes of "null record" behind the lists: look-ahead reads)
     static constexpr int TOTAL = ORW + 32;
     static_assert(STG % 16 == 0 && MOM % 16 == 0 && LST % 16 == 0 && ORW % 16 == 0, "16-byte accesses");
@@ -201,7 +205,10 @@ blend_bwd_kernel(int W, int H, int gx, const uint4* __restrict__ unit_info, cons
 #pragma unroll
         for (int ch = 0; ch < C; ch++) c_[ch] = v[ch + 1];
     };
-    load_snap32(snap + (size_t)(unit + (has_next ? 1u : 0u)) * 256 * SV, Ts, cs);
+    // (unit + (has_next ? 1 : 0): the compiler forms this wave-uniform sum on the vector unit whatever its spelling; read back as
+    // 32 bits here, the 64-bit address arithmetic behind it stays scalar -- three vector instructions instead of six)
+    const uint32_t unit_far = (uint32_t)__builtin_amdgcn_readfirstlane((int)(unit + (has_next ? 1u : 0u)));
+    load_snap32(snap + (size_t)unit_far * 256 * SV, Ts, cs);
     load_snap32(snap + (size_t)unit0 * 256 * SV, Tf, cf);
     const int k = s0 + 63 - lane;                                  // lane l holds list position s0 + 63 - l (back to front)
     const uint32_t kl = (uint32_t)(min(k, n - 1) - s0);
@@ -210,6 +217,20 @@ blend_bwd_kernel(int W, int H, int gx, const uint4* __restrict__ unit_info, cons
     const RecTail<C> rc = at32(rec_c + list0 + s0, kl * (uint32_t)sizeof(RecTail<C>));
     const uint32_t gid = at32(point_list + list0 + s0, kl * 4u);
     if (!has_next) word_next = make_uint2(0u, 0u);
+    // ---- the wave's LDS, set up ONCE while the loads above are in flight: the null record (all zero but its position) and, behind
+    // it, the moment table are one run of zeros -- whole-wave 16-byte stores that spill into the pixel state, which is written
+    // after them --; the lists start as "the null record".  The flush hands every moment word it reads back zeroed, so a later
+    // chunk of this wave finds the table clean and clears nothing.
+    const uint32_t lds0 = lds_byte_address(lds);
+    {
+        constexpr int CLR = (RV + (Q + 1) * (MOM_B / 16) + 63) / 64;   // whole-wave stores: 2 (102 vectors of 128), six channels 3 (136 of 192)
+        static_assert(Q * REC_B + CLR * 1024 <= LST, "the run of zeros ends inside the pixel state");
+        // (plain stores: the compiler places them among the loads; none of the loads waits for them)
+#pragma unroll
+        for (int i = 0; i < CLR; i++) reinterpret_cast<float4*>(lds + REC + Q * REC_B)[lane + 64 * i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (lane == 0) reinterpret_cast<uint32_t*>(lds + REC + Q * REC_B)[6] = 0x7fffffffu;   // (a position no pixel replays)
+        if (lane < Q + 4) reinterpret_cast<uint32_t*>(lds + LST)[lane] = 0x01010101u * (uint32_t)(RV * Q);   // (bytes: record offset / 16)
+    }
     float bg_dot_dpixel = 0.f;
 #pragma unroll
     for (int ch = 0; ch < C; ch++) bg_dot_dpixel += bg[ch] * dp[ch];
@@ -236,13 +257,13 @@ blend_bwd_kernel(int W, int H, int gx, const uint4* __restrict__ unit_info, cons
 #pragma unroll
     for (int ch = 0; ch < C; ch++) accd = __builtin_fmaf(acc[ch], dp[ch], accd);
     {
-        const int lim = my_lim - s0;
-        word.x &= lim >= 32 ? 0xffffffffu : lim > 0 ? (1u << lim) - 1u : 0u;
-        word.y &= lim >= 64 ? 0xffffffffu : lim > 32 ? (1u << (lim - 32)) - 1u : 0u;
+        const int lim = my_lim - s0;   // (<= 64: my_lim <= s1 <= s0 + 64)
+        const unsigned long long low = lim > 0 ? ~0ull >> (64 - lim) : 0ull;   // bits [0, lim): one 64-bit shift instead of two clamped halves
+        word.x &= (uint32_t)low;
+        word.y &= (uint32_t)(low >> 32);
     }
     // ---- the kept words of the four 4x4 sub-blocks: one same-address LDS OR per sub-block (pixel lane l = 8 y + x lies in
     // sub-block 2 (y >> 2) + (x >> 2)), read back by every lane
-    const uint32_t lds0 = lds_byte_address(lds);
     unsigned long long ks[4];
     {
         const uint32_t sub = (uint32_t)(((lane >> 5) << 1) | ((lane >> 2) & 1));
@@ -270,9 +291,14 @@ blend_bwd_kernel(int W, int H, int gx, const uint4* __restrict__ unit_info, cons
         st[1] = make_float4(dp[0], dp[1], dp[2], C > 3 ? dp[3 < C ? 3 : 0] : 0.f);
         if constexpr (C == 6) st[2] = make_float4(dp[4 < C ? 4 : 0], dp[5 < C ? 5 : 0], 0.f, 0.f);
     }
-    const bool keep = ((kany >> (63 - lane)) & 1ull) != 0ull;
-    const unsigned long long m = __ballot(keep);
-    const int cnt_all = __popcll(m);
+    // lane l holds list position 63 - l: the lanes with a kept instance are the kept word bit-reversed -- a scalar, like every
+    // mask below: the lanes take them as their execute mask and count their ranks in them, no lane tests a bit of its own
+    const unsigned long long m = __builtin_bitreverse64(kany);
+    const int cnt_all = __popc((uint32_t)m) + __popc((uint32_t)(m >> 32));   // (two 32-bit counts: the 64-bit one is compared on the vector unit)
+    const auto lanes_of = [](unsigned long long mask) { return __builtin_amdgcn_inverse_ballot_w64(mask); };
+    const auto rank_in = [](unsigned long long mask) {   // number of set bits below this lane's
+        return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+    };
     // (the unit's records arrived with the head's loads and feed the FIRST chunk; a later chunk fetches its lanes' records
     // again -- they are in L2 -- instead of keeping ten registers alive across the trips)
     float4 ra_ = ra, rb_ = rb;
@@ -280,47 +306,54 @@ blend_bwd_kernel(int W, int H, int gx, const uint4* __restrict__ unit_info, cons
 #pragma unroll
     for (int i = 0; i < 4; i++) rcc[i] = i < C - 2 ? rc.c[i < C - 2 ? i : 0] : 0.f;
     uint32_t gid_ = gid;
-    for (int q0 = 0; q0 < (GSR_QUAD_EXP == 2 ? 0 : cnt_all); q0 += Q) {
-        const int cnt = min(cnt_all - q0, Q);
-        const int slot = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)) - q0;
-        const bool mine = ((m >> lane) & 1ull) != 0ull && slot >= 0 && slot < Q;
-        if (q0 > 0) {
-            const uint32_t kl2 = (uint32_t)(min(s0 + 63 - lane, n - 1) - s0);
+    // One chunk of at most Q kept instances.  FIRST is the normal case -- the whole kept set (a unit-block keeps about 28 instances)
+    // -- and straight-line code: slots are ranks in m, the records are the head's, the LDS is as the head left it.  Later chunks
+    // (q0 = Q, 2 Q: the few blocks that keep more than Q instances of a unit) are the cold loop behind it.
+    const auto chunk = [&](auto first_chunk, const int q0) __attribute__((always_inline)) {
+        constexpr bool FIRST = decltype(first_chunk)::value;
+        const int slot = (int)rank_in(m) - q0;
+        unsigned long long mc = m;   // the chunk's lanes
+        if constexpr (FIRST) {
+            if (cnt_all > Q) mc = __ballot(lanes_of(m) && slot < Q);
+        } else {
+            mc = __ballot(lanes_of(m) && slot >= 0 && slot < Q);
+            int lane_c = lane;
+            asm volatile("" : "+v"(lane_c));   // (the cold path's addresses are formed here, not carried in registers from the head)
+            const uint32_t kl2 = (uint32_t)(min(s0 + 63 - lane_c, n - 1) - s0);
             ra_ = at32(rec_a + list0 + s0, kl2 * 16u);
             rb_ = at32(rec_b + list0 + s0, kl2 * 16u);
             const RecTail<C> rc2 = at32(rec_c + list0 + s0, kl2 * (uint32_t)sizeof(RecTail<C>));
 #pragma unroll
             for (int i = 0; i < C - 2; i++) rcc[i] = rc2.c[i];
             gid_ = at32(point_list + list0 + s0, kl2 * 4u);
+            // (the lists of the chunk before: back to "the null record"; the moment table came back clean from its flush)
+            if (lane < Q + 4) reinterpret_cast<uint32_t*>(lds + LST)[lane] = 0x01010101u * (uint32_t)(RV * Q);
         }
-        // records of the chunk, a null record behind them, moment records cleared, lists reset to "the null record"
-        if (mine) {
+        const int cnt = __popc((uint32_t)mc) + __popc((uint32_t)(mc >> 32));
+        // records of the chunk; the last word is the BYTE offset of the Gaussian's record in grad_acc (32 bits: gsr_backward_mt
+        // refuses a table of 4 GiB), multiplied out once per record here and not once per flushed element
+        if (lanes_of(mc)) {
             float4* r = reinterpret_cast<float4*>(lds + REC + slot * REC_B);
             r[0] = make_float4(ra_.x, ra_.y, ra_.z, ra_.w);
-            r[1] = make_float4(rb_.x, rb_.y, __uint_as_float((uint32_t)(s0 + 63 - lane)), __uint_as_float(gid_));
-            r[2] = make_float4(rb_.z, rb_.w, rcc[0], rcc[1]);
+            // (explicit halves: a whole vector would first be copied into four adjacent registers, and plain stores are merged back into one)
+            const uint32_t rec_ad = lds0 + (uint32_t)REC + (uint32_t)(slot * REC_B);
+            lds_store_b64<16>(rec_ad, rb_.x, rb_.y);
+            lds_store_b64<24>(rec_ad, __uint_as_float((uint32_t)(s0 + 63 - lane)), __uint_as_float(gid_ * (uint32_t)(GRAD_RS * 4)));
+            lds_store_b64<32>(rec_ad, rb_.z, rb_.w);
+            lds_store_b64<40>(rec_ad, rcc[0], rcc[1]);
             if constexpr (C == 6) r[3] = make_float4(rcc[2], rcc[3], 0.f, 0.f);
         }
-        if (lane == 0) {
-            float4* r = reinterpret_cast<float4*>(lds + REC + Q * REC_B);
-            r[0] = make_float4(0.f, 0.f, 0.f, 0.f);
-            r[1] = make_float4(0.f, 0.f, __uint_as_float(0x7fffffffu), 0.f);
-            r[2] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if constexpr (C == 6) r[3] = make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-        for (int i = lane; i < (Q + 1) * (MOM_B / 16); i += 64) reinterpret_cast<float4*>(lds + MOM)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (lane < Q + 4) reinterpret_cast<uint32_t*>(lds + LST)[lane] = 0x01010101u * (uint32_t)(RV * Q);   // (bytes: record offset / 16)
         __builtin_amdgcn_wave_barrier();
+        // the sub-blocks' lists: byte `rank` of list s = record offset / 16 of its rank-th kept instance (trip t takes bytes 4 t ..
+        // 4 t + 3).  The sub-block's lanes are its kept word, bit-reversed, within the chunk's; a lane's rank among them is the
+        // byte's index.  (One byte store per sub-block stays: a lane's ranks in two lists differ, and so do its two addresses.)
         int cnt_s[4];
+        const unsigned char rec16 = (unsigned char)(RV * slot);
 #pragma unroll
         for (int s = 0; s < 4; s++) {
-            const bool in_s = mine && ((ks[s] >> (63 - lane)) & 1ull) != 0ull;
-            const unsigned long long ms = __ballot(in_s);
+            const unsigned long long ms = __builtin_bitreverse64(ks[s]) & mc;
             cnt_s[s] = __popcll(ms);
-            if (in_s) {
-                const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(ms >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ms, 0u));
-                lds[LST + s * Q + (rank & 3) * (Q / 4) + (rank >> 2)] = (unsigned char)(RV * slot);
-            }
+            if (lanes_of(ms)) lds[LST + s * Q + (int)rank_in(ms)] = rec16;
         }
         __builtin_amdgcn_wave_barrier();
 #pragma unroll 1
@@ -357,13 +390,13 @@ blend_bwd_kernel(int W, int H, int gx, const uint4* __restrict__ unit_info, cons
             const float pxf = (float)(sx + 4 * bx + kap), pyf = (float)(sy + 4 * by + rho);
             const int ntrip = (ns + 3) >> 2;
             SlotRegs<RV> rec;
-            // this lane's list of the sub-block: byte t = slot of its instance in trip t, read two trips ahead
-            const uint32_t lst_ad = lds0 + LST + (uint32_t)(s * Q + jj * (Q / 4));
+            // this lane's bytes of the sub-block's list: byte 4 t + j = slot of its instance in trip t, read two trips ahead
+            const uint32_t lst_ad = lds0 + LST + (uint32_t)(s * Q + jj);
             uint32_t idx_nxt;
             asm volatile("ds_read_u8 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(idx_nxt) : "v"(lst_ad) : "memory");
             uint32_t ad = (idx_nxt << 4) + (lds0 + REC);
             lds_request<RV, 0>(rec, ad);
-            asm volatile("ds_read_u8 %0, %1 offset:1" : "=v"(idx_nxt) : "v"(lst_ad) : "memory");
+            asm volatile("ds_read_u8 %0, %1 offset:4" : "=v"(idx_nxt) : "v"(lst_ad) : "memory");
 #pragma unroll 1
             for (int t = 0; t < ntrip; t++) {
                 // one trip: four instances; their records are consumed first thing, and the next trip's are requested into the
@@ -390,7 +423,7 @@ blend_bwd_kernel(int W, int H, int gx, const uint4* __restrict__ unit_info, cons
                 // (the next trip's records; past the list's end the bytes name the null record)
                 ad = (idx_nxt << 4) + (lds0 + REC);
                 lds_request<RV, 0>(rec, ad);   // (everything the trip needs of the old records has been computed above)
-                asm volatile("ds_read_u8 %0, %1" : "=v"(idx_nxt) : "v"(lst_ad + (uint32_t)(t + 2)) : "memory");
+                asm volatile("ds_read_u8 %0, %1" : "=v"(idx_nxt) : "v"(lst_ad + 4u * (uint32_t)(t + 2)) : "memory");
                 const float ae = live ? alpha : 0.0f;
                 float A = 1.0f - ae;                            // the pair's map on accum_rec . dL_dpix: A' = A x + B
                 const float rinv = __builtin_amdgcn_rcpf(A);
@@ -456,13 +489,45 @@ blend_bwd_kernel(int W, int H, int gx, const uint4* __restrict__ unit_info, cons
         }
         asm volatile("s_waitcnt lgkmcnt(0)" : : : "memory");
         __builtin_amdgcn_wave_barrier();
-        // flush: lanes walk the (instance, moment) table row-major (one atomic instruction covers several packed records)
-        for (int idx = lane; idx < cnt * NM; idx += 64) {
-            const int e = idx / NM, v = idx - e * NM;
-            const size_t g = __float_as_uint(reinterpret_cast<const float*>(lds + REC + e * REC_B)[7]);
-            atomic_add_f32(grad_acc + g * GRAD_RS + v, reinterpret_cast<const float*>(lds + MOM + e * MOM_B)[v]);
+        // flush: the lanes walk the moment table row-major in ITS geometry -- MW words per record, the pad words included --, RPI
+        // whole records per atomic instruction (5 of 12 words, lanes 60 .. 63 idle; six channels 4 of 16).  A lane keeps its
+        // (record, word) of the instruction for good: pass i is the same two LDS addresses + i * RPI records as immediate
+        // offsets, one compare against the records left and one add (word offset onto the record's byte offset in grad_acc).  An
+        // instruction still covers consecutive floats of packed records and no record is split between two (of the nine-word
+        // walk's instructions every one ended inside a record): requests per view do not grow.  Every word read goes back zeroed.
+        // The pad words -- the trips' lanes without a sum add garbage into them -- are neither flushed nor zeroed: they only
+        // ever collect more garbage, in this chunk and in the next.
+        {
+            constexpr int MW = MOM_B / 4, RPI = 64 / MW, PASSES = (Q + RPI - 1) / RPI;
+            static_assert(REC_B == MOM_B, "record e and its moments: one stride");
+            int lane_f = lane;
+            asm volatile("" : "+v"(lane_f));   // (derived here, per chunk: hoisted to the head these live through its register peak)
+            // lane / 12 (exact below 2^16), lanes 60 .. 63 held at record 4: their word index comes out as 12 .. 15, a pad word's
+            const uint32_t e0 = MW == 16 ? (uint32_t)lane_f >> 4 : min(((uint32_t)lane_f * 43691u) >> 19, (uint32_t)(RPI - 1));
+            const uint32_t v0 = (uint32_t)lane_f - e0 * (uint32_t)MW;
+            const int e_lane = v0 < (uint32_t)NM ? (int)e0 : Q;   // (Q: never below the records left)
+            const unsigned char* const rec_e = lds + REC + e0 * REC_B + 28;
+            unsigned char* const mom_w = lds + MOM + 4 * lane_f;
+            float zero = 0.f;
+            asm volatile("" : "+v"(zero));   // (one register for all passes)
+#pragma unroll
+            for (int i = 0; i < PASSES; i++) {
+                if (i * RPI >= cnt) break;
+                if (e_lane < cnt - i * RPI) {
+                    const uint32_t off = *reinterpret_cast<const uint32_t*>(rec_e + i * RPI * REC_B) + 4u * v0;
+                    float* const w = reinterpret_cast<float*>(mom_w + i * RPI * MOM_B);
+                    const float val = *w;
+                    *w = zero;
+                    atomic_add_f32(reinterpret_cast<float*>(reinterpret_cast<char*>(grad_acc) + off), val);
+                }
+            }
         }
         __builtin_amdgcn_wave_barrier();
+    };
+    if (GSR_QUAD_EXP != 2) {
+        chunk(std::true_type{}, 0);
+#pragma unroll 1
+        for (int q0 = Q; q0 < cnt_all; q0 += Q) chunk(std::false_type{}, q0);
     }
     if (trace && lane == 0) {   // (devtools: a unit's start and the end of its last wave -- monotone clock, max via atomic)
         if (wave == 0) trace[2 * unit] = t_start;

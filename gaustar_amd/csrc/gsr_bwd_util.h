@@ -84,6 +84,13 @@ __device__ __forceinline__ void lds_store_b32(uint32_t addr, float v)
 {
     asm volatile("ds_write_b32 %0, %1 offset:%2" : : "v"(addr), "v"(v), "n"(OFF) : "memory");
 }
+template <int OFF>
+__device__ __forceinline__ void lds_store_b64(uint32_t addr, float a, float b)
+{
+    typedef float f32x2_ __attribute__((ext_vector_type(2)));
+    const f32x2_ v = {a, b};
+    asm volatile("ds_write_b64 %0, %1 offset:%2" : : "v"(addr), "v"(v), "n"(OFF) : "memory");
+}
 // PENDING: LDS operations issued AFTER the request that may still be in flight when the data are used (LDS operations
 // complete in order, so "at most PENDING outstanding" implies the older request has landed).  The pair loop passes 2 --
 // the previous pair's two table stores; waiting for those as well (lgkmcnt(0)) stalled every pair for a store's latency.
