@@ -294,6 +294,15 @@ SIGNATURES = {
     "gsr_hull_camera_bytes": (c_int, []),
     "gsr_hull_carve": (c_int, [c_int, c_void_p, c_void_p, c_double, POINTER(c_int), c_void_p, c_void_p, c_void_p]),
     "gsr_hull_finish": (c_int, [POINTER(c_int), c_void_p, c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # plane-sweep stereo behind a depth prior, the photo-consistency refinement of the hull: gaustar_amd.stereo
+    "gsr_stereo_camera_bytes": (c_int, []),
+    "gsr_stereo_luma": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "gsr_stereo_sweep": (c_int, [c_int, c_int, c_void_p, c_void_p, POINTER(c_double), c_int, c_void_p, c_void_p, POINTER(c_double),
+                                 c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gsr_stereo_consistency": (c_int, [c_int, c_int, c_void_p, c_void_p, POINTER(c_double), c_int, c_void_p, c_void_p, c_double, c_int,
+                                       c_void_p, c_void_p]),
+    "gsr_stereo_merge": (c_int, [POINTER(c_int), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_void_p]),
     # RAFT optical flow, the basic model's inference (data_process/RAFT): gaustar_amd.flow; FlowSlice / FlowConvDesc below
     "gsr_flow_packed_k": (c_int, [c_int]),
     "gsr_flow_packed_n": (c_int, [c_int]),

@@ -18,7 +18,8 @@ SOURCES = ["gsr_api.hip", "gsr_preprocess.hip", "gsr_binning.hip", "gsr_blend_fw
            "gsr_topo.hip", "gsr_warp.hip", "gsr_param_reg.hip", "gsr_fusion.hip", "gsr_regions.hip",
            "gsr_stitch.hip", "gsr_splice.hip", "gsr_handover.hip", "gsr_meshdepth.hip",
            "gsr_track.hip", "gsr_eval.hip", "gsr_remesh.hip", "gsr_mesh_lap.hip", "gsr_knn.hip",
-           "gsr_density.hip", "gsr_prep.hip", "gsr_edit.hip", "gsr_hull.hip", "gsr_flow.hip"]
+           "gsr_density.hip", "gsr_prep.hip", "gsr_edit.hip", "gsr_hull.hip", "gsr_flow.hip",
+           "gsr_stereo.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -fno-slp-vectorize: left on, clang packs neighbouring scalar f32 operations of the per-pair loops into v_pk_*_f32 and
 # pays for it in register moves and s_nops (blend_bwd 0.139 -> 0.136 ms, blend_fwd 0.097 -> 0.094 ms on config C).

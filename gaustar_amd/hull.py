@@ -28,7 +28,8 @@ What to know about the result:
   * the volume carries no colour: dataprep.color_mesh_from_views colours the mesh afterwards;
   * the state is a running minimum of values rounded to f32 and a count: the same bits for every order of the cameras, every
     split into calls, streams and ranks.
-Still external: any photo-consistency refinement of the hull (the RAFT flows: gaustar_amd.flow).
+The photo-consistency refinement of the hull, which sees into those concavities: gaustar_amd.stereo (the RAFT flows:
+gaustar_amd.flow).
 """
 from __future__ import annotations
 

@@ -1267,7 +1267,57 @@ int gsr_hull_carve(int n_cameras, const void* cameras_host, const void* cameras,
 int gsr_hull_finish(const int* grid, const float* field, const int* count, int min_views, double sdf_trunc, float* tsdf, float* weight,
                     unsigned char* touched, gsr_stream_t stream);
 
-/* ---- RAFT optical flow, the basic model's inference: gaustar_amd.flow.  Replaces data_process/RAFT (demo_GauSTAR.py and the
+/* ---- Plane-sweep stereo behind a depth prior: the photo-consistency refinement of the visual hull above, which closes over
+ * every concavity: gaustar_amd.stereo.  The reference has no counterpart (its depth comes from HumanRF meshes, README.md:38-39).
+ * All device pointers unless marked [host]; every call is asynchronous on `stream`, none synchronises the host, none uses
+ * atomics; all arithmetic is double without contraction in the order written here, and every output is a pure function of the
+ * inputs.  tests/stereo_ref.py restates the rules.  Pixel (row r, column c) has its centre at (x, y) = (c, r); znear = 0.01.
+ * gsr_stereo_luma: rgb [H,W,3] uint8 -> luma [H,W] uint8, Y = (77 R + 150 G + 29 B + 128) >> 8.
+ * Camera tables: n_sources (1..8) records of gsr_stereo_camera_bytes() = 152 bytes: 9 doubles R_sr (row-major) and 3 doubles
+ *   t_sr, the source's pose RELATIVE to the reference camera (R_sr = R_s R_r^T, t_sr = t_s - R_sr t_r, each element three
+ *   products added as (a + b) + c, made on the host); the source's fx, fy, cx, cy (doubles); the device pointer of its image
+ *   (sweep: luma [H,W] uint8; consistency: refined depth [H,W] f32); the device pointer of its state [H,W] uint8 from the sweep
+ *   (consistency only); int H, int W.  sources_host: [host] the same bytes, checked (finite, fx, fy > 0, H, W >= 2, pointers)
+ *   before the launch reads the device copy.  ref_cam: [host] the reference camera's fx, fy, cx, cy.
+ * gsr_stereo_sweep: params [host] = step, near, far, background, min_var, min_score; step > 0, near, far >= 0, (near + far) /
+ *   step <= 4096, (background + far) / step < 32768, min_var > 0; radius R in {1, 2, 3}, N = (2 R + 1)^2; 1 <= min_sources, keep
+ *   <= n_sources.  Planes are global per reference camera: z_k = k step, k >= k_min = floor(znear / step) + 1.
+ *   A pixel is covered iff its prior d (f32 widened) has znear < d < background; its band is k_lo = max(k_min, ceil((d - near) /
+ *   step)) .. k_hi = floor((d + far) / step).
+ *   Warp of reference pixel (r, c) on plane k into source s: L = (((c - cx) / fx) z, ((r - cy) / fy) z, z), z = k step; local =
+ *   ((R_i0 L.x + R_i1 L.y) + R_i2 L.z) + t_i per row; invalid unless local.z > znear; px = fx_s (local.x / local.z) + cx_s, py
+ *   alike; valid iff 0 <= px < W_s - 1 and 0 <= py < H_s - 1 (so x0 = floor(px) <= W_s - 2); ax = px - x0, ay = py - y0; w =
+ *   (1 - ay) ((1 - ax) I00 + ax I01) + ay ((1 - ax) I10 + ax I11) on luma widened to double.
+ *   Score of (pixel, k, s) over the (2 R + 1)^2 window: every tap on the reference image and every tap's warp on the CENTRE's
+ *   plane valid, else invalid.  A = sum g, B = sum g^2 (integers), Vr = N B - A^2; invalid if (double) Vr < (double) (N N)
+ *   min_var.  Sw, Sww, Swg: from 0.0, one tap after the other, rows outer, columns inner, left to right (Sww += w w, Swg += w g).
+ *   Vs = N Sww - Sw Sw; invalid unless Vs >= N N min_var.  score = (N Swg - Sw A) / sqrt(Vs Vr).
+ *   Cost of (pixel, k): v valid sources; unusable if v < min_sources; else T = min(keep, v) and cost = (the T highest scores
+ *   added in descending order) / T.
+ *   Pick: k* = the usable plane of the band with the highest cost, ties to the smaller k.  state [H,W] uint8: 0 not covered, 1
+ *   covered without a usable plane, 2 best cost < min_score, 3 accepted.  If k* - 1 and k* + 1 are in the band and usable: den =
+ *   (c- - 2 c0) + c+; if den < 0, delta = clamp((0.5 (c- - c+)) / den, -0.5, 0.5); else delta = 0.
+ *   depth [H,W] f32 = (float) ((k* + delta) step) at state 3, the prior's bits elsewhere; score [H,W] f32 = the best cost at
+ *   states 2 and 3, else -2; plane [H,W] int16 = k* at states 2 and 3, else -1.
+ * gsr_stereo_consistency: for a pixel of state 3 with refined depth z: L as above, local per source; the source agrees iff
+ *   local.z > znear, the pixel (int) (px + 0.5), (int) (py + 0.5) (truncation; valid iff inside the image) has sweep state >= 3
+ *   and |depth_s - local.z| <= tol there.  state_out = 4 iff at least min_consistent sources agree, else the input state.
+ * gsr_stereo_merge: two volumes over one fusion `grid`, arrays 16-byte aligned: tsdf = (w_s >= min_weight and w_h == 1 and t_s >
+ *   t_h) ? t_s : t_h (the hull bounds the surface from outside: stereo only carves); weight = w_h; color [3][voxels] = the stereo
+ *   volume's where w_s > 0, else 0; touched [units] = 1 iff the unit holds a voxel with weight 1 and |tsdf| < 1. */
+int gsr_stereo_camera_bytes(void);
+int gsr_stereo_luma(int H, int W, const unsigned char* rgb, unsigned char* luma, gsr_stream_t stream);
+int gsr_stereo_sweep(int H, int W, const unsigned char* luma, const float* prior, const double* ref_cam, int n_sources,
+                     const void* sources_host, const void* sources, const double* params, int radius, int min_sources, int keep,
+                     float* depth, float* score, unsigned char* state, short* plane, gsr_stream_t stream);
+int gsr_stereo_consistency(int H, int W, const float* depth, const unsigned char* state, const double* ref_cam, int n_sources,
+                           const void* sources_host, const void* sources, double tol, int min_consistent, unsigned char* state_out,
+                           gsr_stream_t stream);
+int gsr_stereo_merge(const int* grid, const float* tsdf_h, const float* weight_h, const float* tsdf_s, const float* weight_s,
+                     const float* color_s, double min_weight, float* tsdf, float* weight, float* color, unsigned char* touched,
+                     gsr_stream_t stream);
+
+/* ---- RAFT optical flow, the basic model's inference: gaustar_amd.flow. Replaces data_process/RAFT (demo_GauSTAR.py and the
  * core/ modules it runs).  All activations are f32, NHWC, on the device; every call is asynchronous on `stream`, none
  * synchronises the host, none uses atomics, and every output is a pure function of the inputs with a fixed order of
  * operations.  tests/flow_ref.py restates the model.
